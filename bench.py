@@ -18,7 +18,19 @@ a torch-CPU fp32 forward of the same seeded ViT-MSN (torch.nn.functional
 linear / layer_norm / erf-GELU / SDPA, as transformers' ViTMSNModel runs it) —
 and numpy cosine top-k, timed on bounded samples on this host's cores.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, warm up, time ``--steps``
+embed steps, print the line (``value``, ``ms_per_step`` and the configuration).
+``--full`` adds everything else described above — the per-GEMM roofline and the
+vendor yardstick, config 5 ingest, the JPEG lines, batch-1 latency, the search
+configs and the CPU baselines — each still governed by its own switch
+(``--no-cpu``, ``--no-search``, ``--no-latency``, ``--ingest-images 0``,
+``--jpeg-images 0``).  ``--dump-outputs DIR`` writes what the last timed step
+returned (``raw`` and ``nrm``, the two [batch, 768] float32 arrays ``embed``
+hands its caller) as ``DIR/raw.npy`` and ``DIR/nrm.npy`` (rank r > 0:
+``raw.rank<r>.npy``); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 ``--gpus N`` without a torch.distributed launcher re-launches this script under
 ``python -m torch.distributed.run --nproc-per-node N`` (one process per GPU)
@@ -486,6 +498,63 @@ def jpeg_300x168_line(model, B: int, world: int, rank: int, barrier, max_over_ra
     return out
 
 
+def gemm_roofline(args, model, images, raw, nrm, B: int, dev):
+    """Roofline of the projection GEMMs (--full): the timed steps run the batch as --parts
+    concurrent slices, so a GEMM launch there shares the GPU; each GEMM's own efficiency is
+    timed on the unsplit batch (the GEMM alone on the chip), with HIP events on the launch
+    stream around every full-batch launch of that projection.  `roofline` prices the one that
+    takes the most time per step; `gemms` lists all four.  Returns (gemms, the dominant one,
+    GEMM ms per step, attention ms, attention launches)."""
+    import torch
+
+    M = B * 197
+    shapes = {"qkv": (M, 2304, 768, "gemm_pp_kernel<4,0,12> (QKV, LayerNorm 1 folded in)"),
+              "oproj": (M, 768, 768, "gemm_w2_kernel<6,0> (O-proj + residual + LN-2 statistics; two workgroups per CU)"),
+              "fc1": (M, 3072, 768, "gemm_pp_kernel<5,0,12> (fc1 + GELU, LayerNorm 2 folded in)"),
+              "fc2": (M, 768, 3072, "gemm_pp_kernel<6,0,48> (fc2 + residual + LN-1 statistics)")}
+    model.set_parts(1)
+    model.embed(images, out=(raw, nrm))
+    torch.cuda.synchronize()
+    model.timing(list(shapes) + ["attention"])
+    model.timing_reset()
+    for _ in range(args.roofline_steps):
+        model.embed(images, out=(raw, nrm))
+    torch.cuda.synchronize()
+    gemms = {}
+    for role, (gm, gn, gk, kname) in shapes.items():
+        ms, n, fl = model.timing_read(role)
+        avg = ms / max(n, 1)
+        tf = (fl / max(n, 1)) / (avg / 1e3) / 1e12 if avg > 0 else 0.0
+        gemms[role] = {"kernel": f"{kname}: M={gm} N={gn} K={gk}", "avg_launch_ms": avg, "launches": n,
+                       "flops_per_launch": fl / max(n, 1), "achieved_tflops": tf, "frac": tf / PEAK_BF16_TFLOPS,
+                       "ms_per_step": ms / args.roofline_steps, "traffic": load_profile_traffic(role)}
+    att_ms, att_n, _ = model.timing_read("attention")
+    model.timing(False)
+    model.set_parts(args.parts)
+    # yardstick: the vendor library's plain GEMM on each shape (torch.mm -> hipBLASLt, random bf16
+    # operands, no epilogue; min over 3 rounds of 10); never on the product path
+    for role, (gm, gn, gk, _) in shapes.items():
+        gv = torch.Generator(device=dev).manual_seed(7)
+        Av = (torch.rand(gm, gk, device=dev, generator=gv) * 2 - 1).to(torch.bfloat16)
+        Wv = ((torch.rand(gn, gk, device=dev, generator=gv) * 2 - 1) * 0.05).to(torch.bfloat16)
+        best = float("inf")
+        for _ in range(3):
+            torch.mm(Av, Wv.t())
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                torch.mm(Av, Wv.t())
+            e1.record()
+            e1.synchronize()
+            best = min(best, e0.elapsed_time(e1) / 10)
+        gemms[role]["vendor_ms"] = best
+        gemms[role]["vs_vendor"] = gemms[role]["avg_launch_ms"] / best
+        del Av, Wv
+    dominant = max(gemms, key=lambda r: gemms[r]["ms_per_step"])
+    gemm_step_ms = sum(g["ms_per_step"] for g in gemms.values())
+    return gemms, gemms[dominant], gemm_step_ms, att_ms, att_n
+
+
 def main():
     import faulthandler
 
@@ -512,7 +581,17 @@ def main():
     ap.add_argument("--no-search", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--dry-run", action="store_true", help="rank plumbing only (gloo, no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the GEMM roofline, ingest, JPEG, latency, search and the CPU baselines "
+                         "(default: the timed embed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (raw, nrm) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline only
+        args.ingest_images = args.jpeg_images = 0
+        args.no_latency = args.no_search = args.no_cpu = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: hand off to torch.distributed.run BEFORE anything touches the GPU
@@ -594,57 +673,15 @@ def main():
     el = max_over_ranks(time.perf_counter() - t0)
     assert torch.isfinite(raw).all()
     imgs_per_s = world * B * args.steps / el
-    # Roofline of the projection GEMMs: the timed steps above run the batch as --parts
-    # concurrent slices, so a GEMM launch there shares the GPU; each GEMM's own efficiency is
-    # timed on the unsplit batch (the GEMM alone on the chip), with HIP events on the launch
-    # stream around every full-batch launch of that projection.  `roofline` prices the one that
-    # takes the most time per step; `gemms` lists all four.
-    M = B * 197
-    shapes = {"qkv": (M, 2304, 768, "gemm_pp_kernel<4,0,12> (QKV, LayerNorm 1 folded in)"),
-              "oproj": (M, 768, 768, "gemm_w2_kernel<6,0> (O-proj + residual + LN-2 statistics; two workgroups per CU)"),
-              "fc1": (M, 3072, 768, "gemm_pp_kernel<5,0,12> (fc1 + GELU, LayerNorm 2 folded in)"),
-              "fc2": (M, 768, 3072, "gemm_pp_kernel<6,0,48> (fc2 + residual + LN-1 statistics)")}
-    model.set_parts(1)
-    model.embed(images, out=(raw, nrm))
-    torch.cuda.synchronize()
-    model.timing(list(shapes) + ["attention"])
-    model.timing_reset()
-    for _ in range(args.roofline_steps):
-        model.embed(images, out=(raw, nrm))
-    torch.cuda.synchronize()
-    gemms = {}
-    for role, (gm, gn, gk, kname) in shapes.items():
-        ms, n, fl = model.timing_read(role)
-        avg = ms / max(n, 1)
-        tf = (fl / max(n, 1)) / (avg / 1e3) / 1e12 if avg > 0 else 0.0
-        gemms[role] = {"kernel": f"{kname}: M={gm} N={gn} K={gk}", "avg_launch_ms": avg, "launches": n,
-                       "flops_per_launch": fl / max(n, 1), "achieved_tflops": tf, "frac": tf / PEAK_BF16_TFLOPS,
-                       "ms_per_step": ms / args.roofline_steps, "traffic": load_profile_traffic(role)}
-    att_ms, att_n, _ = model.timing_read("attention")
-    model.timing(False)
-    model.set_parts(args.parts)
-    # yardstick: the vendor library's plain GEMM on each shape (torch.mm -> hipBLASLt, random bf16
-    # operands, no epilogue; min over 3 rounds of 10); never on the product path
-    for role, (gm, gn, gk, _) in shapes.items():
-        gv = torch.Generator(device=dev).manual_seed(7)
-        Av = (torch.rand(gm, gk, device=dev, generator=gv) * 2 - 1).to(torch.bfloat16)
-        Wv = ((torch.rand(gn, gk, device=dev, generator=gv) * 2 - 1) * 0.05).to(torch.bfloat16)
-        best = float("inf")
-        for _ in range(3):
-            torch.mm(Av, Wv.t())
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(10):
-                torch.mm(Av, Wv.t())
-            e1.record()
-            e1.synchronize()
-            best = min(best, e0.elapsed_time(e1) / 10)
-        gemms[role]["vendor_ms"] = best
-        gemms[role]["vs_vendor"] = gemms[role]["avg_launch_ms"] / best
-        del Av, Wv
-    dominant = max(gemms, key=lambda r: gemms[r]["ms_per_step"])
-    dom = gemms[dominant]
-    gemm_step_ms = sum(g["ms_per_step"] for g in gemms.values())
+    if args.dump_outputs:
+        # what the last timed step handed its caller, before anything below writes raw / nrm again
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        suffix = "" if rank == 0 else f".rank{rank}"
+        for name, t in (("raw", raw), ("nrm", nrm)):
+            np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), t.cpu().numpy().astype(np.float32))
+    gemms, dom, gemm_step_ms, att_ms, att_n = {}, None, 0.0, 0.0, 0
+    if args.full:
+        gemms, dom, gemm_step_ms, att_ms, att_n = gemm_roofline(args, model, images, raw, nrm, B, dev)
     # FLOPs rc_embed executes per image (the CLS-only last layer skips the rows
     # /embed never returns); the full-model figure is reported beside it
     gflop = vit.gflop_per_image(cls_only_last=not args.full_last_layer)
@@ -851,23 +888,6 @@ def main():
             "seq_len": 197,
             "parallelism": f"dp{world}",
         },
-        "roofline": {
-            "kernel": dom["kernel"] + " — the projection GEMM with the most time per step",
-            "bound": "mfma",
-            "achieved": dom["achieved_tflops"],
-            "peak": PEAK_BF16_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": dom["achieved_tflops"] / PEAK_BF16_TFLOPS,
-            "traffic": dom["traffic"],
-            "avg_launch_ms": dom["avg_launch_ms"],
-            "launches": dom["launches"],
-            "flops_per_launch": dom["flops_per_launch"],
-            "measured_on": "unsplit batch (parts=1), HIP events on the launch stream around each full-batch launch",
-        },
-        "gemms": gemms,
-        "gemm_ms_per_step": gemm_step_ms,
-        "attention_ms_per_step": att_ms / args.roofline_steps,
-        "attention_avg_launch_ms": att_ms / max(att_n, 1),
         "embed_parts": args.parts,
         "layernorm": "standalone kernel" if args.no_ln_fold else
         "folded into QKV / fc1 epilogues (producers emit bf16(x) + per-tile mean/M2)",
@@ -878,6 +898,26 @@ def main():
         "model_tflops_per_gpu": model_tflops,
         "model_mfma_frac": model_tflops / PEAK_BF16_TFLOPS,
     }
+    if args.full:
+        result.update({
+            "roofline": {
+                "kernel": dom["kernel"] + " — the projection GEMM with the most time per step",
+                "bound": "mfma",
+                "achieved": dom["achieved_tflops"],
+                "peak": PEAK_BF16_TFLOPS,
+                "unit": "TFLOP/s",
+                "frac": dom["achieved_tflops"] / PEAK_BF16_TFLOPS,
+                "traffic": dom["traffic"],
+                "avg_launch_ms": dom["avg_launch_ms"],
+                "launches": dom["launches"],
+                "flops_per_launch": dom["flops_per_launch"],
+                "measured_on": "unsplit batch (parts=1), HIP events on the launch stream around each full-batch launch",
+            },
+            "gemms": gemms,
+            "gemm_ms_per_step": gemm_step_ms,
+            "attention_ms_per_step": att_ms / args.roofline_steps,
+            "attention_avg_launch_ms": att_ms / max(att_n, 1),
+        })
     if ingest is not None:
         result["ingest"] = ingest
     if jpeg is not None:

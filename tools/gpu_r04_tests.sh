@@ -10,6 +10,6 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout
 rc=$?; tail -3 $O/pytest.log; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 420 python -u bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 420 python -u bench.py --full > $O/bench.json 2> $O/bench.err
 rc=$?; cut -c1-600 $O/bench.json; [ $rc -ne 0 ] && tail -20 $O/bench.err
 exit $rc
