@@ -149,10 +149,6 @@ SIGNATURES = {
 DIAG_SIGNATURES = {
     "rc_diag_set_gemm_variant": (C.c_int, [_vp, _i32]),
     "rc_diag_set_stamps": (C.c_int, [_vp]),
-    "rc_diag_set_attention": (C.c_int, [_vp, _i32]),
-    "rc_diag_set_skinny_wpb": (C.c_int, [_vp, _i32]),
-    "rc_diag_set_part_priority": (C.c_int, [_vp, _i32]),
-    "rc_diag_set_group_m": (C.c_int, [_vp, _i32]),
     "rc_diag_set_band_skip": (C.c_int, [_i32]),
     "rc_diag_set_filter_split": (C.c_int, [_i32]),
     "rc_diag_set_filter_aux": (C.c_int, [_i32]),

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "vit_kernels.h"
 
@@ -84,8 +85,7 @@ __device__ __forceinline__ void nt_store16(T *dst, const T &v) {
 // residual stream is bf16 in a.ln_x (the statistics from the rounded values); otherwise f32
 // a.out_f32, plus the bf16 copy in a.ln_x and the partials when a.ln_x is set.  All lanes run the swaps; rows
 // >= mlim (M, or the end of an image-aligned tile's image) load a clamped row and store nothing.
-// ABL (diagnostic builds): 1024 = the residual read nontemporal, 2048 = the stores nontemporal
-template <int EPI, int NR, int ABL = 0>
+template <int EPI, int NR>
 __device__ __forceinline__ void f32_rows_epilogue(const GemmArgs &a, const f32x4 (&A)[NR][2][2], const int (&rows)[NR],
                                                   int colw, int g, const float4 (&bq)[2][2], int mlim) {
     constexpr bool BS = epi_bf16_stream(EPI);
@@ -103,10 +103,7 @@ __device__ __forceinline__ void f32_rows_epilogue(const GemmArgs &a, const f32x4
             if constexpr (epi_resid(EPI)) {
                 const int64_t off = (int64_t)rr * a.N + col;
                 if constexpr (BS) {
-                    if constexpr ((ABL & 1024) != 0)
-                        sh[r][c] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a.ln_x + off)));
-                    else
-                        sh[r][c] = *reinterpret_cast<const uint4 *>(a.ln_x + off);
+                    sh[r][c] = *reinterpret_cast<const uint4 *>(a.ln_x + off);
                 } else {
                     sf[r][c][0] = *reinterpret_cast<const float4 *>(a.out_f32 + off);
                     sf[r][c][1] = *reinterpret_cast<const float4 *>(a.out_f32 + off + 4);
@@ -156,11 +153,7 @@ __device__ __forceinline__ void f32_rows_epilogue(const GemmArgs &a, const f32x4
             const int64_t off = orow * a.N + colw + 32 * c + cl;
             if constexpr (BS) {
                 const uint4 h = bf16x8_pack(x);
-                if constexpr ((ABL & 2048) != 0) {
-                    if (ok) nt_store16(reinterpret_cast<uint4 *>(a.ln_x + off), h);
-                } else {
-                    if (ok) *reinterpret_cast<uint4 *>(a.ln_x + off) = h;
-                }
+                if (ok) *reinterpret_cast<uint4 *>(a.ln_x + off) = h;
                 float xv[8];
                 bf16x8_unpack(h, xv);
 #pragma unroll
@@ -202,12 +195,10 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs &a, f32x4 (&acc)[2][2
     // swapped with v_permlane16_swap so each lane stores 16 B (8 consecutive columns);
     // lane (g, li) of rows 16-block holds columns 4g..4g+3 of both 16-column halves ni, the
     // swap of rows 1<->0 and 3<->2 between the ni halves makes them 8 contiguous columns.
-    // (Also ABL 64 for the other bf16 epilogues, QKV's LN consumer included, in diagnostic builds.)
-    // Round 6 measured fc1 through the LDS-staged path with its nontemporal 512-B row stores
-    // (ABL 512): fc1 itself +1.5…6 us per launch, the fc2 after it −8 us, step +0.3 % (r06s, r06t)
+    // Round 6 measured fc1 through the LDS-staged path below with its nontemporal 512-B row
+    // stores: fc1 itself +1.5…6 us per launch, the fc2 after it −8 us, step +0.3 % (r06s, r06t)
     // — within the run-to-run spread, so fc1 keeps this form.
-    constexpr bool DIRECT = (EPI == EPI_GELU_BF16_LN && (ABL & 512) == 0) || (epi_bf16_out(EPI) && (ABL & 64) != 0);
-    if constexpr (DIRECT) {
+    if constexpr (EPI == EPI_GELU_BF16_LN) {
         float4 bq[2][2], cq[2][2];
 #pragma unroll
         for (int nq = 0; nq < 2; ++nq)
@@ -263,9 +254,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs &a, f32x4 (&acc)[2][2
                         asm volatile("" ::"v"(u[0][0]), "v"(u[0][1]), "v"(u[1][0]), "v"(u[1][1]));
                     } else if (row < mlim) {
                         uint4 *dst = reinterpret_cast<uint4 *>(a.out_bf16 + (int64_t)row * (a.ldc ? a.ldc : a.N) + col);
-                        const uint4 val = make_uint4(u[0][0], u[0][1], u[1][0], u[1][1]);
-                        if constexpr ((ABL & 32) != 0) nt_store16(dst, val);
-                        else *dst = val;
+                        *dst = make_uint4(u[0][0], u[0][1], u[1][0], u[1][1]);
                     }
                 }
             }
@@ -366,7 +355,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs &a, f32x4 (&acc)[2][2
 #pragma unroll
                     for (int h = 0; h < 2; ++h) A[r][c][h] = acc[mq][c][mi][h];
             }
-            f32_rows_epilogue<EPI, NR, ABL>(a, A, rows, n0 + wc * 64, g, bq, mlim);
+            f32_rows_epilogue<EPI, NR>(a, A, rows, n0 + wc * 64, g, bq, mlim);
         }
 }
 
@@ -469,8 +458,8 @@ __device__ __forceinline__ void pp_kloop(const GemmArgs &a, uint8_t *smem, int m
             // three column tiles at about the same time) is staged nontemporal (aux 2), so it does not
             // displace W and the residual rows in L2 (round 6 in-model A/B: fc2 277.6 -> 264.9 us,
             // r06x); QKV / fc1 re-read their A panels over several rounds and keep the default
-            // (ABL 4096, diagnostic: nontemporal for every GEMM: QKV 186 -> 200, fc1 294 -> 310 us)
-            if (is_a && (epi_resid(EPI) || (ABL & 4096) != 0))
+            // (nontemporal for every GEMM: QKV 186 -> 200, fc1 294 -> 310 us, r06x)
+            if (is_a && epi_resid(EPI))
                 __builtin_amdgcn_global_load_lds((const void *)src, (lds_void_t *)(base + piece * 1024), 16, 0, 2);
             else
                 __builtin_amdgcn_global_load_lds((const void *)src, (lds_void_t *)(base + piece * 1024), 16, 0, 0);
@@ -601,16 +590,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs a) {
     RC_STAMP(sb, RC_NOW());
     RC_STAMP(sb + 4, (uint64_t)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((uint64_t)__builtin_amdgcn_s_getreg(20 | (3 << 11)) << 32));
     RC_STAMP(sb + 5, (uint64_t)tm | ((uint64_t)tn << 32));
-    if constexpr ((ABL & (128 | 256)) != 0) {
-        // diagnostic: staggered start — the first round's workgroups on every other CU of an XCD
-        // (block b runs on XCD b % 8, consecutive b / 8 on neighbouring CUs) wait ~half a tile, so
-        // later rounds' epilogue store bursts fall beside other CUs' K loops
-        constexpr uint64_t D = (ABL & 128) ? 1000 : 500;  // s_memrealtime ticks (100 MHz)
-        if (blockIdx.x < 256 && ((blockIdx.x >> 3) & 1)) {
-            const uint64_t t0 = RC_NOW();
-            while (RC_NOW() - t0 < D) __builtin_amdgcn_s_sleep(8);
-        }
-    }
     float4 biasr[2][2];
     pp_bias_regs<EPI>(a, n0, biasr, threadIdx.x);
     pp_kloop<EPI, ABL, BM>(a, smem, m0, n0, 0, NKT > 0 ? NKT : a.K / PP_BK, acc, threadIdx.x, sb + 1);
@@ -632,23 +611,17 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs a) {
 // Epilogue of a 128 x 256 tile held as acc[mi][ni] by 4 waves (wave w: columns
 // [64w, 64w + 64)): acc[mi][ni][j] = C[m0 + mi*16 + li][n0 + w*64 + ni*16 + 4g + j].
 // The bf16 epilogues stage through `smem` (>= 64 KB; the caller's main loop must be done
-// with it); the f32 ones store from the accumulators.  LayerNorm-fold consumers (EPI_*_LN): the
-// tile rows' (rstd, -rstd*mu) at smem + ln_off, as gemm_pp_kernel keeps them, and the same
-// rstd·(acc − μ·c) + b′ arithmetic (the same bits).
-template <int EPI, int MI = 8, int ABL = 0>
-__device__ __forceinline__ void w2_epilogue(const GemmArgs &a, f32x4 (&acc)[MI][4], uint8_t *smem, int m0, int n0,
-                                            int ln_off = 0) {
+// with it); the f32 ones store from the accumulators.
+template <int EPI, int MI = 8>
+__device__ __forceinline__ void w2_epilogue(const GemmArgs &a, f32x4 (&acc)[MI][4], uint8_t *smem, int m0, int n0) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, li = lane & 15;
     if constexpr (epi_bf16_out(EPI)) {
         static_assert(MI == 8, "bf16 epilogues stage a 128-row tile");
-        float4 bias[4], lc[4];
+        float4 bias[4];
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            bias[ni] = *reinterpret_cast<const float4 *>(a.bias + n0 + wave * 64 + ni * 16 + 4 * g);
-            if constexpr (epi_ln(EPI)) lc[ni] = *reinterpret_cast<const float4 *>(a.ln_c + n0 + wave * 64 + ni * 16 + 4 * g);
-        }
+        for (int ni = 0; ni < 4; ++ni) bias[ni] = *reinterpret_cast<const float4 *>(a.bias + n0 + wave * 64 + ni * 16 + 4 * g);
         __syncthreads();  // every wave's last fragment reads are done: the ring is free
         // 128 x 256 bf16 tile staged in LDS (512-B rows, 16-B chunk XOR (row & 31)),
         // stored as whole 512-B row segments, 16 B per lane.
@@ -659,16 +632,7 @@ __device__ __forceinline__ void w2_epilogue(const GemmArgs &a, f32x4 (&acc)[MI][
             for (int mi = 0; mi < 8; ++mi) {
                 const int rl = mi * 16 + li;
                 const f32x4 v4 = acc[mi][ni];
-                float v0, v1, v2, v3;
-                if constexpr (epi_ln(EPI)) {  // rstd·(acc − μ·c) + b′
-                    const float2 r = *reinterpret_cast<const float2 *>(smem + ln_off + rl * 8);
-                    v0 = fmaf(r.x, v4[0], fmaf(r.y, lc[ni].x, bias[ni].x));
-                    v1 = fmaf(r.x, v4[1], fmaf(r.y, lc[ni].y, bias[ni].y));
-                    v2 = fmaf(r.x, v4[2], fmaf(r.y, lc[ni].z, bias[ni].z));
-                    v3 = fmaf(r.x, v4[3], fmaf(r.y, lc[ni].w, bias[ni].w));
-                } else {
-                    v0 = v4[0] + bias[ni].x, v1 = v4[1] + bias[ni].y, v2 = v4[2] + bias[ni].z, v3 = v4[3] + bias[ni].w;
-                }
+                float v0 = v4[0] + bias[ni].x, v1 = v4[1] + bias[ni].y, v2 = v4[2] + bias[ni].z, v3 = v4[3] + bias[ni].w;
                 if constexpr (epi_gelu(EPI)) {
                     const f32x2 lo = gelu_fast2(f32x2{v0, v1}), hi = gelu_fast2(f32x2{v2, v3});
                     v0 = lo.x;
@@ -715,7 +679,7 @@ __device__ __forceinline__ void w2_epilogue(const GemmArgs &a, f32x4 (&acc)[MI][
 #pragma unroll
                 for (int h = 0; h < 2; ++h) A[r][c][h] = acc[h4 * 4 + r][2 * c + h];
         }
-        f32_rows_epilogue<EPI, 4, ABL>(a, A, rows, n0 + wave * 64, g, bq, a.M);
+        f32_rows_epilogue<EPI, 4>(a, A, rows, n0 + wave * 64, g, bq, a.M);
     }
 #pragma unroll
     for (int m2 = 4 * N4; m2 < MI; m2 += 2) {
@@ -729,7 +693,7 @@ __device__ __forceinline__ void w2_epilogue(const GemmArgs &a, f32x4 (&acc)[MI][
 #pragma unroll
                 for (int h = 0; h < 2; ++h) A[r][c][h] = acc[m2 + r][2 * c + h];
         }
-        f32_rows_epilogue<EPI, 2, ABL>(a, A, rows, n0 + wave * 64, g, bq, a.M);
+        f32_rows_epilogue<EPI, 2>(a, A, rows, n0 + wave * 64, g, bq, a.M);
     }
 }
 
@@ -759,13 +723,12 @@ __device__ __forceinline__ void w2_epilogue(const GemmArgs &a, f32x4 (&acc)[MI][
 // 1 182 = 2.31 rounds (the third 31 % full); launch_gemm picks the BM with the fewer row-rounds.
 template <int EPI, int ABL = 0, int BM = 128>
 __global__ __launch_bounds__(256, 2) void gemm_w2_kernel(GemmArgs a) {
+    static_assert(!epi_ln(EPI), "LayerNorm-fold consumers run on the ping-pong or skinny kernel");
     constexpr int BN = 256, BK = 32, NSLOT = 3, MI = BM / 16;
     constexpr int A_BYTES = BM * BK * 2, SLOT = A_BYTES + BN * BK * 2;  // 8 (10) KB + 16 KB
     constexpr int PIECES = SLOT / 1024;                                  // 24 (26) pieces: A then W
     constexpr int PPW = (PIECES + 3) / 4, PPW_LO = PIECES / 4;           // pieces of waves < PIECES % 4 / the rest
-    constexpr int LN_OFF = NSLOT * SLOT, LN_LDS = epi_ln(EPI) ? BM * 8 : 0;  // LN-fold row scales behind the ring
-    static_assert(!epi_ln(EPI) || LN_OFF >= 64 * 1024, "the staged bf16 tile must not reach the row scales");
-    __shared__ __attribute__((aligned(16))) uint8_t smem[NSLOT * SLOT + LN_LDS];  // 72 (78) KB (+ 1 KB)
+    __shared__ __attribute__((aligned(16))) uint8_t smem[NSLOT * SLOT];  // 72 (78) KB
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -806,10 +769,7 @@ __global__ __launch_bounds__(256, 2) void gemm_w2_kernel(GemmArgs a) {
         for (int i = 0; i < PPW; ++i) {
             const int piece = wave + 4 * i;  // wave-uniform
             if (piece >= PIECES) continue;
-            if ((ABL & 4096) != 0 && piece < MI)  // diagnostic: the A operand's DMA nontemporal
-                __builtin_amdgcn_global_load_lds((const void *)(srcp[i] + k0), (lds_void_t *)(base + piece * 1024), 16, 0, 2);
-            else
-                __builtin_amdgcn_global_load_lds((const void *)(srcp[i] + k0), (lds_void_t *)(base + piece * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const void *)(srcp[i] + k0), (lds_void_t *)(base + piece * 1024), 16, 0, 0);
         }
     };
     // fragment of rows r0 + li (r0 % 16 == 0), k chunk g: 16 B at row*64 + (g ^ h(li))*16
@@ -824,11 +784,6 @@ __global__ __launch_bounds__(256, 2) void gemm_w2_kernel(GemmArgs a) {
     const int nk = K / BK;
     stage(0, 0);
     if (nk > 1) stage(1, BK);
-    if constexpr (epi_ln(EPI)) {  // this tile's row scales, as gemm_pp_kernel's prologue (visible after the loop's barriers)
-        if (tid < BM)
-            *reinterpret_cast<float2 *>(smem + LN_OFF + tid * 8) =
-                ln_row_scale(a.ln_stats + (int64_t)min(m0 + tid, a.M - 1) * LN_STRIDE, a.ln_eps);
-    }
     for (int kt = 0; kt < nk; ++kt) {
         // a raw s_barrier: __syncthreads() would add a full vmcnt(0) drain (its
         // release fence), emptying the DMA pipeline every K-step.  The next slot's pieces of this
@@ -873,7 +828,7 @@ __global__ __launch_bounds__(256, 2) void gemm_w2_kernel(GemmArgs a) {
             for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
         return;
     }
-    w2_epilogue<EPI, MI, ABL>(a, acc, smem, m0, n0, LN_OFF);
+    w2_epilogue<EPI, MI>(a, acc, smem, m0, n0);
 }
 
 // ------------------------------------------- implicit-GEMM patch embedding ----
@@ -1213,21 +1168,20 @@ __device__ __forceinline__ void skinny_epilogue(const GemmArgs &a, const f32x4 (
 
 // One wave per block: the loads are address-bound (PMC: the texture addresser busy for the
 // whole launch on the CUs holding blocks), so a tile per CU where 4-wave blocks put four.
-// WPB > 1 (diagnostic builds): WPB consecutive tiles per block, one wave and one DMA ring each —
-// a one-image fc1 is 1 248 one-wave workgroups (the same bits either way).
-template <int EPI, int NI, int KT, int WPB = 1, int SK = SKINNY_DMA_STAGES>
-__global__ __launch_bounds__(64 * WPB) void gemm_skinny_kernel(GemmArgs a) {
+// (Two or four tiles per block, one wave and one DMA ring each, the same bits: 423.6 / 431.0 vs
+// 427.0 us of device time per one-image request, profiles/r06/r06j_skinny_wpb_ab.log.)
+template <int EPI, int NI, int KT, int SK = SKINNY_DMA_STAGES>
+__global__ __launch_bounds__(64) void gemm_skinny_kernel(GemmArgs a) {
     const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
-    const int wave = WPB > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     const int nct = a.N / (16 * NI), nrt = (a.M + 15) / 16;
-    const int w = skinny_block(blockIdx.x, gridDim.x) * WPB + wave;
+    const int w = skinny_block(blockIdx.x, gridDim.x);
     if (w >= nct * nrt) return;
     const int ct = w / nrt, rt = w % nrt;
     const int K = a.K, n0 = ct * 16 * NI, row = rt * 16 + li;
     f32x4 acc[NI];
     if constexpr (KT > 0) {
-        __shared__ __attribute__((aligned(16))) uint8_t ring[WPB][SK * skinny_dma_stage_bytes<NI>()];
-        skinny_chain_dma<NI, KT / 64, SK>(a.A, rt * 16, a.M, a.W, n0, K, ring[wave], acc);
+        __shared__ __attribute__((aligned(16))) uint8_t ring[SK * skinny_dma_stage_bytes<NI>()];
+        skinny_chain_dma<NI, KT / 64, SK>(a.A, rt * 16, a.M, a.W, n0, K, ring, acc);
     } else {
         const uint16_t *Ar = a.A + (int64_t)min(row, a.M - 1) * K + 8 * g;  // rows past M: clamped loads, no stores
         const uint16_t *Wr = a.W + (int64_t)(n0 + li) * K + 8 * g;
@@ -1475,7 +1429,7 @@ inline void launch_skinny_splitk_resid(const GemmArgs &a, float *part, hipStream
 enum GemmVariant { GEMM_AUTO = 0, GEMM_PINGPONG = 4, GEMM_W2 = 8, GEMM_SKINNY = 9, GEMM_PP_IMG = 10 };
 
 inline int gemm_pick(const GemmArgs &a, int variant, bool patch_epilogue, bool ln_epilogue = false) {
-    if (variant != GEMM_AUTO) return variant;  // (100 + ABL / 200 + ABL: ablation builds, RC_GEMM_ABLATION)
+    if (variant != GEMM_AUTO) return variant;  // (100 + ABL / 200 + ABL: diagnostic builds, RC_GEMM_ABLATION)
     if (a.M <= 256 && !patch_epilogue && a.N % 32 == 0) return GEMM_SKINNY;
     // (Round 5 built image-aligned 224-row tiles for the residual producers — O-proj / fc2 as whole
     // rounds, n x 3 tiles: per launch at parts = 1 fc2 276 vs 297 us, but at the product's parts = 2
@@ -1493,14 +1447,9 @@ inline int gemm_pick(const GemmArgs &a, int variant, bool patch_epilogue, bool l
 // Ping-pong tile order: groups of 8 row tiles (column-major inside a group) when
 // a row has >= 6 column tiles (QKV: 176 -> 170 us, fc1: 285 -> 274 us at batch
 // 256, interleaved A/B in tools/gemm_calib.py), row-major otherwise (fc2 prefers
-// it by 2 %).
-#if defined(RC_GEMM_ABLATION)
-inline int g_skinny_wpb = 1;    // diagnostic builds: tiles (waves) per skinny-GEMM block (rc_diag_set_skinny_wpb)
-inline int g_group_m_wide = 8;  // diagnostic builds: group_m of the wide ping-pong GEMMs (rc_diag_set_group_m)
-inline int gemm_group_m(const GemmArgs &a) { return a.N / 256 >= 6 ? g_group_m_wide : 0; }
-#else
+// it by 2 %).  Groups of 2, 4, 8, 16 in the model: fc1 reads 490 / 444 / 459 / 619 MB, time equal
+// within 1 % (profiles/r06/r06p_group_m_ab.log); tools/gemm_lab/lab.py --groups sweeps the order.
 inline int gemm_group_m(const GemmArgs &a) { return a.N / 256 >= 6 ? 8 : 0; }
-#endif
 
 // The patch embedding of a small batch (M <= 256 patch rows, the bf16 stream: one image is
 // 196 rows, and patch_gemm_kernel's 128 x 256 tiles put it on 6 workgroups, 33 us): the skinny
@@ -1665,6 +1614,23 @@ void launch_pp(const GemmArgs &a, int ntm, hipStream_t s) {
     else hipLaunchKernelGGL((gemm_pp_kernel<EPI, ABL, 0, BM>), gr, bl, 0, s, a);
 }
 
+#if defined(RC_GEMM_ABLATION)
+// The ablation masks the diagnostic build compiles: variant 100 + ABL (ping-pong, 256-row tiles, bits
+// 0-4) and 200 + ABL (two-workgroup, 128-row tiles, bits 0-2).  Each launches the kernel of mask
+// `abl` and returns true, or returns false if `abl` is not in its list.
+using PpAblations = std::integer_sequence<int, 0, 1, 2, 3, 4, 5, 6, 8, 16, 24>;
+using W2Ablations = std::integer_sequence<int, 1, 2, 4, 6>;
+template <int EPI, int... ABL>
+bool launch_pp_ablation(std::integer_sequence<int, ABL...>, int abl, const GemmArgs &a, hipStream_t s) {
+    return ((abl == ABL && (launch_pp<EPI, ABL, PP_BM>(a, (a.M + 255) / 256, s), true)) || ...);
+}
+template <int EPI, int... ABL>
+bool launch_w2_ablation(std::integer_sequence<int, ABL...>, int abl, const GemmArgs &a, hipStream_t s) {
+    const dim3 gr((a.M + 127) / 128 * (a.N / 256)), bl(256);
+    return ((abl == ABL && ([&] { hipLaunchKernelGGL((gemm_w2_kernel<EPI, ABL>), gr, bl, 0, s, a); }(), true)) || ...);
+}
+#endif
+
 template <int EPI>
 void launch_gemm(const GemmArgs &a_in, int variant, hipStream_t s) {
     GemmArgs a = a_in;
@@ -1678,20 +1644,17 @@ void launch_gemm(const GemmArgs &a_in, int variant, hipStream_t s) {
     if constexpr (epi_ln(EPI)) {
         bool ln_ok = pick == GEMM_PINGPONG || pick == GEMM_SKINNY;
 #if defined(RC_GEMM_ABLATION)
-        ln_ok = ln_ok || (pick >= 100 && pick < 200) || pick == GEMM_W2;  // gemm_pp_kernel<EPI, ABL>, round-6 W2 A/B
+        ln_ok = ln_ok || (pick >= 100 && pick < 200);  // gemm_pp_kernel<EPI, ABL>
 #endif
         RC_REQUIRE(ln_ok && a.ln_c && a.ln_stats, RC_ERR_UNSUPPORTED,
                    "LayerNorm-fold consumers run on the ping-pong or skinny kernel");
     }
     switch (pick) {
         case GEMM_W2: {
-#if !defined(RC_GEMM_ABLATION)
-            // LayerNorm-fold consumers on this kernel: diagnostic builds only (round 6 in-model A/B,
-            // bit-identical: fc1 302 vs 273 us, QKV 206 vs 183 on the ping-pong kernel)
+            // LayerNorm-fold consumers on this kernel lost (round 6 in-model A/B, bit-identical: fc1 302
+            // vs 273 us, QKV 206 vs 183 on the ping-pong kernel, profiles/r06/r06i_ln_consumer_w2_ab_p{1,2}.log)
             if constexpr (epi_ln(EPI)) throw Error(RC_ERR_UNSUPPORTED, "LayerNorm-fold consumers: ping-pong or skinny kernel");
-            else
-#endif
-            {
+            else {
                 RC_REQUIRE(a.N % 256 == 0, RC_ERR_UNSUPPORTED, "GEMM N must be a multiple of 256");
                 RC_REQUIRE(a.K % 32 == 0, RC_ERR_UNSUPPORTED, "GEMM K must be a multiple of 32");
                 const int ntn = a.N / 256;
@@ -1724,20 +1687,6 @@ void launch_gemm(const GemmArgs &a_in, int variant, hipStream_t s) {
             }
             const int nrt = (a.M + 15) / 16;
             const dim3 gr(nrt * (a.N / 32));  // one wave (tile) per block
-#if defined(RC_GEMM_ABLATION)
-            if (g_skinny_wpb > 1 && (a.K == 768 || a.K == 3072)) {  // diagnostic: WPB tiles per block
-                const unsigned nb = (unsigned)(((a.M + 15) / 16) * (a.N / 32) + g_skinny_wpb - 1) / g_skinny_wpb;
-                if (g_skinny_wpb == 2 && a.K == 768)
-                    hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 768, 2>), dim3(nb), dim3(128), 0, s, a);
-                else if (g_skinny_wpb == 2)
-                    hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 3072, 2>), dim3(nb), dim3(128), 0, s, a);
-                else if (a.K == 768)
-                    hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 768, 4>), dim3(nb), dim3(256), 0, s, a);
-                else
-                    hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 3072, 4>), dim3(nb), dim3(256), 0, s, a);
-                break;
-            }
-#endif
             // more one-wave tiles than the one-wave kernel holds resident (4-5 per CU: a lone image's
             // fc1, 1 248): row tiles share the weights, SKR per block (fc1 7.68 -> 7.16 us per launch in
             // rocprofv3; QKV's 936 tiles stay one per block: 5.84 vs 6.16 us shared,
@@ -1748,7 +1697,7 @@ void launch_gemm(const GemmArgs &a_in, int variant, hipStream_t s) {
                 else hipLaunchKernelGGL((gemm_skinny_shared_kernel<EPI, 3072>), gs, dim3(64 * SKR), 0, s, a);
                 break;
             }
-            if (a.K == 768) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 768, 1, epi_gelu(EPI) ? SKINNY_FC1_STAGES : SKINNY_DMA_STAGES>), gr, dim3(64), 0, s, a);
+            if (a.K == 768) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 768, epi_gelu(EPI) ? SKINNY_FC1_STAGES : SKINNY_DMA_STAGES>), gr, dim3(64), 0, s, a);
             else if (a.K == 3072) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 3072>), gr, dim3(64), 0, s, a);
             else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, 0>), gr, dim3(64), 0, s, a);
             break;
@@ -1773,66 +1722,16 @@ void launch_gemm(const GemmArgs &a_in, int variant, hipStream_t s) {
             }
             break;
         }
-        case 301: case 302: case 303: {  // residual epilogue nontemporal reads / stores / both, 160-row W2 tiles
-            if constexpr (epi_resid(EPI)) {
-                const dim3 gr((a.M + 159) / 160 * (a.N / 256)), bl(256);
-                if (variant == 301) hipLaunchKernelGGL((gemm_w2_kernel<EPI, 1024, 160>), gr, bl, 0, s, a);
-                else if (variant == 302) hipLaunchKernelGGL((gemm_w2_kernel<EPI, 2048, 160>), gr, bl, 0, s, a);
-                else hipLaunchKernelGGL((gemm_w2_kernel<EPI, 3072, 160>), gr, bl, 0, s, a);
-            }
+        default: {
+            a.group_m = gemm_group_m(a);  // the product tile order (ping-pong)
+            bool ok = launch_pp_ablation<EPI>(PpAblations{}, variant - 100, a, s);
+            if constexpr (!epi_ln(EPI)) ok = ok || launch_w2_ablation<EPI>(W2Ablations{}, variant - 200, a, s);
+            if (!ok) throw Error(RC_ERR_INVALID, "unknown GEMM variant");
             break;
         }
-        case 304: {  // residual producer on 160-row W2 tiles, A operand's DMA nontemporal
-            if constexpr (epi_resid(EPI))
-                hipLaunchKernelGGL((gemm_w2_kernel<EPI, 4096, 160>), dim3((a.M + 159) / 160 * (a.N / 256)), dim3(256), 0, s, a);
-            break;
-        }
-        case 300: {  // the two-workgroup kernel on 128-row tiles whatever M (A/B of the 160-row pick)
-            if constexpr (!epi_ln(EPI))
-                hipLaunchKernelGGL((gemm_w2_kernel<EPI>), dim3((a.M + 127) / 128 * (a.N / 256)), dim3(256), 0, s, a);
-            break;
-        }
-        case 200 + 1: case 200 + 2: case 200 + 4: case 200 + 6: {
-            const int ntm = (a.M + 127) / 128, ntn = a.N / 256;
-            const dim3 gr(ntm * ntn), bl(256);
-            switch (variant - 200) {
-                case 1: hipLaunchKernelGGL((gemm_w2_kernel<EPI, 1>), gr, bl, 0, s, a); break;
-                case 2: hipLaunchKernelGGL((gemm_w2_kernel<EPI, 2>), gr, bl, 0, s, a); break;
-                case 4: hipLaunchKernelGGL((gemm_w2_kernel<EPI, 4>), gr, bl, 0, s, a); break;
-                case 6: hipLaunchKernelGGL((gemm_w2_kernel<EPI, 6>), gr, bl, 0, s, a); break;
-            }
-            break;
-        }
-        case 100 + 0: case 100 + 1: case 100 + 2: case 100 + 3: case 100 + 4: case 100 + 5: case 100 + 6:
-        case 100 + 8: case 100 + 16: case 100 + 24: case 100 + 32: case 100 + 64: case 100 + 96: case 150: case 151: case 152: case 153: case 154: case 155: case 156: {
-            a.group_m = gemm_group_m(a);  // the product tile order
-            const int ntm = (a.M + 255) / 256;
-            switch (variant - 100) {
-                case 0: launch_pp<EPI, 0, PP_BM>(a, ntm, s); break;
-                case 1: launch_pp<EPI, 1, PP_BM>(a, ntm, s); break;
-                case 2: launch_pp<EPI, 2, PP_BM>(a, ntm, s); break;
-                case 3: launch_pp<EPI, 3, PP_BM>(a, ntm, s); break;
-                case 4: launch_pp<EPI, 4, PP_BM>(a, ntm, s); break;
-                case 5: launch_pp<EPI, 5, PP_BM>(a, ntm, s); break;
-                case 6: launch_pp<EPI, 6, PP_BM>(a, ntm, s); break;
-                case 8: launch_pp<EPI, 8, PP_BM>(a, ntm, s); break;
-                case 16: launch_pp<EPI, 16, PP_BM>(a, ntm, s); break;
-                case 24: launch_pp<EPI, 24, PP_BM>(a, ntm, s); break;
-                case 32: launch_pp<EPI, 32, PP_BM>(a, ntm, s); break;
-                case 64: launch_pp<EPI, 64, PP_BM>(a, ntm, s); break;
-                case 96: launch_pp<EPI, 96, PP_BM>(a, ntm, s); break;
-                case 50: launch_pp<EPI, 128, PP_BM>(a, ntm, s); break;  // staggered start, ~10 us
-                case 51: launch_pp<EPI, 256, PP_BM>(a, ntm, s); break;  // staggered start, ~5 us
-                case 52: launch_pp<EPI, 512, PP_BM>(a, ntm, s); break;  // fc1 LDS-staged, nontemporal stores
-                case 53: launch_pp<EPI, 1024, PP_BM>(a, ntm, s); break;  // residual read nontemporal
-                case 54: launch_pp<EPI, 2048, PP_BM>(a, ntm, s); break;  // residual stores nontemporal
-                case 55: launch_pp<EPI, 3072, PP_BM>(a, ntm, s); break;  // both
-                case 56: launch_pp<EPI, 4096, PP_BM>(a, ntm, s); break;  // A operand's DMA nontemporal
-            }
-            break;
-        }
-#endif
+#else
         default: throw Error(RC_ERR_INVALID, "unknown GEMM variant");
+#endif
     }
     RC_LAUNCH_CHECK();
 }

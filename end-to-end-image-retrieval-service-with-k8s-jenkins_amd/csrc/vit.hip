@@ -88,7 +88,6 @@ struct rc_model {
     size_t resize_tmp_bytes = 0;
     KernelTimer timers[T_COUNT];
     int gemm_variant = GEMM_AUTO;  // diagnostic builds only: rc_diag_set_gemm_variant
-    int attn_form = 2;             // attention_v2_kernel; diag builds: 3 = attention_v3_kernel (A/B: v3 lost, 92 vs 75 us)
     int ncu = 256;                 // compute units (persistent grids)
     int split = 2;                 // batch parts encoded concurrently (rc_model_set_parts);
                                    // 2 beats 3 and 4 by 1-2 % at batch 256 (profiles/r01j_ab_parts.jsonl)
@@ -377,19 +376,7 @@ int diag_variant(const GemmArgs &a, int variant, bool patch_epilogue, bool ln_ep
     if (producer && (variant == GEMM_PINGPONG || variant == GEMM_W2 || variant == GEMM_PP_IMG)) return variant;
     if (producer && variant == 11) return a.K <= 768 ? GEMM_W2 : GEMM_PP_IMG;  // O-proj two-workgroup, fc2 image-aligned
     if (producer && variant == 12) return a.K <= 768 ? GEMM_W2 : GEMM_PINGPONG;  // = auto (rounds 4 and 5)
-    if (producer && variant == 13) return a.K <= 768 ? 300 : GEMM_PINGPONG;      // O-proj on 128-row W2 tiles only
     if (producer && variant == 14) return GEMM_W2;                                // fc2 on the two-workgroup kernel too
-    // residual epilogues with nontemporal reads / stores / both: O-proj (W2 160-row tiles) 18-20,
-    // fc2 (ping-pong) 21-23
-    if (producer && variant >= 18 && variant <= 20) return a.K <= 768 ? 300 + (variant - 17) : GEMM_AUTO;
-    if (producer && variant >= 21 && variant <= 23) return a.K > 768 ? 153 + (variant - 21) : GEMM_AUTO;
-    // the A operand's DMA nontemporal: 24 fc2, 25 O-proj, 26 both
-    if (producer && (variant == 24 || variant == 26) && a.K > 768) return 156;
-    if (producer && (variant == 25 || variant == 26) && a.K <= 768) return 304;
-    // LayerNorm-fold consumers of a full batch on the two-workgroup kernel: 15 fc1, 16 QKV, 17 both
-    if (ln_epilogue && pick == GEMM_PINGPONG &&
-        (variant == 17 || (variant == 15 && a.N == 3072) || (variant == 16 && a.N != 3072)))
-        return GEMM_W2;
     if (pick == GEMM_PINGPONG && variant >= 100 && variant < 200) return variant;
     return GEMM_AUTO;
 }
@@ -554,22 +541,6 @@ void encode(rc_model *m, const uint8_t *images, int i0, int n, float *raw, float
         const int items = n * c.heads;
         // fewer items than CUs: each item's query tiles split over 4 blocks (a lone image: 48 blocks)
         const int qsplit = items < m->ncu ? 4 : 1;
-#if defined(RC_GEMM_ABLATION)
-        if (m->attn_form == 3) {  // persistent: two blocks per CU walk the (image, head) items
-            const int nb = std::min(items, 2 * m->ncu);
-            hipLaunchKernelGGL(attention_v3_kernel<197>, dim3(nb), dim3(256), 0, s, qkv, attn, T, c.heads, items,
-                               scale * 1.4426950408889634f);
-        } else if (m->attn_form == 4 && T == 197) {  // v2, co-resident blocks staggered by ~6 us
-            hipLaunchKernelGGL((attention_v2_kernel<197, 600>), dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
-                               scale * 1.4426950408889634f, qsplit);
-        } else if (m->attn_form == 6 && T == 197) {  // v2 with the default-policy K/V DMA (rounds 1-5)
-            hipLaunchKernelGGL((attention_v2_kernel<197, 0, 0>), dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
-                               scale * 1.4426950408889634f, qsplit);
-        } else if (m->attn_form == 5 && T == 197) {  // ~3 us
-            hipLaunchKernelGGL((attention_v2_kernel<197, 300>), dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
-                               scale * 1.4426950408889634f, qsplit);
-        } else
-#endif
         if (T == 197) {
             hipLaunchKernelGGL(attention_v2_kernel<197>, dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
                                scale * 1.4426950408889634f, qsplit);
@@ -997,67 +968,15 @@ extern "C" int rc_diag_set_stamps(void *dev) {
     return guard([&] { RC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_rc_stamps), &dev, sizeof(dev))); });
 }
 
-// diagnostic builds: the priority of the part streams 1..3 (part 0 runs on the caller's stream):
-// -1 = higher than the default, 1 = lower, 0 = default (the product's)
-extern "C" int rc_diag_set_part_priority(rc_model *m, int prio) {
-    return guard([&] {
-        RC_REQUIRE(m && prio >= -1 && prio <= 1, RC_ERR_INVALID, "part priority: -1, 0 or 1");
-        std::lock_guard<std::mutex> lk(m->mu);
-        DeviceScope ds(m->device);
-        m->clear_graphs();
-        int lo = 0, hi = 0;
-        RC_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        const int pr = prio < 0 ? hi : (prio > 0 ? lo : 0);
-        RC_HIP(hipDeviceSynchronize());
-        for (int p = 1; p < kMaxParts; ++p) {
-            RC_HIP(hipStreamDestroy(m->sp[p]));
-            RC_HIP(hipStreamCreateWithPriority(&m->sp[p], hipStreamNonBlocking, pr));
-        }
-    });
-}
-
-// diagnostic builds: the ping-pong tile order of the wide GEMMs (QKV, fc1): groups of g row tiles
-// walked column-major (8, the product's; 0 = row-major)
-extern "C" int rc_diag_set_group_m(rc_model *m, int g) {
-    return guard([&] {
-        RC_REQUIRE(m && g >= 0 && g <= 64, RC_ERR_INVALID, "group_m in [0, 64]");
-        std::lock_guard<std::mutex> lk(m->mu);
-        m->clear_graphs();
-        g_group_m_wide = g;
-    });
-}
-
-// diagnostic builds: tiles (one wave each) per block of the skinny GEMM (1, the product's; 2; 4)
-extern "C" int rc_diag_set_skinny_wpb(rc_model *m, int wpb) {
-    return guard([&] {
-        RC_REQUIRE(m && (wpb == 1 || wpb == 2 || wpb == 4), RC_ERR_INVALID, "skinny waves per block: 1, 2 or 4");
-        std::lock_guard<std::mutex> lk(m->mu);
-        m->clear_graphs();
-        g_skinny_wpb = wpb;
-    });
-}
-
-// diagnostic builds: attention_v2_kernel (2, the product's) or attention_v3_kernel (3, lost the
-// A/B) for the full-token layers (the same bits)
-extern "C" int rc_diag_set_attention(rc_model *m, int form) {
-    return guard([&] {
-        RC_REQUIRE(m && form >= 2 && form <= 6, RC_ERR_INVALID,
-                   "attention form must be 2 (v2), 3 (v3), 4 / 5 (v2 staggered), 6 (v2, default-policy K/V DMA)");
-        std::lock_guard<std::mutex> lk(m->mu);
-        m->clear_graphs();
-        m->attn_form = form;
-    });
-}
-
 // diagnostic builds: the A/B kernel of the full-batch projections (diag_variant); not in the
 // product ABI — the product picks one kernel per shape
 extern "C" int rc_diag_set_gemm_variant(rc_model *m, int variant) {
     return guard([&] {
         RC_REQUIRE(m, RC_ERR_INVALID, "null model");
         RC_REQUIRE(variant == GEMM_AUTO || variant == GEMM_PINGPONG || variant == GEMM_W2 || variant == GEMM_PP_IMG ||
-                       (variant >= 11 && variant <= 26) || (variant >= 100 && variant < 200),
-                   RC_ERR_INVALID, "GEMM variant: 0 auto, 4 ping-pong, 8 two-workgroup, 10 image-aligned, 11-14 producer "
-                                   "mixes, 15-17 LN consumers on the two-workgroup kernel, 100 + ABL");
+                       variant == 11 || variant == 12 || variant == 14 || (variant >= 100 && variant < 100 + 32),
+                   RC_ERR_INVALID, "GEMM variant: 0 auto, 4 ping-pong, 8 two-workgroup, 10 image-aligned, 11 / 12 / 14 "
+                                   "producer mixes, 100 + ABL (ABL < 32)");
         std::lock_guard<std::mutex> lk(m->mu);
         m->clear_graphs();
         m->gemm_variant = variant;

@@ -443,23 +443,16 @@ __device__ __forceinline__ void att_pv_store(const uint8_t *Vs, const f32x4 (&st
 // qsplit > 1 (small batches: a lone image is 12 (image, head) items for 256 CUs): block b is
 // part b % qsplit of item b / qsplit and takes query tiles qs·4 + wave, stepping 4·qsplit — each
 // part stages the head's K and V (L2 hits after the first) and runs the same per-tile arithmetic.
-// STAG > 0 (diagnostic builds): the first round's second and third blocks of each CU (blockIdx
-// 256..767 under the dispatcher's round-robin placement) start STAG and 2·STAG s_memrealtime
-// ticks (10 ns) late, so that co-resident blocks are out of phase (one's K/V DMA under the others'
-// math) for the rest of the launch.
-// AUX: the cache-policy bits of the K/V LDS-DMA — 2 = nontemporal: every K/V row is read by exactly
-// one block (round 6 in-model A/B, bit-identical: 72.8 -> 71.5 us per launch, step 9.19 -> 9.14 ms
-// at parts = 2, profiles/r06/r06u_attention_nt_dma_ab_p{1,2}.log); 0 = the default policy (rounds
-// 1-5, diagnostic builds)
-template <int TOK, int STAG = 0, int AUX = 2>
+// (Round 6 started the first round's second and third blocks of each CU 3 / 6 and 6 / 12 us late, so
+// that co-resident blocks run out of phase, one's K/V DMA under the others' math: 74.4 and 76.3 us
+// per launch against 74.6, profiles/r06/r06n_attention_stagger_ab_p{1,2}.log.)
+// The cache-policy bits of the K/V LDS-DMA: 2 = nontemporal — every K/V row is read by exactly
+// one block (round 6 in-model A/B against the default policy 0 of rounds 1-5, bit-identical: 72.8 ->
+// 71.5 us per launch, step 9.19 -> 9.14 ms at parts = 2, profiles/r06/r06u_attention_nt_dma_ab_p{1,2}.log)
+constexpr int ATT2_KV_DMA_AUX = 2;
+template <int TOK>
 __global__ __launch_bounds__(256, 3) void attention_v2_kernel(const uint16_t *__restrict__ qkv, uint16_t *__restrict__ out,
                                                           int tokens_rt, int heads, float scale_log2e, int qsplit) {
-    if constexpr (STAG > 0) {
-        if (blockIdx.x >= 256 && blockIdx.x < 768) {
-            const uint64_t t0 = __builtin_amdgcn_s_memrealtime(), d = (uint64_t)STAG * (blockIdx.x >> 8);
-            while (__builtin_amdgcn_s_memrealtime() - t0 < d) __builtin_amdgcn_s_sleep(8);
-        }
-    }
     constexpr int W = 4, HALF = W / 2, HD = 64, PPW = ATT2_TILES * 2 / HALF;  // 13 DMA pieces per wave
     const int tokens = TOK > 0 ? TOK : tokens_rt;
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * ATT2_ROWS * 128];
@@ -502,7 +495,7 @@ __global__ __launch_bounds__(256, 3) void attention_v2_kernel(const uint16_t *__
         const int c = isv ? (pc ^ (((r >> 1) & 3) << 1)) : (pc ^ ((r >> 1) & 7));
         const int rr = r < tokens ? r : tokens - 1;
         const uint16_t *src = base + (int64_t)rr * H3 + (isv ? 2 * H : H) + c * 8;
-        __builtin_amdgcn_global_load_lds((const void *)src, (lds_void_t *)(lds + piece * 1024), 16, 0, AUX);
+        __builtin_amdgcn_global_load_lds((const void *)src, (lds_void_t *)(lds + piece * 1024), 16, 0, ATT2_KV_DMA_AUX);
     }
     auto bar = [] {
         asm volatile("" ::: "memory");
@@ -540,106 +533,11 @@ __global__ __launch_bounds__(256, 3) void attention_v2_kernel(const uint16_t *__
     }
 }
 
-// Self-attention v3: the per-(image, head) arithmetic of attention_v2_kernel (att_scores /
-// att_pv_store: the same bits), re-scheduled so that HBM never idles.  In v2 every block loads
-// its K and V, then computes, then stores — and with all blocks of a round doing the same
-// thing at the same time, the chip alternates between an HBM-bound load phase and a latency-
-// bound math phase (0.5 of HBM, mfma_busy 0.18).  Here the grid is persistent: two blocks per
-// CU, each walking items (image, head) = blockIdx.x, + gridDim.x, ...; while it computes item i
-// from LDS, the block's lanes already hold item i+1's Q, K and V in registers (20 16-B loads per
-// lane, issued before the math: register staging, issue early / write late), which are written
-// into LDS between two barriers once every wave is done with item i.  Q joins K and V in LDS
-// (3 x 208 rows x 128 B = 78 KB per block, XOR-swizzled as in v2: conflict-free ds_read_b128
-// fragments and ds_write_b128 rows).
-constexpr int ATT3_CHUNKS = 3 * ATT2_ROWS * 8;             // 16-B chunks of Q, K, V (208 rows each)
-constexpr int ATT3_PER_LANE = (ATT3_CHUNKS + 255) / 256;   // 20 (the last one on lanes 0-127 only)
-typedef unsigned int att_u32x4 __attribute__((ext_vector_type(4)));  // (a HIP uint4 array stayed in scratch)
-
-// (Diagnostic builds only, rc_diag_set_attention: measured 92.4 vs 75.3 us per launch for v2 —
-// two blocks of 4 waves per CU leave the latency-bound math too few waves, and each item's
-// barrier waits for the wave with the 13th query tile; profiles/r05/.)
-template <int TOK>
-__global__ __launch_bounds__(256, 2) void attention_v3_kernel(const uint16_t *__restrict__ qkv, uint16_t *__restrict__ out,
-                                                          int tokens_rt, int heads, int items, float scale_log2e) {
-    constexpr int W = 4, HD = 64, TB = ATT2_ROWS * 128;  // waves, head dim, bytes per staged tensor
-    const int tokens = TOK > 0 ? TOK : tokens_rt;
-    __shared__ __attribute__((aligned(16))) uint8_t lds[3 * TB];  // Q | K | V
-    const uint8_t *Qs = lds, *Ks = lds + TB, *Vs = lds + 2 * TB;
-    const int H = heads * HD, H3 = 3 * H;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 4, li = lane & 15;
-    const int nqt = (tokens + 15) / 16;
-
-    // chunk c = tid + 256 i: tensor c / (208·8) (0 Q, 1 K, 2 V; the tensors sit at column
-    // offsets 0, H, 2H of a qkv row), row (c / 8) % 208, 16-B column chunk c % 8 — eight lanes
-    // read one 128-B row segment; rows >= tokens re-read the last token (finite, masked later)
-    // (tensor ts, row r) of chunk i: 208·8 = 6.5·256, so ts and r follow from compares; the
-    // column chunk is tid & 7 for every i
-    const int ch = tid & 7;
-    // (lanes past the last chunk, i = 19, tid >= 128, re-load the last chunk: every pf[i] is loaded
-    // on every lane — no conditional load, which made hipcc keep pf in scratch — and only stored
-    // where it is real)
-    auto chunk_rows = [&](int i, int &ts, int &r) __attribute__((always_inline)) {
-        const int c = min(tid + 256 * i, ATT3_CHUNKS - 8 + ch);
-        ts = (c >= ATT2_ROWS * 8) + (c >= 2 * ATT2_ROWS * 8);
-        r = (c - ts * (ATT2_ROWS * 8)) >> 3;
-    };
-    att_u32x4 pf[ATT3_PER_LANE];
-    auto load_item = [&](int item) __attribute__((always_inline)) {
-        const int img = item / heads, h = item - img * heads;
-        const uint16_t *base = qkv + (int64_t)img * tokens * H3 + h * HD + ch * 8;
-#pragma unroll
-        for (int i = 0; i < ATT3_PER_LANE; ++i) {
-            int ts, r;
-            chunk_rows(i, ts, r);
-            const int rr = r < tokens ? r : tokens - 1;
-            pf[i] = *reinterpret_cast<const att_u32x4 *>(base + (int64_t)rr * H3 + ts * H);
-        }
-    };
-    // source chunk ch of row r goes to 16-B slot ch ^ s(r): s = (r >> 1) & 7 for Q and K (the
-    // att_scores fragment reads), ((r >> 1) & 3) << 1 for V (the transposed P·V reads)
-    auto store_item = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < ATT3_PER_LANE; ++i) {
-            int ts, r;
-            chunk_rows(i, ts, r);
-            const int slot = ts == 2 ? (ch ^ (((r >> 1) & 3) << 1)) : (ch ^ ((r >> 1) & 7));
-            if (i < ATT3_PER_LANE - 1 || tid < ATT3_CHUNKS - 256 * (ATT3_PER_LANE - 1))
-                *reinterpret_cast<att_u32x4 *>(lds + ts * TB + r * 128 + slot * 16) = pf[i];
-        }
-    };
-
-    int item = blockIdx.x;
-    if (item >= items) return;  // (the host launches at most `items` blocks)
-    load_item(item);
-    store_item();
-    __syncthreads();
-    for (; item < items; item += gridDim.x) {
-        const int nxt = item + gridDim.x;  // block-uniform
-        if (nxt < items) load_item(nxt);   // lands under this item's math
-        const int img = item / heads, h = item - img * heads;
-        uint16_t *obase = out + (int64_t)img * tokens * H + h * HD;
-        for (int qt = wave; qt < nqt; qt += W) {
-            bf16x8 qf[2];
-            const int q = qt * 16 + li;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int c = s * 4 + g;
-                qf[s] = *reinterpret_cast<const bf16x8 *>(Qs + q * 128 + ((c ^ ((q >> 1) & 7)) << 4));
-            }
-            f32x4 st[ATT2_TILES];
-            float sum = 0.f;
-            att_scores<TOK>(Ks, qf, tokens, scale_log2e, st, sum);
-            att_pv_store(Vs, st, sum, qt, tokens, obase, H);
-        }
-        __syncthreads();  // every wave is done reading this item from LDS
-        if (nxt < items) {
-            store_item();
-            __syncthreads();
-        }
-    }
-}
+// (Rounds 5-6 also carried a persistent form of this kernel, two blocks per CU walking the (image,
+// head) items with the next item's Q, K and V register-staged under the current item's math, so
+// that HBM never idles: measured 92.4 vs 75.3 us per launch for v2 — two blocks of 4 waves per CU
+// leave the latency-bound math too few waves, and each item's barrier waits for the wave with the
+// 13th query tile; profiles/r05/.  Removed.)
 
 // ------------------------------------------------- last layer, CLS rows only
 // /embed returns last_hidden_state[:, 0, :] (embedding/main.py:113-114), and in

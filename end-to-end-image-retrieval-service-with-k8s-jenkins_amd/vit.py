@@ -371,7 +371,10 @@ class VitMsnEmbedder:
 
     def set_gemm_variant(self, variant: int) -> None:
         """Diagnostic builds only (tools/build_diag.sh, RC_LIB_PATH): the A/B kernel of the
-        full-batch projections (0 auto, 4 ping-pong, 8 two-workgroup, 10 image-aligned, 100 + ABL).
+        full-batch projections: 0 auto; 4 ping-pong, 8 two-workgroup, 10 image-aligned for the
+        residual producers (O-proj, fc2); 11 / 12 / 14 producer mixes; 100 + ABL, the timing-only
+        ablation masks of the ping-pong kernel (bits 0-4: no DMA, no MFMA, no epilogue, no C stores,
+        no GELU) where auto picks it.
         The product library picks one kernel per shape and has no such knob."""
         fn = getattr(self.lib, "rc_diag_set_gemm_variant", None)
         if fn is None:

@@ -1,5 +1,7 @@
 #!/bin/bash
-# Diagnostic build (GEMM ablation variants, A/B knobs) into lib/diag/, loaded with RC_LIB_PATH.
+# Diagnostic build into lib/diag/, loaded with RC_LIB_PATH: the GEMM kernels' timing-only ablation
+# masks (variant 100 + ABL / 200 + ABL) and phase stamps, the residual producers' kernel-choice
+# variants, and the JPEG decoder's and int8 filter's knobs (the rc_diag_* entry points).
 # ONLY="vit index" rebuilds just those sources' objects before relinking.
 set -eu
 cd "$(dirname "$0")/.."
