@@ -101,6 +101,7 @@ SIGNATURES = {
     "rc_index_export": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "rc_index_import": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "rc_index_search_ex": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp]),
+    "rc_index_search_masked": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
     "rc_index_gemm_timing_read": (C.c_int, [_vp, _pd, _pi64, _pd, _pi64]),
     "rc_index_fill_random": (C.c_int, [_vp, C.c_uint64, _i64, _i64, _vp]),
     "rc_topk_merge": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -119,6 +120,8 @@ SIGNATURES = {
     "rc_sharded_fetch": (C.c_int, [_vp, _vp, _i64, _vp, _i32]),
     "rc_sharded_search": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp]),
     "rc_sharded_query_host": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "rc_sharded_search_masked": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "rc_sharded_query_host_masked": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rc_index_timing": (C.c_int, [_vp, _i32]),
     "rc_index_timing_read": (C.c_int, [_vp, _pd, _pi64, _pd]),
     "rc_model_create": (C.c_int, [_i32, C.POINTER(VitConfig), C.POINTER(_vp)]),

@@ -480,11 +480,12 @@ void dispatch_dtype(int dtype, F &&f) {
 }
 
 
-void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
-                 hipStream_t s) {
+// mask (optional): the row-eligibility bitmap of rc_index_search_masked; the masked scan kernels.
+void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask, float *scores,
+                 int64_t *out_rows, hipStream_t s) {
     // queries per scan pass: a power of two the kernel is instantiated for (1, 2, 4)
     int qb = 1;
-    while (qb * 2 <= std::min(nq, scan_max_qb(h->nch, k))) qb *= 2;
+    while (qb * 2 <= std::min(nq, scan_max_qb(h->nch, k, mask != nullptr))) qb *= 2;
     const int nq_pad = (nq + qb - 1) / qb * qb;  // every scan pass runs qb real-or-zero query slots
     ensure_workspace(h, nq_pad, k);  // (the scan normalises the queries itself: no separate launch)
     int nblk = (int)std::min<int64_t>(kMaxBlocks, std::max<int64_t>(1, (n_rows + 511) / 512));
@@ -505,6 +506,7 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
         a.qraw = queries;
         a.dim = h->dim;
         a.nq_real = nq;
+        a.mask = mask;
         launch_scan(h, a);
         h->timer.end(slot, s, bytes);
     }
@@ -516,13 +518,16 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
 // in fallback mode (blocks early-exit for unflagged queries) over the batched
 // path's normalised queries (the same f32 arithmetic as normalize_queries_kernel),
 // and merge_partials_kernel over the flagged queries' partial lists.
-void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, float *scores,
-                          int64_t *out_rows, hipStream_t s) {
+// With a mask the rescoring drops ineligible candidates (search_mfma.hip) and the
+// fallback is the masked scan; the merge is the same.
+void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                          float *scores, int64_t *out_rows, hipStream_t s) {
     h->bws.ensure(nq, k, h->ld, (int)dtype_size(h->dtype));
     BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, n_rows, h->row_base, h->row_stride, queries, nq, k, scores, out_rows};
     p.rows8 = h->rows8;
     p.rsx = h->rsx;
     p.rex = h->rex;
+    p.mask = mask;
     if (h->gtimer.enabled) h->gtimer.create();
     batched_search(p, h->bws, s, h->gtimer.enabled ? &h->gtimer : nullptr);
     int nblk = (int)std::min<int64_t>(h->bws.fb_blocks, std::max<int64_t>(1, (n_rows + 511) / 512));
@@ -532,6 +537,7 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
     ScanArgs a{h->rows, h->ld, h->nch, n_rows, rpb, nblk, h->bws.qn, 0, 1, nq, k, h->bws.fb_partial, s};
     a.flags = h->bws.flags;
     a.grid_y = std::min(nq, FB_QSTRIDE);
+    a.mask = mask;
     launch_scan(h, a);
     launch_merge_partials(h, h->bws.fb_partial, h->bws.flags, nblk, nq, nq, k, scores, out_rows, s);
 }
@@ -899,6 +905,11 @@ int rc_index_search(rc_index *h, const float *queries, int nq, int64_t n_rows, i
 
 int rc_index_search_ex(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, float *scores,
                        int64_t *out_rows, int mode, void *stream) {
+    return rc_index_search_masked(h, queries, nq, n_rows, k, nullptr, scores, out_rows, mode, stream);
+}
+
+int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                           float *scores, int64_t *out_rows, int mode, void *stream) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
         RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
@@ -918,13 +929,15 @@ int rc_index_search_ex(rc_index *h, const float *queries, int nq, int64_t n_rows
         const bool mfma_ok = h->dtype != RC_F32 || h->rows8 != nullptr;
         RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
                    "batched MFMA search needs an f16/bf16 index or the int8 filter copy");
-        const bool use_mfma = mode == RC_SEARCH_MFMA ||
-                              (mode == RC_SEARCH_AUTO && mfma_ok && nq >= kBatchMinQueries && n_rows >= kBatchMinRows);
+        // with a mask AUTO scans: only the caller knows the eligible share, and a selective mask
+        // makes the scan cheaper while the filter GEMM still reads every row (MFMA on request)
+        const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && mask == nullptr && mfma_ok &&
+                                                         nq >= kBatchMinQueries && n_rows >= kBatchMinRows);
         if (!use_mfma) {
-            scan_search(h, queries, nq, n_rows, k, scores, out_rows, s);
+            scan_search(h, queries, nq, n_rows, k, mask, scores, out_rows, s);
             return;
         }
-        batched_search_exact(h, queries, nq, n_rows, k, scores, out_rows, s);
+        batched_search_exact(h, queries, nq, n_rows, k, mask, scores, out_rows, s);
     });
 }
 

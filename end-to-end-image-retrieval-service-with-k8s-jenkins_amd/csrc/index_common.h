@@ -87,11 +87,17 @@ struct ScanArgs {
     // qn is not read.  nullptr: qn holds the normalised queries.
     const float *qraw = nullptr;
     int dim = 0, nq_real = 0;
+    // Row-masked scan (rc_index_search_masked): device bitmap over the local rows, bit r & 31 of
+    // word r >> 5 = row r is eligible, ceil(n_rows / 32) words (bits at or past n_rows are not
+    // trusted).  nullptr: every row is eligible (the unmasked kernels; no runtime test of it on
+    // the device, the host picks the instantiation).
+    const uint32_t *mask = nullptr;
 };
 
 // largest queries-per-pass for a row width: query registers per lane = QB*nch*8 floats <= 64
-inline int scan_max_qb(int nch, int k) {
-    if (k > 128) return 1;
+// (the masked scan is instantiated for multi-query passes at the smallest list size only)
+inline int scan_max_qb(int nch, int k, bool masked = false) {
+    if (k > (masked ? 64 : 128)) return 1;
     return nch <= 2 ? 4 : (nch <= 4 ? 2 : 1);
 }
 
@@ -218,6 +224,8 @@ struct BatchPlan {
     const int8_t *rows8 = nullptr;  // [cap_pad][ld] x8, x̃ = sx · x8
     const float *rsx = nullptr;     // [cap_pad] sx, at i8_slot(row)
     const float *rex = nullptr;     // [cap_pad] ||x̂ - x̃||₂ (rounded up), at i8_slot(row)
+    // row-eligibility bitmap over the local rows (ScanArgs::mask), or null: applied in rescore_kernel
+    const uint32_t *mask = nullptr;
 };
 
 // The int8 filter keeps a row's scale and residual norm at a tile-transposed slot:
@@ -251,10 +259,18 @@ struct ScanShape {
 
 // One block's pass over its row range for the QB queries held in registers q (lane sub's
 // chunks sub + 16 i): partial top-k keys of queries q0 .. q0 + QB.
-template <typename T, int NCH, int QB, int CAP>
+// MASKED: only rows whose bit is set in `mask` (see ScanArgs) enter the top-k.  A wave's
+// iteration covers the 8 rows g .. g + 7 with g = r0 + 8 wave + 32 it and r0 a multiple of 32
+// (rows_per_block is), so their bits are byte (g & 31) / 8 of word g >> 5: one wave-uniform word
+// per iteration, loaded one iteration ahead of its use.  A zero byte skips the iteration's row
+// loads altogether (wave-uniform branch: every reserve / push stays wave-collective) — the HBM
+// bytes a selective filter saves.  The per-row arithmetic is untouched, so an eligible row's
+// score has the bits the unmasked scan gives it.
+template <typename T, int NCH, int QB, int CAP, bool MASKED = false>
 __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t ld, int64_t n_rows, int64_t rows_per_block,
                                             const float (&q)[QB][ScanShape<T, NCH>::CPL][ScanShape<T, NCH>::EPC], int q0,
-                                            int nq_total, int k, uint64_t *__restrict__ partial) {
+                                            int nq_total, int k, uint64_t *__restrict__ partial,
+                                            const uint32_t *__restrict__ mask = nullptr) {
     constexpr int EPC = ScanShape<T, NCH>::EPC;
     constexpr int CPL = ScanShape<T, NCH>::CPL;
     __shared__ uint64_t lds[4][QB][CAP];
@@ -269,7 +285,20 @@ __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t 
     const uint4 *base4 = reinterpret_cast<const uint4 *>(rows);
     const int64_t ld4 = ld / EPC;  // row stride in 16-B chunks
 
+    static_assert(!MASKED || 16 * SCAN_U == 32, "the masked scan reads one mask word per 32-row block step");
+    [[maybe_unused]] uint32_t mword = 0;  // MASKED: the mask word of this wave's next iteration
+    if constexpr (MASKED) {
+        const int64_t g0 = r0 + wave * 4 * SCAN_U;
+        if (g0 < r1) mword = mask[g0 >> 5];  // g0 < r1 <= n_rows: inside the bitmap's ceil(n_rows / 32) words
+    }
     for (int64_t g = r0 + wave * 4 * SCAN_U; g < r1; g += 16 * SCAN_U) {
+        [[maybe_unused]] uint32_t mbyte = 0xffu;  // MASKED: bit j = row g + j is eligible
+        if constexpr (MASKED) {
+            mbyte = ((uint32_t)__builtin_amdgcn_readfirstlane((int)mword) >> (uint32_t)(g & 31)) & 0xffu;
+            const int64_t gn = g + 16 * SCAN_U;
+            if (gn < r1) mword = mask[gn >> 5];
+            if (mbyte == 0u) continue;  // wave-uniform: none of the 8 rows is eligible, no row is loaded
+        }
         uint4 x[SCAN_U][CPL];
 #pragma unroll
         for (int u = 0; u < SCAN_U; ++u) {
@@ -301,7 +330,10 @@ __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t 
                 constexpr int b = bc.value;
                 const float s = sum16(acc[b]);
                 tk[b].reserve(4);
-                tk[b].push(sub == 0 && r < r1, make_key(s, (uint32_t)r));
+                if constexpr (MASKED)
+                    tk[b].push(sub == 0 && r < r1 && ((mbyte >> (u * 4 + rg)) & 1u) != 0u, make_key(s, (uint32_t)r));
+                else
+                    tk[b].push(sub == 0 && r < r1, make_key(s, (uint32_t)r));
             });
         }
     }
@@ -328,11 +360,11 @@ __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t 
     }
 }
 
-template <typename T, int NCH, int QB, int CAP>
+template <typename T, int NCH, int QB, int CAP, bool MASKED = false>
 __device__ __forceinline__ void scan_rows(const T *__restrict__ rows, int64_t ld, int64_t n_rows, int64_t rows_per_block,
                                           const float *__restrict__ qn, int q0, int nq_total, int k,
                                           uint64_t *__restrict__ partial, const float *__restrict__ qraw = nullptr,
-                                          int dim = 0, int nq_real = 0) {
+                                          int dim = 0, int nq_real = 0, const uint32_t *__restrict__ mask = nullptr) {
     constexpr int EPC = ScanShape<T, NCH>::EPC;
     constexpr int CPL = ScanShape<T, NCH>::CPL;
     const int lane = threadIdx.x & 63, sub = lane & 15;
@@ -362,7 +394,7 @@ __device__ __forceinline__ void scan_rows(const T *__restrict__ rows, int64_t ld
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) q[b][i][e] = qn[(int64_t)(q0 + b) * ld + (sub + 16 * i) * EPC + e];
     }
-    scan_rows_q<T, NCH, QB, CAP>(rows, ld, n_rows, rows_per_block, q, q0, nq_total, k, partial);
+    scan_rows_q<T, NCH, QB, CAP, MASKED>(rows, ld, n_rows, rows_per_block, q, q0, nq_total, k, partial, mask);
 }
 
 // f32 rows of 512 (config 3): 131 VGPRs by default = 3 waves per SIMD; capped at 128 (no spill)
@@ -387,6 +419,25 @@ __global__ __launch_bounds__(256, (scan_min_waves<T, NCH, QB, CAP>())) void scan
     scan_rows<T, NCH, QB, CAP>(rows, ld, n_rows, rows_per_block, qn, q0, nq_total, k, partial, qraw, dim, nq_real);
 }
 
+// The row-masked form of scan_topk_kernel (both of its modes).  A kernel of its own, not a
+// runtime test of a null mask: the unmasked instantiations keep their code and registers (the
+// f32 / 512-wide one sits at the 128-VGPR cap above).
+template <typename T, int NCH, int QB, int CAP>
+__global__ __launch_bounds__(256, (scan_min_waves<T, NCH, QB, CAP>())) void scan_topk_masked_kernel(
+    const T *__restrict__ rows, int64_t ld, int64_t n_rows, int64_t rows_per_block, const float *__restrict__ qn, int q0,
+    int nq_total, int k, uint64_t *__restrict__ partial, const int *__restrict__ flags, const float *__restrict__ qraw, int dim,
+    int nq_real, const uint32_t *__restrict__ mask) {
+    if (flags != nullptr) {  // exact fallback of the masked batched search
+        for (int qf = blockIdx.y; qf < nq_total; qf += gridDim.y)
+            if (flags[qf]) {
+                scan_rows<T, NCH, QB, CAP, true>(rows, ld, n_rows, rows_per_block, qn, qf, nq_total, k, partial, nullptr, 0, 0, mask);
+                __syncthreads();
+            }
+        return;
+    }
+    scan_rows<T, NCH, QB, CAP, true>(rows, ld, n_rows, rows_per_block, qn, q0, nq_total, k, partial, qraw, dim, nq_real, mask);
+}
+
 template <typename T, int NCH, int QB, int CAP>
 void launch_scan_t(const ScanArgs &a) {
     hipLaunchKernelGGL((scan_topk_kernel<T, NCH, QB, CAP>), dim3(a.nblk, a.grid_y), dim3(256), 0, a.stream, (const T *)a.rows,
@@ -395,9 +446,25 @@ void launch_scan_t(const ScanArgs &a) {
     RC_LAUNCH_CHECK();
 }
 
+template <typename T, int NCH, int QB, int CAP>
+void launch_scan_masked_t(const ScanArgs &a) {
+    hipLaunchKernelGGL((scan_topk_masked_kernel<T, NCH, QB, CAP>), dim3(a.nblk, a.grid_y), dim3(256), 0, a.stream,
+                       (const T *)a.rows, a.ld, a.n_rows, a.rows_per_block, a.qn, a.q0, a.nq_total, a.k, a.partial, a.flags,
+                       a.qraw, a.dim, a.nq_real, a.mask);
+    RC_LAUNCH_CHECK();
+}
+
 template <typename T, int NCH, int QB>
 void launch_scan_cap(const ScanArgs &a) {
     const int cap = topk_cap(a.k);
+    if (a.mask != nullptr) {  // host-side choice of the masked instantiations (scan_max_qb(.., masked))
+        if (cap <= 128) return launch_scan_masked_t<T, NCH, QB, 128>(a);
+        if constexpr (QB == 1) {
+            if (cap <= 256) return launch_scan_masked_t<T, NCH, QB, 256>(a);
+            return launch_scan_masked_t<T, NCH, QB, 512>(a);
+        }
+        throw Error(RC_ERR_UNSUPPORTED, "masked multi-query pass needs k <= 64");
+    }
     if (cap <= 128) return launch_scan_t<T, NCH, QB, 128>(a);
     if (cap <= 256) return launch_scan_t<T, NCH, QB, 256>(a);
     if constexpr (QB == 1) return launch_scan_t<T, NCH, QB, 512>(a);

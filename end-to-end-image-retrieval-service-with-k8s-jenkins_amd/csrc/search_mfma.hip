@@ -808,14 +808,27 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
 // reduction), merged with the running top-k keys, and the threshold for the
 // next stage is set.  Overflow (more candidates than cap) is flagged for the
 // host's exact fallback; the counter is reset for the next stage.
-template <typename T, int NCH, int CAP>
+//
+// MASKED (rc_index_search_masked; `mask` as in ScanArgs): a candidate whose bit is clear is
+// scored but not pushed; the filter kernels are untouched.  Why that is exact: the running
+// list then holds eligible rows only, so thr[q] is -inf or (kth best exact score among the
+// ELIGIBLE rows seen so far) - eps[q], a lower bound of the final masked kth best minus eps;
+// by the header's argument every eligible row of the masked top-k has s' >= thr[q] at its
+// stage, passes the filter, and is rescored here.  Ineligible rows only take candidate slots:
+// thr rises more slowly than in an unmasked search (it stays -inf until k eligible rows were
+// seen), so a selective mask overflows sooner.  An overflowed query is flagged exactly as
+// before — n counts every appended candidate, eligible or not, so a list that lost entries
+// is never trusted — and the fallback is the MASKED scan (index.hip), whose lists the
+// unchanged merge writes over this kernel's output.  Candidate rows are < r_end <= n_rows
+// (every filter epilogue tests that), so mask[row >> 5] stays inside the bitmap.
+template <typename T, int NCH, int CAP, bool MASKED>
 __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows, int64_t ld, const float *__restrict__ qn,
                                                      int k, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ cand,
                                                      int cap, uint64_t *__restrict__ keys, const float *__restrict__ eps,
                                                      float *__restrict__ thr, int *__restrict__ flags,
                                                      int *__restrict__ ovf_total, int final_pass, int64_t row_base,
                                                      int64_t row_stride, float *__restrict__ out_scores,
-                                                     int64_t *__restrict__ out_rows) {
+                                                     int64_t *__restrict__ out_rows, const uint32_t *__restrict__ mask) {
     constexpr int EPC = 16 / sizeof(T);
     constexpr int CPL = NCH * 128 / (16 * EPC);
     constexpr int U = 2;
@@ -848,10 +861,12 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
     for (int j0 = wave * 4 * U; j0 < nn; j0 += 16 * U) {
         uint4 x[U][CPL];
         uint32_t rr[U];
+        [[maybe_unused]] uint32_t mw[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = j0 + u * 4 + rg;
             rr[u] = cl[j < nn ? j : 0];
+            if constexpr (MASKED) mw[u] = mask[rr[u] >> 5];
 #pragma unroll
             for (int i = 0; i < CPL; ++i) x[u][i] = base4[(int64_t)rr[u] * ld4 + sub + 16 * i];
         }
@@ -868,7 +883,8 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
             }
             const float s = sum16(acc);
             tk.reserve(4);
-            tk.push(sub == 0 && j < nn, make_key(s, rr[u]));
+            if constexpr (MASKED) tk.push(sub == 0 && j < nn && ((mw[u] >> (rr[u] & 31u)) & 1u) != 0u, make_key(s, rr[u]));
+            else tk.push(sub == 0 && j < nn, make_key(s, rr[u]));
         }
     }
     tk.compact();
@@ -905,14 +921,20 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
 template <typename T, int NCH>
 void launch_rescore_cap(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
     const int cap = topk_cap(p.k);
-#define RC_RESCORE(CAPV)                                                                                         \
-    hipLaunchKernelGGL((rescore_kernel<T, NCH, CAPV>), dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn, \
-                       p.k, ws.cnt, ws.cand, ws.cap, ws.keys, ws.eps, ws.thr, ws.flags, ws.ovf, final_pass, p.row_base,  \
-                       p.row_stride, p.out_scores, p.out_rows)
+#define RC_RESCORE_M(CAPV, MASKEDV)                                                                                       \
+    hipLaunchKernelGGL((rescore_kernel<T, NCH, CAPV, MASKEDV>), dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn, \
+                       p.k, ws.cnt, ws.cand, ws.cap, ws.keys, ws.eps, ws.thr, ws.flags, ws.ovf, final_pass, p.row_base,    \
+                       p.row_stride, p.out_scores, p.out_rows, p.mask)
+#define RC_RESCORE(CAPV)                       \
+    do {                                       \
+        if (p.mask != nullptr) RC_RESCORE_M(CAPV, true); \
+        else RC_RESCORE_M(CAPV, false);        \
+    } while (0)
     if (cap <= 128) RC_RESCORE(128);
     else if (cap <= 256) RC_RESCORE(256);
     else RC_RESCORE(512);
 #undef RC_RESCORE
+#undef RC_RESCORE_M
     RC_LAUNCH_CHECK();
 }
 

@@ -98,6 +98,12 @@ struct rc_sharded {
     std::vector<int64_t *> row_h;
     std::vector<float *> fo_h;     // [st_cap][dim] pinned host landing of fetched rows
     hipEvent_t ev_gather = nullptr;  // leader stream: the remote subsets are gathered
+    // masked search (rc_sharded_search_masked): the caller's global bitmap de-interleaved into one
+    // local bitmap per shard (pinned), and its copy on the shard's device; grown on demand
+    int64_t mk_cap = 0;                // words per shard
+    std::vector<uint32_t *> mk_h;      // [mk_cap] pinned
+    std::vector<uint32_t *> mk_d;      // [mk_cap] on the shard's device
+    std::vector<hipEvent_t> ev_mask;   // per shard: its bitmap's H2D copy is done (the pinned words are free again)
     // host-in / host-out query (rc_sharded_query_host): its own leader stream, one pinned
     // staging block and one device block, each laid out [queries | scores | rows | values]
     hipStream_t qs = nullptr;
@@ -196,6 +202,78 @@ void ensure_staging(rc_sharded *h, int64_t m) {
 // rows of the global range [0, n_rows) that shard s holds
 int64_t shard_rows(const rc_sharded *h, int s, int64_t n_rows) { return n_rows > s ? (n_rows - s + h->n - 1) / h->n : 0; }
 
+void free_mask(rc_sharded *h) {
+    for (int s = 0; s < h->n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        if (h->mk_d[s] != nullptr) (void)hipDeviceSynchronize();  // no search may still read the bitmap
+        dfree(h->mk_d[s]);
+        hfree(h->mk_h[s]);
+        h->mk_d[s] = nullptr;
+        h->mk_h[s] = nullptr;
+    }
+    h->mk_cap = 0;
+}
+
+// Split the caller's bitmap over global rows [0, n_rows) into the shards' local bitmaps (global
+// row g = local row g / n of shard g % n; with one shard a straight copy) and enqueue each
+// shard's H2D copy on the shard's own stream, ahead of its wait for the leader (the bitmap
+// does not depend on the queries).  A single shard searches on the caller's stream `ls`, which
+// is made to wait for the copy.  Bits at or past n_rows are dropped here; the kernels do not
+// rely on that.
+// Returns with the copies in flight: wait_mask() before the pinned words are reused.
+void stage_mask(rc_sharded *h, const uint32_t *mask, int64_t n_rows, hipStream_t ls) {
+    const int n = h->n;
+    const int64_t words = (n_rows + 31) / 32;
+    const int64_t lw_max = std::max<int64_t>(1, (shard_rows(h, 0, n_rows) + 31) / 32);
+    if (lw_max > h->mk_cap) {
+        const int64_t w2 = std::max<int64_t>(lw_max, 2 * h->mk_cap);
+        free_mask(h);
+        for (int s = 0; s < n; ++s) {
+            DeviceScope ds(h->dev[s]);
+            h->mk_d[s] = (uint32_t *)dmalloc((size_t)w2 * sizeof(uint32_t));
+            h->mk_h[s] = (uint32_t *)hmalloc((size_t)w2 * sizeof(uint32_t));
+        }
+        h->mk_cap = w2;
+    }
+    if (n == 1) {
+        std::memcpy(h->mk_h[0], mask, (size_t)words * sizeof(uint32_t));
+    } else {
+        for (int s = 0; s < n; ++s) std::memset(h->mk_h[s], 0, (size_t)lw_max * sizeof(uint32_t));
+        for (int64_t w = 0; w < words; ++w) {
+            uint32_t bits = mask[w];
+            while (bits) {  // the set bits only: a selective filter costs its eligible count
+                const int64_t g = w * 32 + __builtin_ctz(bits);
+                bits &= bits - 1;
+                if (g >= n_rows) break;
+                const int64_t l = g / n;
+                h->mk_h[g - l * n][l >> 5] |= 1u << (l & 31);
+            }
+        }
+    }
+    for (int s = 0; s < n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        const int64_t lw = std::max<int64_t>(1, (shard_rows(h, s, n_rows) + 31) / 32);
+        RC_HIP(hipMemcpyAsync(h->mk_d[s], h->mk_h[s], (size_t)lw * sizeof(uint32_t), hipMemcpyHostToDevice, h->st[s]));
+        RC_HIP(hipEventRecord(h->ev_mask[s], h->st[s]));
+    }
+    if (n == 1) RC_HIP(hipStreamWaitEvent(ls, h->ev_mask[0], 0));  // the single shard searches on the caller's stream
+}
+
+// Single shard: its search ran on the caller's stream; the shard's own stream (which carries the
+// next call's bitmap copy) must not overtake it, whatever stream the next caller brings.
+void fence_mask_single(rc_sharded *h, hipStream_t ls) {
+    DeviceScope ds(h->dev[0]);
+    RC_HIP(hipEventRecord(h->ev_done[0], ls));
+    RC_HIP(hipStreamWaitEvent(h->st[0], h->ev_done[0], 0));
+}
+
+void wait_mask(rc_sharded *h) {
+    for (int s = 0; s < h->n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        RC_HIP(hipEventSynchronize(h->ev_mask[s]));
+    }
+}
+
 void free_query(rc_sharded *h) {
     DeviceScope dl(h->dev[0]);
     hfree(h->qh);
@@ -234,6 +312,7 @@ void ensure_query(rc_sharded *h, int64_t bytes) {
 void destroy(rc_sharded *h) {
     free_search(h);
     free_staging(h);
+    free_mask(h);
     if (h->qs) {
         free_query(h);
         DeviceScope dl(h->dev[0]);
@@ -244,6 +323,7 @@ void destroy(rc_sharded *h) {
         if (h->st[s]) (void)hipStreamDestroy(h->st[s]);
         if (h->ev_done[s]) (void)hipEventDestroy(h->ev_done[s]);
         if (h->ev_start[s]) (void)hipEventDestroy(h->ev_start[s]);
+        if (h->ev_mask[s]) (void)hipEventDestroy(h->ev_mask[s]);
         if (h->shard[s]) (void)rc_index_destroy(h->shard[s]);
     }
     if (h->ev_gather) {
@@ -290,6 +370,9 @@ int rc_sharded_create(int n_shards, const int *devices, int dim, int dtype, int6
         h->idx_h.assign(n_shards, nullptr);
         h->row_h.assign(n_shards, nullptr);
         h->fo_h.assign(n_shards, nullptr);
+        h->mk_h.assign(n_shards, nullptr);
+        h->mk_d.assign(n_shards, nullptr);
+        h->ev_mask.assign(n_shards, nullptr);
         try {
             for (int s = 0; s < n_shards; ++s) {
                 check_status(rc_index_create(h->dev[s], dim, dtype, capacity_per_shard, s, &h->shard[s]));
@@ -297,6 +380,7 @@ int rc_sharded_create(int n_shards, const int *devices, int dim, int dtype, int6
                 DeviceScope ds(h->dev[s]);
                 RC_HIP(hipStreamCreateWithFlags(&h->st[s], hipStreamNonBlocking));
                 RC_HIP(hipEventCreateWithFlags(&h->ev_done[s], hipEventDisableTiming));
+                RC_HIP(hipEventCreateWithFlags(&h->ev_mask[s], hipEventDisableTiming));
                 if (h->dev[s] != h->dev[0]) {  // direct xGMI peer copies where the platform allows them
                     if (hipDeviceEnablePeerAccess(h->dev[0], 0) != hipSuccess) (void)hipGetLastError();
                     DeviceScope dl(h->dev[0]);
@@ -484,11 +568,20 @@ void fetch_locked(rc_sharded *h, const int64_t *rows, int64_t n, float *out, int
 }
 
 // rc_sharded_search's body (caller holds h->mu; device buffers on the leader, stream = leader stream)
+// mask (optional): HOST bitmap over the global rows; staged per shard first, and the call then
+// returns only once the staged words were copied (the next call may overwrite them).
 void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
-                   int mode, void *stream) {
+                   int mode, void *stream, const uint32_t *mask = nullptr) {
         hipStream_t ls = (hipStream_t)stream;
+        const bool masked = mask != nullptr;
+        if (masked) stage_mask(h, mask, n_rows, ls);
         if (h->n == 1) {
-            check_status(rc_index_search_ex(h->shard[0], queries, nq, n_rows, k, scores, out_rows, mode, stream));
+            check_status(rc_index_search_masked(h->shard[0], queries, nq, n_rows, k, masked ? h->mk_d[0] : nullptr, scores,
+                                                out_rows, mode, stream));
+            if (masked) {
+                fence_mask_single(h, ls);
+                wait_mask(h);
+            }
             return;
         }
         ensure_search(h, nq, k);
@@ -508,7 +601,8 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
             }
             float *so = local ? h->g_s + s * slice : h->s_loc[s];
             int64_t *ro = local ? h->g_r + s * slice : h->r_loc[s];
-            check_status(rc_index_search_ex(h->shard[s], q, nq, shard_rows(h, s, n_rows), k, so, ro, mode, h->st[s]));
+            check_status(rc_index_search_masked(h->shard[s], q, nq, shard_rows(h, s, n_rows), k,
+                                                masked ? h->mk_d[s] : nullptr, so, ro, mode, h->st[s]));
             if (!local) {
                 RC_HIP(hipMemcpyPeerAsync(h->g_s + s * slice, h->dev[0], so, h->dev[s], slice * sizeof(float), h->st[s]));
                 RC_HIP(hipMemcpyPeerAsync(h->g_r + s * slice, h->dev[0], ro, h->dev[s], slice * sizeof(int64_t), h->st[s]));
@@ -518,6 +612,7 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
         DeviceScope dl(h->dev[0]);
         for (int s = 0; s < h->n; ++s) RC_HIP(hipStreamWaitEvent(ls, h->ev_done[s], 0));
         check_status(rc_topk_merge(h->g_s, h->g_r, h->n, nq, k, k, scores, out_rows, stream));
+        if (masked) wait_mask(h);
 }
 
 }  // namespace
@@ -537,6 +632,11 @@ int rc_sharded_fetch(rc_sharded *h, const int64_t *rows, int64_t n, float *out, 
 
 int rc_sharded_search(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores,
                       int64_t *out_rows, int mode, void *stream) {
+    return rc_sharded_search_masked(h, queries, nq, n_rows, k, nullptr, scores, out_rows, mode, stream);
+}
+
+int rc_sharded_search_masked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                             float *scores, int64_t *out_rows, int mode, void *stream) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
         RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
@@ -545,12 +645,17 @@ int rc_sharded_search(rc_sharded *h, const float *queries, int nq, int64_t n_row
         if (nq == 0) return;
         RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
         std::lock_guard<std::mutex> lk(h->mu);
-        search_locked(h, queries, nq, n_rows, k, scores, out_rows, mode, stream);
+        search_locked(h, queries, nq, n_rows, k, scores, out_rows, mode, stream, mask);
     });
 }
 
 int rc_sharded_query_host(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, int with_values,
                           float *scores, int64_t *out_rows, float *values) {
+    return rc_sharded_query_host_masked(h, queries, nq, n_rows, k, with_values, nullptr, scores, out_rows, values);
+}
+
+int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, int with_values,
+                                 const uint32_t *mask, float *scores, int64_t *out_rows, float *values) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
         RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
@@ -571,7 +676,7 @@ int rc_sharded_query_host(rc_sharded *h, const float *queries, int nq, int64_t n
         const QueryLayout L = query_layout(h, nq, k, dev_values);
         ensure_query(h, L.total);
         DeviceScope dl(h->dev[0]);
-        if (h->n == 1 && nq == 1) {
+        if (h->n == 1 && nq == 1 && mask == nullptr) {
             // the request path: one launch pair (query in the kernel arguments, results written
             // straight into the pinned block), no copies; the host polls the completion word
             float *hs = (float *)(h->qh + L.sc);
@@ -592,7 +697,7 @@ int rc_sharded_query_host(rc_sharded *h, const float *queries, int nq, int64_t n
         RC_HIP(hipMemcpyAsync(h->qd + L.q, h->qh + L.q, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, h->qs));
         float *dsc = (float *)(h->qd + L.sc);
         int64_t *drw = (int64_t *)(h->qd + L.rw);
-        search_locked(h, (const float *)(h->qd + L.q), nq, n_rows, k, dsc, drw, RC_SEARCH_AUTO, h->qs);
+        search_locked(h, (const float *)(h->qd + L.q), nq, n_rows, k, dsc, drw, RC_SEARCH_AUTO, h->qs, mask);
         if (dev_values) check_status(rc_index_fetch(h->shard[0], drw, nk, (float *)(h->qd + L.val), h->qs));
         RC_HIP(hipMemcpyAsync(h->qh + L.sc, h->qd + L.sc, (size_t)(L.total - L.sc), hipMemcpyDeviceToHost, h->qs));
         RC_HIP(hipStreamSynchronize(h->qs));

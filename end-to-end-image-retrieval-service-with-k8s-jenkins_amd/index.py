@@ -23,8 +23,19 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, metafilter
 from ._lib import check, ptr, stream_ptr
+
+# query_batch(filter=..., mode="auto") takes the batched MFMA path when the unmasked conditions
+# hold AND at least this share of the rows is eligible.  Ineligible rows still pass the filter
+# GEMM and take candidate slots (the threshold only rises with eligible rows), so candidates per
+# stage grow by 1 / share and overflow into the exact fallback scan below a share of about
+# 0.37 (k = 100).  Measured on an MI355X (tools/masked_search_micro.py; DESIGN.md, "Masked
+# search"; 1M x 512 f16, 256 queries x top-100): MFMA is 23x faster than the masked scan at
+# share 0.5 with no fallback, level with it at 0.1 (every query falls back) and 4.8x slower at
+# 0.01.  0.5 is the lowest measured share at which MFMA wins without falling back.
+MASKED_MFMA_MIN_SHARE = 0.5
+BITMAP_CACHE_ENTRIES = 8
 
 
 def _device_index(device) -> int:
@@ -141,11 +152,14 @@ class DeviceIndex:
         check(self.lib.rc_index_fetch(self.handle, ptr(rows), rows.numel(), ptr(out), stream_ptr(stream)))
         return out
 
-    def search(self, queries: torch.Tensor, k: int, n_rows: int, stream=None, out=None, mode: str = "auto"):
+    def search(self, queries: torch.Tensor, k: int, n_rows: int, stream=None, out=None, mode: str = "auto", mask=None):
         """Exact cosine top-k over rows [0, n_rows): (scores f32 [nq,k], global rows i64 [nq,k]).
 
         ``mode``: "scan" (HBM-bound streaming scan), "mfma" (batched filter GEMM +
-        exact rescoring, f16/bf16 index) or "auto" (MFMA for >= 8 queries)."""
+        exact rescoring, f16/bf16 index) or "auto" (MFMA for >= 8 queries).
+        ``mask``: optional row-eligibility bitmap over the LOCAL rows (rc_index_search_masked):
+        an int32 / uint32 tensor of ceil(n_rows / 32) words on this device, bit r & 31 of word
+        r >> 5 = row r may be returned; "auto" then scans."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
         q = self._vecs(queries)
@@ -155,8 +169,15 @@ class DeviceIndex:
             rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         else:
             scores, rows = out
-        check(self.lib.rc_index_search_ex(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(scores), ptr(rows),
-                                          _lib.SEARCH_MODES[mode], stream_ptr(stream)))
+        if mask is None:
+            check(self.lib.rc_index_search_ex(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(scores), ptr(rows),
+                                              _lib.SEARCH_MODES[mode], stream_ptr(stream)))
+            return scores, rows
+        if mask.dtype not in (torch.int32, torch.uint32) or mask.numel() < (int(n_rows) + 31) // 32:
+            raise ValueError("mask must hold ceil(n_rows / 32) 32-bit words")
+        mask = mask.to(device=self.device).contiguous()
+        check(self.lib.rc_index_search_masked(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(mask), ptr(scores),
+                                              ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
     def export_rows(self, row0: int, n: int, stream=None):
@@ -448,6 +469,7 @@ class ShardSet:
         self.cross_device_rows = 0
         self._qbufs: dict = {}  # query_host's reused host buffers per (nq, k, values)
         self._query_fn = self.lib.rc_sharded_query_host
+        self._query_masked_fn = self.lib.rc_sharded_query_host_masked
         self._shards = []
         for sh in range(self.n):
             ih = _lib.C.c_void_p()
@@ -556,11 +578,20 @@ class ShardSet:
         for d in touched:
             torch.cuda.synchronize(d)
 
-    def query_host(self, q: np.ndarray, k: int, n_rows: int, with_values: bool):
+    @staticmethod
+    def _host_mask(mask, n_rows: int) -> np.ndarray:
+        """A host bitmap over the global rows as C-contiguous uint32 [>= ceil(n_rows / 32)]."""
+        m = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
+        if m.shape[0] < (int(n_rows) + 31) // 32:
+            raise ValueError("mask must hold ceil(n_rows / 32) uint32 words")
+        return m
+
+    def query_host(self, q: np.ndarray, k: int, n_rows: int, with_values: bool, mask=None):
         """Host f32 [nq, dim] → host (scores [nq, k], global rows [nq, k], values [nq, k, dim] or
         None): rc_sharded_query_host — one H2D copy, the search and the matched rows' gather, one
         D2H copy, one synchronisation.  The arrays are this ShardSet's reused buffers: valid
-        until its next query_host call (the Index consumes them under its lock)."""
+        until its next query_host call (the Index consumes them under its lock).  ``mask``: an
+        optional HOST uint32 bitmap over the global rows (rc_sharded_query_host_masked)."""
         nq = int(q.shape[0])
         key = (nq, int(k), bool(with_values))
         bufs = self._qbufs.get(key)
@@ -578,7 +609,11 @@ class ShardSet:
         h = self._h
         if h is None:
             raise RuntimeError("index is closed")
-        check(self._query_fn(h, q.ctypes.data, nq, n_rows, k, ptrs[0], ptrs[1], ptrs[2], ptrs[3]))
+        if mask is None:
+            check(self._query_fn(h, q.ctypes.data, nq, n_rows, k, ptrs[0], ptrs[1], ptrs[2], ptrs[3]))
+        else:
+            m = self._host_mask(mask, n_rows)
+            check(self._query_masked_fn(h, q.ctypes.data, nq, n_rows, k, ptrs[0], m.ctypes.data, ptrs[1], ptrs[2], ptrs[3]))
         return sc, rw, val
 
     def fetch_rows(self, rows, stored: bool = False) -> torch.Tensor:
@@ -589,8 +624,9 @@ class ShardSet:
             check(self.lib.rc_sharded_fetch(self.handle, ptr(rows), rows.numel(), ptr(out), 1 if stored else 0))
         return out
 
-    def search(self, queries: torch.Tensor, k: int, n_rows: int, mode: str = "auto", stream=None):
-        """Exact cosine top-k over global rows [0, n_rows): (scores f32 [nq,k], rows i64 [nq,k]) on the leader."""
+    def search(self, queries: torch.Tensor, k: int, n_rows: int, mode: str = "auto", stream=None, mask=None):
+        """Exact cosine top-k over global rows [0, n_rows): (scores f32 [nq,k], rows i64 [nq,k]) on the leader.
+        ``mask``: an optional HOST uint32 bitmap over the global rows (rc_sharded_search_masked)."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
         if queries.dim() == 1:
@@ -599,8 +635,13 @@ class ShardSet:
         nq = q.shape[0]
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        check(self.lib.rc_sharded_search(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(scores), ptr(rows),
-                                         _lib.SEARCH_MODES[mode], stream_ptr(stream)))
+        if mask is None:
+            check(self.lib.rc_sharded_search(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(scores), ptr(rows),
+                                             _lib.SEARCH_MODES[mode], stream_ptr(stream)))
+        else:
+            m = self._host_mask(mask, n_rows)
+            check(self.lib.rc_sharded_search_masked(self.handle, ptr(q), nq, int(n_rows), int(k), m.ctypes.data,
+                                                    ptr(scores), ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
     # raw stored rows in GLOBAL row order (the snapshot layout, independent of the shard count)
@@ -646,6 +687,14 @@ class Index:
     (``rc_sharded``): results are identical to a single-shard index holding the
     same vectors.  Capacity grows on demand (doubling), as a Pinecone index
     has no fixed size.
+
+    Two things are called "filter" here.  The constructor's ``filter="native" | "i8"`` is
+    the kind of filter GEMM the batched search runs (``DeviceIndex.set_filter``); it never
+    changes a result.  ``query(..., filter={...})`` / ``query_batch(..., filter={...})`` is
+    Pinecone's metadata filter (``metafilter``): only vectors whose metadata satisfies it can
+    be returned, and the restriction happens inside the exact search (a row-eligibility
+    bitmap the masked scan takes), so the top-k of the eligible vectors is exact however
+    selective the filter is.
     """
 
     def __init__(self, name: str, dimension: int = 768, metric: str = "cosine", dtype: str = "float32",
@@ -674,6 +723,9 @@ class Index:
         # fetches the same ids (retriever/main.py:142) — each row leaves the GPU once
         self._gen = 0
         self._recent: tuple[int, dict[str, np.ndarray]] = (-1, {})
+        # metadata-filter bitmaps, most recently used last: (canonical filter JSON, _gen) ->
+        # (bitmap, eligible count); any upsert bumps _gen, so stale entries can never be hit
+        self._bitmaps: dict[tuple[str, int], tuple[np.ndarray, int]] = {}
 
     @property
     def shard_set(self) -> ShardSet:
@@ -843,8 +895,30 @@ class Index:
         self._device_write(self._set.upsert_rows, vecs, rows)
         self._commit_rows(items, rows)
 
+    def _bitmap_locked(self, flt) -> tuple[np.ndarray, int] | None:
+        """The row-eligibility bitmap of a metadata filter and its eligible count (None for no
+        filter: ``None`` or ``{}``).  Cached per (canonical filter, generation)."""
+        if flt is None:
+            return None
+        if not isinstance(flt, dict):
+            raise ValueError("filter must be a dict (Pinecone metadata filter) or None")
+        if not flt:
+            return None
+        key = (metafilter.canonical(flt), self._gen)
+        hit = self._bitmaps.pop(key, None)
+        if hit is None:
+            hit = metafilter.build_bitmap(metafilter.compile_filter(flt), self._ids, self._meta)
+            for old in [k for k in self._bitmaps if k[1] != self._gen]:
+                del self._bitmaps[old]
+            while len(self._bitmaps) >= BITMAP_CACHE_ENTRIES:
+                del self._bitmaps[next(iter(self._bitmaps))]  # least recently used
+        self._bitmaps[key] = hit  # (re)inserted last = most recently used
+        return hit
+
     def query(self, vector=None, top_k: int = 10, include_values: bool = False, include_metadata: bool = False,
-              id: str | None = None, namespace: str = "", **_: Any) -> dict:
+              id: str | None = None, namespace: str = "", filter: dict | None = None, **_: Any) -> dict:
+        """``filter``: a Pinecone-style metadata filter (``metafilter``); ``None`` / ``{}`` = no
+        filter.  Not the constructor's ``filter`` (the filter-GEMM kind)."""
         if vector is None and id is None:
             raise ValueError("query needs a vector or an id")
         if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 1:
@@ -859,12 +933,16 @@ class Index:
                     return {"matches": [], "namespace": namespace}
                 vector = self._set.fetch_rows([r])[0]
             q = _as_vector_np(vector, self.dimension)
-            res = self._query_host_locked(q, top_k, include_values, include_metadata)[0]
+            bm = self._bitmap_locked(filter)
+            res = self._query_host_locked(q, top_k, include_values, include_metadata, bm)[0]
         return {"matches": res, "namespace": namespace}
 
     def query_batch(self, vectors, top_k: int = 10, include_values: bool = False,
-                    include_metadata: bool = False, mode: str = "auto") -> list[dict]:
-        """Batched form of ``query`` (f16/bf16 shards run the MFMA path for >= 8 queries)."""
+                    include_metadata: bool = False, mode: str = "auto", filter: dict | None = None) -> list[dict]:
+        """Batched form of ``query`` (f16/bf16 shards run the MFMA path for >= 8 queries).
+        ``filter``: one metadata filter for the whole batch (see ``query``); with ``mode="auto"``
+        a filtered batch takes the MFMA path only at an eligible share of at least
+        ``MASKED_MFMA_MIN_SHARE``."""
         if top_k < 1 or top_k > _lib.RC_TOPK_MAX:
             raise ValueError(f"top_k must be in [1, {_lib.RC_TOPK_MAX}]")
         if isinstance(vectors, torch.Tensor):
@@ -874,15 +952,35 @@ class Index:
         else:
             q = torch.tensor([_as_vector(v, self.dimension) for v in vectors], dtype=torch.float32)
         with self._mu:
-            res = self._query_locked(q, top_k, include_values, include_metadata, mode)
+            res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter))
         return [{"matches": m, "namespace": ""} for m in res]
 
+    def _masked_mode(self, mode: str, nq: int, n: int, eligible: int) -> str:
+        """The library's "auto" scans whenever a mask is given (it does not know the eligible
+        share); this layer does, and asks for MFMA when the unmasked conditions hold (>= 8
+        queries, >= 64k rows per shard, an f16/bf16 index or the int8 filter copy) and the share
+        reaches MASKED_MFMA_MIN_SHARE."""
+        if mode != "auto":
+            return mode
+        mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter == "i8"
+        if mfma_ok and nq >= 8 and n // self._set.n >= 65536 and eligible >= MASKED_MFMA_MIN_SHARE * n:
+            return "mfma"
+        return "scan"
+
     def _query_locked(self, q: torch.Tensor, k: int, include_values: bool, include_metadata: bool,
-                      mode: str = "auto") -> list[list[dict]]:
+                      mode: str = "auto", bitmap=None) -> list[list[dict]]:
         n = len(self._ids)
         if n == 0 or q.shape[0] == 0:
             return [[] for _ in range(q.shape[0])]
-        scores, rows = self._set.search(q, k, n, mode=mode)
+        if bitmap is None:
+            scores, rows = self._set.search(q, k, n, mode=mode)
+        elif bitmap[1] == 0:  # nothing is eligible: no device work
+            return [[] for _ in range(q.shape[0])]
+        else:
+            if mode not in _lib.SEARCH_MODES:
+                raise ValueError(f"unknown search mode {mode!r}")
+            scores, rows = self._set.search(q, k, n, mode=self._masked_mode(mode, q.shape[0], n, bitmap[1]),
+                                            mask=bitmap[0])
         scores = scores.cpu().tolist()
         rows = rows.cpu().tolist()
         out = []
@@ -904,13 +1002,17 @@ class Index:
             self._recent = (self._gen, recent)
         return out
 
-    def _query_host_locked(self, q: np.ndarray, k: int, include_values: bool, include_metadata: bool) -> list[list[dict]]:
+    def _query_host_locked(self, q: np.ndarray, k: int, include_values: bool, include_metadata: bool,
+                           bitmap=None) -> list[list[dict]]:
         """The request path (a query or a few): ``ShardSet.query_host``, one library call, the
         lists and (include_values) the matched rows' values come back together."""
         n = len(self._ids)
-        if n == 0:
+        if n == 0 or (bitmap is not None and bitmap[1] == 0):  # (a filter nothing satisfies: no device work)
             return [[] for _ in range(q.shape[0])]
-        sc, rw, val = self._set.query_host(q, k, n, include_values)
+        if bitmap is None:
+            sc, rw, val = self._set.query_host(q, k, n, include_values)
+        else:
+            sc, rw, val = self._set.query_host(q, k, n, include_values, mask=bitmap[0])
         out = []
         recent: dict[str, np.ndarray] = {}
         ids, meta = self._ids, self._meta

@@ -5,7 +5,10 @@ Contract kept (``retriever/main.py:94-169``):
   GET  /healthz       → {"status": "OK!"}
   POST /search_image  multipart ``file`` → list of ≤ TOP_K image URLs, best match first
                       ([] when the index has no match); 400 "Uploaded file is not a valid
-                      image."; 422 without ``file``
+                      image."; 422 without ``file``; an optional form field ``filter`` (a JSON
+                      object, Pinecone's metadata-filter language, see ``metafilter``) restricts
+                      the search to matching vectors — 400 "Invalid filter." if it is not JSON,
+                      not an object, or not a valid filter (not in the reference)
 
 Flow as in the reference: validation decode (``:111-117``; folded into the in-process embed,
 which validates with the same 400 body before the model runs) → ``get_feature_vector``
@@ -16,6 +19,7 @@ GCS signing is the no-op ``StorageHook``, blob storage being out of scope).
 """
 from __future__ import annotations
 
+import json
 from io import BytesIO
 
 from fastapi import FastAPI, HTTPException, Request
@@ -26,6 +30,7 @@ from ..config import Config
 from ..ingesting.core import StorageHook
 from ..ingesting.utils import embed_locally, get_index
 from ..ingesting.utils import get_feature_vector as _remote_feature_vector
+from ..metafilter import compile_filter
 from ..multipart import parse_form
 from .utils import search
 
@@ -56,6 +61,21 @@ def health_check():
     return {"status": "OK!"}
 
 
+def _parse_filter(field):
+    """The optional ``filter`` form field → a validated filter dict, or None when absent."""
+    if field is None:
+        return None
+    try:
+        raw = field.data if hasattr(field, "data") else field
+        flt = json.loads(raw.decode("utf-8") if isinstance(raw, (bytes, bytearray)) else raw)
+        if not isinstance(flt, dict):
+            raise ValueError("not an object")
+        compile_filter(flt)
+    except (ValueError, UnicodeDecodeError):
+        raise HTTPException(status_code=400, detail="Invalid filter.")
+    return flt
+
+
 @app.post("/search_image")
 async def search_image(request: Request):
     form = parse_form(await request.body(), request.headers.get("content-type", ""))
@@ -63,6 +83,7 @@ async def search_image(request: Request):
     if f is None:
         raise RequestValidationError([{"type": "missing", "loc": ("body", "file"), "msg": "Field required",
                                        "input": None}])
+    flt = _parse_filter(form.get("filter"))
     feature_fn = _feature_fn(request)
     if not getattr(feature_fn, "validates_image", False):
         try:
@@ -73,7 +94,10 @@ async def search_image(request: Request):
     # the model runs — a GPU-decodable JPEG is decoded once (on the GPU) instead of twice
     feature = feature_fn(f.data)
     ix = index()
-    match_ids = search(ix, feature, top_k=Config.TOP_K)
+    if flt is None:  # no filter field: the reference's call, unchanged
+        match_ids = search(ix, feature, top_k=Config.TOP_K)
+    else:
+        match_ids = search(ix, feature, top_k=Config.TOP_K, filter=flt)
     if not match_ids:
         return []
     response = ix.fetch(ids=match_ids)

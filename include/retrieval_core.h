@@ -144,6 +144,21 @@ int rc_index_search(rc_index *h, const float *queries, int nq, int64_t n_rows, i
 int rc_index_search_ex(rc_index *h, const float *queries, int nq, int64_t n_rows, int k,
                        float *scores, int64_t *out_rows, int mode, void *stream);
 
+/* replaces index.query(vector, top_k, filter={...}) — the row-eligibility form of
+ * rc_index_search_ex (the reference never passes Pinecone's `filter`; users of a
+ * Pinecone-shaped index do).  The host evaluates the metadata predicate; the device
+ * gets a bitmap and restricts the exact search to the eligible rows INSIDE the scan.
+ * mask: device u32 [ceil(n_rows/32)], bit (r & 31) of word r >> 5 = local row r is
+ * eligible; bits at or past n_rows are ignored.  NULL = rc_index_search_ex.
+ * Same contract otherwise: an eligible row's score is bit-identical to the unmasked
+ * search's, ties order by row, slots past the eligible rows get -inf / -1 (a mask
+ * with no eligible row is valid).  Modes: RC_SEARCH_SCAN skips the row loads of
+ * every 8-row group without an eligible row; RC_SEARCH_MFMA keeps the filter GEMM
+ * as it is and drops ineligible candidates when rescoring (overflowed queries fall
+ * back to the masked scan on the device); RC_SEARCH_AUTO with a mask scans. */
+int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_rows, int k,
+                           const uint32_t *mask, float *scores, int64_t *out_rows, int mode, void *stream);
+
 /* Filter copy for the batched search (no reference counterpart: Pinecone's query
  * internals; results are unchanged, only the speed of RC_SEARCH_MFMA):
  *   RC_FILTER_NATIVE — the filter GEMM reads the stored rows (f16/bf16 MFMA);
@@ -219,6 +234,21 @@ int rc_sharded_search(rc_sharded *h, const float *queries, int nq, int64_t n_row
  * rc_sharded_fetch. */
 int rc_sharded_query_host(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, int with_values,
                           float *scores, int64_t *out_rows, float *values);
+/* The masked forms of rc_sharded_search / rc_sharded_query_host (index.query with
+ * filter=...).  mask: HOST u32 [ceil(n_rows/32)] over GLOBAL rows (as
+ * rc_sharded_upsert takes host rows), bit (g & 31) of word g >> 5 = global row g is
+ * eligible; NULL = the unmasked call.  The library de-interleaves it into one local
+ * bitmap per shard (global row g = local row g / n of shard g % n) in pinned staging
+ * and copies each to its shard's device on that shard's stream; no allocation once
+ * the staging has grown to the call's size.  The call returns once the staged
+ * bitmaps were copied (the host words may be reused at once); the search itself is
+ * ordered on `stream` as rc_sharded_search's is.  The masked query_host always takes
+ * the multi-kernel path (no masked form of the one-launch single-query path). */
+int rc_sharded_search_masked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k,
+                             const uint32_t *mask, float *scores, int64_t *out_rows, int mode, void *stream);
+int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k,
+                                 int with_values, const uint32_t *mask, float *scores, int64_t *out_rows,
+                                 float *values);
 /* rc_index_set_filter on every shard; all or nothing (a failure restores
  * RC_FILTER_NATIVE on every shard). */
 int rc_sharded_set_filter(rc_sharded *h, int kind);
