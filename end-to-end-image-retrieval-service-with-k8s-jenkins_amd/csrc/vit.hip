@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "gemm.h"
+#include "qkv_attention.h"
 #include "resample.h"
 #include "vit_kernels.h"
 
@@ -46,6 +47,8 @@ struct Layer {
 };
 
 constexpr int kMaxParts = 4;
+// rc_model_set_qkv_fusion(1): fewest images of a part for the fused QKV + attention kernel
+constexpr int kQkvFusionMinImages = 32;
 
 // T_GEMM: every GEMM; T_QKV / T_OPROJ / T_FC1 / T_FC2: that projection's full-batch
 // launches (M = images x 197 rows), each priced on its own in the bench
@@ -79,6 +82,7 @@ struct rc_model {
     float *hidden = nullptr;
     float *ln_stats = nullptr;     // [Mp][LN_PARTS][2] LayerNorm-fold partials (per 64-column block: mean, M2)
     bool ln_fold = true;           // rc_model_set_ln_fold: LN folded into QKV / fc1 for M > 256 rows
+    int qkv_fusion = 1;            // rc_model_set_qkv_fusion: 0 off, 1 auto (kQkvFusionMinImages), 2 any batch
     // last layer on the CLS rows only (compact [max_batch + pad][·] streams)
     bool cls_only_last = true;     // rc_model_set_last_layer
     float *cls_hidden = nullptr, *cls_stats = nullptr;
@@ -516,9 +520,20 @@ void encode(rc_model *m, const uint8_t *images, int i0, int n, float *raw, float
     }
     // 3. encoder layers
     const float scale = 1.0f / std::sqrt((float)(H / c.heads));
+    // the fused QKV + attention kernel serves the model's real shape under the fold only
+    const bool fuse = fold && T == QA_TOK && H == QA_H && c.heads == QA_HEADS &&
+                      (m->qkv_fusion == 2 || (m->qkv_fusion == 1 && n >= kQkvFusionMinImages));
     for (int l = 0; l < c.layers; ++l) {
         const Layer &L = m->layers[l];
-        if (fold) {
+        const bool cls_last = m->cls_only_last && l == c.layers - 1;
+        if (fuse && !cls_last) {
+            // QKV projection + attention in one launch (qkv_attention.h): no qkv tensor
+            const int tq = m->timers[T_QKV].begin(s);
+            QkvAttnArgs q{ln, L.w_qkv_f, L.b_qkv_f, L.c_qkv, st, attn, n, c.ln_eps, scale * 1.4426950408889634f};
+            hipLaunchKernelGGL(qkv_attention_kernel, dim3(qkv_attention_grid(n)), dim3(64 * QA_WAVES), 0, s, q);
+            RC_LAUNCH_CHECK();
+            m->timers[T_QKV].end(tq, s, 2.0 * M * 3 * H * H + 4.0 * n * c.heads * (double)T * T * (H / c.heads));
+        } else if (fold) {
             // the CLS-only last layer needs Q on the CLS rows alone (last_layer_cls): K and V
             // here, into their columns of the qkv rows
             const bool kv_only = m->cls_only_last && l == c.layers - 1;
@@ -533,23 +548,25 @@ void encode(rc_model *m, const uint8_t *images, int i0, int n, float *raw, float
             layernorm(m, hidden, L.ln1_w, L.ln1_b, ln, M, s);
             gemm<EPI_BF16>(m, GemmArgs{ln, L.w_qkv, L.b_qkv, M, 3 * H, H, qkv, nullptr, nullptr, T}, s, T_QKV);
         }
-        if (m->cls_only_last && l == c.layers - 1) {
+        if (cls_last) {
             last_layer_cls(m, L, i0, n, qkv, hidden, fold ? ln : nullptr, st, scale, s);
             break;
         }
-        const int ta = m->timers[T_ATTN].begin(s);
-        const int items = n * c.heads;
-        // fewer items than CUs: each item's query tiles split over 4 blocks (a lone image: 48 blocks)
-        const int qsplit = items < m->ncu ? 4 : 1;
-        if (T == 197) {
-            hipLaunchKernelGGL(attention_v2_kernel<197>, dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
-                               scale * 1.4426950408889634f, qsplit);
-        } else {
-            hipLaunchKernelGGL(attention_v2_kernel<0>, dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
-                               scale * 1.4426950408889634f, qsplit);
+        if (!fuse) {
+            const int ta = m->timers[T_ATTN].begin(s);
+            const int items = n * c.heads;
+            // fewer items than CUs: each item's query tiles split over 4 blocks (a lone image: 48 blocks)
+            const int qsplit = items < m->ncu ? 4 : 1;
+            if (T == 197) {
+                hipLaunchKernelGGL(attention_v2_kernel<197>, dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
+                                   scale * 1.4426950408889634f, qsplit);
+            } else {
+                hipLaunchKernelGGL(attention_v2_kernel<0>, dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
+                                   scale * 1.4426950408889634f, qsplit);
+            }
+            RC_LAUNCH_CHECK();
+            m->timers[T_ATTN].end(ta, s, 4.0 * n * c.heads * (double)T * T * (H / c.heads));
         }
-        RC_LAUNCH_CHECK();
-        m->timers[T_ATTN].end(ta, s, 4.0 * n * c.heads * (double)T * T * (H / c.heads));
         {
             GemmArgs o = produce(GemmArgs{attn, L.w_o, L.b_o, M, H, H, nullptr, hidden, nullptr, T}, true);
             o.row_step = T;  // rows per image (diagnostic builds: image-aligned tiles, gemm_pp_kernel<.., 224>)
@@ -938,6 +955,16 @@ int rc_model_set_ln_fold(rc_model *m, int on) {
         std::lock_guard<std::mutex> lk(m->mu);
         m->clear_graphs();
         m->ln_fold = on != 0;
+    });
+}
+
+int rc_model_set_qkv_fusion(rc_model *m, int mode) {
+    return guard([&] {
+        RC_REQUIRE(m, RC_ERR_INVALID, "null model");
+        RC_REQUIRE(mode >= 0 && mode <= 2, RC_ERR_INVALID, "qkv fusion mode: 0 off, 1 auto, 2 whenever the shape qualifies");
+        std::lock_guard<std::mutex> lk(m->mu);
+        m->clear_graphs();
+        m->qkv_fusion = mode;
     });
 }
 

@@ -360,6 +360,11 @@ class VitMsnEmbedder:
         """Fold the LayerNorms into the GEMMs around them (default) or run the LN kernel."""
         check(self.lib.rc_model_set_ln_fold(self._h, int(bool(on))))
 
+    def set_qkv_fusion(self, mode: int) -> None:
+        """QKV projection fused into attention (the same bits): 0 off, 1 auto (default: the batch
+        sizes where it measured faster), 2 whenever the model's shape qualifies."""
+        check(self.lib.rc_model_set_qkv_fusion(self._h, int(mode)))
+
     def set_last_layer(self, cls_only: bool) -> None:
         """Run the last encoder layer on the CLS rows only (default) or on every row."""
         check(self.lib.rc_model_set_last_layer(self._h, int(bool(cls_only))))
@@ -575,6 +580,10 @@ class EmbedderPool:
     def set_ln_fold(self, on: bool) -> None:
         for m in self.members:
             m.set_ln_fold(on)
+
+    def set_qkv_fusion(self, mode: int) -> None:
+        for m in self.members:
+            m.set_qkv_fusion(mode)
 
     def set_last_layer(self, cls_only: bool) -> None:
         for m in self.members:

@@ -317,6 +317,14 @@ int rc_model_set_last_layer(rc_model *m, int cls_only);
  * parity tests). */
 int rc_model_set_ln_fold(rc_model *m, int on);
 
+/* QKV projection fused into attention (default 1 = auto).  For the model's real shape (197
+ * tokens, hidden 768, 12 heads, LayerNorm fold on) one kernel computes a head's Q, K and V
+ * from the residual rows into LDS and runs attention there, so the qkv tensor never goes
+ * through HBM.  Same bits as the two kernels it replaces.  0 = off; 1 = for the batch
+ * parts where it measured faster; 2 = whenever the shape qualifies, at any batch size.
+ * Other shapes, and the CLS-only last layer, always run the separate kernels. */
+int rc_model_set_qkv_fusion(rc_model *m, int mode);
+
 /* Batch-1 HIP graphs (default 1): an rc_embed of one image at the model's input size
  * (the reference's /embed request, embedding/main.py:88-124) replays a HIP graph of its
  * launch chain, captured on first use per (images, raw_out, normed_out) buffer triple
