@@ -8,7 +8,7 @@
 // Same bits as the two kernels it replaces: every output element is the same chain of
 // mfma_f32_16x16x32_bf16 (weight fragment first, K blocks ascending, lane group g holding k =
 // 32 kt + 8 g ..) as pp_kloop / gemm_w2_kernel, the LN-fold consumer epilogue is pp_epilogue's
-// fmaf(rstd, acc, fmaf(-rstd·mu, c, b')) rounded with pack_bf16x2, and the attention phase is
+// (ln_apply4, the one function both call) rounded with pack_bf16x2, and the attention phase is
 // att_scores<197> / att_pv_store on K and V in the LDS layouts attention_v2_kernel stages.
 //
 // GEMM phase (gemm_w2_kernel's loop): 4 waves, wave w owns all 13 row blocks x output columns
@@ -171,14 +171,9 @@ __global__ __launch_bounds__(64 * QA_WAVES, 2) void qkv_attention_kernel(QkvAttn
         for (int mi = 0; mi < ATT2_TILES; ++mi) {
             const int row = mi * 16 + li;
             const float2 r = *reinterpret_cast<const float2 *>(smem + QA_LN_OFF + row * 8);
-            const f32x4 v4 = acc[mi][ni];
-            const float v0 = fmaf(r.x, v4[0], fmaf(r.y, c4.x, b4.x));
-            const float v1 = fmaf(r.x, v4[1], fmaf(r.y, c4.y, b4.y));
-            const float v2 = fmaf(r.x, v4[2], fmaf(r.y, c4.z, b4.z));
-            const float v3 = fmaf(r.x, v4[3], fmaf(r.y, c4.w, b4.w));
+            const float4 v = ln_apply4(r, acc[mi][ni], c4, b4);
             const int swz = mat == 2 ? ((row >> 1) & 3) << 1 : (row >> 1) & 7;
-            *reinterpret_cast<uint2 *>(mbase + row * 128 + (((d >> 3) ^ swz) << 4)) =
-                make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+            *reinterpret_cast<uint2 *>(mbase + row * 128 + (((d >> 3) ^ swz) << 4)) = pack_bf16x4(v);
         }
         __builtin_amdgcn_sched_barrier(0);
     }

@@ -81,7 +81,7 @@ struct rc_model {
     uint16_t *ln = nullptr, *qkv = nullptr, *attn = nullptr, *mlp = nullptr;
     float *hidden = nullptr;
     float *ln_stats = nullptr;     // [Mp][LN_PARTS][2] LayerNorm-fold partials (per 64-column block: mean, M2)
-    bool ln_fold = true;           // rc_model_set_ln_fold: LN folded into QKV / fc1 for M > 256 rows
+    bool ln_fold = true;           // rc_model_set_ln_fold: LN folded into QKV / fc1, at every M
     int qkv_fusion = 1;            // rc_model_set_qkv_fusion: 0 off, 1 auto (kQkvFusionMinImages), 2 any batch
     // last layer on the CLS rows only (compact [max_batch + pad][·] streams)
     bool cls_only_last = true;     // rc_model_set_last_layer
@@ -401,6 +401,15 @@ void gemm(rc_model *m, const GemmArgs &a, hipStream_t s, int role = -1) {
     m->timers[T_GEMM].end(t0, s, flops);
 }
 
+// LayerNorm-fold consumer (QKV, fc1): `a` carries W∘γ and b + W·β; c = the row sums of W∘γ,
+// stats = the producers' block partials of a's rows
+GemmArgs ln_consumer(GemmArgs a, const float *c, float *stats, float eps) {
+    a.ln_c = c;
+    a.ln_stats = stats;
+    a.ln_eps = eps;
+    return a;
+}
+
 // residual-stream producer GEMM (O-proj, fc2): f32 stream, or bf16 under the fold
 void resid_gemm(rc_model *m, const GemmArgs &a, hipStream_t s, int role) {
     if (a.resid_bf16) gemm<EPI_RESID_BF16>(m, a, s, role);
@@ -437,11 +446,8 @@ void last_layer_cls(rc_model *m, const Layer &L, int i0, int n, const uint16_t *
                        st_rows, cst);
     RC_LAUNCH_CHECK();
     if (q_cls) {
-        GemmArgs q{lc, L.w_qkv_f, L.b_qkv_f, n, H, H, qc, nullptr, nullptr, 1};
-        q.ln_c = L.c_qkv;
-        q.ln_stats = cst;
-        q.ln_eps = c.ln_eps;
-        gemm<EPI_BF16_LN>(m, q, s);
+        const GemmArgs q{lc, L.w_qkv_f, L.b_qkv_f, n, H, H, qc, nullptr, nullptr, 1};
+        gemm<EPI_BF16_LN>(m, ln_consumer(q, L.c_qkv, cst, c.ln_eps), s);
     }
     const int ta = m->timers[T_ATTN].begin(s);
     const int items = n * c.heads;
@@ -455,11 +461,8 @@ void last_layer_cls(rc_model *m, const Layer &L, int i0, int n, const uint16_t *
         o.ln_x = lc;
         o.ln_stats = st;
         gemm<EPI_RESID_F32>(m, o, s);
-        GemmArgs f{lc, L.w_fc1_f, L.b_fc1_f, n, c.mlp, H, mc, nullptr, nullptr, 1};
-        f.ln_c = L.c_fc1;
-        f.ln_stats = st;
-        f.ln_eps = c.ln_eps;
-        gemm<EPI_GELU_BF16_LN>(m, f, s);
+        const GemmArgs f{lc, L.w_fc1_f, L.b_fc1_f, n, c.mlp, H, mc, nullptr, nullptr, 1};
+        gemm<EPI_GELU_BF16_LN>(m, ln_consumer(f, L.c_fc1, st, c.ln_eps), s);
     } else {
         gemm<EPI_RESID_F32>(m, o, s);
         layernorm(m, hc, L.ln2_w, L.ln2_b, lc, n, s);
@@ -540,10 +543,7 @@ void encode(rc_model *m, const uint8_t *images, int i0, int n, float *raw, float
             const int64_t q0 = kv_only ? H : 0;
             GemmArgs a{ln, L.w_qkv_f + q0 * H, L.b_qkv_f + q0, M, 3 * H - (int)q0, H, qkv + q0, nullptr, nullptr, T};
             a.ldc = 3 * H;
-            a.ln_c = L.c_qkv + q0;
-            a.ln_stats = st;
-            a.ln_eps = c.ln_eps;
-            gemm<EPI_BF16_LN>(m, a, s, kv_only ? -1 : T_QKV);
+            gemm<EPI_BF16_LN>(m, ln_consumer(a, L.c_qkv + q0, st, c.ln_eps), s, kv_only ? -1 : T_QKV);
         } else {
             layernorm(m, hidden, L.ln1_w, L.ln1_b, ln, M, s);
             gemm<EPI_BF16>(m, GemmArgs{ln, L.w_qkv, L.b_qkv, M, 3 * H, H, qkv, nullptr, nullptr, T}, s, T_QKV);
@@ -573,11 +573,8 @@ void encode(rc_model *m, const uint8_t *images, int i0, int n, float *raw, float
             resid_gemm(m, o, s, T_OPROJ);
         }
         if (fold) {
-            GemmArgs a{ln, L.w_fc1_f, L.b_fc1_f, M, c.mlp, H, mlp, nullptr, nullptr, T};
-            a.ln_c = L.c_fc1;
-            a.ln_stats = st;
-            a.ln_eps = c.ln_eps;
-            gemm<EPI_GELU_BF16_LN>(m, a, s, T_FC1);
+            const GemmArgs a{ln, L.w_fc1_f, L.b_fc1_f, M, c.mlp, H, mlp, nullptr, nullptr, T};
+            gemm<EPI_GELU_BF16_LN>(m, ln_consumer(a, L.c_fc1, st, c.ln_eps), s, T_FC1);
         } else {
             layernorm(m, hidden, L.ln2_w, L.ln2_b, ln, M, s);
             gemm<EPI_GELU_BF16>(m, GemmArgs{ln, L.w_fc1, L.b_fc1, M, c.mlp, H, mlp, nullptr, nullptr, T}, s, T_FC1);

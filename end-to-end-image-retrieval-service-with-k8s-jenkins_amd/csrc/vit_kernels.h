@@ -201,6 +201,13 @@ __device__ __forceinline__ float2 ln_row_scale(const float *__restrict__ st, flo
     const float rstd = 1.0f / sqrtf(fmaf(M2, 1.0f / (64 * LN_PARTS), eps));
     return make_float2(rstd, -rstd * mu);
 }
+// The consumer's correction on four columns, rstd·(acc − μ·c) + b′, with rs = ln_row_scale's pair:
+// the one form every LayerNorm-fold consumer epilogue (tiled, skinny, fused QKV + attention)
+// applies, so a row gets the same bits from each
+__device__ __forceinline__ float4 ln_apply4(float2 rs, f32x4 acc, float4 c, float4 b) {
+    return make_float4(fmaf(rs.x, acc[0], fmaf(rs.y, c.x, b.x)), fmaf(rs.x, acc[1], fmaf(rs.y, c.y, b.y)),
+                       fmaf(rs.x, acc[2], fmaf(rs.y, c.z, b.z)), fmaf(rs.x, acc[3], fmaf(rs.y, c.w, b.w)));
+}
 
 // One wave per row of H = 256*NV f32 values → bf16 LayerNorm output.
 template <int NV>
