@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void fill_random_kernel(T *__restrict__ rows, 
 
 // The int8 filter copy (search_mfma.hip, filter_i8_kernel): one wave per stored row x̂,
 // sx = max|x̂| / 127, x8 = rne(x̂ / sx) clamped to [-127, 127], ex = ||x̂ - sx·x8||₂ rounded
-// up (x1.001 covers the f32 sum of squares, +1e-7 the f32 residuals), sx and ex at
+// up (i8_scale / i8_round / i8_resid_bound, which the queries share), sx and ex at
 // i8_slot(row).  Rows come from slots[v] (upsert) or row0 + v (fill / import / enable).
 template <typename T>
 __global__ __launch_bounds__(256) void quantize_rows_kernel(const T *__restrict__ rows, int64_t ld,
@@ -114,12 +114,12 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const T *__restrict_
         float mx = 0.f;
         for (int c = lane; c < ld; c += 64) mx = fmaxf(mx, fabsf(Elem<T>::load(src, c)));
         mx = wave_max(mx);
-        const float s = mx * (1.0f / 127.0f), is = mx > 0.f ? 127.0f / mx : 0.f;
+        const float s = i8_scale(mx), is = i8_inv_scale(mx);
         float e = 0.f;
         int8_t *dst = rows8 + r * ld;
         for (int c = lane; c < ld; c += 64) {
             const float x = Elem<T>::load(src, c);
-            const float q = fminf(127.f, fmaxf(-127.f, rintf(x * is)));
+            const float q = i8_round(x, is);
             dst[c] = (int8_t)q;
             const float d = x - s * q;
             e = fmaf(d, d, e);
@@ -127,23 +127,9 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const T *__restrict_
         e = wave_sum(e);
         if (lane == 0) {
             rsx[i8_slot(r)] = s;
-            rex[i8_slot(r)] = sqrtf(e) * 1.001f + 1e-7f;
+            rex[i8_slot(r)] = i8_resid_bound(e);
         }
     }
-}
-
-// queries [nq, dim] f32 → normalised, zero-padded [nq, ld]
-// rows >= nq (padding up to a multiple of the scan's queries-per-pass) are zero.
-__global__ __launch_bounds__(64) void normalize_queries_kernel(const float *__restrict__ q, int nq, int dim, int64_t ld,
-                                                              float *__restrict__ qn) {
-    const int lane = threadIdx.x;
-    const bool valid = (int)blockIdx.x < nq;
-    const float *src = q + (int64_t)(valid ? blockIdx.x : 0) * dim;
-    float ss = 0.f;
-    for (int c = lane; c < dim; c += 64) ss = valid ? fmaf(src[c], src[c], ss) : 0.f;
-    ss = wave_sum(ss);
-    const float inv = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
-    for (int c = lane; c < ld; c += 64) qn[(int64_t)blockIdx.x * ld + c] = (valid && c < dim) ? src[c] * inv : 0.f;
 }
 
 // One block per query: top-k over nlist sorted partial lists of k keys each.
@@ -164,9 +150,7 @@ __global__ __launch_bounds__(256) void merge_partials_kernel(const uint64_t *__r
     if (wave == 0) {
         for (int j = lane; j < k; j += 64) {
             const uint64_t key = tk.buf[j];
-            const bool ok = key != KEY_EMPTY;
-            out_scores[(int64_t)qi * k + j] = ok ? key_score(key) : -INFINITY;
-            out_rows[(int64_t)qi * k + j] = ok ? row_base + (int64_t)key_idx(key) * row_stride : -1;
+            RC_EMIT_KEY(key, row_base, row_stride, out_scores[(int64_t)qi * k + j], out_rows[(int64_t)qi * k + j]);
         }
     }
 }
@@ -214,13 +198,7 @@ __global__ __launch_bounds__(256) void merge_heads_kernel(const uint64_t *__rest
     if (tid == 0) ccount = 0;
     __syncthreads();
     if (wave == 0) {
-        for (int w = 1; w < 4; ++w)
-            for (int j = 0; j < k; j += 64) {
-                const uint64_t key = (j + lane < k) ? as_lds(&lds[w][0])[j + lane] : KEY_EMPTY;
-                tk.reserve(64);
-                tk.push(key != KEY_EMPTY, key);
-            }
-        tk.compact();
+        fold_wave_lists<CAP>(&lds[0][0], CAP, tk, k);
         if (lane == 0) hk_s = tk.count >= k ? tk.buf[k - 1] : KEY_EMPTY;
     }
     __syncthreads();
@@ -260,9 +238,7 @@ __global__ __launch_bounds__(256) void merge_heads_kernel(const uint64_t *__rest
     if (wave == 0) {
         for (int j = lane; j < k; j += 64) {
             const uint64_t key = tk.buf[j];
-            const bool ok = key != KEY_EMPTY;
-            out_scores[(int64_t)qi * k + j] = ok ? key_score(key) : -INFINITY;
-            out_rows[(int64_t)qi * k + j] = ok ? row_base + (int64_t)key_idx(key) * row_stride : -1;
+            RC_EMIT_KEY(key, row_base, row_stride, out_scores[(int64_t)qi * k + j], out_rows[(int64_t)qi * k + j]);
         }
     }
 }
@@ -299,18 +275,10 @@ __global__ __launch_bounds__(256) void merge_lists_kernel(const float *__restric
     tk.compact();
     __syncthreads();
     if (wave == 0) {
-        for (int w = 1; w < 4; ++w)
-            for (int j = 0; j < k; j += 64) {
-                const uint64_t key = (j + lane < k) ? as_lds(&lds[w][0])[j + lane] : KEY_EMPTY;
-                tk.reserve(64);
-                tk.push(key != KEY_EMPTY, key);
-            }
-        tk.compact();
+        fold_wave_lists<CAP>(&lds[0][0], CAP, tk, k);
         for (int j = lane; j < k; j += 64) {
             const uint64_t key = tk.buf[j];
-            const bool ok = key != KEY_EMPTY;
-            out_scores[(int64_t)qi * k + j] = ok ? key_score(key) : -INFINITY;
-            out_rows[(int64_t)qi * k + j] = ok ? (int64_t)key_idx(key) : -1;
+            RC_EMIT_KEY(key, 0, 1, out_scores[(int64_t)qi * k + j], out_rows[(int64_t)qi * k + j]);
         }
     }
 }
@@ -353,7 +321,7 @@ struct rc_index {
     unsigned q1_seq = 0;
     BatchWs bws;         // batched MFMA search workspace (search_mfma.hip)
     KernelTimer timer;   // scan_topk_kernel launches (bytes)
-    KernelTimer gtimer;  // filter_gemm_kernel launches (flops)
+    KernelTimer gtimer;  // the batched search's filter launches, whichever filter kernel (flops)
 };
 
 namespace {
@@ -429,8 +397,7 @@ void launch_fetch(rc_index *h, const int64_t *slots, int64_t n, float *out, bool
 
 template <typename T>
 void launch_fill(rc_index *h, uint64_t seed, int64_t row0, int64_t n, hipStream_t s) {
-    const int64_t waves = (n + 0) ;
-    unsigned grid = (unsigned)std::min<int64_t>((waves + 3) / 4, 256 * 32);
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 3) / 4, 256 * 32);
     if (grid == 0) return;
     hipLaunchKernelGGL(fill_random_kernel<T>, dim3(grid), dim3(256), 0, s, (T *)h->rows, h->norms, h->ld, h->dim, seed, row0, n);
     RC_LAUNCH_CHECK();
@@ -438,47 +405,25 @@ void launch_fill(rc_index *h, uint64_t seed, int64_t row0, int64_t n, hipStream_
 }
 
 void launch_scan(rc_index *h, const ScanArgs &a) {
-    switch (h->dtype) {
-        case RC_F32: return launch_scan_f32(a);
-        case RC_F16: return launch_scan_f16(a);
-        case RC_BF16: return launch_scan_bf16(a);
-        default: throw Error(RC_ERR_INVALID, "unknown dtype");
-    }
+    dispatch_dtype(h->dtype, [&](auto t) { rc::launch_scan<decltype(t)>(a); });
 }
 
 // Top-k over nlist sorted partial lists per query, one block per query: past MERGE_HEADS_MIN lists
 // through the lists' heads (merge_heads_kernel), else over every key (merge_partials_kernel).  The
 // same keys either way.
-template <int CAP>
-void launch_merge_partials_t(rc_index *h, const uint64_t *partial, const int *flags, int nlist, int nq, int nq_stride, int k,
-                             float *scores, int64_t *rows, hipStream_t s) {
-    if (nlist >= MERGE_HEADS_MIN)
-        hipLaunchKernelGGL(merge_heads_kernel<CAP>, dim3(nq), dim3(256), 0, s, partial, nlist, nq_stride, k, h->row_base,
-                           h->row_stride, flags, scores, rows);
-    else
-        hipLaunchKernelGGL(merge_partials_kernel<CAP>, dim3(nq), dim3(256), 0, s, partial, nlist, nq_stride, k, h->row_base,
-                           h->row_stride, flags, scores, rows);
-    RC_LAUNCH_CHECK();
-}
-
 void launch_merge_partials(rc_index *h, const uint64_t *partial, const int *flags, int nlist, int nq, int nq_stride, int k,
                            float *scores, int64_t *rows, hipStream_t s) {
-    const int cap = topk_cap(k);
-    if (cap <= 128) return launch_merge_partials_t<128>(h, partial, flags, nlist, nq, nq_stride, k, scores, rows, s);
-    if (cap <= 256) return launch_merge_partials_t<256>(h, partial, flags, nlist, nq, nq_stride, k, scores, rows, s);
-    return launch_merge_partials_t<512>(h, partial, flags, nlist, nq, nq_stride, k, scores, rows, s);
+    with_topk_cap(topk_cap(k), [&](auto cap) {
+        constexpr int CAP = decltype(cap)::value;
+        if (nlist >= MERGE_HEADS_MIN)
+            hipLaunchKernelGGL(merge_heads_kernel<CAP>, dim3(nq), dim3(256), 0, s, partial, nlist, nq_stride, k, h->row_base,
+                               h->row_stride, flags, scores, rows);
+        else
+            hipLaunchKernelGGL(merge_partials_kernel<CAP>, dim3(nq), dim3(256), 0, s, partial, nlist, nq_stride, k, h->row_base,
+                               h->row_stride, flags, scores, rows);
+    });
+    RC_LAUNCH_CHECK();
 }
-
-template <typename F>
-void dispatch_dtype(int dtype, F &&f) {
-    switch (dtype) {
-        case RC_F32: f(float{}); break;
-        case RC_F16: f(f16_t{}); break;
-        case RC_BF16: f(bf16_t{}); break;
-        default: throw Error(RC_ERR_INVALID, "unknown dtype");
-    }
-}
-
 
 // mask (optional): the row-eligibility bitmap of rc_index_search_masked; the masked scan kernels.
 void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask, float *scores,
@@ -516,7 +461,7 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
 // Batched MFMA search, then — still on the device, no host synchronisation —
 // the exact scan for every query whose candidates overflowed: scan_topk_kernel
 // in fallback mode (blocks early-exit for unflagged queries) over the batched
-// path's normalised queries (the same f32 arithmetic as normalize_queries_kernel),
+// path's normalised queries (wave_inv_norm / RC_UNIT_ELEM, the scan's own normalisation),
 // and merge_partials_kernel over the flagged queries' partial lists.
 // With a mask the rescoring drops ineligible candidates (search_mfma.hip) and the
 // fallback is the masked scan; the merge is the same.
@@ -603,19 +548,10 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
         *seq = a.seq;
     }
     std::memcpy(a.q, query, (size_t)h->dim * sizeof(float));
-    switch (h->dtype) {
-        case RC_F32: launch_query1_f32(a, s); break;
-        case RC_F16: launch_query1_f16(a, s); break;
-        case RC_BF16: launch_query1_bf16(a, s); break;
-        default: throw Error(RC_ERR_INVALID, "unknown dtype");
-    }
+    dispatch_dtype(h->dtype, [&](auto t) { launch_query1<decltype(t)>(a, s); });
     return true;
 }
 }  // namespace rc
-
-namespace {
-
-}  // namespace
 
 extern "C" {
 
@@ -947,13 +883,10 @@ int rc_topk_merge(const float *scores, const int64_t *rows, int nlists, int nq, 
         RC_REQUIRE(nlists >= 1 && nq >= 0 && k_in >= 1 && k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "bad merge sizes");
         if (nq == 0) return;
         hipStream_t s = (hipStream_t)stream;
-        const int cap = topk_cap(k);
-        if (cap <= 128)
-            hipLaunchKernelGGL(merge_lists_kernel<128>, dim3(nq), dim3(256), 0, s, scores, rows, nlists, nq, k_in, k, out_scores, out_rows);
-        else if (cap <= 256)
-            hipLaunchKernelGGL(merge_lists_kernel<256>, dim3(nq), dim3(256), 0, s, scores, rows, nlists, nq, k_in, k, out_scores, out_rows);
-        else
-            hipLaunchKernelGGL(merge_lists_kernel<512>, dim3(nq), dim3(256), 0, s, scores, rows, nlists, nq, k_in, k, out_scores, out_rows);
+        with_topk_cap(topk_cap(k), [&](auto cap) {
+            hipLaunchKernelGGL(merge_lists_kernel<decltype(cap)::value>, dim3(nq), dim3(256), 0, s, scores, rows, nlists, nq, k_in,
+                               k, out_scores, out_rows);
+        });
         RC_LAUNCH_CHECK();
     });
 }

@@ -2,7 +2,7 @@
 // (BASELINE config 4: 1024 queries x top-100 over a 125M x 512 fp16 shard).
 //
 // Replaces index.query(vector, top_k) (retriever/utils.py:62-64) for a batch of
-// query vectors; the single-query path is the HBM-bound scan (index_common.h).
+// query vectors; the single-query path is the HBM-bound scan (scan.h).
 //
 // A query batch is a GEMM: S = Q · Xᵀ (queries x rows, K = ld).  S is never
 // materialised.  The search runs in STAGES over growing row ranges
@@ -11,9 +11,9 @@
 //                       tiles; the epilogue keeps (query, row) iff
 //                       s'(q,r) >= thr[q] and appends the row to the query's
 //                       candidate list (atomic counter, capacity CAND_CAP);
-//   rescore_kernel      per query: exact f32 score of every candidate (the same
-//                       arithmetic as the single-query scan, so both paths give
-//                       bit-identical scores), wavefront top-k merge with the
+//   rescore_kernel      per query: exact f32 score of every candidate (RC_ROW_FMA16
+//                       + sum16, the single-query scan's own row score, so both paths
+//                       give bit-identical scores), wavefront top-k merge with the
 //                       running top-k keys, thr[q] = kth_best - eps[q].
 // Why it is exact: s' uses the query rounded to the storage dtype q̂.  For a
 // stored row x̂ (||x̂|| <= 1.01) |s' - s| <= ||q - q̂||·||x̂|| + two f32
@@ -56,7 +56,7 @@ constexpr int SB_TILE = 256;  // queries per query block = rows per row tile
 
 // ------------------------------------------------------ query preparation --
 // One wave per query slot q < nq_pad: qn = q/||q|| (f32, the exact rescoring
-// operand, same arithmetic as normalize_queries_kernel), qh = cast(qn) (the
+// operand: wave_inv_norm / RC_UNIT_ELEM, as the scan normalises), qh = cast(qn) (the
 // MFMA operand), eps = error bound of s' (see header), thr = -inf (real
 // query) or +inf (padding slot: never appends).
 template <typename T>
@@ -67,13 +67,10 @@ __global__ __launch_bounds__(64) void prepare_queries_kernel(const float *__rest
     const int qi = blockIdx.x;
     const bool valid = qi < nq;
     const float *src = q + (int64_t)(valid ? qi : 0) * dim;
-    float ss = 0.f;
-    for (int c = lane; c < dim; c += 64) ss = valid ? fmaf(src[c], src[c], ss) : 0.f;
-    ss = wave_sum(ss);
-    const float inv = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
+    const float inv = wave_inv_norm(src, dim, lane, valid);
     float err = 0.f;
     for (int c = lane; c < ld; c += 64) {
-        const float v = (valid && c < dim) ? src[c] * inv : 0.f;
+        const float v = RC_UNIT_ELEM(src, c, dim, inv, valid);
         const T h = Elem<T>::cast(v);
         const float d = v - Elem<T>::load(&h, 0);
         err = fmaf(d, d, err);
@@ -105,6 +102,30 @@ struct FilterArgs {
     const float *rsx = nullptr, *rex = nullptr, *sq = nullptr, *aq = nullptr;
 };
 
+// Block → (query block, row chunk), for tiles of RT rows: blocks b and b+8 share an XCD; the nqb
+// blocks of one chunk are consecutive on one XCD, so each row tile is read from HBM once and
+// served to the other query blocks from that XCD's L2.  The block's row tiles are [rt0, rt1)
+// (none: rt0 >= rt1, a block-uniform early return for the caller).
+struct FilterBlock {
+    int qb;
+    int64_t rt0, rt1;
+    __device__ __forceinline__ FilterBlock(const FilterArgs &a, int RT) {
+        const int b = blockIdx.x, xcd = b & 7, jx = b >> 3;
+        qb = jx % a.nqb;
+        const int64_t chunk = (int64_t)(jx / a.nqb) * 8 + xcd;
+        const int64_t rt_total = (a.r_end - a.r_begin + RT - 1) / RT;
+        rt0 = chunk * a.tiles_per_chunk;
+        rt1 = min(rt_total, rt0 + a.tiles_per_chunk);
+    }
+};
+
+// Row `row` passed query q's filter: append it to q's candidate list (the count keeps running
+// past cap: rescore_kernel reads an overflow from it).
+__device__ __forceinline__ void append_candidate(const FilterArgs &a, int q, int64_t row) {
+    const uint32_t pos = atomicAdd(&a.cnt[q], 1u);
+    if ((int)pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = (uint32_t)row;
+}
+
 // 256x256x64 tile, 512 threads = 8 waves in two groups (G0 = waves 0-3 own
 // query rows 0-127, G1 = waves 4-7 rows 128-255; wave w and w+4 share a SIMD).
 // Each wave owns 128 queries x 64 index rows as 4 quadrants of 64x32.  The
@@ -117,9 +138,6 @@ struct FilterArgs {
 // reads LDS.  MFMA roles: A operand = index rows, B operand = queries, so a
 // lane's accumulator holds 4 consecutive ROWS of one query: the epilogue tests
 // one per-lane threshold against 16 values at a time.
-// Block → (query block, chunk): blocks b and b+8 share an XCD; the nqb blocks
-// of one chunk are consecutive on one XCD, so each row tile is read from HBM
-// once and served to the other query blocks from that XCD's L2.
 template <typename T>
 __global__ __launch_bounds__(512, 1) void filter_gemm_kernel(FilterArgs a) {
     using Op = MfmaOp<T>;
@@ -133,12 +151,9 @@ __global__ __launch_bounds__(512, 1) void filter_gemm_kernel(FilterArgs a) {
     const int grp = wave >> 2, wc = wave & 3;
     const int g = lane >> 4, li = lane & 15;
 
-    const int b = blockIdx.x, xcd = b & 7, jx = b >> 3;
-    const int qb = jx % a.nqb;
-    const int64_t chunk = (int64_t)(jx / a.nqb) * 8 + xcd;
-    const int64_t rt_total = (a.r_end - a.r_begin + SB_TILE - 1) / SB_TILE;
-    const int64_t rt0 = chunk * a.tiles_per_chunk;
-    const int64_t rt1 = min(rt_total, rt0 + a.tiles_per_chunk);
+    const FilterBlock fb(a, SB_TILE);
+    const int qb = fb.qb;
+    const int64_t rt0 = fb.rt0, rt1 = fb.rt1;
     if (rt0 >= rt1) return;  // block-uniform
     const int nkt = a.nkt;
     const int64_t ld = a.ld;
@@ -265,10 +280,7 @@ __global__ __launch_bounds__(512, 1) void filter_gemm_kernel(FilterArgs a) {
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) {
                                     const int64_t row = rbase + nq * 32 + ni * 16 + j;
-                                    if (acc[mq][nq][mi][ni][j] >= t && row < a.r_end) {
-                                        const uint32_t pos = atomicAdd(&a.cnt[q], 1u);
-                                        if ((int)pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = (uint32_t)row;
-                                    }
+                                    if (acc[mq][nq][mi][ni][j] >= t && row < a.r_end) append_candidate(a, q, row);
                                 }
                     }
                 }
@@ -316,12 +328,9 @@ __global__ __launch_bounds__(512, 1) void filter_qs_kernel(FilterArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, li = lane & 15;
 
-    const int b = blockIdx.x, xcd = b & 7, jx = b >> 3;
-    const int qb = jx % a.nqb;
-    const int64_t chunk = (int64_t)(jx / a.nqb) * 8 + xcd;
-    const int64_t rt_total = (a.r_end - a.r_begin + QS_RT - 1) / QS_RT;
-    const int64_t rt0 = chunk * a.tiles_per_chunk;
-    const int64_t rt1 = min(rt_total, rt0 + a.tiles_per_chunk);
+    const FilterBlock fb(a, QS_RT);
+    const int qb = fb.qb;
+    const int64_t rt0 = fb.rt0, rt1 = fb.rt1;
     if (rt0 >= rt1) return;  // block-uniform
     const int64_t ld = a.ld;
     const int ntiles = (int)(rt1 - rt0);  // per-block counters in 32 bits: uniform SALU compares
@@ -462,10 +471,7 @@ __global__ __launch_bounds__(512, 1) void filter_qs_kernel(FilterArgs a) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int64_t row = rbase + rf * 16 + j;
-                        if (acc[rf][qt][j] >= th && row < a.r_end) {
-                            const uint32_t pos = atomicAdd(&a.cnt[q], 1u);
-                            if ((int)pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = (uint32_t)row;
-                        }
+                        if (acc[rf][qt][j] >= th && row < a.r_end) append_candidate(a, q, row);
                     }
             }
         }
@@ -497,29 +503,26 @@ __global__ __launch_bounds__(64) void prepare_queries_i8_kernel(const float *__r
     const int qi = blockIdx.x;
     const bool valid = qi < nq;
     const float *src = q + (int64_t)(valid ? qi : 0) * dim;
-    float ss = 0.f;
-    for (int c = lane; c < dim; c += 64) ss = valid ? fmaf(src[c], src[c], ss) : 0.f;
-    ss = wave_sum(ss);
-    const float inv = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
+    const float inv = wave_inv_norm(src, dim, lane, valid);
     float mx = 0.f;
     for (int c = lane; c < ld; c += 64) {
-        const float v = (valid && c < dim) ? src[c] * inv : 0.f;
+        const float v = RC_UNIT_ELEM(src, c, dim, inv, valid);
         mx = fmaxf(mx, fabsf(v));
         if (valid) qn[(int64_t)qi * ld + c] = v;
     }
     mx = wave_max(mx);
-    const float s = mx * (1.0f / 127.0f), is = mx > 0.f ? 127.0f / mx : 0.f;
+    const float s = i8_scale(mx), is = i8_inv_scale(mx);  // quantised as the rows are (quantize_rows_kernel)
     float err = 0.f;
     for (int c = lane; c < ld; c += 64) {
-        const float v = (valid && c < dim) ? src[c] * inv : 0.f;  // the value stored in qn above
-        const float r = fminf(127.f, fmaxf(-127.f, rintf(v * is)));
+        const float v = RC_UNIT_ELEM(src, c, dim, inv, valid);  // the value stored in qn above
+        const float r = i8_round(v, is);
         q8[(int64_t)qi * ld + c] = (int8_t)r;
         const float d = v - s * r;
         err = fmaf(d, d, err);
     }
     err = wave_sum(err);
     if (lane == 0) {
-        const float eq = sqrtf(err) * 1.001f + 1e-7f;
+        const float eq = i8_resid_bound(err);
         sq[qi] = s;
         aq[qi] = 1.0001f + eq;
         eps[qi] = 1.01f * eq + 6.6e-5f;
@@ -577,12 +580,9 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, li = lane & 15;
 
-    const int b = blockIdx.x, xcd = b & 7, jx = b >> 3;
-    const int qb = jx % a.nqb;
-    const int64_t chunk = (int64_t)(jx / a.nqb) * 8 + xcd;
-    const int64_t rt_total = (a.r_end - a.r_begin + RT - 1) / RT;
-    const int64_t rt0 = chunk * a.tiles_per_chunk;
-    const int64_t rt1 = min(rt_total, rt0 + a.tiles_per_chunk);
+    const FilterBlock fb(a, RT);
+    const int qb = fb.qb;
+    const int64_t rt0 = fb.rt0, rt1 = fb.rt1;
     if (rt0 >= rt1) return;  // block-uniform
     const int64_t ldb = a.ld;  // bytes per row
     const int ntiles = (int)(rt1 - rt0);
@@ -778,8 +778,7 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
                             if (p < (uint32_t)I8_SL) {
                                 lds_write_u32(&lbuf[ql * I8_SL + p], (uint32_t)row);
                             } else {  // this block's slots of q are full: straight to the global list
-                                const uint32_t pos = atomicAdd(&a.cnt[q], 1u);
-                                if ((int)pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = (uint32_t)row;
+                                append_candidate(a, q, row);
                             }
                         }
                     }
@@ -804,8 +803,8 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
 
 // ------------------------------------------------------- exact rescoring --
 // One block per query.  Candidates are scored exactly as scan_topk_kernel
-// scores a row (16 lanes per row, 16-B chunks, f32 FMA in chunk order, DPP
-// reduction), merged with the running top-k keys, and the threshold for the
+// scores a row (RC_ROW_FMA16 + sum16: 16 lanes per row, 16-B chunks, f32 FMA in chunk
+// order, DPP reduction), merged with the running top-k keys, and the threshold for the
 // next stage is set.  Overflow (more candidates than cap) is flagged for the
 // host's exact fallback; the counter is reset for the next stage.
 //
@@ -829,19 +828,19 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
                                                      int *__restrict__ ovf_total, int final_pass, int64_t row_base,
                                                      int64_t row_stride, float *__restrict__ out_scores,
                                                      int64_t *__restrict__ out_rows, const uint32_t *__restrict__ mask) {
-    constexpr int EPC = 16 / sizeof(T);
-    constexpr int CPL = NCH * 128 / (16 * EPC);
+    constexpr int EPC = RowShape<T, NCH>::EPC;
+    constexpr int CPL = RowShape<T, NCH>::CPL;
     constexpr int U = 2;
     __shared__ uint64_t lds[4][CAP];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane & 15, rg = lane >> 4;
     const int qi = blockIdx.x;
 
-    float q[CPL][EPC];
+    float q[1][CPL][EPC];
 #pragma unroll
     for (int i = 0; i < CPL; ++i)
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) q[i][e] = qn[(int64_t)qi * ld + (sub + 16 * i) * EPC + e];
+        for (int e = 0; e < EPC; ++e) q[0][i][e] = qn[(int64_t)qi * ld + (sub + 16 * i) * EPC + e];
 
     const uint32_t n = cnt[qi];
     const int nn = (int)min<uint32_t>(n, (uint32_t)cap);
@@ -873,15 +872,9 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = j0 + u * 4 + rg;
-            float acc = 0.f;
-#pragma unroll
-            for (int i = 0; i < CPL; ++i) {
-                float f[EPC];
-                unpack16<T>(x[u][i], f);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) acc = fmaf(f[e], q[i][e], acc);
-            }
-            const float s = sum16(acc);
+            float acc[1];
+            RC_ROW_FMA16(T, 1, CPL, EPC, x[u], q, acc);
+            const float s = sum16(acc[0]);
             tk.reserve(4);
             if constexpr (MASKED) tk.push(sub == 0 && j < nn && ((mw[u] >> (rr[u] & 31u)) & 1u) != 0u, make_key(s, rr[u]));
             else tk.push(sub == 0 && j < nn, make_key(s, rr[u]));
@@ -890,20 +883,12 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
     tk.compact();
     __syncthreads();
     if (wave == 0) {
-        for (int w = 1; w < 4; ++w)
-            for (int j = 0; j < k; j += 64) {
-                const uint64_t key = (j + lane < k) ? as_lds(&lds[w][0])[j + lane] : KEY_EMPTY;
-                tk.reserve(64);
-                tk.push(key != KEY_EMPTY, key);
-            }
-        tk.compact();
+        RC_FOLD_WAVE_LISTS(&lds[w][0], tk, k, lane);
         for (int j = lane; j < k; j += 64) {
             const uint64_t key = tk.buf[j];
             keys[(int64_t)qi * k + j] = key;
             if (final_pass) {
-                const bool ok = key != KEY_EMPTY;
-                out_scores[(int64_t)qi * k + j] = ok ? key_score(key) : -INFINITY;
-                out_rows[(int64_t)qi * k + j] = ok ? row_base + (int64_t)key_idx(key) * row_stride : -1;
+                RC_EMIT_KEY(key, row_base, row_stride, out_scores[(int64_t)qi * k + j], out_rows[(int64_t)qi * k + j]);
             }
         }
         if (lane == 0) {
@@ -918,39 +903,22 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
 }
 
 // ------------------------------------------------------------------ host ---
-template <typename T, int NCH>
-void launch_rescore_cap(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
-    const int cap = topk_cap(p.k);
-#define RC_RESCORE_M(CAPV, MASKEDV)                                                                                       \
-    hipLaunchKernelGGL((rescore_kernel<T, NCH, CAPV, MASKEDV>), dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn, \
-                       p.k, ws.cnt, ws.cand, ws.cap, ws.keys, ws.eps, ws.thr, ws.flags, ws.ovf, final_pass, p.row_base,    \
-                       p.row_stride, p.out_scores, p.out_rows, p.mask)
-#define RC_RESCORE(CAPV)                       \
-    do {                                       \
-        if (p.mask != nullptr) RC_RESCORE_M(CAPV, true); \
-        else RC_RESCORE_M(CAPV, false);        \
-    } while (0)
-    if (cap <= 128) RC_RESCORE(128);
-    else if (cap <= 256) RC_RESCORE(256);
-    else RC_RESCORE(512);
-#undef RC_RESCORE
-#undef RC_RESCORE_M
-    RC_LAUNCH_CHECK();
-}
-
 template <typename T>
 void launch_rescore(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
-    switch (p.nch) {
-        case 1: return launch_rescore_cap<T, 1>(p, ws, final_pass, s);
-        case 2: return launch_rescore_cap<T, 2>(p, ws, final_pass, s);
-        case 3: return launch_rescore_cap<T, 3>(p, ws, final_pass, s);
-        case 4: return launch_rescore_cap<T, 4>(p, ws, final_pass, s);
-        case 6: return launch_rescore_cap<T, 6>(p, ws, final_pass, s);
-        case 8: return launch_rescore_cap<T, 8>(p, ws, final_pass, s);
-        case 12: return launch_rescore_cap<T, 12>(p, ws, final_pass, s);
-        case 16: return launch_rescore_cap<T, 16>(p, ws, final_pass, s);
-        default: throw Error(RC_ERR_UNSUPPORTED, "unsupported row width");
-    }
+    const bool ok = with_nch(p.nch, [&](auto nch) {
+        with_topk_cap(topk_cap(p.k), [&](auto cap) {
+            auto launch = [&](auto masked) {
+                hipLaunchKernelGGL((rescore_kernel<T, decltype(nch)::value, decltype(cap)::value, decltype(masked)::value>),
+                                   dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn, p.k, ws.cnt, ws.cand, ws.cap, ws.keys,
+                                   ws.eps, ws.thr, ws.flags, ws.ovf, final_pass, p.row_base, p.row_stride, p.out_scores, p.out_rows,
+                                   p.mask);
+            };
+            if (p.mask != nullptr) launch(std::true_type{});
+            else launch(std::false_type{});
+        });
+    });
+    if (!ok) throw Error(RC_ERR_UNSUPPORTED, "unsupported row width");
+    RC_LAUNCH_CHECK();
 }
 
 int batch_stage_ratio(int k, int cap, int inflation) {
@@ -1069,12 +1037,13 @@ void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
     RC_REQUIRE(p.n_rows > 0, RC_ERR_INVALID, "batched search over an empty range");
     if (p.rows8 != nullptr) {
         RC_REQUIRE(i8_filter_supported(p.ld), RC_ERR_UNSUPPORTED, "int8 filter needs ld 256, 512 or 768");
-        if (p.dtype == RC_F16) return run_batched_i8<f16_t>(p, ws, s, timer);
-        if (p.dtype == RC_BF16) return run_batched_i8<bf16_t>(p, ws, s, timer);
-        if (p.dtype == RC_F32) return run_batched_i8<float>(p, ws, s, timer);
+        if (p.dtype == RC_F16 || p.dtype == RC_BF16 || p.dtype == RC_F32)
+            return dispatch_dtype(p.dtype, [&](auto t) { run_batched_i8<decltype(t)>(p, ws, s, timer); });
     }
-    if (p.dtype == RC_F16) return run_batched<f16_t>(p, ws, s, timer);
-    if (p.dtype == RC_BF16) return run_batched<bf16_t>(p, ws, s, timer);
+    if (p.dtype == RC_F16 || p.dtype == RC_BF16)  // the MFMA operand dtypes
+        return dispatch_dtype(p.dtype, [&](auto t) {
+            if constexpr (!std::is_same_v<decltype(t), float>) run_batched<decltype(t)>(p, ws, s, timer);
+        });
     throw Error(RC_ERR_UNSUPPORTED, "batched MFMA search needs an f16 or bf16 index (or the int8 filter copy)");
 }
 
@@ -1105,41 +1074,23 @@ void BatchWs::ensure(int nq, int k, int64_t ld, int dtype_bytes) {
 }
 
 void BatchWs::release() {
-    dfree(qn);
-    dfree(qh);
-    dfree(eps);
-    dfree(thr);
-    dfree(cnt);
-    dfree(cand);
-    dfree(keys);
-    dfree(flags);
-    dfree(sq);
-    dfree(aq);
-    dfree(ovf);
-    dfree(fb_partial);
-    qn = nullptr;
-    qh = nullptr;
-    eps = thr = nullptr;
-    cnt = cand = nullptr;
-    keys = nullptr;
-    flags = ovf = nullptr;
-    sq = aq = nullptr;
-    fb_partial = nullptr;
-    fb_blocks = 0;
-    nq_cap = k_cap = 0;
-    ld_cap = 0;
+    for (void *p : {(void *)qn, qh, (void *)eps, (void *)thr, (void *)cnt, (void *)cand, (void *)keys, (void *)flags, (void *)sq,
+                    (void *)aq, (void *)ovf, (void *)fb_partial})
+        dfree(p);
+    *this = BatchWs{};
 }
 
 }  // namespace rc
 
 #if defined(RC_GEMM_ABLATION)
-// diagnostic builds: log2 of the bytes of rows per filter sub-launch (31 = the product's 2 GB)
+// diagnostic builds: the int8 filter's row DMA cache policy (0, or 2 = nontemporal)
 extern "C" int rc_diag_set_filter_aux(int aux) {
     return rc::guard([&] {
         RC_REQUIRE(aux == 0 || aux == 2, RC_ERR_INVALID, "aux 0 or 2");
         rc::g_diag_filter_aux = aux;
     });
 }
+// diagnostic builds: log2 of the bytes of rows per filter sub-launch (31 = the product's 2 GB)
 extern "C" int rc_diag_set_filter_split(int log2_bytes) {
     return rc::guard([&] {
         RC_REQUIRE(log2_bytes >= 24 && log2_bytes <= 40, RC_ERR_INVALID, "log2 bytes in [24, 40]");

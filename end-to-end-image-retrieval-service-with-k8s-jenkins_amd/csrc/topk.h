@@ -155,4 +155,42 @@ struct WaveTopK {
     }
 };
 
+// The two rules below are statement macros, expanded in place at every site.  As functions they
+// are simplified on their own before they are inlined, and some kernels then compile to other
+// code than before (the selects of RC_EMIT_KEY stop folding into one branch in three kernels,
+// a few scan / rescore instantiations reschedule around the fold); in place, every kernel has
+// the instructions it had when each site spelt these lines out.
+
+// A 4-wave block's last selection step, on wave 0 only, after every wave's compact() and a block
+// barrier: fold the other three waves' lists (k sorted keys each; LIST is a pointer to wave w's,
+// an expression in `w`) into wave 0's WaveTopK TK and compact.  Sites: merge_partial_lists,
+// merge_heads_kernel, merge_lists_kernel (through fold_wave_lists), scan_rows_q, rescore_kernel.
+#define RC_FOLD_WAVE_LISTS(LIST, TK, K, LANE)                                                \
+    do {                                                                                     \
+        for (int w = 1; w < 4; ++w) {                                                        \
+            const lds_u64 *src_ = as_lds(LIST);                                              \
+            for (int j_ = 0; j_ < (K); j_ += 64) {                                           \
+                const uint64_t key_ = (j_ + (LANE) < (K)) ? src_[j_ + (LANE)] : KEY_EMPTY;   \
+                (TK).reserve(64);                                                            \
+                (TK).push(key_ != KEY_EMPTY, key_);                                          \
+            }                                                                                \
+        }                                                                                    \
+        (TK).compact();                                                                      \
+    } while (0)
+template <int CAP>
+__device__ __forceinline__ void fold_wave_lists(uint64_t *lds, int wave_stride, WaveTopK<CAP> &tk, int k) {
+    const int lane = threadIdx.x & 63;
+    RC_FOLD_WAVE_LISTS(lds + w * wave_stride, tk, k, lane);
+}
+
+// A key as a search result: SCORE = its score, ROW = BASE + local row * STRIDE, or (-inf, -1)
+// for an empty slot.  Sites: merge_partials_kernel, merge_heads_kernel, merge_lists_kernel
+// (BASE 0, STRIDE 1), rescore_kernel, query1_finish: every search output.
+#define RC_EMIT_KEY(KEY, BASE, STRIDE, SCORE, ROW)                                \
+    do {                                                                          \
+        const bool ok_ = (KEY) != KEY_EMPTY;                                      \
+        (SCORE) = ok_ ? key_score(KEY) : -INFINITY;                               \
+        (ROW) = ok_ ? (BASE) + (int64_t)key_idx(KEY) * (STRIDE) : -1;             \
+    } while (0)
+
 }  // namespace rc

@@ -1,18 +1,20 @@
 #!/usr/bin/env python3
 """Compare the device code of two source trees, kernel by kernel.  CPU only.
 
-    tools/kernel_asm_diff.py A B [-D MACRO ...] [-o report.txt] [--show N]
+    tools/kernel_asm_diff.py A B [-D MACRO ...] [-o report.txt] [--show N] [--allow-removed NAME ...]
 
 A and B are each a source tree (a directory holding the package with build.py and csrc/) or
 a git revision of this repository, which is exported to a temporary directory.  Every
 csrc/*.hip of both is compiled to gfx950 assembly with the tree's own build.py CFLAGS
 (hipcc --cuda-device-only -S), the assembly is split per kernel symbol, and each kernel is
 reported as identical (same instruction stream and same .amdhsa_* block), differing, only in
-A or only in B.  Exit status 0 only if every kernel of every source is identical.
+A or only in B.  Exit status 0 only if every kernel of every source is identical; a kernel
+deleted on purpose is named with --allow-removed (its demangled name without template and
+function arguments, e.g. rc::some_kernel: every instantiation), and then may be only in A.
 
 The comparison is a plain text diff after dropping comments and renumbering the
-compiler's local labels (.LBB<function>_<block>: the function number depends on the order
-in which kernels are emitted, not on their code).  Refactors that must not change device
+compiler's local labels (.LBB<function>_<block> and the long-branch .Lpost_getpc<n>: the
+function number and n depend on the order in which kernels are emitted, not on their code).  Refactors that must not change device
 code (moving kernels between headers, merging duplicated device helpers) are checked with
     tools/kernel_asm_diff.py <parent revision> .
 """
@@ -59,7 +61,7 @@ def compile_asm(build, src: str, extra: list[str], out: str) -> str:
     return open(out).read()
 
 
-LOCAL_LABEL = re.compile(r"\.L(BB|func_begin|func_end|tmp)(\d+)")
+LOCAL_LABEL = re.compile(r"\.L(BB|func_begin|func_end|tmp|post_getpc)(\d+)")
 
 
 def normalise(lines: list[str]) -> list[str]:
@@ -119,6 +121,8 @@ def main() -> int:
     ap.add_argument("--show", type=int, default=40, help="diff lines shown per differing kernel")
     ap.add_argument("--only", action="append", default=[], metavar="NAME", help="only csrc/NAME.hip (default: every source)")
     ap.add_argument("--keep", metavar="DIR", help="keep the assembly files (A_<source>.s, B_<source>.s) in DIR")
+    ap.add_argument("--allow-removed", action="append", default=[], metavar="NAME",
+                    help="a kernel that may be only in A (demangled name without template / function arguments)")
     ap.add_argument("-j", dest="jobs", type=int, default=min(8, os.cpu_count() or 4))
     args = ap.parse_args()
     extra = ["-D" + d for d in args.defines]
@@ -156,6 +160,7 @@ def main() -> int:
 
     say(f"kernel_asm_diff  A = {args.a}  B = {args.b}  flags: {' '.join(extra) or '(product build)'}")
     total = {"identical": 0, "differing": 0, "only in A": 0, "only in B": 0}
+    removed = 0  # kernels only in A that --allow-removed names
     for name in sorted(set(srcs["A"]) | set(srcs["B"])):
         ka, kb = asm.get(("A", name), {}), asm.get(("B", name), {})
         status = {}
@@ -168,7 +173,9 @@ def main() -> int:
         say(f"{name}: {len(status)} kernels: " + ", ".join(f"{count[s]} {s}" for s in total))
         pretty = demangle(list(status))
         for k, s in status.items():
-            say(f"  {s:10s} {pretty[k]}")
+            allowed = s == "only in A" and re.split(r"[<(]", pretty[k])[0].split()[-1] in args.allow_removed
+            removed += allowed
+            say(f"  {s:10s} {pretty[k]}" + ("  (allowed: --allow-removed)" if allowed else ""))
             if s == "differing":
                 for part, x, y in (("instructions", ka[k][0], kb[k][0]), (".amdhsa", ka[k][1], kb[k][1])):
                     d = list(difflib.unified_diff(x, y, "A", "B", lineterm="", n=1))
@@ -178,8 +185,9 @@ def main() -> int:
                         say(f"      {part}: ... {len(d) - args.show} more diff lines")
     say()
     say("total: " + ", ".join(f"{total[s]} {s}" for s in total))
-    ok = total["differing"] == 0 and total["only in A"] == 0 and total["only in B"] == 0
-    say("RESULT: " + ("device code identical" if ok else "DEVICE CODE DIFFERS"))
+    ok = total["differing"] == 0 and total["only in A"] == removed and total["only in B"] == 0
+    say("RESULT: " + ("DEVICE CODE DIFFERS" if not ok else
+                      f"device code identical, {removed} kernel(s) removed as allowed" if removed else "device code identical"))
     if args.report:
         os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
         with open(args.report, "w") as f:
