@@ -153,6 +153,7 @@ SIGNATURES = {
 DIAG_SIGNATURES = {
     "rc_diag_set_gemm_variant": (C.c_int, [_vp, _i32]),
     "rc_diag_set_stamps": (C.c_int, [_vp]),
+    "rc_diag_set_qkv_sched": (C.c_int, [_vp, _i32]),
     "rc_diag_set_band_skip": (C.c_int, [_i32]),
     "rc_diag_set_filter_split": (C.c_int, [_i32]),
     "rc_diag_set_filter_aux": (C.c_int, [_i32]),

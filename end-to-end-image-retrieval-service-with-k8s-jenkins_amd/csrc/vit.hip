@@ -92,6 +92,7 @@ struct rc_model {
     size_t resize_tmp_bytes = 0;
     KernelTimer timers[T_COUNT];
     int gemm_variant = GEMM_AUTO;  // diagnostic builds only: rc_diag_set_gemm_variant
+    int qkv_sched = -1;            // diagnostic builds only: rc_diag_set_qkv_sched (-1: the product kernel)
     int ncu = 256;                 // compute units (persistent grids)
     int split = 2;                 // batch parts encoded concurrently (rc_model_set_parts);
                                    // 2 beats 3 and 4 by 1-2 % at batch 256 (profiles/r01j_ab_parts.jsonl)
@@ -533,6 +534,10 @@ void encode(rc_model *m, const uint8_t *images, int i0, int n, float *raw, float
             // QKV projection + attention in one launch (qkv_attention.h): no qkv tensor
             const int tq = m->timers[T_QKV].begin(s);
             QkvAttnArgs q{ln, L.w_qkv_f, L.b_qkv_f, L.c_qkv, st, attn, n, c.ln_eps, scale * 1.4426950408889634f};
+#if defined(RC_GEMM_ABLATION)
+            if (m->qkv_sched >= 0) launch_qkv_attention_diag(m->qkv_sched, q, n, s);
+            else
+#endif
             hipLaunchKernelGGL(qkv_attention_kernel, dim3(qkv_attention_grid(n)), dim3(64 * QA_WAVES), 0, s, q);
             RC_LAUNCH_CHECK();
             m->timers[T_QKV].end(tq, s, 2.0 * M * 3 * H * H + 4.0 * n * c.heads * (double)T * T * (H / c.heads));
@@ -1004,6 +1009,18 @@ extern "C" int rc_diag_set_gemm_variant(rc_model *m, int variant) {
         std::lock_guard<std::mutex> lk(m->mu);
         m->clear_graphs();
         m->gemm_variant = variant;
+    });
+}
+
+// diagnostic builds: the fused QKV + attention kernel's schedule variant (qkv_attention.h: bits
+// QA_S_EPI | QA_S_KSTEP, + 8 for the phase stamps), or -1 for the product kernel
+extern "C" int rc_diag_set_qkv_sched(rc_model *m, int v) {
+    return guard([&] {
+        RC_REQUIRE(m, RC_ERR_INVALID, "null model");
+        RC_REQUIRE(v == -1 || (v & ~(8 | 3)) == 0, RC_ERR_INVALID, "QKV schedule variant: -1 product, 0 .. 3 (+ 8: stamps)");
+        std::lock_guard<std::mutex> lk(m->mu);
+        m->clear_graphs();
+        m->qkv_sched = v;
     });
 }
 #endif

@@ -386,6 +386,15 @@ class VitMsnEmbedder:
             raise RuntimeError("GEMM variants are a diagnostic-build knob (tools/build_diag.sh)")
         check(fn(self._h, int(variant)))
 
+    def set_qkv_sched(self, variant: int) -> None:
+        """Diagnostic builds only: the fused QKV + attention kernel's schedule variant (bits: 1 the
+        epilogue's loads hoisted, 2 the K-step's DMA among its MFMAs behind counted LDS waits; + 8 for
+        the phase stamps), -1 the product kernel."""
+        fn = getattr(self.lib, "rc_diag_set_qkv_sched", None)
+        if fn is None:
+            raise RuntimeError("QKV schedule variants are a diagnostic-build knob (tools/build_diag.sh)")
+        check(fn(self._h, int(variant)))
+
     def timing_reset(self) -> None:
         check(self.lib.rc_model_timing_reset(self._h))
 
