@@ -95,6 +95,8 @@ SIGNATURES = {
     "rc_index_data": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "rc_index_reserve": (C.c_int, [_vp, _i32, _i32]),
     "rc_index_upsert": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "rc_index_move_rows": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
+    "rc_sharded_move_rows": (C.c_int, [_vp, _vp, _vp, _i64]),
     "rc_index_fetch": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "rc_index_fetch_stored": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "rc_index_search": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),

@@ -63,6 +63,52 @@ __global__ __launch_bounds__(256) void fetch_kernel(const T *__restrict__ rows, 
     for (int c = lane; c < dim; c += 64) out[v * dim + c] = Elem<T>::load(rows, r * ld + c) * nrm;
 }
 
+// Row move (Index.delete's swap-remove compaction): stored row dst_idx[v] of the destination
+// block = stored row src_idx[v] of the source block, bit for bit, with its f32 norm.  A null
+// list means "contiguous from row 0 of that block", so the one kernel moves rows inside a
+// shard (both lists, one block), packs a shard's outgoing rows into a staging block (source
+// list only) and unpacks a staging block into a shard's rows (destination list only).  One wave
+// per row, 16-byte pieces (ld is a multiple of 128 elements: a row is a whole number of them for
+// every dtype), four loads in flight per lane; grid-stride over the rows.  An index outside its
+// block is skipped, never read or written (the guard of upsert_kernel).  The int8 filter copy is
+// not moved: the host re-quantises the destination slots (launch_move_rows).
+// Callers keep the rows read and the rows written disjoint and every destination distinct.
+template <typename T>
+__global__ __launch_bounds__(256) void move_rows_kernel(const T *__restrict__ src_rows, const float *__restrict__ src_norms,
+                                                       const int64_t *__restrict__ src_idx, int64_t src_cap,
+                                                       T *__restrict__ dst_rows, float *__restrict__ dst_norms,
+                                                       const int64_t *__restrict__ dst_idx, int64_t dst_cap, int64_t ld,
+                                                       int64_t n) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * 4;
+    const int pieces = (int)(ld * (int64_t)sizeof(T) / 16);
+    for (int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); v < n; v += nw) {
+        const int64_t rs = src_idx ? src_idx[v] : v;
+        const int64_t rd = dst_idx ? dst_idx[v] : v;
+        if (rs < 0 || rs >= src_cap || rd < 0 || rd >= dst_cap) continue;  // wave-uniform
+        const uint4 *sp = reinterpret_cast<const uint4 *>(src_rows + rs * ld);
+        uint4 *dp = reinterpret_cast<uint4 *>(dst_rows + rd * ld);
+        // a lane's pieces in groups of 4, then 2, then 1: inside a group nothing is predicated, so
+        // its loads are all issued before the first store waits (with a bounds test per piece
+        // hipcc sinks every load into its store's branch: one load in flight)
+        int c = lane;
+        for (; c + 192 < pieces; c += 256) {
+            const uint4 t0 = sp[c], t1 = sp[c + 64], t2 = sp[c + 128], t3 = sp[c + 192];
+            dp[c] = t0;
+            dp[c + 64] = t1;
+            dp[c + 128] = t2;
+            dp[c + 192] = t3;
+        }
+        for (; c + 64 < pieces; c += 128) {
+            const uint4 t0 = sp[c], t1 = sp[c + 64];
+            dp[c] = t0;
+            dp[c + 64] = t1;
+        }
+        if (c < pieces) dp[c] = sp[c];
+        if (lane == 0) dst_norms[rd] = src_norms[rs];
+    }
+}
+
 // splitmix64 finaliser: the synthetic-row generator (reproducible in numpy).
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -387,6 +433,21 @@ void launch_upsert(rc_index *h, const float *vecs, const int64_t *src_idx, int64
     launch_quantize<T>(h, slots, 0, n, s);
 }
 
+// rows dst_idx[v] of `to` = rows src_idx[v] of `from`; a null index stands for the staging
+// block `stage` on that side (and its list is then null: contiguous).  Refreshes the int8
+// filter copy of the written slots, as launch_upsert does: i8_slot's layout keeps one writer.
+template <typename T>
+void launch_move_rows(rc_index *from, const int64_t *src_idx, rc_index *to, const int64_t *dst_idx, const RowBlock &stage,
+                      int64_t n, hipStream_t s) {
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 3) / 4, kMaxBlocks);
+    hipLaunchKernelGGL(move_rows_kernel<T>, dim3(grid), dim3(256), 0, s, (const T *)(from ? from->rows : stage.rows),
+                       (const float *)(from ? from->norms : stage.norms), src_idx, from ? from->capacity : stage.cap,
+                       (T *)(to ? to->rows : stage.rows), to ? to->norms : stage.norms, dst_idx,
+                       to ? to->capacity : stage.cap, (from ? from : to)->ld, n);
+    RC_LAUNCH_CHECK();
+    if (to != nullptr) launch_quantize<T>(to, dst_idx, 0, n, s);
+}
+
 template <typename T>
 void launch_fetch(rc_index *h, const int64_t *slots, int64_t n, float *out, bool stored, hipStream_t s) {
     const unsigned grid = (unsigned)((n + 3) / 4);
@@ -503,6 +564,33 @@ void index_upsert_gather(rc_index *h, const float *vecs, const int64_t *src_idx,
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceScope ds(h->device);
     dispatch_dtype(h->dtype, [&](auto t) { launch_upsert<decltype(t)>(h, vecs, src_idx, n, rows, s); });
+}
+
+// Internal (sharded.hip) and rc_index_move_rows: move n stored rows from `from` (rows src_idx[i])
+// to `to` (rows dst_idx[i]) on the current stream `s` of their device.  One of the two may be
+// null: that side is the staging block `stage` (same device), read or written contiguously from
+// its row 0, and its list is null (pack / unpack).  from == to moves inside a shard; two
+// different handles must share a device and a layout (two shards of one GPU).
+void index_move_rows(rc_index *from, const int64_t *src_idx, rc_index *to, const int64_t *dst_idx, const RowBlock &stage,
+                     int64_t n, hipStream_t s) {
+    if (n == 0) return;
+    rc_index *any = from ? from : to;
+    RC_REQUIRE(any != nullptr, RC_ERR_INVALID, "null index");
+    RC_REQUIRE((from != nullptr) == (src_idx != nullptr) && (to != nullptr) == (dst_idx != nullptr), RC_ERR_INVALID,
+               "a row list goes with an index, none with the staging block");
+    if (from && to && from != to)
+        RC_REQUIRE(from->device == to->device && from->ld == to->ld && from->dtype == to->dtype, RC_ERR_INVALID,
+                   "a direct move needs two shards of one device and one layout");
+    std::unique_lock<std::mutex> l1, l2;
+    if (from && to && from != to) {
+        std::lock(from->mu, to->mu);
+        l1 = std::unique_lock<std::mutex>(from->mu, std::adopt_lock);
+        l2 = std::unique_lock<std::mutex>(to->mu, std::adopt_lock);
+    } else {
+        l1 = std::unique_lock<std::mutex>(any->mu);
+    }
+    DeviceScope ds(any->device);
+    dispatch_dtype(any->dtype, [&](auto t) { launch_move_rows<decltype(t)>(from, src_idx, to, dst_idx, stage, n, s); });
 }
 
 // Internal (sharded.hip, rc_sharded_query_host): one query as ONE launch (query1_kernel) —
@@ -766,6 +854,16 @@ int rc_index_upsert(rc_index *h, const float *vecs, int64_t n, const int64_t *ro
         std::lock_guard<std::mutex> lk(h->mu);
         DeviceScope ds(h->device);
         dispatch_dtype(h->dtype, [&](auto t) { launch_upsert<decltype(t)>(h, vecs, nullptr, n, rows, (hipStream_t)stream); });
+    });
+}
+
+int rc_index_move_rows(rc_index *h, const int64_t *src_rows, const int64_t *dst_rows, int64_t n, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(n >= 0, RC_ERR_INVALID, "negative count");
+        if (n == 0) return;
+        RC_REQUIRE(src_rows && dst_rows, RC_ERR_INVALID, "null buffer");
+        index_move_rows(h, src_rows, h, dst_rows, RowBlock{}, n, (hipStream_t)stream);
     });
 }
 

@@ -32,6 +32,14 @@ template <> struct Elem<bf16_t> {
 
 inline size_t dtype_size(int dtype) { return dtype == RC_F32 ? 4 : 2; }
 
+// A staging block of stored rows outside any index (row moves between shards, sharded.hip):
+// cap rows of ld elements in the storage dtype, and their f32 norms.
+struct RowBlock {
+    void *rows = nullptr;
+    float *norms = nullptr;
+    int64_t cap = 0;
+};
+
 // unpack one 16-B chunk into its 4 (f32) or 8 (f16/bf16) values
 template <typename T>
 __device__ __forceinline__ void unpack16(const uint4 &x, float *out);

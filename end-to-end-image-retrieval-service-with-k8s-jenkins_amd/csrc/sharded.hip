@@ -28,6 +28,8 @@
 namespace rc {
 void index_upsert_gather(rc_index *h, const float *vecs, const int64_t *src_idx, int64_t n, const int64_t *rows,
                          hipStream_t s);
+void index_move_rows(rc_index *from, const int64_t *src_idx, rc_index *to, const int64_t *dst_idx, const RowBlock &stage,
+                     int64_t n, hipStream_t s);
 bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int with_values, float *out_scores,
                   int64_t *out_rows, float *out_values, hipStream_t s, volatile unsigned **done = nullptr,
                   unsigned *seq = nullptr);
@@ -98,6 +100,15 @@ struct rc_sharded {
     std::vector<int64_t *> row_h;
     std::vector<float *> fo_h;     // [st_cap][dim] pinned host landing of fetched rows
     hipEvent_t ev_gather = nullptr;  // leader stream: the remote subsets are gathered
+    // row moves (rc_sharded_move_rows): per shard the local source / destination rows of one
+    // round (kMoveRound entries, pinned + device, made on the first move), and the staging
+    // blocks of stored rows that cross devices: mv_out on the source, mv_in on the destination
+    // (mv_cap rows each, grown on demand up to kMoveRound, reused)
+    bool mv_lists = false;
+    int64_t mv_cap = 0;
+    std::vector<int64_t *> mv_src_h, mv_dst_h, mv_src_d, mv_dst_d;
+    std::vector<RowBlock> mv_out, mv_in;
+    std::vector<hipEvent_t> ev_pack;  // per shard, on st[s]: its lists are copied and its outgoing rows packed
     // masked search (rc_sharded_search_masked): the caller's global bitmap de-interleaved into one
     // local bitmap per shard (pinned), and its copy on the shard's device; grown on demand
     int64_t mk_cap = 0;                // words per shard
@@ -197,6 +208,82 @@ void ensure_staging(rc_sharded *h, int64_t m) {
         h->fo_h[s] = (float *)hmalloc(vb);
     }
     h->st_cap = m2;
+}
+
+// Row moves run in rounds of this many (source, destination) pairs: the lists and the staging
+// blocks are sized by it, not by the call (a delete of millions of rows allocates no more).
+constexpr int64_t kMoveRound = 16384;
+
+void free_move_blocks(rc_sharded *h) {
+    for (int s = 0; s < h->n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        for (RowBlock *b : {&h->mv_out[s], &h->mv_in[s]}) {
+            dfree(b->rows);
+            dfree(b->norms);
+            *b = RowBlock{};
+        }
+    }
+    h->mv_cap = 0;
+}
+
+void free_move(rc_sharded *h) {
+    free_move_blocks(h);
+    for (int s = 0; s < h->n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        dfree(h->mv_src_d[s]);
+        dfree(h->mv_dst_d[s]);
+        hfree(h->mv_src_h[s]);
+        hfree(h->mv_dst_h[s]);
+        h->mv_src_d[s] = h->mv_dst_d[s] = h->mv_src_h[s] = h->mv_dst_h[s] = nullptr;
+        if (h->ev_pack[s]) (void)hipEventDestroy(h->ev_pack[s]);
+        h->ev_pack[s] = nullptr;
+    }
+    h->mv_lists = false;
+}
+
+// The lists of one round per shard, once; and staging blocks of at least m rows on every shard
+// that stages (callers pass m <= kMoveRound; m = 0: no pair crosses devices).
+void ensure_move(rc_sharded *h, int64_t m, size_t row_bytes) {
+    if (!h->mv_lists) {
+        try {
+            for (int s = 0; s < h->n; ++s) {
+                DeviceScope ds(h->dev[s]);
+                h->mv_src_d[s] = (int64_t *)dmalloc((size_t)kMoveRound * sizeof(int64_t));
+                h->mv_dst_d[s] = (int64_t *)dmalloc((size_t)kMoveRound * sizeof(int64_t));
+                h->mv_src_h[s] = (int64_t *)hmalloc((size_t)kMoveRound * sizeof(int64_t));
+                h->mv_dst_h[s] = (int64_t *)hmalloc((size_t)kMoveRound * sizeof(int64_t));
+                RC_HIP(hipEventCreateWithFlags(&h->ev_pack[s], hipEventDisableTiming));
+                // stored rows go straight from their source GPU to their destination GPU
+                for (int t = 0; t < s; ++t) {
+                    if (h->dev[t] == h->dev[s]) continue;
+                    if (hipDeviceEnablePeerAccess(h->dev[t], 0) != hipSuccess) (void)hipGetLastError();
+                    DeviceScope dt(h->dev[t]);
+                    if (hipDeviceEnablePeerAccess(h->dev[s], 0) != hipSuccess) (void)hipGetLastError();
+                }
+            }
+        } catch (...) {
+            free_move(h);
+            throw;
+        }
+        h->mv_lists = true;
+    }
+    if (m <= h->mv_cap) return;
+    const int64_t m2 = std::min<int64_t>(kMoveRound, std::max<int64_t>(m, 2 * h->mv_cap));
+    free_move_blocks(h);
+    try {
+        for (int s = 0; s < h->n; ++s) {
+            DeviceScope ds(h->dev[s]);
+            for (RowBlock *b : {&h->mv_out[s], &h->mv_in[s]}) {
+                b->rows = dmalloc((size_t)m2 * row_bytes);
+                b->norms = (float *)dmalloc((size_t)m2 * sizeof(float));
+                b->cap = m2;
+            }
+        }
+    } catch (...) {
+        free_move_blocks(h);
+        throw;
+    }
+    h->mv_cap = m2;
 }
 
 // rows of the global range [0, n_rows) that shard s holds
@@ -312,6 +399,7 @@ void ensure_query(rc_sharded *h, int64_t bytes) {
 void destroy(rc_sharded *h) {
     free_search(h);
     free_staging(h);
+    free_move(h);
     free_mask(h);
     if (h->qs) {
         free_query(h);
@@ -370,6 +458,13 @@ int rc_sharded_create(int n_shards, const int *devices, int dim, int dtype, int6
         h->idx_h.assign(n_shards, nullptr);
         h->row_h.assign(n_shards, nullptr);
         h->fo_h.assign(n_shards, nullptr);
+        h->mv_src_h.assign(n_shards, nullptr);
+        h->mv_dst_h.assign(n_shards, nullptr);
+        h->mv_src_d.assign(n_shards, nullptr);
+        h->mv_dst_d.assign(n_shards, nullptr);
+        h->mv_out.assign(n_shards, RowBlock{});
+        h->mv_in.assign(n_shards, RowBlock{});
+        h->ev_pack.assign(n_shards, nullptr);
         h->mk_h.assign(n_shards, nullptr);
         h->mk_d.assign(n_shards, nullptr);
         h->ev_mask.assign(n_shards, nullptr);
@@ -520,6 +615,117 @@ int rc_sharded_upsert(rc_sharded *h, const float *vecs, int64_t n, const int64_t
             if (cnt[s] == 0) continue;
             DeviceScope ds(h->dev[s]);
             RC_HIP(hipStreamSynchronize(h->st[s]));
+        }
+    });
+}
+
+int rc_sharded_move_rows(rc_sharded *h, const int64_t *src_rows, const int64_t *dst_rows, int64_t n) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(n >= 0, RC_ERR_INVALID, "negative count");
+        if (n == 0) return;
+        RC_REQUIRE(src_rows && dst_rows, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const int ns = h->n;
+        {  // everything is checked before the first device call: a refused call has moved nothing
+            std::vector<int64_t> a(src_rows, src_rows + n), b(dst_rows, dst_rows + n);
+            for (int64_t i = 0; i < n; ++i)
+                RC_REQUIRE(a[i] >= 0 && a[i] / ns < h->cap && b[i] >= 0 && b[i] / ns < h->cap, RC_ERR_INVALID,
+                           "row out of capacity");
+            std::sort(a.begin(), a.end());
+            std::sort(b.begin(), b.end());
+            RC_REQUIRE(std::adjacent_find(a.begin(), a.end()) == a.end(), RC_ERR_INVALID, "a source row occurs twice");
+            RC_REQUIRE(std::adjacent_find(b.begin(), b.end()) == b.end(), RC_ERR_INVALID, "a destination row occurs twice");
+            for (int64_t i = 0, j = 0; i < n && j < n;) {
+                RC_REQUIRE(a[i] != b[j], RC_ERR_INVALID, "a row is both a source and a destination");
+                if (a[i] < b[j]) ++i; else ++j;
+            }
+        }
+        int64_t ld = 0;
+        check_status(rc_index_info(h->shard[0], nullptr, nullptr, nullptr, &ld));
+        const size_t rb = (size_t)ld * dtype_size(h->dtype);
+        // a pair (source shard a, destination shard b) is staged when its rows cross devices (or
+        // after rc_sharded_force_remote, as if they did); two shards of one GPU move directly
+        auto staged = [&](int a, int b) { return a != b && (h->dev[a] != h->dev[b] || h->remote[a] || h->remote[b]); };
+        // per (a, b): pairs, offset of the segment in a's source list and in b's destination list;
+        // in both lists the staged segments come last, so one pack and one unpack launch per shard
+        // cover them and a segment's place in the staging block is its offset past the first
+        std::vector<int64_t> cnt((size_t)ns * ns), soff((size_t)ns * ns), doff((size_t)ns * ns), cur((size_t)ns * ns);
+        std::vector<int64_t> s_tot(ns), s_stg(ns), d_tot(ns), d_stg(ns);  // list lengths, first staged entry
+        for (int64_t r0 = 0; r0 < n; r0 += kMoveRound) {
+            const int64_t m = std::min<int64_t>(kMoveRound, n - r0);
+            std::fill(cnt.begin(), cnt.end(), 0);
+            for (int64_t i = r0; i < r0 + m; ++i) ++cnt[(size_t)(src_rows[i] % ns) * ns + dst_rows[i] % ns];
+            int64_t need = 0;
+            for (int a = 0; a < ns; ++a) {
+                int64_t so = 0, dof = 0;
+                for (int pass = 0; pass < 2; ++pass) {
+                    if (pass == 1) s_stg[a] = so, d_stg[a] = dof;
+                    for (int b = 0; b < ns; ++b) {
+                        if (staged(a, b) == (pass == 1)) soff[(size_t)a * ns + b] = so, so += cnt[(size_t)a * ns + b];
+                        if (staged(b, a) == (pass == 1)) doff[(size_t)b * ns + a] = dof, dof += cnt[(size_t)b * ns + a];
+                    }
+                }
+                s_tot[a] = so;
+                d_tot[a] = dof;
+                need = std::max(need, std::max(so - s_stg[a], dof - d_stg[a]));
+            }
+            ensure_move(h, need, rb);
+            std::fill(cur.begin(), cur.end(), 0);
+            for (int64_t i = r0; i < r0 + m; ++i) {
+                const int64_t gs = src_rows[i], gd = dst_rows[i];
+                const int a = (int)(gs % ns), b = (int)(gd % ns);
+                const size_t ab = (size_t)a * ns + b;
+                const int64_t k = cur[ab]++;
+                h->mv_src_h[a][soff[ab] + k] = gs / ns;
+                h->mv_dst_h[b][doff[ab] + k] = gd / ns;
+            }
+            // Sources and destinations never overlap (validated above; Index.delete's sources are
+            // rows at or past the new length, its destinations rows below it), so no row is read
+            // after it was written or written twice: the packs, the copies and the unpacks need no
+            // order among themselves beyond each pair's own chain (lists -> pack -> copy -> unpack).
+            for (int a = 0; a < ns; ++a) {  // each shard's stream: its lists, its own pairs, its pack
+                if (s_tot[a] == 0 && d_tot[a] == 0) continue;
+                DeviceScope ds(h->dev[a]);
+                hipStream_t sa = h->st[a];
+                if (s_tot[a])
+                    RC_HIP(hipMemcpyAsync(h->mv_src_d[a], h->mv_src_h[a], s_tot[a] * sizeof(int64_t), hipMemcpyHostToDevice, sa));
+                if (d_tot[a])
+                    RC_HIP(hipMemcpyAsync(h->mv_dst_d[a], h->mv_dst_h[a], d_tot[a] * sizeof(int64_t), hipMemcpyHostToDevice, sa));
+                const size_t aa = (size_t)a * ns + a;
+                index_move_rows(h->shard[a], h->mv_src_d[a] + soff[aa], h->shard[a], h->mv_dst_d[a] + doff[aa], RowBlock{},
+                                cnt[aa], sa);
+                index_move_rows(h->shard[a], h->mv_src_d[a] + s_stg[a], nullptr, nullptr, h->mv_out[a], s_tot[a] - s_stg[a], sa);
+                RC_HIP(hipEventRecord(h->ev_pack[a], sa));
+            }
+            for (int b = 0; b < ns; ++b) {  // each destination's stream: what other shards send it
+                if (d_tot[b] == 0) continue;
+                DeviceScope ds(h->dev[b]);
+                hipStream_t sb = h->st[b];
+                for (int a = 0; a < ns; ++a) {
+                    const size_t ab = (size_t)a * ns + b;
+                    if (a == b || cnt[ab] == 0) continue;
+                    RC_HIP(hipStreamWaitEvent(sb, h->ev_pack[a], 0));
+                    if (!staged(a, b)) {  // one GPU: a's source list is readable here
+                        index_move_rows(h->shard[a], h->mv_src_d[a] + soff[ab], h->shard[b], h->mv_dst_d[b] + doff[ab],
+                                        RowBlock{}, cnt[ab], sb);
+                        continue;
+                    }
+                    const int64_t from = soff[ab] - s_stg[a], to = doff[ab] - d_stg[b];
+                    RC_HIP(hipMemcpyPeerAsync((uint8_t *)h->mv_in[b].rows + (size_t)to * rb, h->dev[b],
+                                              (const uint8_t *)h->mv_out[a].rows + (size_t)from * rb, h->dev[a],
+                                              (size_t)cnt[ab] * rb, sb));
+                    RC_HIP(hipMemcpyPeerAsync(h->mv_in[b].norms + to, h->dev[b], h->mv_out[a].norms + from, h->dev[a],
+                                              (size_t)cnt[ab] * sizeof(float), sb));
+                }
+                index_move_rows(nullptr, nullptr, h->shard[b], h->mv_dst_d[b] + d_stg[b], h->mv_in[b], d_tot[b] - d_stg[b], sb);
+            }
+            // the pinned lists and the staging blocks are reused by the next round: finish here
+            for (int s = 0; s < ns; ++s) {
+                if (s_tot[s] == 0 && d_tot[s] == 0) continue;
+                DeviceScope ds(h->dev[s]);
+                RC_HIP(hipStreamSynchronize(h->st[s]));
+            }
         }
     });
 }

@@ -23,7 +23,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 import torch
 
-from . import _lib, metafilter
+from . import _lib, compaction, metafilter
 from ._lib import check, ptr, stream_ptr
 
 # query_batch(filter=..., mode="auto") takes the batched MFMA path when the unmasked conditions
@@ -145,6 +145,15 @@ class DeviceIndex:
         if rows.numel() != vecs.shape[0]:
             raise ValueError("rows and vectors differ in length")
         check(self.lib.rc_index_upsert(self.handle, ptr(vecs), vecs.shape[0], ptr(rows), stream_ptr(stream)))
+
+    def move_rows(self, src, dst, stream=None) -> None:
+        """Stored row dst[i] becomes a bit-for-bit copy of stored row src[i], norm included
+        (rc_index_move_rows).  The two lists must be disjoint and dst must hold no row twice."""
+        src = torch.as_tensor(src, dtype=torch.int64).to(self.device).contiguous()
+        dst = torch.as_tensor(dst, dtype=torch.int64).to(self.device).contiguous()
+        if src.numel() != dst.numel():
+            raise ValueError("src and dst differ in length")
+        check(self.lib.rc_index_move_rows(self.handle, ptr(src), ptr(dst), src.numel(), stream_ptr(stream)))
 
     def fetch_rows(self, rows: torch.Tensor, stream=None) -> torch.Tensor:
         rows = rows.to(device=self.device, dtype=torch.int64).contiguous()
@@ -548,6 +557,16 @@ class ShardSet:
             raise ValueError("rows and vectors differ in length")
         check(self.lib.rc_sharded_upsert(self.handle, ptr(vecs), vecs.shape[0], ptr(rows), stream_ptr(None)))
 
+    def move_rows(self, src, dst) -> None:
+        """Stored global row dst[i] becomes a copy of stored global row src[i]
+        (rc_sharded_move_rows; host lists, validated there: in capacity, no row twice in either
+        list, none in both).  Synchronous."""
+        src = torch.as_tensor(src, dtype=torch.int64).cpu().contiguous()
+        dst = torch.as_tensor(dst, dtype=torch.int64).cpu().contiguous()
+        if src.numel() != dst.numel():
+            raise ValueError("src and dst differ in length")
+        check(self.lib.rc_sharded_move_rows(self.handle, ptr(src), ptr(dst), src.numel()))
+
     def upsert_parts(self, parts) -> None:
         """Upsert vectors that already live on several devices (an ``EmbedderPool`` batch):
         ``parts`` = [(global rows: host i64 [m], vecs: f32 [m, dim] on any GPU)].  Each part's
@@ -679,7 +698,8 @@ class Index:
     ids (within one call the last occurrence of an id wins); ``query`` returns
     ``{"matches": [{"id", "score", ["values"], ["metadata"]}], "namespace": ""}``
     best first; ``fetch`` returns ``{"vectors": {id: {"id", "values",
-    "metadata"}}, "namespace": ""}``.
+    "metadata"}}, "namespace": ""}``; ``delete(ids=... | filter=... | delete_all=True)``
+    removes vectors and returns ``{}``.
 
     The rows live on ``shards`` shards (``devices``: one GPU per shard, entries
     may repeat; default one shard on ``device``), routed round-robin by the
@@ -718,13 +738,13 @@ class Index:
         self._ids: list[str] = []
         self._meta: dict[str, dict] = {}
         self._mu = threading.Lock()
-        # values the last query(include_values=True) fetched, valid until the next upsert: the
+        # values the last query(include_values=True) fetched, valid until the next upsert or delete: the
         # reference's search (retriever/utils.py:62-64) asks for values and its caller then
         # fetches the same ids (retriever/main.py:142) — each row leaves the GPU once
         self._gen = 0
         self._recent: tuple[int, dict[str, np.ndarray]] = (-1, {})
         # metadata-filter bitmaps, most recently used last: (canonical filter JSON, _gen) ->
-        # (bitmap, eligible count); any upsert bumps _gen, so stale entries can never be hit
+        # (bitmap, eligible count); any upsert or delete bumps _gen, so stale entries can never be hit
         self._bitmaps: dict[tuple[str, int], tuple[np.ndarray, int]] = {}
 
     @property
@@ -894,6 +914,72 @@ class Index:
         rows = self._plan_rows(items)
         self._device_write(self._set.upsert_rows, vecs, rows)
         self._commit_rows(items, rows)
+
+    def delete(self, ids: Sequence[str] | None = None, delete_all: bool = False, namespace: str = "",
+               filter: dict | None = None) -> dict:
+        """Pinecone's ``delete``: remove the vectors named by ``ids``, or every vector whose
+        metadata satisfies ``filter`` (``query``'s metadata filter), or all of them
+        (``delete_all=True``).  Exactly one of the three selects (``ValueError`` otherwise; an
+        empty ``filter`` selects nothing and does not count); unknown and repeated ids are
+        ignored.  Returns ``{}``.
+
+        The live rows stay dense (``compaction``): each deleted row below the new length is
+        overwritten with a surviving row of the tail, so at most as many stored rows move as
+        are deleted, no search kernel changes and unfiltered queries pay nothing.  Rows at or
+        past the new length keep stale bytes that no search scores (they all stop at
+        ``n_rows``); capacity never shrinks, and the next upserts reuse the freed rows.
+
+        If the device move raises, no id is removed: surviving ids are intact (moves only
+        write into rows of ids being deleted), but the ids being deleted may now hold another
+        vector's values.  The cached values and bitmaps are invalidated and the error is
+        re-raised; repeat the call."""
+        self._delete(ids, delete_all, filter)
+        return {}
+
+    def _delete(self, ids, delete_all, flt) -> int:
+        """``delete``'s body; returns how many vectors were removed (Pinecone's call reports
+        nothing; the package's ``/delete_images`` route answers with the count)."""
+        if flt is not None and not isinstance(flt, dict):
+            raise ValueError("filter must be a dict (Pinecone metadata filter) or None")
+        if isinstance(ids, (str, bytes)):
+            raise ValueError("ids must be a list of ids, not one string")
+        if (ids is not None) + bool(delete_all) + bool(flt) != 1:
+            raise ValueError("delete needs exactly one of ids, delete_all=True or a non-empty filter")
+        with self._mu:
+            if delete_all:
+                n = len(self._ids)
+                self._ids, self._rows, self._meta = [], {}, {}  # the stored rows are simply never searched again
+                self._gen += 1
+                return n
+            if ids is not None:
+                rows = sorted({self._rows[i] for i in ids if i in self._rows})
+            else:
+                bitmap, eligible = self._bitmap_locked(flt)
+                bits = np.unpackbits(bitmap.view(np.uint8), bitorder="little")[:len(self._ids)]
+                rows = np.flatnonzero(bits).tolist() if eligible else []
+            self._delete_rows_locked(rows)
+            return len(rows)
+
+    def _delete_rows_locked(self, rows: list[int]) -> None:
+        """rows: distinct live rows, ascending.  Plan, device moves, then the host maps in
+        O(len(rows)), then a new generation (no cached bitmap or value can be hit again)."""
+        if not rows:
+            return
+        n = len(self._ids)
+        src, dst = compaction.plan_compaction(n, rows, self._set.n)
+        if src:
+            self._device_write(self._set.move_rows, src, dst)
+        ids = self._ids
+        for r in rows:
+            vid = ids[r]
+            del self._rows[vid]
+            self._meta.pop(vid, None)
+        for s, d in zip(src, dst):
+            vid = ids[s]
+            ids[d] = vid
+            self._rows[vid] = d
+        del ids[n - len(rows):]
+        self._gen += 1
 
     def _bitmap_locked(self, flt) -> tuple[np.ndarray, int] | None:
         """The row-eligibility bitmap of a metadata filter and its eligible count (None for no

@@ -6,6 +6,8 @@ Contract kept (``ingesting/main.py:91-168``):
   POST /push_image   multipart ``file`` → {"message", "file_id", "gcs_path", "signed_url"}
                      400 "Only .jpg/.jpeg/.png allowed" / "Invalid image file"; 422 without ``file``
   POST /push_images  (batched form) repeated ``files`` → one such dict per image (ingesting.core.ingest_many)
+  POST /delete_images JSON ``{"ids": [...]}`` → {"deleted_count": ids that existed}; 422 without a list ``ids``
+                     (no reference counterpart: ``Index.delete``)
 
 ``get_feature_vector`` is a module-level name, as in the reference (whose tests
 monkeypatch ``ingesting.main.get_feature_vector``); by default it embeds in
@@ -15,6 +17,8 @@ import, ``:37``).  GCS is a no-op ``StorageHook`` (blob storage is out of scope)
 OTel/Prometheus instrumentation is out of scope.
 """
 from __future__ import annotations
+
+import json
 
 from fastapi import FastAPI, Request
 from fastapi.exceptions import RequestValidationError
@@ -72,3 +76,20 @@ async def push_images(request: Request):
     if not parts:
         raise _missing_file("files")
     return core.ingest_many([(f.filename, f.data, f.content_type) for f in parts], index, storage=storage)
+
+
+@app.post("/delete_images")
+async def delete_images(request: Request):
+    """Remove ingested images from the index by the ``file_id`` /push_image returned
+    (``Index.delete``; the reference has no such route: its Pinecone index is only ever
+    written).  Unknown ids are ignored; the stored blob is the storage hook's business."""
+    try:
+        body = json.loads(await request.body() or b"null")
+    except ValueError:
+        body = None
+    ids = body.get("ids") if isinstance(body, dict) else None
+    if not isinstance(ids, list) or not all(isinstance(i, str) for i in ids):
+        raise RequestValidationError([{"type": "list_type", "loc": ("body", "ids"), "msg": "Input should be a list of ids",
+                                       "input": None}])
+    # Index.delete is Pinecone's call and returns {}; its body reports how many ids existed
+    return {"deleted_count": index()._delete(ids, False, None) if ids else 0}

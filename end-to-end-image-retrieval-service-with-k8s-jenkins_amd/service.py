@@ -18,6 +18,7 @@ reads.  The per-service apps stay importable for their own contract tests.
                           for a probe or client of the old retriever URL that checks the body)
   POST /embed, /embed_batch                  (embedding/main.py:88-124)
   POST /push_image, /push_images             (ingesting/main.py:101-168)
+  POST /delete_images                        (no reference counterpart: Index.delete)
   POST /search_image                         (retriever/main.py:104-169)
 
 Run: ``uvicorn "<package>.service:app" --host 0.0.0.0 --port 5000`` (one process: the

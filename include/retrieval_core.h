@@ -104,6 +104,18 @@ int rc_index_reserve(rc_index *h, int max_nq, int max_k);
  * occurrence of a repeated id before calling. */
 int rc_index_upsert(rc_index *h, const float *vecs, int64_t n, const int64_t *rows, void *stream);
 
+/* The device half of index.delete(ids) (Pinecone's call; the reference never deletes):
+ * the host layer keeps the live rows dense by swap-remove (Index.delete fills each
+ * hole below the new length with a surviving row of the tail) and this moves the rows.
+ * src_rows, dst_rows: device i64 [n] local rows; stored row dst_rows[i] becomes a
+ * bit-for-bit copy of stored row src_rows[i] (ld elements and the norm), and the
+ * int8 filter copy of the written rows is refreshed as upsert refreshes it.
+ * Precondition: the two lists are disjoint (no row is both read and written) and
+ * dst_rows holds no row twice (one wave per row: two writers of one row would
+ * interleave).  A row outside [0, capacity) in either list skips that pair on the
+ * device; the hosts validate first. */
+int rc_index_move_rows(rc_index *h, const int64_t *src_rows, const int64_t *dst_rows, int64_t n, void *stream);
+
 /* replaces index.fetch(ids)["vectors"][id]["values"] — retriever/main.py:142.
  * rows: device i64 [n]; out: device f32 [n, dim] = stored row × stored norm. */
 int rc_index_fetch(rc_index *h, const int64_t *rows, int64_t n, float *out, void *stream);
@@ -214,6 +226,16 @@ int rc_sharded_grow(rc_sharded *h, int64_t new_capacity_per_shard);
  * [n, dim]; rows: HOST i64 [n] global rows.  Synchronous (ordered after work
  * already queued on `stream`). */
 int rc_sharded_upsert(rc_sharded *h, const float *vecs, int64_t n, const int64_t *rows, void *stream);
+/* rc_index_move_rows over the shards (index.delete's compaction).  src_rows, dst_rows:
+ * HOST i64 [n] global rows; stored row dst_rows[i] becomes a copy of stored row
+ * src_rows[i].  Before any device call the lists are validated: every row within
+ * capacity, no row twice in src_rows, none twice in dst_rows, none in both — else
+ * RC_ERR_INVALID and nothing has moved.  Pairs on one shard move inside it; pairs
+ * between two shards of one GPU move in one launch; pairs between GPUs are packed into
+ * a staging block on the source GPU, copied straight to the destination GPU and unpacked
+ * there.  Staging (stored bytes, ld * sizeof(dtype) + 4 per row) grows on demand and is
+ * bounded: long lists run in rounds of 16384 rows.  Synchronous. */
+int rc_sharded_move_rows(rc_sharded *h, const int64_t *src_rows, const int64_t *dst_rows, int64_t n);
 /* replaces index.fetch — retriever/main.py:142.  rows: HOST i64 [n] global rows;
  * out: HOST f32 [n, dim] (stored = 0: the upserted values; 1: the normalised
  * stored rows the search scores).  Synchronous. */
