@@ -32,6 +32,8 @@ SEARCH_MODES = {"auto": RC_SEARCH_AUTO, "scan": RC_SEARCH_SCAN, "mfma": RC_SEARC
 DTYPES = {"float32": RC_F32, "f32": RC_F32, "float16": RC_F16, "f16": RC_F16, "bfloat16": RC_BF16, "bf16": RC_BF16}
 RC_FILTER_NATIVE, RC_FILTER_I8 = 0, 1
 FILTERS = {"native": RC_FILTER_NATIVE, "i8": RC_FILTER_I8}
+RC_METRIC_COSINE, RC_METRIC_DOT, RC_METRIC_EUCLIDEAN = 0, 1, 2
+METRICS = {"cosine": RC_METRIC_COSINE, "dotproduct": RC_METRIC_DOT, "euclidean": RC_METRIC_EUCLIDEAN}  # Pinecone's names
 
 
 class RetrievalCoreError(RuntimeError):
@@ -112,6 +114,9 @@ SIGNATURES = {
     "rc_index_set_filter": (C.c_int, [_vp, _i32, _vp]),
     "rc_index_get_filter": (C.c_int, [_vp, _pi32]),
     "rc_sharded_set_filter": (C.c_int, [_vp, _i32]),
+    "rc_index_set_metric": (C.c_int, [_vp, _i32]),
+    "rc_index_get_metric": (C.c_int, [_vp, _pi32]),
+    "rc_sharded_set_metric": (C.c_int, [_vp, _i32]),
     "rc_sharded_create": (C.c_int, [_i32, _pi32, _i32, _i32, _i64, C.POINTER(_vp)]),
     "rc_sharded_destroy": (C.c_int, [_vp]),
     "rc_sharded_force_remote": (C.c_int, [_vp]),

@@ -12,6 +12,9 @@
 //     register bitonic sort) per wave, merged per block → partial keys;
 //   merge_partials_kernel: per query, top-k over all blocks' partial lists.
 // Algorithmic HBM bytes per query pass: n_rows * ld * sizeof(T).
+// Under a non-cosine metric (rc_index_set_metric) the same pass runs the metric kernels
+// (scan_metric.h): each row's key carries q · v_r or −‖q − v_r‖² instead of the cosine, formed
+// from the cosine and norms[r] before the top-k; nothing after the push differs.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -357,6 +360,7 @@ struct rc_index {
     float *norms = nullptr;
     // int8 filter copy (RC_FILTER_I8): [cap_pad][ld] x8, sx / ex [cap_pad] at i8_slot(row)
     int filter = RC_FILTER_NATIVE;
+    int metric = RC_METRIC_COSINE;  // scoring rule of the searches (rc_index_set_metric); storage does not depend on it
     int8_t *rows8 = nullptr;
     float *rsx = nullptr, *rex = nullptr;
     // search workspace
@@ -491,7 +495,7 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
                  int64_t *out_rows, hipStream_t s) {
     // queries per scan pass: a power of two the kernel is instantiated for (1, 2, 4)
     int qb = 1;
-    while (qb * 2 <= std::min(nq, scan_max_qb(h->nch, k, mask != nullptr))) qb *= 2;
+    while (qb * 2 <= std::min(nq, scan_max_qb(h->nch, k, mask != nullptr, h->metric))) qb *= 2;
     const int nq_pad = (nq + qb - 1) / qb * qb;  // every scan pass runs qb real-or-zero query slots
     ensure_workspace(h, nq_pad, k);  // (the scan normalises the queries itself: no separate launch)
     int nblk = (int)std::min<int64_t>(kMaxBlocks, std::max<int64_t>(1, (n_rows + 511) / 512));
@@ -513,6 +517,8 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
         a.dim = h->dim;
         a.nq_real = nq;
         a.mask = mask;
+        a.metric = h->metric;  // non-cosine: the metric kernels, which also read the norms
+        a.norms = h->norms;
         launch_scan(h, a);
         h->timer.end(slot, s, bytes);
     }
@@ -618,6 +624,7 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
     a.nblk = (int)((n_rows + rpb - 1) / rpb);
     a.k = k;
     a.with_values = with_values;
+    a.metric = h->metric;
     a.row_base = h->row_base;
     a.row_stride = h->row_stride;
     a.partial = h->partial;
@@ -818,6 +825,8 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
             free_filter(h);
             return;
         }
+        RC_REQUIRE(h->metric == RC_METRIC_COSINE, RC_ERR_UNSUPPORTED,
+                   "the int8 filter serves the batched MFMA search, which is cosine-only");
         RC_REQUIRE(i8_filter_supported(h->ld), RC_ERR_UNSUPPORTED,
                    "the int8 filter needs a row width (dim rounded up to 128) of 256, 512 or 768");
         const int64_t pad = cap_pad(h->capacity);
@@ -842,6 +851,25 @@ int rc_index_get_filter(const rc_index *h, int *kind) {
     return guard([&] {
         RC_REQUIRE(h && kind, RC_ERR_INVALID, "null argument");
         *kind = h->filter;
+    });
+}
+
+int rc_index_set_metric(rc_index *h, int metric) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(metric == RC_METRIC_COSINE || metric == RC_METRIC_DOT || metric == RC_METRIC_EUCLIDEAN, RC_ERR_INVALID,
+                   "metric must be RC_METRIC_COSINE, RC_METRIC_DOT or RC_METRIC_EUCLIDEAN");
+        std::lock_guard<std::mutex> lk(h->mu);
+        RC_REQUIRE(metric == RC_METRIC_COSINE || h->rows8 == nullptr, RC_ERR_UNSUPPORTED,
+                   "a non-cosine metric on an index with the int8 filter copy (the batched MFMA search is cosine-only)");
+        h->metric = metric;  // no device call: searches already enqueued took the metric they were launched with
+    });
+}
+
+int rc_index_get_metric(const rc_index *h, int *metric) {
+    return guard([&] {
+        RC_REQUIRE(h && metric, RC_ERR_INVALID, "null argument");
+        *metric = h->metric;
     });
 }
 
@@ -956,11 +984,15 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
         std::lock_guard<std::mutex> lk(h->mu);
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
+        // the batched path's candidate threshold is a bound in cosine space: a non-cosine index
+        // scans (AUTO) and refuses MFMA, whatever it holds
+        RC_REQUIRE(mode != RC_SEARCH_MFMA || h->metric == RC_METRIC_COSINE, RC_ERR_UNSUPPORTED,
+                   "batched MFMA search is cosine-only (this index scores by dotproduct or euclidean)");
         if (n_rows == 0) {  // an empty shard answers (-inf, -1) in every mode
             empty_search(nq, k, scores, out_rows, s);
             return;
         }
-        const bool mfma_ok = h->dtype != RC_F32 || h->rows8 != nullptr;
+        const bool mfma_ok = h->metric == RC_METRIC_COSINE && (h->dtype != RC_F32 || h->rows8 != nullptr);
         RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
                    "batched MFMA search needs an f16/bf16 index or the int8 filter copy");
         // with a mask AUTO scans: only the caller knows the eligible share, and a selective mask

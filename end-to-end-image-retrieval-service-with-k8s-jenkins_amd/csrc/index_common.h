@@ -1,7 +1,7 @@
 // index_common.h — what the exact cosine index's translation units share: the storage dtypes,
 // the device helpers and in-place macros that carry the search paths' bit-identity (query
-// normalisation, the row score's FMA chain, the int8 quantisation, the partial-list merge; the
-// wave fold and the output rule are in topk.h), the
+// normalisation, the row score's FMA chain, the non-cosine metrics' per-row rule, the int8
+// quantisation, the partial-list merge; the wave fold and the output rule are in topk.h), the
 // host dispatch over dtype / row width / list size, and the scan's, one-launch query's and
 // batched search's argument structs.  The scan's device code is in scan.h.
 #pragma once
@@ -78,14 +78,46 @@ __device__ __forceinline__ void unpack16<bf16_t>(const uint4 &x, float *o) {
 // differently in every scan kernel).  Sites: prepare_queries_kernel and prepare_queries_i8_kernel
 // (which store the values as qn), scan_rows' raw-query branch and query1_scan (src in LDS), which
 // keep them in registers: the same bits everywhere.
+// wave_sum_sq is the sum of squares alone (every lane holds the same bits: wave_sum adds
+// commutatively in a butterfly) and inv_norm_of the reciprocal norm from it, for the metric
+// scans, which need both (metric_coef below).
 template <typename P>
-__device__ __forceinline__ float wave_inv_norm(P src, int dim, int lane, bool valid = true) {
+__device__ __forceinline__ float wave_sum_sq(P src, int dim, int lane, bool valid = true) {
     float ss = 0.f;
     for (int c = lane; c < dim; c += 64) ss = valid ? fmaf(src[c], src[c], ss) : 0.f;
-    ss = wave_sum(ss);
-    return ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
+    return wave_sum(ss);
+}
+__device__ __forceinline__ float inv_norm_of(float ss) { return ss > 0.f ? 1.0f / sqrtf(ss) : 0.f; }
+template <typename P>
+__device__ __forceinline__ float wave_inv_norm(P src, int dim, int lane, bool valid = true) {
+    return inv_norm_of(wave_sum_sq(src, dim, lane, valid));
 }
 #define RC_UNIT_ELEM(SRC, C, DIM, INV, VALID) (((VALID) && (C) < (DIM)) ? (SRC)[C] * (INV) : 0.f)
+
+// The non-cosine metrics' per-row rule (rc_index_set_metric; retrieval_core.h states the
+// semantics).  A stored row is the direction x̂_r and its f32 norm n = norms[r]; fetch returns
+// v_r = x̂_r · n.  With c the row's exact cosine (sum16 of the RC_ROW_FMA16 chain), ss the raw
+// query's sum of squares (wave_sum_sq) and qn = sqrtf(ss):
+//   dotproduct  q · v_r        = n · (qn · c)                (alpha, beta, gamma) = (qn, 0, 0)
+//   euclidean   −‖q − v_r‖²    = n · (2 qn · c − n) − ss                            (2 qn, 1, ss)
+// as t = fmaf(alpha, c, −(beta · n)), s = fmaf(n, t, −gamma): one code path, runtime constants.
+// s is the top-k key's score and the score returned (descending, so Euclidean distances come
+// back negated): the merges and the output rule take it as they take a cosine.  It depends on
+// the row and the query alone, so every search path and every sharding give it the same bits.
+// Sites: scan_rows_q's metric form (the scan kernels and query1_scan).
+struct MetricCoef {
+    float alpha, beta, gamma;
+};
+__device__ __forceinline__ MetricCoef metric_coef(int metric, float ss) {
+    // wave-uniform (see wave_sum_sq): kept in scalar registers
+    ss = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(ss)));
+    const float qn = sqrtf(ss);
+    return metric == RC_METRIC_EUCLIDEAN ? MetricCoef{2.0f * qn, 1.0f, ss} : MetricCoef{qn, 0.0f, 0.0f};
+}
+__device__ __forceinline__ float metric_score(const MetricCoef &m, float c, float n) {
+    const float t = fmaf(m.alpha, c, -(m.beta * n));
+    return fmaf(n, t, -m.gamma);
+}
 
 // Exact row scores take 16 lanes per row: lane sub = lane & 15 holds the row's 16-B chunks
 // sub + 16 i (CPL of them, EPC values each) in X[CPL] (uint4) and the same chunks of QB normalised
@@ -198,17 +230,26 @@ struct ScanArgs {
     // trusted).  nullptr: every row is eligible (the unmasked kernels; no runtime test of it on
     // the device, the host picks the instantiation).
     const uint32_t *mask = nullptr;
+    // Scoring rule (rc_index_set_metric).  Not RC_METRIC_COSINE: the metric kernels
+    // (launch_scan_metric), which read norms [n_rows] and need raw queries (qraw), one per pass
+    // (qb = 1), and no flags.
+    int metric = RC_METRIC_COSINE;
+    const float *norms = nullptr;
 };
 
 // largest queries-per-pass for a row width: query registers per lane = QB*nch*8 floats <= 64
-// (the masked scan is instantiated for multi-query passes at the smallest list size only)
-inline int scan_max_qb(int nch, int k, bool masked = false) {
+// (the masked scan is instantiated for multi-query passes at the smallest list size only, the
+// metric scans for single-query passes only)
+inline int scan_max_qb(int nch, int k, bool masked = false, int metric = RC_METRIC_COSINE) {
+    if (metric != RC_METRIC_COSINE) return 1;
     if (k > (masked ? 64 : 128)) return 1;
     return nch <= 2 ? 4 : (nch <= 4 ? 2 : 1);
 }
 
 template <typename T>
 void launch_scan(const ScanArgs &a);  // scan.h; instantiated in scan_{f32,f16,bf16}.hip
+template <typename T>
+void launch_scan_metric(const ScanArgs &a);  // scan_metric.h; instantiated in scan_metric_{f32,f16,bf16}.hip
 
 // One query, one launch (rc_sharded_query_host's request path): query1_kernel normalises the
 // query (carried in the kernel arguments: no copy), scans its block's rows, and the last block
@@ -228,6 +269,7 @@ struct Query1Args {
     int nblk;
     int k;
     int with_values;
+    int metric;             // RC_METRIC_*; sits in what was padding: the cosine kernels' argument layout is unchanged
     int64_t row_base, row_stride;
     uint64_t *partial;      // [nblk][k]
     float *out_scores;      // [k]
@@ -237,8 +279,12 @@ struct Query1Args {
     unsigned seq;
     float q[QUERY1_MAX_DIM];
 };
+static_assert(sizeof(Query1Args) == 3200, "Query1Args is the one-launch kernels' argument block");
 template <typename T>
 void launch_query1(const Query1Args &a, hipStream_t s);  // scan.h; instantiated in scan_{f32,f16,bf16}.hip
+// phase 1 under a non-cosine metric (launch_query1 calls it); scan_metric.h, instantiated in scan_metric_{f32,f16,bf16}.hip
+template <typename T>
+void launch_query1_metric_scan(const Query1Args &a, hipStream_t s);
 
 // Merge nlist sorted partial lists of k keys (query qi of nq_total) into wave 0's tk: the body
 // of merge_partials_kernel, shared with query1_kernel's last block.  Block-collective.

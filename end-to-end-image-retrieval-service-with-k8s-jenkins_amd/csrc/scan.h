@@ -1,7 +1,9 @@
 // scan.h — the single-query streaming scan (HBM-bound GEMV + fused wavefront top-k) and the
 // one-launch query of the exact cosine index: device code and launch chains.  Included only by
 // scan_{f32,f16,bf16}.hip, which instantiate launch_scan<T> / launch_query1<T> for one storage
-// dtype each, so the three translation units compile in parallel.
+// dtype each, so the three translation units compile in parallel.  The device functions' METRIC
+// forms (dotproduct / euclidean scores) are instantiated by scan_metric.h's kernels, in
+// scan_metric_{f32,f16,bf16}.hip.
 #pragma once
 
 #include "index_common.h"
@@ -26,11 +28,17 @@ typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4)));  // the nontempor
 // loads altogether (wave-uniform branch: every reserve / push stays wave-collective) — the HBM
 // bytes a selective filter saves.  The per-row arithmetic is untouched, so an eligible row's
 // score has the bits the unmasked scan gives it.
-template <typename T, int NCH, int QB, int CAP, bool MASKED = false>
+// METRIC (one query per pass): the key's score is metric_score(mc, cosine, norms[row]), formed
+// per row before the top-k, so the list is the metric's own top-k (index_common.h has the rule).
+// The iteration's norms are loaded ahead of its rows, under the rows' clamp: they return first
+// and no wait for a row group reaches past it.
+template <typename T, int NCH, int QB, int CAP, bool MASKED = false, bool METRIC = false>
 __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t ld, int64_t n_rows, int64_t rows_per_block,
                                             const float (&q)[QB][RowShape<T, NCH>::CPL][RowShape<T, NCH>::EPC], int q0,
                                             int nq_total, int k, uint64_t *__restrict__ partial,
-                                            const uint32_t *__restrict__ mask = nullptr) {
+                                            const uint32_t *__restrict__ mask = nullptr,
+                                            const float *__restrict__ norms = nullptr, MetricCoef mc = MetricCoef{}) {
+    static_assert(!METRIC || QB == 1, "the metric scans take one query per pass");
     constexpr int EPC = RowShape<T, NCH>::EPC;
     constexpr int CPL = RowShape<T, NCH>::CPL;
     __shared__ uint64_t lds[4][QB][CAP];
@@ -59,6 +67,14 @@ __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t 
             if (gn < r1) mword = mask[gn >> 5];
             if (mbyte == 0u) continue;  // wave-uniform: none of the 8 rows is eligible, no row is loaded
         }
+        [[maybe_unused]] float nrm[SCAN_U];  // METRIC: the norms of this lane's rows
+        if constexpr (METRIC) {
+#pragma unroll
+            for (int u = 0; u < SCAN_U; ++u) {
+                const int64_t r = g + u * 4 + rg;
+                nrm[u] = norms[r < r1 ? r : r0];  // r0 < r1 <= n_rows: inside the norms
+            }
+        }
         uint4 x[SCAN_U][CPL];
 #pragma unroll
         for (int u = 0; u < SCAN_U; ++u) {
@@ -78,7 +94,8 @@ __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t 
             RC_ROW_FMA16(T, QB, CPL, EPC, x[u], q, acc);
             static_for<QB>([&](auto bc) {
                 constexpr int b = bc.value;
-                const float s = sum16(acc[b]);
+                float s = sum16(acc[b]);
+                if constexpr (METRIC) s = metric_score(mc, s, nrm[u]);
                 tk[b].reserve(4);
                 if constexpr (MASKED)
                     tk[b].push(sub == 0 && r < r1 && ((mbyte >> (u * 4 + rg)) & 1u) != 0u, make_key(s, (uint32_t)r));
@@ -105,21 +122,32 @@ __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t 
 // The scan kernels' query set-up: the QB queries' register chunks, either from the normalised
 // rows qn or (qraw: the single-query scans) normalised here from the raw queries, every wave
 // for itself (wave_inv_norm / RC_UNIT_ELEM: the bits qn would hold).
-template <typename T, int NCH, int QB, int CAP, bool MASKED = false>
+// METRIC: raw queries only (qn is not read); the same sum of squares gives the normalisation
+// and the metric's per-query constants (metric_coef).
+template <typename T, int NCH, int QB, int CAP, bool MASKED = false, bool METRIC = false>
 __device__ __forceinline__ void scan_rows(const T *__restrict__ rows, int64_t ld, int64_t n_rows, int64_t rows_per_block,
                                           const float *__restrict__ qn, int q0, int nq_total, int k,
                                           uint64_t *__restrict__ partial, const float *__restrict__ qraw = nullptr,
-                                          int dim = 0, int nq_real = 0, const uint32_t *__restrict__ mask = nullptr) {
+                                          int dim = 0, int nq_real = 0, const uint32_t *__restrict__ mask = nullptr,
+                                          const float *__restrict__ norms = nullptr, int metric = RC_METRIC_COSINE) {
     constexpr int EPC = RowShape<T, NCH>::EPC;
     constexpr int CPL = RowShape<T, NCH>::CPL;
     const int lane = threadIdx.x & 63, sub = lane & 15;
     float q[QB][CPL][EPC];
-    if (qraw != nullptr) {  // block-uniform
+    [[maybe_unused]] MetricCoef mc{};
+    if (METRIC || qraw != nullptr) {  // block-uniform
 #pragma unroll
         for (int b = 0; b < QB; ++b) {
             const bool valid = q0 + b < nq_real;
             const float *src = qraw + (int64_t)(valid ? q0 + b : 0) * dim;
-            const float inv = wave_inv_norm(src, dim, lane, valid);
+            float inv;
+            if constexpr (METRIC) {
+                const float ss = wave_sum_sq(src, dim, lane, valid);
+                inv = inv_norm_of(ss);
+                mc = metric_coef(metric, ss);
+            } else {
+                inv = wave_inv_norm(src, dim, lane, valid);
+            }
 #pragma unroll
             for (int i = 0; i < CPL; ++i)
 #pragma unroll
@@ -136,7 +164,7 @@ __device__ __forceinline__ void scan_rows(const T *__restrict__ rows, int64_t ld
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) q[b][i][e] = qn[(int64_t)(q0 + b) * ld + (sub + 16 * i) * EPC + e];
     }
-    scan_rows_q<T, NCH, QB, CAP, MASKED>(rows, ld, n_rows, rows_per_block, q, q0, nq_total, k, partial, mask);
+    scan_rows_q<T, NCH, QB, CAP, MASKED, METRIC>(rows, ld, n_rows, rows_per_block, q, q0, nq_total, k, partial, mask, norms, mc);
 }
 
 // f32 rows of 512 (config 3): 131 VGPRs by default = 3 waves per SIMD; capped at 128 (no spill)
@@ -206,6 +234,7 @@ void launch_scan_qb(const ScanArgs &a) {
 
 template <typename T>
 void launch_scan(const ScanArgs &a) {
+    if (a.metric != RC_METRIC_COSINE) return launch_scan_metric<T>(a);  // the metric kernels' own translation units
     const bool ok = with_nch(a.nch, [&](auto nch) {
         constexpr int NCH = decltype(nch)::value;
         if constexpr (NCH <= 2) {  // queries per pass: scan_max_qb's register budget
@@ -227,7 +256,7 @@ void launch_scan(const ScanArgs &a) {
 // blocks, each writing its partial list; PHASE 2: one block merges them (the kernel boundary
 // orders the lists: a one-launch form with a last-block ticket behind device-scope fences
 // measured 5.6 us slower per 10k-row call, round 4) and gathers the values.
-template <typename T, int NCH, int CAP>
+template <typename T, int NCH, int CAP, bool METRIC = false>
 __device__ __forceinline__ void query1_scan(const Query1Args &a) {
     constexpr int EPC = RowShape<T, NCH>::EPC;
     constexpr int CPL = RowShape<T, NCH>::CPL;
@@ -244,7 +273,15 @@ __device__ __forceinline__ void query1_scan(const Query1Args &a) {
         for (int i = 0; i < PER; ++i) qs[threadIdx.x + 256 * i] = v[i];
     }
     __syncthreads();
-    const float inv = wave_inv_norm(qs, a.dim, lane);
+    float inv;
+    [[maybe_unused]] MetricCoef mc{};
+    if constexpr (METRIC) {  // as scan_rows' metric form: one sum of squares, the same bits
+        const float ss = wave_sum_sq(qs, a.dim, lane);
+        inv = inv_norm_of(ss);
+        mc = metric_coef(a.metric, ss);
+    } else {
+        inv = wave_inv_norm(qs, a.dim, lane);
+    }
     float q[1][CPL][EPC];
 #pragma unroll
     for (int i = 0; i < CPL; ++i)
@@ -253,7 +290,8 @@ __device__ __forceinline__ void query1_scan(const Query1Args &a) {
             const int c = (sub + 16 * i) * EPC + e;
             q[0][i][e] = RC_UNIT_ELEM(qs, c, a.dim, inv, true);
         }
-    scan_rows_q<T, NCH, 1, CAP>((const T *)a.rows, a.ld, a.n_rows, a.rows_per_block, q, 0, 1, a.k, a.partial);
+    scan_rows_q<T, NCH, 1, CAP, false, METRIC>((const T *)a.rows, a.ld, a.n_rows, a.rows_per_block, q, 0, 1, a.k, a.partial,
+                                               nullptr, a.norms, mc);
 }
 
 template <typename T, int CAP>
@@ -323,8 +361,12 @@ void launch_query1(const Query1Args &a, hipStream_t s) {
     const bool ok = with_nch<6>(a.nch, [&](auto nch) {
         const bool cap_ok = with_topk_cap<256>(topk_cap(a.k), [&](auto cap) {
             constexpr int NCH = decltype(nch)::value, CAP = decltype(cap)::value;
-            hipLaunchKernelGGL((query1_kernel<T, NCH, CAP, 1>), dim3(a.nblk), dim3(256), 0, s, a);
-            RC_LAUNCH_CHECK();
+            if (a.metric != RC_METRIC_COSINE) {  // phase 1 under the metric; phase 2 is the same
+                launch_query1_metric_scan<T>(a, s);
+            } else {
+                hipLaunchKernelGGL((query1_kernel<T, NCH, CAP, 1>), dim3(a.nblk), dim3(256), 0, s, a);
+                RC_LAUNCH_CHECK();
+            }
             hipLaunchKernelGGL((query1_kernel<T, NCH, CAP, 2>), dim3(1), dim3(256), 0, s, a);
             RC_LAUNCH_CHECK();
         });

@@ -555,6 +555,23 @@ int rc_sharded_set_filter(rc_sharded *h, int kind) {
     });
 }
 
+int rc_sharded_set_metric(rc_sharded *h, int metric) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(metric == RC_METRIC_COSINE || metric == RC_METRIC_DOT || metric == RC_METRIC_EUCLIDEAN, RC_ERR_INVALID,
+                   "metric must be RC_METRIC_COSINE, RC_METRIC_DOT or RC_METRIC_EUCLIDEAN");
+        std::lock_guard<std::mutex> lk(h->mu);
+        // validated on every shard before any is set: a refused call leaves one metric everywhere
+        for (int s = 0; s < h->n && metric != RC_METRIC_COSINE; ++s) {
+            int kind = RC_FILTER_NATIVE;
+            check_status(rc_index_get_filter(h->shard[s], &kind));
+            RC_REQUIRE(kind == RC_FILTER_NATIVE, RC_ERR_UNSUPPORTED,
+                       "a non-cosine metric on an index with the int8 filter copy (the batched MFMA search is cosine-only)");
+        }
+        for (int s = 0; s < h->n; ++s) check_status(rc_index_set_metric(h->shard[s], metric));
+    });
+}
+
 int rc_sharded_upsert(rc_sharded *h, const float *vecs, int64_t n, const int64_t *rows, void *stream) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");

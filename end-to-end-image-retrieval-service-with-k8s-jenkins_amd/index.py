@@ -56,10 +56,12 @@ class DeviceIndex:
     the global rows of a round-robin shard."""
 
     def __init__(self, dim: int, dtype: str = "float32", capacity: int = 1 << 20, device=None, row_base: int = 0,
-                 row_stride: int = 1, _handle=None):
+                 row_stride: int = 1, _handle=None, metric: str = "cosine"):
         self.lib = _lib.load()
         if dtype not in _lib.DTYPES:
             raise ValueError(f"unknown index dtype {dtype!r}")
+        if metric not in _lib.METRICS:
+            raise ValueError(f"unknown metric {metric!r} (expected one of {sorted(_lib.METRICS)})")
         self.dim = int(dim)
         self.dtype = dtype
         self.device_index = _device_index(device)
@@ -74,7 +76,9 @@ class DeviceIndex:
             self._h = h
             if self.row_stride != 1:
                 self.set_row_map(self.row_base, self.row_stride)
-        else:  # a shard borrowed from an rc_sharded handle (owned there)
+            if metric != "cosine":
+                self.set_metric(metric)
+        else:  # a shard borrowed from an rc_sharded handle (owned there, its metric set there)
             self._h = _handle
 
     @property
@@ -131,6 +135,20 @@ class DeviceIndex:
         check(self.lib.rc_index_get_filter(self.handle, _lib.C.byref(k)))
         return {v: n for n, v in _lib.FILTERS.items()}[k.value]
 
+    def set_metric(self, metric: str) -> None:
+        """Scoring rule of the later searches (rc_index_set_metric): "cosine", "dotproduct" or
+        "euclidean".  Touches no stored data, so it is legal on a populated index.  ``search``
+        returns scores descending under every metric: Euclidean ones are ``-||q - v||^2``."""
+        if metric not in _lib.METRICS:
+            raise ValueError(f"unknown metric {metric!r} (expected one of {sorted(_lib.METRICS)})")
+        check(self.lib.rc_index_set_metric(self.handle, _lib.METRICS[metric]))
+
+    @property
+    def metric(self) -> str:
+        m = _lib.C.c_int()
+        check(self.lib.rc_index_get_metric(self.handle, _lib.C.byref(m)))
+        return {v: n for n, v in _lib.METRICS.items()}[m.value]
+
     def _vecs(self, vecs: torch.Tensor) -> torch.Tensor:
         if vecs.dim() == 1:
             vecs = vecs[None]
@@ -162,10 +180,11 @@ class DeviceIndex:
         return out
 
     def search(self, queries: torch.Tensor, k: int, n_rows: int, stream=None, out=None, mode: str = "auto", mask=None):
-        """Exact cosine top-k over rows [0, n_rows): (scores f32 [nq,k], global rows i64 [nq,k]).
+        """Exact top-k over rows [0, n_rows) by the index's metric (cosine unless ``set_metric``
+        said otherwise): (scores f32 [nq,k] descending, global rows i64 [nq,k]).
 
         ``mode``: "scan" (HBM-bound streaming scan), "mfma" (batched filter GEMM +
-        exact rescoring, f16/bf16 index) or "auto" (MFMA for >= 8 queries).
+        exact rescoring, f16/bf16 index, cosine only) or "auto" (MFMA for >= 8 queries).
         ``mask``: optional row-eligibility bitmap over the LOCAL rows (rc_index_search_masked):
         an int32 / uint32 tensor of ceil(n_rows / 32) words on this device, bit r & 31 of word
         r >> 5 = row r may be returned; "auto" then scans."""
@@ -455,10 +474,13 @@ class ShardSet:
     SURVEY §8(e)); ``devices[s]`` is shard s's GPU (entries may repeat), and
     ``devices[0]`` (the leader) holds queries and merged results."""
 
-    def __init__(self, dim: int, dtype: str = "float32", capacity_per_shard: int = 1 << 20, devices=None):
+    def __init__(self, dim: int, dtype: str = "float32", capacity_per_shard: int = 1 << 20, devices=None,
+                 metric: str = "cosine"):
         self.lib = _lib.load()
         if dtype not in _lib.DTYPES:
             raise ValueError(f"unknown index dtype {dtype!r}")
+        if metric not in _lib.METRICS:
+            raise ValueError(f"unknown metric {metric!r} (expected one of {sorted(_lib.METRICS)})")
         devs = [_device_index(d) for d in (devices if devices is not None else [None])]
         if not devs:
             raise ValueError("a sharded index needs at least one device")
@@ -484,6 +506,8 @@ class ShardSet:
             ih = _lib.C.c_void_p()
             check(self.lib.rc_sharded_shard(h, sh, _lib.C.byref(ih)))
             self._shards.append(DeviceIndex(dim, dtype=dtype, device=devs[sh], row_base=sh, row_stride=self.n, _handle=ih))
+        if metric != "cosine":
+            self.set_metric(metric)
 
     @property
     def handle(self):
@@ -544,6 +568,16 @@ class ShardSet:
     @property
     def filter(self) -> str:
         return self._shards[0].filter
+
+    def set_metric(self, metric: str) -> None:
+        """``DeviceIndex.set_metric`` on every shard (rc_sharded_set_metric: all or none)."""
+        if metric not in _lib.METRICS:
+            raise ValueError(f"unknown metric {metric!r} (expected one of {sorted(_lib.METRICS)})")
+        check(self.lib.rc_sharded_set_metric(self.handle, _lib.METRICS[metric]))
+
+    @property
+    def metric(self) -> str:
+        return self._shards[0].metric
 
     def upsert_rows(self, vecs: torch.Tensor, rows) -> None:
         """vecs f32 [n, dim] (any device; moved to the leader), rows: global rows (host)."""
@@ -644,7 +678,8 @@ class ShardSet:
         return out
 
     def search(self, queries: torch.Tensor, k: int, n_rows: int, mode: str = "auto", stream=None, mask=None):
-        """Exact cosine top-k over global rows [0, n_rows): (scores f32 [nq,k], rows i64 [nq,k]) on the leader.
+        """Exact top-k over global rows [0, n_rows) by the index's metric: (scores f32 [nq,k]
+        descending, rows i64 [nq,k]) on the leader.
         ``mask``: an optional HOST uint32 bitmap over the global rows (rc_sharded_search_masked)."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
@@ -691,7 +726,21 @@ class ShardSet:
 
 
 class Index:
-    """Pinecone-shaped index (what ``get_index`` returns), cosine metric only.
+    """Pinecone-shaped index (what ``get_index`` returns).
+
+    ``metric`` is Pinecone's ``create_index(metric=...)``: ``"cosine"`` (default),
+    ``"dotproduct"`` or ``"euclidean"``.  With ``v`` the vector ``fetch`` returns for an id (the
+    stored direction, dtype-rounded, times its f32 norm) and ``q`` the raw query, a match's
+    score is the cosine, ``q · v`` (higher is better) or the SQUARED distance ``‖q − v‖²`` as
+    Pinecone reports it (lower is better).  Matches come most similar first, so Euclidean scores
+    ascend; ties order by ascending row under every metric.  The top-k is chosen by the
+    metric's score inside the exact scan (the library returns Euclidean scores negated, so
+    every search sorts descending; ``query`` / ``query_batch`` report ``max(0.0, -s)``).  The
+    metric is a scoring rule over unchanged storage: ``upsert``, ``fetch``, ``delete``,
+    ``query(id=...)`` and metadata filters work alike under all three, and ``save`` / ``load``
+    keep it.  The batched MFMA search is cosine-only: a non-cosine index always scans,
+    ``mode="mfma"`` and ``filter="i8"`` raise ``ValueError`` on it.  All-zero vectors and
+    queries are rejected under every metric.
 
     ``upsert(vectors)`` accepts ``(id, values)``, ``(id, values, metadata)``
     tuples or ``{"id", "values", "metadata"}`` dicts and overwrites existing
@@ -720,10 +769,12 @@ class Index:
     def __init__(self, name: str, dimension: int = 768, metric: str = "cosine", dtype: str = "float32",
                  capacity: int = 1 << 20, device=None, shards: int | None = None, devices=None,
                  filter: str = "native"):
-        if metric != "cosine":
-            raise ValueError("only metric='cosine' is supported")
+        if metric not in _lib.METRICS:
+            raise ValueError(f"unknown metric {metric!r} (expected one of {sorted(_lib.METRICS)})")
         if filter not in _lib.FILTERS:
             raise ValueError(f"unknown filter {filter!r} (expected one of {sorted(_lib.FILTERS)})")
+        if metric != "cosine" and filter != "native":
+            raise ValueError(f"filter={filter!r} serves the batched MFMA search, which is cosine-only (metric={metric!r})")
         if devices is None:
             devices = [device] * int(shards or 1)
         self.name = name
@@ -731,7 +782,7 @@ class Index:
         self.metric = metric
         n = len(devices)
         self._set = ShardSet(self.dimension, dtype=dtype, capacity_per_shard=max(1, -(-int(capacity) // n)),
-                             devices=devices)
+                             devices=devices, metric=metric)
         if filter != "native":
             self._set.set_filter(filter)
         self._rows: dict[str, int] = {}
@@ -1048,6 +1099,8 @@ class Index:
         reaches MASKED_MFMA_MIN_SHARE."""
         if mode != "auto":
             return mode
+        if self.metric != "cosine":  # the batched MFMA path is cosine-only
+            return "scan"
         mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter == "i8"
         if mfma_ok and nq >= 8 and n // self._set.n >= 65536 and eligible >= MASKED_MFMA_MIN_SHARE * n:
             return "mfma"
@@ -1067,7 +1120,10 @@ class Index:
                 raise ValueError(f"unknown search mode {mode!r}")
             scores, rows = self._set.search(q, k, n, mode=self._masked_mode(mode, q.shape[0], n, bitmap[1]),
                                             mask=bitmap[0])
-        scores = scores.cpu().tolist()
+        scores = scores.cpu().numpy()
+        if self.metric == "euclidean":  # the library's -||q - v||^2 (descending) as Pinecone's squared distance
+            scores = np.maximum(np.float32(0.0), -scores)
+        scores = scores.tolist()
         rows = rows.cpu().tolist()
         out = []
         recent: dict[str, np.ndarray] = {}
@@ -1105,7 +1161,10 @@ class Index:
         for qi in range(q.shape[0]):
             rows = rw[qi].tolist()
             live = k - rows.count(-1)  # the lists are sorted: empty slots (-1) come last
-            scores = sc[qi, :live].tolist()
+            if self.metric == "euclidean":  # as in _query_locked
+                scores = np.maximum(np.float32(0.0), -sc[qi, :live]).tolist()
+            else:
+                scores = sc[qi, :live].tolist()
             if include_values:
                 # the reused host buffer is copied once (one memcpy); each match keeps its row as f32
                 # and builds the Python list only if read (Record)

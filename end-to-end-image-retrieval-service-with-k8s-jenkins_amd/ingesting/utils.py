@@ -43,14 +43,15 @@ def index_devices(spec: str | None = None, shards: int | None = None) -> list:
 
 def get_index(index_name: str, dimension: int | None = None, dtype: str | None = None, capacity: int | None = None,
               devices: list | None = None):
-    """Open or create the named index (reference ``:23-38``): one logical cosine index of
-    ``Config.INPUT_RESOLUTION`` dims, row-sharded over ``devices`` (default: ``Config.INDEX_DEVICES``)."""
+    """Open or create the named index (reference ``:23-38``): one logical index of
+    ``Config.INPUT_RESOLUTION`` dims scored by ``Config.INDEX_METRIC`` (cosine unless configured),
+    row-sharded over ``devices`` (default: ``Config.INDEX_DEVICES``)."""
     from ..index import Index
 
     with _lock:
         idx = _indexes.get(index_name)
         if idx is None:
-            idx = Index(index_name, dimension=dimension or Config.INPUT_RESOLUTION, metric="cosine",
+            idx = Index(index_name, dimension=dimension or Config.INPUT_RESOLUTION, metric=Config.INDEX_METRIC,
                         dtype=dtype or Config.INDEX_DTYPE, capacity=capacity or Config.INDEX_CAPACITY,
                         devices=devices if devices is not None else index_devices(), filter=Config.INDEX_FILTER)
             _indexes[index_name] = idx

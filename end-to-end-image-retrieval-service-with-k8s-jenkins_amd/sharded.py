@@ -75,7 +75,10 @@ class RowCoverage:
 class ShardedIndex:
     def __init__(self, dim: int, dtype: str = "float16", capacity_per_rank: int = 1 << 20, group=None,
                  device=None, backend_factory: Callable | None = None, merge_fn: Callable | None = None,
-                 filter: str = "native"):
+                 filter: str = "native", metric: str = "cosine"):
+        """``metric``: the scoring rule of the default backend's ``DeviceIndex`` ("cosine",
+        "dotproduct", "euclidean"; ``search`` returns scores descending, Euclidean ones negated).
+        The merge needs no change: a shard's keys already carry the final scores."""
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -87,11 +90,13 @@ class ShardedIndex:
         if self.capacity < 1 or (self.capacity - 1) * self.world + self.world - 1 >= (1 << 32) - 1:
             raise ValueError(f"capacity_per_rank x world = {self.capacity} x {self.world} exceeds the 2^32 - 1 "
                              "global rows the top-k merge can key")
+        if backend_factory is not None and metric != "cosine":
+            raise ValueError("metric= configures the default backend; a backend_factory sets its own")
         if backend_factory is None:
             from .index import DeviceIndex, topk_merge
 
             backend_factory = lambda: DeviceIndex(dim, dtype=dtype, capacity=capacity_per_rank, device=device,
-                                                  row_base=self.rank, row_stride=self.world)
+                                                  row_base=self.rank, row_stride=self.world, metric=metric)
             merge_fn = merge_fn or topk_merge
         self.local = backend_factory()
         if filter != "native":  # the batched search's int8 filter copy (DeviceIndex.set_filter)

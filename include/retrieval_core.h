@@ -187,6 +187,36 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
 int rc_index_set_filter(rc_index *h, int kind, void *stream);
 int rc_index_get_filter(const rc_index *h, int *kind);
 
+/* replaces the metric= argument of pc.create_index — ingesting/utils.py:29-36 (the
+ * reference asks for "cosine"; Pinecone also offers "dotproduct" and "euclidean").
+ * The metric is a scoring rule over unchanged storage: setting it touches no data,
+ * applies to later searches and is legal on a populated index.  Every stored row r is
+ * an L2-normalised direction x̂_r in the storage dtype plus its f32 norm n_r, and
+ * v_r = x̂_r · n_r is the vector rc_index_fetch returns; q is the raw query.
+ *   RC_METRIC_COSINE    — the default, as documented at rc_index_search;
+ *   RC_METRIC_DOT       — score = q · v_r, higher is better, best first;
+ *   RC_METRIC_EUCLIDEAN — the SQUARED distance ‖q − v_r‖², as Pinecone reports it,
+ *                         lower is better.  Every search keeps its contract of
+ *                         returning scores descending: the library returns
+ *                         s = −‖q − v_r‖², most similar first, and the host layer
+ *                         reports max(0, −s), so its scores ascend.
+ * Ties order by ascending row under every metric.  The top-k is chosen by the metric's
+ * score inside the exact scan (never a re-ranked cosine top-k): with c the row's exact
+ * cosine, ss the f32 sum of squares of q and qn = sqrtf(ss), the score is
+ * s = fmaf(n_r, fmaf(alpha, c, −(beta · n_r)), −gamma) with (alpha, beta, gamma) =
+ * (qn, 0, 0) for RC_METRIC_DOT and (2 qn, 1, ss) for RC_METRIC_EUCLIDEAN.  It is a
+ * function of the row and the query alone: every search path and a sharded index give
+ * the same bits.  All-zero vectors and queries stay rejected by the host layer.
+ * The batched MFMA path is cosine-only (its candidate threshold is a bound in cosine
+ * space): on a non-cosine index RC_SEARCH_AUTO scans, RC_SEARCH_MFMA and
+ * rc_index_set_filter(RC_FILTER_I8) are RC_ERR_UNSUPPORTED, and so is a non-cosine
+ * metric on an index that holds the int8 copy.  An unknown metric is RC_ERR_INVALID. */
+#define RC_METRIC_COSINE 0
+#define RC_METRIC_DOT 1
+#define RC_METRIC_EUCLIDEAN 2
+int rc_index_set_metric(rc_index *h, int metric);
+int rc_index_get_metric(const rc_index *h, int *metric);
+
 /* Synthetic rows for benchmarks (no reference counterpart): rows
  * [row0, row0+n) get uniform[-1,1) values from a counter-based hash of
  * (seed, row, col), normalised and cast like an upsert. */
@@ -274,6 +304,9 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
 /* rc_index_set_filter on every shard; all or nothing (a failure restores
  * RC_FILTER_NATIVE on every shard). */
 int rc_sharded_set_filter(rc_sharded *h, int kind);
+/* rc_index_set_metric on every shard; the metric is validated against every shard
+ * before any is set (an unknown metric, or a shard with the int8 copy, changes none). */
+int rc_sharded_set_metric(rc_sharded *h, int metric);
 
 /* ------------------------------------------------------------------------
  * ViT-MSN image embedding.  Replaces the /embed compute path —
