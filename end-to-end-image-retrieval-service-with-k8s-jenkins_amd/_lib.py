@@ -25,11 +25,26 @@ RC_ERR_OOM = 3
 RC_ERR_UNSUPPORTED = 4
 RC_ERR_STATE = 5
 
-RC_F32, RC_F16, RC_BF16 = 0, 1, 2
+RC_F32, RC_F16, RC_BF16, RC_F8 = 0, 1, 2, 3
 RC_TOPK_MAX = 256
 RC_SEARCH_AUTO, RC_SEARCH_SCAN, RC_SEARCH_MFMA = 0, 1, 2
 SEARCH_MODES = {"auto": RC_SEARCH_AUTO, "scan": RC_SEARCH_SCAN, "mfma": RC_SEARCH_MFMA}
-DTYPES = {"float32": RC_F32, "f32": RC_F32, "float16": RC_F16, "f16": RC_F16, "bfloat16": RC_BF16, "bf16": RC_BF16}
+DTYPES = {"float32": RC_F32, "f32": RC_F32, "float16": RC_F16, "f16": RC_F16, "bfloat16": RC_BF16, "bf16": RC_BF16,
+          "float8_e4m3fn": RC_F8, "f8": RC_F8}
+DTYPE_BYTES = {RC_F32: 4, RC_F16: 2, RC_BF16: 2, RC_F8: 1}
+
+
+def dtype_bytes(dtype: str) -> int:
+    """Bytes per stored element of an index dtype name (the raw rows of export / import / snapshots)."""
+    if dtype not in DTYPES:
+        raise ValueError(f"unknown index dtype {dtype!r}")
+    return DTYPE_BYTES[DTYPES[dtype]]
+
+
+def is_f8(dtype: str) -> bool:
+    return DTYPES.get(dtype) == RC_F8
+
+
 RC_FILTER_NATIVE, RC_FILTER_I8 = 0, 1
 FILTERS = {"native": RC_FILTER_NATIVE, "i8": RC_FILTER_I8}
 RC_METRIC_COSINE, RC_METRIC_DOT, RC_METRIC_EUCLIDEAN = 0, 1, 2

@@ -23,6 +23,7 @@ class Config:
     # reference: Config for embedding service
     EMBEDDING_SERVICE_URL = os.getenv("EMBEDDING_SERVICE_URL", "http://localhost:5000/embed")
     # build-side knobs
+    # storage of the index rows: "float32", "float16", "bfloat16" or "float8_e4m3fn" ("f8": exact scans only)
     INDEX_DTYPE = os.getenv("RC_INDEX_DTYPE", "float32")
     INDEX_CAPACITY = int(os.getenv("RC_INDEX_CAPACITY", str(1 << 20)))  # initial rows; grows on demand
     # batched-search filter copy: "native" or "i8" (int8 copy of the rows; dims up to 768)

@@ -2,8 +2,9 @@
 // (reference: get_index ingesting/utils.py:23-38, upsert ingesting/main.py:156-158,
 //  query retriever/utils.py:59-66, fetch retriever/main.py:142).
 //
-// HBM layout: rows [capacity][ld] in the storage dtype (f32 / f16 / bf16),
-// L2-normalised at upsert, ld = 128 * nch (zero-padded), plus norms [capacity] f32.
+// HBM layout: rows [capacity][ld] in the storage dtype (f32 / f16 / bf16 / f8: e4m3 bytes of
+// the direction x 2^8, index_common.h), L2-normalised at upsert, ld = 128 * nch (zero-padded;
+// nch even for f8), plus norms [capacity] f32.
 //
 // Search (single / few queries) is one streaming pass over the rows:
 //   scan_topk_kernel: 16 lanes per row, 16-B loads, f32 FMA against the
@@ -387,10 +388,11 @@ bool row_map_fits(int64_t row_base, int64_t row_stride, int64_t cap) {
     return (double)row_base + (double)(cap - 1) * (double)row_stride < 4294967295.0;
 }
 
-int pick_nch(int dim) {
+// f8 rows are whole 256-element steps (16 lanes x 16 B): an even nch (RowShape::WHOLE)
+int pick_nch(int dim, int dtype) {
     const int need = (dim + 127) / 128;
     for (int n : kNchSet)
-        if (n >= need) return n;
+        if (n >= need && (dtype != RC_F8 || n % 2 == 0)) return n;
     return -1;
 }
 
@@ -658,11 +660,12 @@ int rc_index_create(int device, int dim, int dtype, int64_t capacity, int64_t ro
     return guard([&] {
         RC_REQUIRE(out != nullptr, RC_ERR_INVALID, "out is NULL");
         RC_REQUIRE(dim > 0, RC_ERR_INVALID, "dimension must be positive");
-        RC_REQUIRE(dtype == RC_F32 || dtype == RC_F16 || dtype == RC_BF16, RC_ERR_INVALID, "dtype must be RC_F32/RC_F16/RC_BF16");
+        RC_REQUIRE(dtype == RC_F32 || dtype == RC_F16 || dtype == RC_BF16 || dtype == RC_F8, RC_ERR_INVALID,
+                   "dtype must be RC_F32/RC_F16/RC_BF16/RC_F8");
         RC_REQUIRE(capacity > 0 && capacity < (int64_t(1) << 32), RC_ERR_INVALID, "capacity must be in [1, 2^32)");
         RC_REQUIRE(row_base >= 0 && row_map_fits(row_base, 1, capacity), RC_ERR_INVALID,
                    "row_base + capacity must stay below 2^32 - 1 (global rows key the top-k merge)");
-        const int nch = pick_nch(dim);
+        const int nch = pick_nch(dim, dtype);
         RC_REQUIRE(nch > 0, RC_ERR_UNSUPPORTED, "dimension > 2048 is not supported");
         DeviceScope ds(device);
         auto *h = new rc_index();
@@ -827,6 +830,8 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
         }
         RC_REQUIRE(h->metric == RC_METRIC_COSINE, RC_ERR_UNSUPPORTED,
                    "the int8 filter serves the batched MFMA search, which is cosine-only");
+        // its bound assumes ||x̂|| <= 1.01; an f8 row's norm is off by up to 2^-4 relative
+        RC_REQUIRE(h->dtype != RC_F8, RC_ERR_UNSUPPORTED, "the int8 filter is not available on a float8 index (exact scans only)");
         RC_REQUIRE(i8_filter_supported(h->ld), RC_ERR_UNSUPPORTED,
                    "the int8 filter needs a row width (dim rounded up to 128) of 256, 512 or 768");
         const int64_t pad = cap_pad(h->capacity);
@@ -992,7 +997,8 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
             empty_search(nq, k, scores, out_rows, s);
             return;
         }
-        const bool mfma_ok = h->metric == RC_METRIC_COSINE && (h->dtype != RC_F32 || h->rows8 != nullptr);
+        // (a float8 index has neither an MFMA filter nor the int8 copy: it scans)
+        const bool mfma_ok = h->metric == RC_METRIC_COSINE && ((h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr);
         RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
                    "batched MFMA search needs an f16/bf16 index or the int8 filter copy");
         // with a mask AUTO scans: only the caller knows the eligible share, and a selective mask

@@ -15,6 +15,13 @@ namespace rc {
 
 struct f16_t { uint16_t b; };
 struct bf16_t { uint16_t b; };
+// OCP e4m3fn byte of x̂_c · 2⁸ (round to nearest even): the stored value is decode(b) · 2⁻⁸.
+// |x̂_c| <= 1, so nothing reaches e4m3's 448, and elements down to 2⁻¹⁴ stay normal.  The scale
+// is a power of two, hence exact wherever it is applied: Elem<f8_t>::load applies it to the
+// value (fetch, stored rows), the scans fold it into their query registers (F8_UNSCALE at the
+// three sites that form them), so unpack16<f8_t> is the bare conversion.
+struct f8_t { uint8_t b; };
+constexpr float F8_SCALE = 256.0f, F8_UNSCALE = 1.0f / 256.0f;
 
 template <typename T> struct Elem;
 template <> struct Elem<float> {
@@ -30,7 +37,15 @@ template <> struct Elem<bf16_t> {
     __device__ static bf16_t cast(float x) { return bf16_t{f32_to_bf16(x)}; }
 };
 
-inline size_t dtype_size(int dtype) { return dtype == RC_F32 ? 4 : 2; }
+template <> struct Elem<f8_t> {
+    __device__ static float load(const f8_t *p, int64_t i) { return __builtin_amdgcn_cvt_f32_fp8((int)p[i].b, 0) * F8_UNSCALE; }
+    __device__ static f8_t cast(float x) { return f8_t{(uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(x * F8_SCALE, 0.f, 0, false) & 0xff)}; }
+};
+// What a scan multiplies its query registers by, so that its FMA chain over unpack16's values
+// yields the score of the stored values: 1 for every dtype but f8.
+template <typename T> constexpr float query_unscale() { return sizeof(T) == 1 ? F8_UNSCALE : 1.0f; }
+
+inline size_t dtype_size(int dtype) { return dtype == RC_F32 ? 4 : dtype == RC_F8 ? 1 : 2; }
 
 // A staging block of stored rows outside any index (row moves between shards, sharded.hip):
 // cap rows of ld elements in the storage dtype, and their f32 norms.
@@ -40,7 +55,7 @@ struct RowBlock {
     int64_t cap = 0;
 };
 
-// unpack one 16-B chunk into its 4 (f32) or 8 (f16/bf16) values
+// unpack one 16-B chunk into its 4 (f32), 8 (f16/bf16) or 16 (f8: decode(b), unscaled) values
 template <typename T>
 __device__ __forceinline__ void unpack16(const uint4 &x, float *out);
 template <>
@@ -66,6 +81,21 @@ __device__ __forceinline__ void unpack16<bf16_t>(const uint4 &x, float *o) {
     for (int i = 0; i < 4; ++i) {
         o[2 * i] = __uint_as_float(w[i] << 16);
         o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+}
+
+typedef float rc_f32x2 __attribute__((ext_vector_type(2)));
+template <>
+__device__ __forceinline__ void unpack16<f8_t>(const uint4 &x, float *o) {
+    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {  // v_cvt_pk_f32_fp8: two bytes of a word per instruction
+        const rc_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+        const rc_f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        o[4 * i] = lo.x;
+        o[4 * i + 1] = lo.y;
+        o[4 * i + 2] = hi.x;
+        o[4 * i + 3] = hi.y;
     }
 }
 
@@ -130,6 +160,9 @@ template <typename T, int NCH>
 struct RowShape {
     static constexpr int EPC = 16 / sizeof(T);           // values per 16-B chunk
     static constexpr int CPL = NCH * 128 / (16 * EPC);   // chunks per lane
+    // 16 lanes x CPL chunks cover the row exactly: every NCH but an odd one of f8 rows (16 lanes
+    // x 16 B = 256 elements), which no index has (pick_nch) and with_nch does not instantiate
+    static constexpr bool WHOLE = CPL * 16 * EPC == NCH * 128;
 };
 #define RC_ROW_FMA16(T, QB, CPL, EPC, X, Q, ACC)                                                 \
     do {                                                                                         \
@@ -162,6 +195,7 @@ void dispatch_dtype(int dtype, F &&f) {
         case RC_F32: f(float{}); break;
         case RC_F16: f(f16_t{}); break;
         case RC_BF16: f(bf16_t{}); break;
+        case RC_F8: f(f8_t{}); break;
         default: throw Error(RC_ERR_INVALID, "unknown dtype");
     }
 }
@@ -185,20 +219,21 @@ bool with_topk_cap(int cap, F &&f) {
 }
 
 // f(integral_constant<NCH>) for the row width ld = 128 * nch, nch in {1, 2, 3, 4, 6, 8, 12, 16}
-// up to MAX_NCH; false (f not called) for any other.
-template <int MAX_NCH, typename F, int... N>
+// up to MAX_NCH that rows of T can have (RowShape::WHOLE: the even ones for f8); false (f not
+// called, nor instantiated) for any other.
+template <int MAX_NCH, typename T, typename F, int... N>
 bool with_nch_of(int nch, F &&f, std::integer_sequence<int, N...>) {
     auto one = [&](auto n) {
-        if constexpr (decltype(n)::value <= MAX_NCH) {
+        if constexpr (decltype(n)::value <= MAX_NCH && RowShape<T, decltype(n)::value>::WHOLE) {
             if (nch == decltype(n)::value) return f(n), true;
         }
         return false;
     };
     return (one(std::integral_constant<int, N>{}) || ...);
 }
-template <int MAX_NCH = 16, typename F>
+template <int MAX_NCH = 16, typename T = float, typename F>
 bool with_nch(int nch, F &&f) {
-    return with_nch_of<MAX_NCH>(nch, f, std::integer_sequence<int, 1, 2, 3, 4, 6, 8, 12, 16>{});
+    return with_nch_of<MAX_NCH, T>(nch, f, std::integer_sequence<int, 1, 2, 3, 4, 6, 8, 12, 16>{});
 }
 
 struct ScanArgs {
@@ -247,9 +282,9 @@ inline int scan_max_qb(int nch, int k, bool masked = false, int metric = RC_METR
 }
 
 template <typename T>
-void launch_scan(const ScanArgs &a);  // scan.h; instantiated in scan_{f32,f16,bf16}.hip
+void launch_scan(const ScanArgs &a);  // scan.h; instantiated in scan_{f32,f16,bf16,f8}.hip
 template <typename T>
-void launch_scan_metric(const ScanArgs &a);  // scan_metric.h; instantiated in scan_metric_{f32,f16,bf16}.hip
+void launch_scan_metric(const ScanArgs &a);  // scan_metric.h; instantiated in scan_metric_{f32,f16,bf16,f8}.hip
 
 // One query, one launch (rc_sharded_query_host's request path): query1_kernel normalises the
 // query (carried in the kernel arguments: no copy), scans its block's rows, and the last block
@@ -281,8 +316,8 @@ struct Query1Args {
 };
 static_assert(sizeof(Query1Args) == 3200, "Query1Args is the one-launch kernels' argument block");
 template <typename T>
-void launch_query1(const Query1Args &a, hipStream_t s);  // scan.h; instantiated in scan_{f32,f16,bf16}.hip
-// phase 1 under a non-cosine metric (launch_query1 calls it); scan_metric.h, instantiated in scan_metric_{f32,f16,bf16}.hip
+void launch_query1(const Query1Args &a, hipStream_t s);  // scan.h; instantiated in scan_{f32,f16,bf16,f8}.hip
+// phase 1 under a non-cosine metric (launch_query1 calls it); scan_metric.h, instantiated in scan_metric_{f32,f16,bf16,f8}.hip
 template <typename T>
 void launch_query1_metric_scan(const Query1Args &a, hipStream_t s);
 

@@ -1,9 +1,9 @@
 // scan.h — the single-query streaming scan (HBM-bound GEMV + fused wavefront top-k) and the
 // one-launch query of the exact cosine index: device code and launch chains.  Included only by
-// scan_{f32,f16,bf16}.hip, which instantiate launch_scan<T> / launch_query1<T> for one storage
-// dtype each, so the three translation units compile in parallel.  The device functions' METRIC
+// scan_{f32,f16,bf16,f8}.hip, which instantiate launch_scan<T> / launch_query1<T> for one storage
+// dtype each, so the four translation units compile in parallel.  The device functions' METRIC
 // forms (dotproduct / euclidean scores) are instantiated by scan_metric.h's kernels, in
-// scan_metric_{f32,f16,bf16}.hip.
+// scan_metric_{f32,f16,bf16,f8}.hip.
 #pragma once
 
 #include "index_common.h"
@@ -14,8 +14,13 @@ namespace rc {
 // queries, so every slot is computed and stored unconditionally.
 // Block = 4 waves over a contiguous row range.  Lane = (row-in-group rg = lane>>4,
 // position sub = lane&15); 16-B chunk j = sub + 16 i of a row holds elements
-// [j*EPC, (j+1)*EPC).  SCAN_U row-groups are loaded before any is consumed.
-constexpr int SCAN_U = 2;
+// [j*EPC, (j+1)*EPC).  scan_u<T, QB>() row-groups are loaded before any is consumed: 2, and 4
+// for single-query passes over one-byte elements, whose row group is half the bytes — the same
+// bytes in flight per wave (SCAN_U x 4 rows x ld bytes) and the same x[][] registers as an f16
+// row of that width.  (Multi-query passes do QB times the arithmetic per byte and keep 2: with 4
+// copies of a QB = 4 body hipcc leaves the consuming loop rolled and x[][] goes to scratch.)
+template <typename T, int QB>
+constexpr int scan_u() { return sizeof(T) == 1 && QB == 1 ? 4 : 2; }
 
 typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4)));  // the nontemporal load's operand type
 
@@ -24,9 +29,11 @@ typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4)));  // the nontempor
 // MASKED: only rows whose bit is set in `mask` (see ScanArgs) enter the top-k.  A wave's
 // iteration covers the 8 rows g .. g + 7 with g = r0 + 8 wave + 32 it and r0 a multiple of 32
 // (rows_per_block is), so their bits are byte (g & 31) / 8 of word g >> 5: one wave-uniform word
-// per iteration, loaded one iteration ahead of its use.  A zero byte skips the iteration's row
-// loads altogether (wave-uniform branch: every reserve / push stays wave-collective) — the HBM
-// bytes a selective filter saves.  The per-row arithmetic is untouched, so an eligible row's
+// per iteration, loaded one iteration ahead of its use.  (In general 4 SCAN_U rows, a divisor of
+// 32: with SCAN_U = 4 the 16 rows from g = r0 + 16 wave + 64 it are half a word, and "byte"
+// below reads as those 16 bits.)  A zero byte skips the iteration's row loads altogether
+// (wave-uniform branch: every reserve / push stays wave-collective) — the HBM bytes a selective
+// filter saves.  The per-row arithmetic is untouched, so an eligible row's
 // score has the bits the unmasked scan gives it.
 // METRIC (one query per pass): the key's score is metric_score(mc, cosine, norms[row]), formed
 // per row before the top-k, so the list is the metric's own top-k (index_common.h has the rule).
@@ -41,6 +48,8 @@ __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t 
     static_assert(!METRIC || QB == 1, "the metric scans take one query per pass");
     constexpr int EPC = RowShape<T, NCH>::EPC;
     constexpr int CPL = RowShape<T, NCH>::CPL;
+    constexpr int SCAN_U = scan_u<T, QB>();
+    static_assert(RowShape<T, NCH>::WHOLE, "16 lanes x CPL chunks must cover the row");
     __shared__ uint64_t lds[4][QB][CAP];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane & 15, rg = lane >> 4;
@@ -53,19 +62,21 @@ __device__ __forceinline__ void scan_rows_q(const T *__restrict__ rows, int64_t 
     const uint4 *base4 = reinterpret_cast<const uint4 *>(rows);
     const int64_t ld4 = ld / EPC;  // row stride in 16-B chunks
 
-    static_assert(!MASKED || 16 * SCAN_U == 32, "the masked scan reads one mask word per 32-row block step");
+    // a wave's 4 SCAN_U rows start at a multiple of 4 SCAN_U (r0 is one of 32): inside one word
+    static_assert(!MASKED || 32 % (4 * SCAN_U) == 0, "the masked scan reads a wave's row bits from one mask word");
+    [[maybe_unused]] constexpr uint32_t MBITS = (1u << (4 * SCAN_U)) - 1u;
     [[maybe_unused]] uint32_t mword = 0;  // MASKED: the mask word of this wave's next iteration
     if constexpr (MASKED) {
         const int64_t g0 = r0 + wave * 4 * SCAN_U;
         if (g0 < r1) mword = mask[g0 >> 5];  // g0 < r1 <= n_rows: inside the bitmap's ceil(n_rows / 32) words
     }
     for (int64_t g = r0 + wave * 4 * SCAN_U; g < r1; g += 16 * SCAN_U) {
-        [[maybe_unused]] uint32_t mbyte = 0xffu;  // MASKED: bit j = row g + j is eligible
+        [[maybe_unused]] uint32_t mbyte = MBITS;  // MASKED: bit j = row g + j is eligible
         if constexpr (MASKED) {
-            mbyte = ((uint32_t)__builtin_amdgcn_readfirstlane((int)mword) >> (uint32_t)(g & 31)) & 0xffu;
+            mbyte = ((uint32_t)__builtin_amdgcn_readfirstlane((int)mword) >> (uint32_t)(g & 31)) & MBITS;
             const int64_t gn = g + 16 * SCAN_U;
             if (gn < r1) mword = mask[gn >> 5];
-            if (mbyte == 0u) continue;  // wave-uniform: none of the 8 rows is eligible, no row is loaded
+            if (mbyte == 0u) continue;  // wave-uniform: none of the wave's rows is eligible, no row is loaded
         }
         [[maybe_unused]] float nrm[SCAN_U];  // METRIC: the norms of this lane's rows
         if constexpr (METRIC) {
@@ -154,6 +165,7 @@ __device__ __forceinline__ void scan_rows(const T *__restrict__ rows, int64_t ld
                 for (int e = 0; e < EPC; ++e) {
                     const int c = (sub + 16 * i) * EPC + e;
                     q[b][i][e] = RC_UNIT_ELEM(src, c, dim, inv, valid);
+                    if constexpr (sizeof(T) == 1) q[b][i][e] *= query_unscale<T>();  // exact: a power of two
                 }
         }
     } else {
@@ -162,7 +174,10 @@ __device__ __forceinline__ void scan_rows(const T *__restrict__ rows, int64_t ld
 #pragma unroll
             for (int i = 0; i < CPL; ++i)
 #pragma unroll
-                for (int e = 0; e < EPC; ++e) q[b][i][e] = qn[(int64_t)(q0 + b) * ld + (sub + 16 * i) * EPC + e];
+                for (int e = 0; e < EPC; ++e) {
+                    q[b][i][e] = qn[(int64_t)(q0 + b) * ld + (sub + 16 * i) * EPC + e];
+                    if constexpr (sizeof(T) == 1) q[b][i][e] *= query_unscale<T>();
+                }
     }
     scan_rows_q<T, NCH, QB, CAP, MASKED, METRIC>(rows, ld, n_rows, rows_per_block, q, q0, nq_total, k, partial, mask, norms, mc);
 }
@@ -235,7 +250,7 @@ void launch_scan_qb(const ScanArgs &a) {
 template <typename T>
 void launch_scan(const ScanArgs &a) {
     if (a.metric != RC_METRIC_COSINE) return launch_scan_metric<T>(a);  // the metric kernels' own translation units
-    const bool ok = with_nch(a.nch, [&](auto nch) {
+    const bool ok = with_nch<16, T>(a.nch, [&](auto nch) {
         constexpr int NCH = decltype(nch)::value;
         if constexpr (NCH <= 2) {  // queries per pass: scan_max_qb's register budget
             if (a.qb == 4) return launch_scan_qb<T, NCH, 4>(a);
@@ -289,6 +304,7 @@ __device__ __forceinline__ void query1_scan(const Query1Args &a) {
         for (int e = 0; e < EPC; ++e) {
             const int c = (sub + 16 * i) * EPC + e;
             q[0][i][e] = RC_UNIT_ELEM(qs, c, a.dim, inv, true);
+            if constexpr (sizeof(T) == 1) q[0][i][e] *= query_unscale<T>();  // as scan_rows
         }
     scan_rows_q<T, NCH, 1, CAP, false, METRIC>((const T *)a.rows, a.ld, a.n_rows, a.rows_per_block, q, 0, 1, a.k, a.partial,
                                                nullptr, a.norms, mc);
@@ -358,7 +374,7 @@ __global__ __launch_bounds__(256) void query1_kernel(const Query1Args a) {
 // Instantiated for row widths up to 768 (QUERY1_MAX_DIM) and k <= 128.
 template <typename T>
 void launch_query1(const Query1Args &a, hipStream_t s) {
-    const bool ok = with_nch<6>(a.nch, [&](auto nch) {
+    const bool ok = with_nch<6, T>(a.nch, [&](auto nch) {
         const bool cap_ok = with_topk_cap<256>(topk_cap(a.k), [&](auto cap) {
             constexpr int NCH = decltype(nch)::value, CAP = decltype(cap)::value;
             if (a.metric != RC_METRIC_COSINE) {  // phase 1 under the metric; phase 2 is the same

@@ -1,7 +1,7 @@
 // scan_metric.h — the scan and the one-launch query under a non-cosine metric (dotproduct,
 // euclidean: rc_index_set_metric): kernels over scan.h's METRIC device functions and their launch
-// chains.  Included only by scan_metric_{f32,f16,bf16}.hip, which instantiate
-// launch_scan_metric<T> / launch_query1_metric_scan<T> for one storage dtype each: three more
+// chains.  Included only by scan_metric_{f32,f16,bf16,f8}.hip, which instantiate
+// launch_scan_metric<T> / launch_query1_metric_scan<T> for one storage dtype each: four more
 // translation units that compile in parallel, and the cosine units keep their kernels.
 #pragma once
 
@@ -27,7 +27,7 @@ void launch_scan_metric(const ScanArgs &a) {
     if (a.qraw == nullptr || a.norms == nullptr || a.qb != 1 || a.flags != nullptr)
         throw Error(RC_ERR_INVALID, "internal: a metric scan takes raw queries, one per pass, and the norms");
     const dim3 grid(a.nblk);
-    const bool ok = with_nch(a.nch, [&](auto nch) {
+    const bool ok = with_nch<16, T>(a.nch, [&](auto nch) {
         with_topk_cap(topk_cap(a.k), [&](auto cap) {
             constexpr int NCH = decltype(nch)::value, CAP = decltype(cap)::value;
             auto launch = [&](auto masked) {
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void query1_metric_kernel(const Query1Args a) 
 
 template <typename T>
 void launch_query1_metric_scan(const Query1Args &a, hipStream_t s) {
-    const bool ok = with_nch<6>(a.nch, [&](auto nch) {
+    const bool ok = with_nch<6, T>(a.nch, [&](auto nch) {
         const bool cap_ok = with_topk_cap<256>(topk_cap(a.k), [&](auto cap) {
             hipLaunchKernelGGL((query1_metric_kernel<T, decltype(nch)::value, decltype(cap)::value>), dim3(a.nblk), dim3(256), 0, s, a);
         });

@@ -1038,11 +1038,13 @@ void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
     if (p.rows8 != nullptr) {
         RC_REQUIRE(i8_filter_supported(p.ld), RC_ERR_UNSUPPORTED, "int8 filter needs ld 256, 512 or 768");
         if (p.dtype == RC_F16 || p.dtype == RC_BF16 || p.dtype == RC_F32)
-            return dispatch_dtype(p.dtype, [&](auto t) { run_batched_i8<decltype(t)>(p, ws, s, timer); });
+            return dispatch_dtype(p.dtype, [&](auto t) {  // (no batched search on f8 rows: nothing instantiated)
+                if constexpr (!std::is_same_v<decltype(t), f8_t>) run_batched_i8<decltype(t)>(p, ws, s, timer);
+            });
     }
     if (p.dtype == RC_F16 || p.dtype == RC_BF16)  // the MFMA operand dtypes
         return dispatch_dtype(p.dtype, [&](auto t) {
-            if constexpr (!std::is_same_v<decltype(t), float>) run_batched<decltype(t)>(p, ws, s, timer);
+            if constexpr (!std::is_same_v<decltype(t), float> && !std::is_same_v<decltype(t), f8_t>) run_batched<decltype(t)>(p, ws, s, timer);
         });
     throw Error(RC_ERR_UNSUPPORTED, "batched MFMA search needs an f16 or bf16 index (or the int8 filter copy)");
 }

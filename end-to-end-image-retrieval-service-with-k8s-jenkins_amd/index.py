@@ -184,7 +184,8 @@ class DeviceIndex:
         said otherwise): (scores f32 [nq,k] descending, global rows i64 [nq,k]).
 
         ``mode``: "scan" (HBM-bound streaming scan), "mfma" (batched filter GEMM +
-        exact rescoring, f16/bf16 index, cosine only) or "auto" (MFMA for >= 8 queries).
+        exact rescoring, f16/bf16 index, cosine only) or "auto" (MFMA for >= 8 queries; a
+        float8 index always scans and refuses "mfma").
         ``mask``: optional row-eligibility bitmap over the LOCAL rows (rc_index_search_masked):
         an int32 / uint32 tensor of ceil(n_rows / 32) words on this device, bit r & 31 of word
         r >> 5 = row r may be returned; "auto" then scans."""
@@ -210,7 +211,7 @@ class DeviceIndex:
 
     def export_rows(self, row0: int, n: int, stream=None):
         """Raw stored rows [row0, row0+n) (storage dtype bits, ld-padded) and norms, on the device."""
-        el = 4 if self.dtype in ("float32", "f32") else 2
+        el = _lib.dtype_bytes(self.dtype)
         rows = torch.empty((n, self.ld * el), dtype=torch.uint8, device=self.device)
         norms = torch.empty((n,), dtype=torch.float32, device=self.device)
         check(self.lib.rc_index_export(self.handle, int(row0), int(n), ptr(rows), ptr(norms), stream_ptr(stream)))
@@ -218,7 +219,7 @@ class DeviceIndex:
 
     def import_rows(self, row0: int, rows: torch.Tensor, norms: torch.Tensor, stream=None) -> None:
         """Inverse of export_rows: write raw stored rows + norms at [row0, row0+n)."""
-        el = 4 if self.dtype in ("float32", "f32") else 2
+        el = _lib.dtype_bytes(self.dtype)
         rows = rows.to(device=self.device, dtype=torch.uint8).contiguous()
         norms = norms.to(device=self.device, dtype=torch.float32).contiguous()
         n = norms.numel()
@@ -702,7 +703,7 @@ class ShardSet:
     def export_rows(self, n_rows: int):
         import numpy as np
 
-        el = 4 if self.dtype in ("float32", "f32") else 2
+        el = _lib.dtype_bytes(self.dtype)
         rows = np.zeros((n_rows, self.ld * el), dtype=np.uint8)
         norms = np.zeros((n_rows,), dtype=np.float32)
         for s in range(self.n):
@@ -742,6 +743,11 @@ class Index:
     ``mode="mfma"`` and ``filter="i8"`` raise ``ValueError`` on it.  All-zero vectors and
     queries are rejected under every metric.
 
+    ``dtype`` is the storage of the normalised rows: ``"float32"``, ``"float16"``, ``"bfloat16"``
+    or ``"float8_e4m3fn"`` (alias ``"f8"``: one byte per element, each element of the direction
+    rounded to 3 mantissa bits; exact scans only, so ``mode="mfma"`` and ``filter="i8"`` raise
+    ``ValueError`` on it and ``"auto"`` scans).
+
     ``upsert(vectors)`` accepts ``(id, values)``, ``(id, values, metadata)``
     tuples or ``{"id", "values", "metadata"}`` dicts and overwrites existing
     ids (within one call the last occurrence of an id wins); ``query`` returns
@@ -775,6 +781,8 @@ class Index:
             raise ValueError(f"unknown filter {filter!r} (expected one of {sorted(_lib.FILTERS)})")
         if metric != "cosine" and filter != "native":
             raise ValueError(f"filter={filter!r} serves the batched MFMA search, which is cosine-only (metric={metric!r})")
+        if _lib.is_f8(dtype) and filter != "native":
+            raise ValueError(f"filter={filter!r} serves the batched MFMA search, which a float8 index does not have")
         if devices is None:
             devices = [device] * int(shards or 1)
         self.name = name
@@ -1099,7 +1107,7 @@ class Index:
         reaches MASKED_MFMA_MIN_SHARE."""
         if mode != "auto":
             return mode
-        if self.metric != "cosine":  # the batched MFMA path is cosine-only
+        if self.metric != "cosine" or _lib.is_f8(self._set.dtype):  # the batched MFMA path: cosine, not float8
             return "scan"
         mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter == "i8"
         if mfma_ok and nq >= 8 and n // self._set.n >= 65536 and eligible >= MASKED_MFMA_MIN_SHARE * n:

@@ -41,6 +41,11 @@ extern "C" {
 #define RC_F32 0
 #define RC_F16 1
 #define RC_BF16 2
+/* float8: each element is the OCP e4m3fn byte (round to nearest even) of x̂_c · 2⁸, the stored
+ * value is decode(byte) · 2⁻⁸ (3 mantissa bits; |x̂_c| <= 1, so nothing saturates, and elements
+ * down to 2⁻¹⁴ stay normal).  One byte per element, ld = round_up(dim, 256).  Exact scans only:
+ * RC_SEARCH_MFMA and RC_FILTER_I8 are RC_ERR_UNSUPPORTED on it, RC_SEARCH_AUTO scans. */
+#define RC_F8 3
 
 /* Pillow resampling filters (PIL.Image.Resampling values) */
 #define RC_RESAMPLE_BILINEAR 2
@@ -66,7 +71,7 @@ int64_t rc_alloc_count(void);
  *   index.query(v, top_k)      retriever/utils.py:62-64
  *   index.fetch(ids)           retriever/main.py:142
  * Rows are stored L2-normalised in `dtype`, row-major with leading dimension
- * ld = round_up(dim, 128) (zero padded).  String ids and metadata stay on the
+ * ld = round_up(dim, 128) (round_up(dim, 256) for RC_F8; zero padded).  String ids and metadata stay on the
  * host; the device only knows row numbers.  A search returns
  * row_base + local_row * row_stride (row_stride = 1 unless rc_index_set_row_map
  * says otherwise): the global row of a shard in a multi-GPU index.
@@ -165,7 +170,7 @@ int rc_index_search_ex(rc_index *h, const float *queries, int nq, int64_t n_rows
  * Same contract otherwise: an eligible row's score is bit-identical to the unmasked
  * search's, ties order by row, slots past the eligible rows get -inf / -1 (a mask
  * with no eligible row is valid).  Modes: RC_SEARCH_SCAN skips the row loads of
- * every 8-row group without an eligible row; RC_SEARCH_MFMA keeps the filter GEMM
+ * every 8-row group (16-row on an RC_F8 index) without an eligible row; RC_SEARCH_MFMA keeps the filter GEMM
  * as it is and drops ineligible candidates when rescoring (overflowed queries fall
  * back to the masked scan on the device); RC_SEARCH_AUTO with a mask scans. */
 int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_rows, int k,
