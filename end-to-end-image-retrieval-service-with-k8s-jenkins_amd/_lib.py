@@ -45,8 +45,8 @@ def is_f8(dtype: str) -> bool:
     return DTYPES.get(dtype) == RC_F8
 
 
-RC_FILTER_NATIVE, RC_FILTER_I8 = 0, 1
-FILTERS = {"native": RC_FILTER_NATIVE, "i8": RC_FILTER_I8}
+RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8 = 0, 1, 2
+FILTERS = {"native": RC_FILTER_NATIVE, "i8": RC_FILTER_I8, "f8": RC_FILTER_F8}
 RC_METRIC_COSINE, RC_METRIC_DOT, RC_METRIC_EUCLIDEAN = 0, 1, 2
 METRICS = {"cosine": RC_METRIC_COSINE, "dotproduct": RC_METRIC_DOT, "euclidean": RC_METRIC_EUCLIDEAN}  # Pinecone's names
 
@@ -128,6 +128,7 @@ SIGNATURES = {
     "rc_index_grow": (C.c_int, [_vp, _i64, _vp]),
     "rc_index_set_filter": (C.c_int, [_vp, _i32, _vp]),
     "rc_index_get_filter": (C.c_int, [_vp, _pi32]),
+    "rc_index_filter_scores": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),
     "rc_sharded_set_filter": (C.c_int, [_vp, _i32]),
     "rc_index_set_metric": (C.c_int, [_vp, _i32]),
     "rc_index_get_metric": (C.c_int, [_vp, _pi32]),

@@ -381,6 +381,18 @@ constexpr int kNchSet[] = {1, 2, 3, 4, 6, 8, 12, 16};
 constexpr int kMaxBlocks = 2048;
 constexpr int kBatchMinQueries = 8;      // below this the HBM-bound scan wins (1-4 queries per pass)
 constexpr int64_t kBatchMinRows = 65536;  // tiny shards: the staged path's fixed cost dominates
+// The float8 filter (RC_FILTER_F8) has a corner of its own: the scan it competes with reads half the
+// bytes of an f16 scan, and at the two thresholds above that scan wins (16 queries x top-10, wall
+// ms per call, filter / scan, tools/f8_filter_micro.py --crossover, profiles/f8_filter/): 70 000 x 256
+// 0.331 / 0.232, 70 000 x 512 0.365 / 0.352, 300 000 x 256 0.465 / 0.339, and with 8 queries
+// everywhere up to 300 000 x 512.  What decides is how many passes the scan needs, P = ceil(nq /
+// queries per pass) (scan_max_qb: 4, 2 or 1 by row width), at about 20 us plus the row bytes each.
+// Measured: P = 16 wins from 140 000 rows at every width (1.17-2.2x; at 66 000 x 768, top-100, it
+// is 0.91x), P = 8 is at parity from 72 MB of rows and ahead from 230 MB (1.12x; 512 MB: 2.0x).
+constexpr int kF8BatchMinPasses = 16;
+constexpr int64_t kF8BatchMinRows = 131072;
+constexpr int kF8BatchMinPassesLarge = 8;                     // ... with at least
+constexpr int64_t kF8BatchMinBytesLarge = int64_t(1) << 28;  // this many bytes of rows
 
 // Every global row a shard can report must fit the 32-bit row word of the top-k
 // keys (merge_lists_kernel) below the all-ones value: row_base + (cap - 1) * stride < 2^32 - 1.
@@ -527,6 +539,9 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
     launch_merge_partials(h, h->partial, nullptr, nblk, nq, nq_pad, k, scores, out_rows, s);
 }
 
+// bytes per element of BatchWs::qh: the storage dtype's, and two byte planes (q_hi, q_lo) on a float8 index
+int batch_query_bytes(const rc_index *h) { return h->dtype == RC_F8 ? 2 : (int)dtype_size(h->dtype); }
+
 // Batched MFMA search, then — still on the device, no host synchronisation —
 // the exact scan for every query whose candidates overflowed: scan_topk_kernel
 // in fallback mode (blocks early-exit for unflagged queries) over the batched
@@ -536,8 +551,9 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
 // fallback is the masked scan; the merge is the same.
 void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
                           float *scores, int64_t *out_rows, hipStream_t s) {
-    h->bws.ensure(nq, k, h->ld, (int)dtype_size(h->dtype));
+    h->bws.ensure(nq, k, h->ld, batch_query_bytes(h));
     BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, n_rows, h->row_base, h->row_stride, queries, nq, k, scores, out_rows};
+    p.f8_filter = h->filter == RC_FILTER_F8;
     p.rows8 = h->rows8;
     p.rsx = h->rsx;
     p.rex = h->rex;
@@ -818,7 +834,8 @@ int rc_index_reserve(rc_index *h, int max_nq, int max_k) {
 int rc_index_set_filter(rc_index *h, int kind, void *stream) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_I8, RC_ERR_INVALID, "filter must be RC_FILTER_NATIVE or RC_FILTER_I8");
+        RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_I8 || kind == RC_FILTER_F8, RC_ERR_INVALID,
+                   "filter must be RC_FILTER_NATIVE, RC_FILTER_I8 or RC_FILTER_F8");
         std::lock_guard<std::mutex> lk(h->mu);
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
@@ -828,10 +845,20 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
             free_filter(h);
             return;
         }
+        if (kind == RC_FILTER_F8) {  // allocates nothing: the filter GEMM reads the stored rows
+            RC_REQUIRE(h->dtype == RC_F8, RC_ERR_UNSUPPORTED, "the float8 filter reads stored float8 rows: it needs a float8 index");
+            RC_REQUIRE(h->metric == RC_METRIC_COSINE, RC_ERR_UNSUPPORTED,
+                       "the float8 filter serves the batched MFMA search, which is cosine-only");
+            RC_REQUIRE(f8_filter_supported(h->ld), RC_ERR_UNSUPPORTED,
+                       "the float8 filter needs a row width (dim rounded up to 256) of 256, 512 or 768");
+            h->filter = RC_FILTER_F8;  // (h->rows8 is null: the int8 copy is refused on a float8 index)
+            return;
+        }
         RC_REQUIRE(h->metric == RC_METRIC_COSINE, RC_ERR_UNSUPPORTED,
                    "the int8 filter serves the batched MFMA search, which is cosine-only");
         // its bound assumes ||x̂|| <= 1.01; an f8 row's norm is off by up to 2^-4 relative
-        RC_REQUIRE(h->dtype != RC_F8, RC_ERR_UNSUPPORTED, "the int8 filter is not available on a float8 index (exact scans only)");
+        RC_REQUIRE(h->dtype != RC_F8, RC_ERR_UNSUPPORTED,
+                   "the int8 filter is not available on a float8 index (its batched search is RC_FILTER_F8)");
         RC_REQUIRE(i8_filter_supported(h->ld), RC_ERR_UNSUPPORTED,
                    "the int8 filter needs a row width (dim rounded up to 128) of 256, 512 or 768");
         const int64_t pad = cap_pad(h->capacity);
@@ -865,8 +892,8 @@ int rc_index_set_metric(rc_index *h, int metric) {
         RC_REQUIRE(metric == RC_METRIC_COSINE || metric == RC_METRIC_DOT || metric == RC_METRIC_EUCLIDEAN, RC_ERR_INVALID,
                    "metric must be RC_METRIC_COSINE, RC_METRIC_DOT or RC_METRIC_EUCLIDEAN");
         std::lock_guard<std::mutex> lk(h->mu);
-        RC_REQUIRE(metric == RC_METRIC_COSINE || h->rows8 == nullptr, RC_ERR_UNSUPPORTED,
-                   "a non-cosine metric on an index with the int8 filter copy (the batched MFMA search is cosine-only)");
+        RC_REQUIRE(metric == RC_METRIC_COSINE || h->filter == RC_FILTER_NATIVE, RC_ERR_UNSUPPORTED,
+                   "a non-cosine metric on an index with the int8 filter copy or the float8 filter (the batched MFMA search is cosine-only)");
         h->metric = metric;  // no device call: searches already enqueued took the metric they were launched with
     });
 }
@@ -997,19 +1024,45 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
             empty_search(nq, k, scores, out_rows, s);
             return;
         }
-        // (a float8 index has neither an MFMA filter nor the int8 copy: it scans)
-        const bool mfma_ok = h->metric == RC_METRIC_COSINE && ((h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr);
+        // (a float8 index scans unless its own filter is switched on: RC_FILTER_F8)
+        const bool mfma_ok = h->metric == RC_METRIC_COSINE && ((h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr ||
+                                                               h->filter == RC_FILTER_F8);
         RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
-                   "batched MFMA search needs an f16/bf16 index or the int8 filter copy");
+                   "batched MFMA search needs an f16/bf16 index, the int8 filter copy, or a float8 index with RC_FILTER_F8");
         // with a mask AUTO scans: only the caller knows the eligible share, and a selective mask
         // makes the scan cheaper while the filter GEMM still reads every row (MFMA on request)
-        const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && mask == nullptr && mfma_ok &&
-                                                         nq >= kBatchMinQueries && n_rows >= kBatchMinRows);
+        bool auto_mfma = nq >= kBatchMinQueries && n_rows >= kBatchMinRows;
+        if (h->filter == RC_FILTER_F8) {  // its own corner (see kF8BatchMinPasses)
+            const int qb = scan_max_qb(h->nch, k);
+            const int passes = (nq + qb - 1) / qb;
+            auto_mfma = (passes >= kF8BatchMinPasses && n_rows >= kF8BatchMinRows) ||
+                        (passes >= kF8BatchMinPassesLarge && n_rows * h->ld >= kF8BatchMinBytesLarge);
+        }
+        const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && mask == nullptr && mfma_ok && auto_mfma);
         if (!use_mfma) {
             scan_search(h, queries, nq, n_rows, k, mask, scores, out_rows, s);
             return;
         }
         batched_search_exact(h, queries, nq, n_rows, k, mask, scores, out_rows, s);
+    });
+}
+
+int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t row0, int64_t n, float *out_scores,
+                           float *out_eps, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0 && n >= 0, RC_ERR_INVALID, "negative count");
+        RC_REQUIRE(row0 >= 0 && row0 % 128 == 0 && row0 + n <= h->capacity, RC_ERR_INVALID,
+                   "row0 must be a multiple of 128 and the rows inside the capacity");
+        if (nq == 0 || n == 0) return;
+        RC_REQUIRE(queries && out_scores && out_eps, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        RC_REQUIRE(h->filter == RC_FILTER_F8, RC_ERR_UNSUPPORTED, "filter scores are the float8 filter's (RC_FILTER_F8)");
+        DeviceScope ds(h->device);
+        h->bws.ensure(nq, 16, h->ld, batch_query_bytes(h));
+        BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, row0 + n, h->row_base, h->row_stride, queries, nq, 16, nullptr, nullptr};
+        p.f8_filter = true;
+        filter_scores_f8(p, h->bws, row0, n, out_scores, out_eps, (hipStream_t)stream);
     });
 }
 

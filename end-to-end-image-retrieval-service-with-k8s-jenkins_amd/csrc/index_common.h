@@ -367,7 +367,7 @@ struct BatchWs {
     int64_t ld_cap = 0;
     int cap = BATCH_CAND_CAP;
     float *qn = nullptr;        // [nq_cap][ld] normalised queries (f32)
-    void *qh = nullptr;         // [nq_cap][ld] queries in the storage dtype (MFMA operand)
+    void *qh = nullptr;         // [nq_cap][ld] queries in the storage dtype (MFMA operand); float8: two byte planes
     float *eps = nullptr;       // [nq_cap] bound on |s' - s|
     float *thr = nullptr;       // [nq_cap] current filter threshold
     uint32_t *cnt = nullptr;    // [nq_cap] candidates appended this stage
@@ -403,6 +403,8 @@ struct BatchPlan {
     const float *rex = nullptr;     // [cap_pad] ||x̂ - x̃||₂ (rounded up), at i8_slot(row)
     // row-eligibility bitmap over the local rows (ScanArgs::mask), or null: applied in rescore_kernel
     const uint32_t *mask = nullptr;
+    // float8 index with rc_index_set_filter(RC_FILTER_F8): the filter GEMM reads the stored e4m3 rows
+    bool f8_filter = false;
 };
 
 // The int8 filter keeps a row's scale and residual norm at a tile-transposed slot:
@@ -412,9 +414,14 @@ __host__ __device__ __forceinline__ int64_t i8_slot(int64_t row) {
     return (row & ~int64_t(127)) + (row & 15) * 8 + ((row & 127) >> 4);
 }
 bool i8_filter_supported(int64_t ld);  // row widths filter_i8_kernel is instantiated for
+bool f8_filter_supported(int64_t ld);  // ... and filter_f8_kernel
 
 // Enqueue the staged filter-GEMM / rescore search on `s` (no host sync).
 void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer);
 int batch_stage_ratio(int k, int cap, int inflation = 1);
+// The float8 filter's scores s' of p.queries against local rows [row0, row0 + n) (row0 a multiple
+// of 128), f32 [nq][n], and its eps [nq], enqueued on `s` (rc_index_filter_scores).
+void filter_scores_f8(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, float *out_scores, float *out_eps,
+                      hipStream_t s);
 
 }  // namespace rc

@@ -801,6 +801,290 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
     }
 }
 
+// ------------------------------------------- float8 filter (RC_FILTER_F8) --
+// A float8 index's own filter GEMM (rc_index_set_filter(RC_FILTER_F8)): it reads the stored e4m3
+// bytes, no copy.  The instruction is the block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 with both
+// operands e4m3 (twice the f16 MFMA rate at K = 128 per instruction); its E8M0 scale operands
+// carry every power of two, exactly: 127 is 2⁰, the stored rows' 2⁻⁸ (F8_UNSCALE) is 119.
+//
+// Query in TERMS e4m3 terms.  One term (the storage rule applied to qn) leaves ||qn - q_hi|| ≈
+// 0.026 for a unit query, a hundred times the f16 filter's rounding.  With two,
+//   q_hi = e4m3(qn·2⁸)·2⁻⁸            (scale byte 119, the rows' rule: Elem<f8_t>::cast)
+//   q_lo = e4m3((qn - q_hi)·2¹²)·2⁻¹²  (scale byte 115; |qn_c - q_hi,c| <= 2⁻⁴, so |·2¹²| <= 256 < 448)
+// the residual ||qn - q_hi - q_lo|| is ≈ 6e-4, the f16 filter's order, and the stage ratio needs no
+// inflation.  Both terms accumulate into the same accumulators: s' = (q_hi + q_lo)·x̂.
+//
+// Bound.  |s' - s| <= ||qn - q_hi - q_lo||·||x̂||max + c_acc, with ||x̂||max = 1.07 (a stored
+// float8 row's norm is within 2⁻⁴ relative of 1) and c_acc = 6.5e-5 (the f32 chain of the exact
+// score, as in the header) + c_mfma.  ASSUMPTION: the order and rounding of the MFMA's internal
+// sums are not documented; c_mfma bounds them as a truncation (relative 2⁻²³) at every one of the
+// ld products' additions and the TERMS·ld/128 accumulator additions of a score, on partial sums
+// whose magnitude stays below ||q̃||·||x̂|| <= 1.07: c_mfma = (ld + TERMS·ld/128)·2⁻²³·1.07
+// (1.0e-4 at ld 768).  rc_index_filter_scores exposes s' so that tests measure the real error
+// against it.  eps[q] = 1.07·(residual norm, rounded up as i8_resid_bound) + c_acc, rounded up.
+constexpr int F8_SCALE_ROWS = 119;  // E8M0 of F8_UNSCALE = 2⁻⁸: stored rows and q_hi
+constexpr int F8_SCALE_QLO = 115;   // E8M0 of 2⁻¹²: q_lo
+constexpr float F8_QLO_SCALE = 4096.0f, F8_QLO_UNSCALE = 1.0f / 4096.0f;
+constexpr float F8_ROW_NORM_MAX = 1.07f;
+__host__ __device__ constexpr float f8_filter_c_acc(int64_t ld, int terms) {
+    return 6.5e-5f + (float)(ld + terms * (ld / 128)) * (1.0f / 8388608.0f) * F8_ROW_NORM_MAX;
+}
+
+// Queries: qn exactly as prepare_queries_kernel forms it (the rescored bits stay the scan's), the
+// two e4m3 planes qh[0] = q_hi, qh[1] = q_lo ([nq_pad][ld] bytes each; TERMS = 1: q_lo is not
+// written and the residual is qn - q_hi), eps and thr.
+template <int TERMS>
+__global__ __launch_bounds__(64) void prepare_queries_f8_kernel(const float *__restrict__ q, int nq, int dim, int64_t ld,
+                                                               int64_t plane, float *__restrict__ qn, f8_t *__restrict__ qh,
+                                                               float *__restrict__ eps, float *__restrict__ thr) {
+    const int lane = threadIdx.x;
+    const int qi = blockIdx.x;
+    const bool valid = qi < nq;
+    const float *src = q + (int64_t)(valid ? qi : 0) * dim;
+    const float inv = wave_inv_norm(src, dim, lane, valid);
+    float err = 0.f;
+    for (int c = lane; c < ld; c += 64) {
+        const float v = RC_UNIT_ELEM(src, c, dim, inv, valid);
+        const f8_t hi = Elem<f8_t>::cast(v);
+        float d = v - Elem<f8_t>::load(&hi, 0);
+        qh[(int64_t)qi * ld + c] = hi;
+        if constexpr (TERMS == 2) {
+            const uint8_t lo = (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(d * F8_QLO_SCALE, 0.f, 0, false) & 0xff);
+            d -= __builtin_amdgcn_cvt_f32_fp8((int)lo, 0) * F8_QLO_UNSCALE;
+            qh[plane + (int64_t)qi * ld + c] = f8_t{lo};
+        }
+        err = fmaf(d, d, err);
+        if (valid) qn[(int64_t)qi * ld + c] = v;
+    }
+    err = wave_sum(err);
+    if (lane == 0) {
+        eps[qi] = (F8_ROW_NORM_MAX * i8_resid_bound(err) + f8_filter_c_acc(ld, TERMS)) * 1.0001f;
+        thr[qi] = valid ? -INFINITY : INFINITY;
+    }
+}
+
+struct FilterF8Args {
+    FilterArgs a;         // rows: the stored e4m3 rows; qh: the q_hi plane; ld = bytes per row; nqb: blocks of 128·QT queries
+    const uint8_t *qlo;   // the q_lo plane (TERMS 2)
+    float *dump;          // DUMP: s' of queries [0, dump_nq) x rows [r_begin, r_end), [dump_nq][r_end - r_begin]
+    int dump_nq;
+};
+
+// Query-stationary, as filter_qs_kernel / filter_i8_kernel: same FilterBlock mapping, 8 waves, the
+// same LDS ring of RT rows x 128 B per step filled by buffer-descriptor DMA, every ring step issued
+// (past the block's range through a zero-size descriptor) so that each wait counts a fixed number
+// of younger loads.  One ring step is one MFMA K: 128 bytes = 128 e4m3 elements.  A wave holds
+// 16·QT queries as TERMS x NKT fragments of 8 VGPRs per query tile (NKT = ld / 128).
+// MFMA roles as filter_qs_kernel (A = index rows from LDS, B = queries in registers): lane
+// (li, g) of acc[rf][qt] holds rows 16·rf + 4g + j of query 16·qt + li; one threshold per
+// (lane, qt), the same two-level epilogue.
+// Operand bytes: lane (li, g) supplies 32 bytes for row / query li.  Only consistency matters
+// (the k indices a lane's bytes stand for are the same set for A and for B, whichever the
+// hardware assigns them, and both scales are uniform): both sides give bytes [32g, 32g + 32) of
+// the 128-byte K chunk in memory order — the query from global memory, the row fragment from LDS
+// as the 16-B chunks 2g and 2g + 1 of row 16·rf + li.  LDS layout as the other two kernels: chunk c
+// of row r at position c ^ ((r >> 1) & 7) of the row's 128 bytes.  Bank conflicts: a quarter-wave
+// is 16 lanes of one g, rows li = 0..15; its 16-B reads sit at bank (li & 1)·32 + 4·((2g + h) ^
+// (li >> 1)): the 8 values of li >> 1 give 8 distinct positions in each half of the 64 banks, so
+// the 16 lanes cover all 64 banks once — no conflict, for either chunk h.
+// Registers (256 per lane at 2 waves per SIMD): query fragments TERMS·NKT·8·QT, accumulators
+// RT/16·QT·4, GF row-fragment slots of 8 (2 slots where the query fragments take 128, else 4).
+//   ld 256: QT 2, RT 128:  64 + 64 + 32, 207 VGPRs in all
+//   ld 512: QT 2, RT  64: 128 + 32 + 16, 221 (RT 128 needs 256 and spills 84 bytes)
+//   ld 768: QT 1, RT  64:  96 + 16 + 32, 170 (QT 2 would hold 192 in query fragments alone: a block
+//           is 128 queries there, and a row-fragment read feeds 2 MFMAs instead of 4)
+// No instantiation uses scratch.  The ring is NS = 8 steps of 128 rows or 16 steps of 64: 128 KB.
+// DUMP (rc_index_filter_scores): the epilogue stores s' instead of testing it; the fragment
+// loads, the ring and the MFMAs are the product's.
+typedef int i32x8_t __attribute__((ext_vector_type(8)));
+typedef int i32x4v_t __attribute__((ext_vector_type(4)));
+
+// acc + (stored-row fragment, scale 2⁻⁸) x (query fragment, E8M0 scale byte qscale), both e4m3.  The
+// scale words hold the byte in all four bytes, so any op_sel reads it.
+__device__ __forceinline__ f32x4_t mfma_f8_scaled(i32x8_t row, i32x8_t query, f32x4_t acc, int qscale) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(row, query, acc, 0, 0, 0, F8_SCALE_ROWS * 0x01010101, 0,
+                                                            qscale * 0x01010101);
+}
+
+template <int NKT, int RT, int TERMS, int QT, bool DUMP = false>
+__global__ __launch_bounds__(512, 1) void filter_f8_kernel(FilterF8Args fa) {
+    constexpr int WAVES = 8, QPB = WAVES * 16 * QT, RF = RT / 16, RH = RF / 4;
+    constexpr int STEP_BYTES = RT * 128;
+    constexpr int NS = QS_NS * 128 / RT;  // ring steps: 128 KB of rows either way
+    constexpr int SPS = 2;
+    constexpr int PPW = 2 * RF / WAVES;
+    constexpr int GF = TERMS * NKT * QT * 8 >= 128 ? 2 : 4;  // row-fragment register slots (8 VGPRs each)
+    static_assert((RT == 128 || RT == 64) && (TERMS == 1 || TERMS == 2) && NKT % SPS == 0 && (NS - 2 * SPS) * PPW < 64,
+                  "layout; vmcnt is 6 bits");
+    __shared__ __attribute__((aligned(16))) uint8_t smem[NS * STEP_BYTES];
+    const FilterArgs &a = fa.a;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, li = lane & 15;
+
+    const FilterBlock fb(a, RT);
+    const int qb = fb.qb;
+    const int64_t rt0 = fb.rt0, rt1 = fb.rt1;
+    if (rt0 >= rt1) return;  // block-uniform
+    const int64_t ldb = a.ld;  // bytes per row
+    const int ntiles = (int)(rt1 - rt0);
+    const int nsteps = ntiles * NKT;
+    const int64_t row0 = a.r_begin + rt0 * RT;  // a multiple of RT (host check)
+    const uint8_t *Rg = (const uint8_t *)a.rows + row0 * ldb;
+
+    // this lane's query fragments for the whole K: bytes [128 ks + 32 g, + 32) of query q0 + 16 qt + li
+    i32x8_t qf[TERMS][QT][NKT];
+    const int q0 = qb * QPB + wave * 16 * QT;
+#pragma unroll
+    for (int tm = 0; tm < TERMS; ++tm)
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+            for (int ks = 0; ks < NKT; ++ks) {
+                const uint8_t *src = (tm == 0 ? (const uint8_t *)a.qh : fa.qlo) + (int64_t)(q0 + qt * 16 + li) * ldb + ks * 128 + g * 32;
+                qf[tm][qt][ks] = *reinterpret_cast<const i32x8_t *>(src);  // 32-B aligned: two 16-B loads into one tuple
+            }
+    float thr[QT];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) thr[qt] = a.thr[q0 + qt * 16 + li];
+    // consume the query loads here: the compiler's vmcnt waits for them sit before the K loop
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        asm volatile("" ::"v"(thr[qt]));
+#pragma unroll
+        for (int tm = 0; tm < TERMS; ++tm)
+#pragma unroll
+            for (int ks = 0; ks < NKT; ++ks) {
+                // (in 16-byte halves: a 32-byte "v" operand is no operand of the host pass's target, and
+                // in a template that drops the kernel's stub without a diagnostic)
+                const i32x4v_t h0 = __builtin_shufflevector(qf[tm][qt][ks], qf[tm][qt][ks], 0, 1, 2, 3);
+                const i32x4v_t h1 = __builtin_shufflevector(qf[tm][qt][ks], qf[tm][qt][ks], 4, 5, 6, 7);
+                asm volatile("" ::"v"(h0), "v"(h1));
+            }
+    }
+
+    uint32_t loff[PPW];  // byte offset of this lane's 16 B within the step's rows
+#pragma unroll
+    for (int i = 0; i < PPW; ++i) {
+        const int r = (wave + WAVES * i) * 8 + (lane >> 3);
+        loff[i] = (uint32_t)(r * (int)ldb + (((lane & 7) ^ ((r >> 1) & 7)) << 4));
+    }
+    auto issue = [&](int t) {
+        const bool ok = t < nsteps;
+        const int tile = t / NKT;
+        const int ks = t - tile * NKT;
+        uint8_t *base = smem + (t % NS) * STEP_BYTES;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(ok ? Rg + (int64_t)tile * RT * ldb + ks * 128 : Rg), (short)0, ok ? 0x7fffffff : 0, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) {
+            lds_void *dst = (lds_void *)(base + (wave + WAVES * i) * 1024);
+            const uint32_t off = loff[i];
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, off, 0, 0, 0);
+        }
+    };
+    for (int t = 0; t < NS - SPS; ++t) issue(t);
+
+    f32x4_t acc[RF][QT];
+    for (int tile = 0; tile < ntiles; ++tile) {
+#pragma unroll
+        for (int rf = 0; rf < RF; ++rf)
+#pragma unroll
+            for (int qt = 0; qt < QT; ++qt) acc[rf][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kp = 0; kp < NKT / SPS; ++kp) {
+            const int t = tile * NKT + SPS * kp;
+            // steps t..t+SPS-1 must have landed; the NS - 2·SPS younger steps (PPW DMAs each, always
+            // issued) may be in flight.  What an epilogue issued (atomics, stores) only makes the
+            // wait stricter.
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2 * SPS) * PPW) : "memory");
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_s_barrier();  // every wave's DMA of t..t+SPS-1 landed; slots of t-SPS..t-1 are free
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int j = NS - SPS; j < NS; ++j) issue(t + j);
+            // The sync group's SPS·RF row fragments f = (k-step kl, row group rf), GF register slots,
+            // rolling as filter_i8_kernel: fragment f + GF is read into the slot of fragment f as soon as
+            // f's QT·TERMS MFMAs have issued, so its LDS latency runs under the MFMAs between.  Row
+            // r = 16 rf + li: its swizzle (r >> 1) & 7 = (li >> 1) & 7 does not depend on rf.
+            constexpr int NF = SPS * RF;
+            const int sw = (li >> 1) & 7;
+            auto read_frag = [&](int f) {
+                const int kl = f / RF, rf = f % RF;
+                const uint8_t *Sr = smem + ((t + kl) % NS) * STEP_BYTES + (16 * rf + li) * 128;
+                const i32x4v_t lo = *reinterpret_cast<const i32x4v_t *>(Sr + (((2 * g) ^ sw) << 4));
+                const i32x4v_t hi = *reinterpret_cast<const i32x4v_t *>(Sr + (((2 * g + 1) ^ sw) << 4));
+                return (i32x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            };
+            i32x8_t cur[GF];
+#pragma unroll
+            for (int f = 0; f < GF; ++f) cur[f] = read_frag(f);
+            __builtin_amdgcn_sched_barrier(0);  // the first GF fragments' reads go out together, ahead of the pattern
+#pragma unroll
+            for (int f = 0; f < NF; ++f) {
+                const int ks = SPS * kp + f / RF, rf = f % RF;
+#pragma unroll
+                for (int qt = 0; qt < QT; ++qt) {
+                    acc[rf][qt] = mfma_f8_scaled(cur[f % GF], qf[0][qt][ks], acc[rf][qt], F8_SCALE_ROWS);
+                    if constexpr (TERMS == 2)
+                        acc[rf][qt] = mfma_f8_scaled(cur[f % GF], qf[TERMS - 1][qt][ks], acc[rf][qt], F8_SCALE_QLO);
+                }
+                if (f + GF < NF) cur[f % GF] = read_frag(f + GF);
+                __builtin_amdgcn_sched_group_barrier(0x008, QT * TERMS, 0);
+                if (f + GF < NF) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            }
+            // pin the accumulators here: the step issue's branches split the basic block, and the
+            // compiler otherwise sinks this sync group's MFMAs into the next one's block, where all of
+            // its row fragments stay live at once (128 registers; the kernel spilled)
+#pragma unroll
+            for (int rf = 0; rf < RF; ++rf)
+#pragma unroll
+                for (int qt = 0; qt < QT; ++qt) asm volatile("" : "+v"(acc[rf][qt]));
+        }
+        // rows in 32 bits from here (a local row is below the capacity, < 2^32): the tile's first row
+        // of this lane, and how many rows from it are inside the range
+        const uint32_t rbase = (uint32_t)(row0 + (int64_t)tile * RT) + 4u * (uint32_t)g;
+        const int64_t left64 = a.r_end - (row0 + (int64_t)tile * RT) - 4 * g;
+        const int left = (int)(left64 < RT ? left64 : RT);  // row rbase + o is in range iff o < left
+        if constexpr (DUMP) {  // rc_index_filter_scores: s' itself
+            const int64_t n = a.r_end - a.r_begin;
+#pragma unroll
+            for (int qt = 0; qt < QT; ++qt) {
+                const int q = q0 + qt * 16 + li;
+                float *dst = fa.dump + (int64_t)q * n + ((int64_t)rbase - a.r_begin);
+#pragma unroll
+                for (int rf = 0; rf < RF; ++rf)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (q < fa.dump_nq && rf * 16 + j < left) dst[rf * 16 + j] = acc[rf][qt][j];
+            }
+            continue;
+        }
+        // ---- epilogue of the tile: candidates s' >= thr[q]
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) {
+            const float th = thr[qt];
+            float m = -INFINITY;
+#pragma unroll
+            for (int rf = 0; rf < RF; ++rf) {
+                const f32x4_t v = acc[rf][qt];
+                m = fmaxf(m, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+            }
+            if (__ballot(m >= th) == 0) continue;  // wave-uniform: the common case
+            if (m >= th) {
+                const int q = q0 + qt * 16 + li;
+#pragma unroll
+                for (int rf = 0; rf < RF; ++rf)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (acc[rf][qt][j] >= th && rf * 16 + j < left) append_candidate(a, q, (int64_t)(rbase + (uint32_t)(rf * 16 + j)));
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the zero-size tail steps of the ring
+}
+
 // ------------------------------------------------------- exact rescoring --
 // One block per query.  Candidates are scored exactly as scan_topk_kernel
 // scores a row (RC_ROW_FMA16 + sum16: 16 lanes per row, 16-B chunks, f32 FMA in chunk
@@ -840,7 +1124,10 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
 #pragma unroll
     for (int i = 0; i < CPL; ++i)
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) q[0][i][e] = qn[(int64_t)qi * ld + (sub + 16 * i) * EPC + e];
+        for (int e = 0; e < EPC; ++e) {
+            q[0][i][e] = qn[(int64_t)qi * ld + (sub + 16 * i) * EPC + e];
+            if constexpr (sizeof(T) == 1) q[0][i][e] *= query_unscale<T>();  // as scan_rows: the scan's bits
+        }
 
     const uint32_t n = cnt[qi];
     const int nn = (int)min<uint32_t>(n, (uint32_t)cap);
@@ -905,7 +1192,8 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
 // ------------------------------------------------------------------ host ---
 template <typename T>
 void launch_rescore(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
-    const bool ok = with_nch(p.nch, [&](auto nch) {
+    // (float8 rows: the even widths up to 768, what the float8 filter serves)
+    const bool ok = with_nch<(sizeof(T) == 1 ? 6 : 16), T>(p.nch, [&](auto nch) {
         with_topk_cap(topk_cap(p.k), [&](auto cap) {
             auto launch = [&](auto masked) {
                 hipLaunchKernelGGL((rescore_kernel<T, decltype(nch)::value, decltype(cap)::value, decltype(masked)::value>),
@@ -1030,11 +1318,64 @@ void run_batched_i8(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
     run_stages<T>(p, ws, s, timer, batch_stage_ratio(p.k, ws.cap, I8_STAGE_INFLATION), p.ld, filter);
 }
 
+// The float8 filter (filter_f8_kernel): two e4m3 query terms, no stage inflation.  ld 768 runs
+// QT = 1 (blocks of 128 queries): its 192 query-fragment registers at QT = 2 leave no room.
+constexpr int F8_TERMS = 2;
+
+// launch filter_f8_kernel<.., DUMP> over rows [c0, c1) in nchunk row chunks for nq_pad query slots
+template <bool DUMP>
+void launch_filter_f8(const BatchPlan &p, const BatchWs &ws, int nq_pad, int64_t c0, int64_t c1, int64_t nchunk, float *dump,
+                      hipStream_t s) {
+    const int nkt = (int)(p.ld / 128);
+    const int rt = nkt >= 4 ? 64 : 128, qt = nkt == 6 ? 1 : QS_QT;
+    const int nqb = nq_pad / (128 * qt);
+    RC_REQUIRE(c0 % rt == 0, RC_ERR_INVALID, "internal: float8 filter range not tile-aligned");
+    const int64_t tpc = ((c1 - c0 + rt - 1) / rt + nchunk - 1) / nchunk;
+    FilterF8Args fa{FilterArgs{p.rows, ws.qh, p.ld, nkt, c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
+                    (const uint8_t *)ws.qh + (int64_t)nq_pad * p.ld, dump, p.nq};
+    const dim3 gr((unsigned)(nchunk * nqb)), bl(512);
+    if (nkt == 4) hipLaunchKernelGGL((filter_f8_kernel<4, 64, F8_TERMS, QS_QT, DUMP>), gr, bl, 0, s, fa);
+    else if (nkt == 6) hipLaunchKernelGGL((filter_f8_kernel<6, 64, F8_TERMS, 1, DUMP>), gr, bl, 0, s, fa);
+    else hipLaunchKernelGGL((filter_f8_kernel<2, 128, F8_TERMS, QS_QT, DUMP>), gr, bl, 0, s, fa);
+}
+
+void prepare_queries_f8(const BatchPlan &p, const BatchWs &ws, int nq_pad, hipStream_t s) {
+    hipLaunchKernelGGL(prepare_queries_f8_kernel<F8_TERMS>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld,
+                       (int64_t)nq_pad * p.ld, ws.qn, (f8_t *)ws.qh, ws.eps, ws.thr);
+    RC_LAUNCH_CHECK();
+}
+
+void run_batched_f8(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
+    const int nq_pad = (p.nq + SB_TILE - 1) / SB_TILE * SB_TILE;
+    prepare_queries_f8(p, ws, nq_pad, s);
+    auto filter = [&](int64_t c0, int64_t c1, int64_t nchunk, int) {
+        launch_filter_f8<false>(p, ws, nq_pad, c0, c1, nchunk, nullptr, s);
+    };
+    run_stages<f8_t>(p, ws, s, timer, batch_stage_ratio(p.k, ws.cap), p.ld, filter);
+}
+
 bool i8_filter_supported(int64_t ld) { return ld == 256 || ld == 512 || ld == 768; }
+bool f8_filter_supported(int64_t ld) { return ld == 256 || ld == 512 || ld == 768; }
+
+// rc_index_filter_scores: the float8 filter's own s' (DUMP form of filter_f8_kernel) and eps
+void filter_scores_f8(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, float *out_scores, float *out_eps,
+                      hipStream_t s) {
+    RC_REQUIRE(f8_filter_supported(p.ld), RC_ERR_UNSUPPORTED, "float8 filter needs ld 256, 512 or 768");
+    const int nq_pad = (p.nq + SB_TILE - 1) / SB_TILE * SB_TILE;
+    prepare_queries_f8(p, ws, nq_pad, s);
+    launch_filter_f8<true>(p, ws, nq_pad, row0, row0 + n, 8, out_scores, s);
+    RC_LAUNCH_CHECK();
+    RC_HIP(hipMemcpyAsync(out_eps, ws.eps, (size_t)p.nq * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
 
 void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
     RC_REQUIRE(p.ld % 64 == 0, RC_ERR_UNSUPPORTED, "batched search needs ld % 64 == 0");
     RC_REQUIRE(p.n_rows > 0, RC_ERR_INVALID, "batched search over an empty range");
+    if (p.f8_filter) {
+        RC_REQUIRE(p.dtype == RC_F8 && f8_filter_supported(p.ld), RC_ERR_UNSUPPORTED,
+                   "float8 filter needs a float8 index of ld 256, 512 or 768");
+        return run_batched_f8(p, ws, s, timer);
+    }
     if (p.rows8 != nullptr) {
         RC_REQUIRE(i8_filter_supported(p.ld), RC_ERR_UNSUPPORTED, "int8 filter needs ld 256, 512 or 768");
         if (p.dtype == RC_F16 || p.dtype == RC_BF16 || p.dtype == RC_F32)

@@ -566,7 +566,7 @@ int rc_sharded_set_metric(rc_sharded *h, int metric) {
             int kind = RC_FILTER_NATIVE;
             check_status(rc_index_get_filter(h->shard[s], &kind));
             RC_REQUIRE(kind == RC_FILTER_NATIVE, RC_ERR_UNSUPPORTED,
-                       "a non-cosine metric on an index with the int8 filter copy (the batched MFMA search is cosine-only)");
+                       "a non-cosine metric on an index with the int8 filter copy or the float8 filter (the batched MFMA search is cosine-only)");
         }
         for (int s = 0; s < h->n; ++s) check_status(rc_index_set_metric(h->shard[s], metric));
     });

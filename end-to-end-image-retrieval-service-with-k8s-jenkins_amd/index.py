@@ -122,9 +122,11 @@ class DeviceIndex:
         check(self.lib.rc_index_reserve(self.handle, int(max_nq), int(max_k)))
 
     def set_filter(self, kind: str, stream=None) -> None:
-        """Filter copy of the batched search (rc_index_set_filter): "native" (the filter GEMM
-        reads the stored rows) or "i8" (an int8 copy of every row, int8 MFMA at twice the f16
-        rate; results unchanged — candidates are rescored exactly on the stored rows)."""
+        """Filter kind of the batched search (rc_index_set_filter): "native" (the filter GEMM
+        reads the stored f16/bf16 rows), "i8" (an int8 copy of every row, int8 MFMA at twice the
+        f16 rate) or "f8" (a float8 index only: the block-scaled fp8 MFMA on the stored rows, no
+        copy; it is what gives a float8 index ``mode="mfma"``).  Results never change —
+        candidates are rescored exactly on the stored rows."""
         if kind not in _lib.FILTERS:
             raise ValueError(f"unknown filter {kind!r} (expected one of {sorted(_lib.FILTERS)})")
         check(self.lib.rc_index_set_filter(self.handle, _lib.FILTERS[kind], stream_ptr(stream)))
@@ -134,6 +136,18 @@ class DeviceIndex:
         k = _lib.C.c_int()
         check(self.lib.rc_index_get_filter(self.handle, _lib.C.byref(k)))
         return {v: n for n, v in _lib.FILTERS.items()}[k.value]
+
+    def filter_scores(self, queries: torch.Tensor, row0: int, n: int, stream=None):
+        """What the "f8" filter computes (rc_index_filter_scores): its scores ``s'`` of the
+        queries against local rows [row0, row0 + n) (``row0`` a multiple of 128), f32 [nq, n],
+        and each query's bound ``eps`` on ``|s' - exact score|``, f32 [nq].  Raises unless the
+        filter kind is "f8"."""
+        q = self._vecs(queries)
+        out = torch.empty((q.shape[0], int(n)), dtype=torch.float32, device=self.device)
+        eps = torch.empty((q.shape[0],), dtype=torch.float32, device=self.device)
+        check(self.lib.rc_index_filter_scores(self.handle, ptr(q), q.shape[0], int(row0), int(n), ptr(out), ptr(eps),
+                                              stream_ptr(stream)))
+        return out, eps
 
     def set_metric(self, metric: str) -> None:
         """Scoring rule of the later searches (rc_index_set_metric): "cosine", "dotproduct" or
@@ -185,7 +199,7 @@ class DeviceIndex:
 
         ``mode``: "scan" (HBM-bound streaming scan), "mfma" (batched filter GEMM +
         exact rescoring, f16/bf16 index, cosine only) or "auto" (MFMA for >= 8 queries; a
-        float8 index always scans and refuses "mfma").
+        float8 index scans and refuses "mfma" unless its filter is "f8").
         ``mask``: optional row-eligibility bitmap over the LOCAL rows (rc_index_search_masked):
         an int32 / uint32 tensor of ceil(n_rows / 32) words on this device, bit r & 31 of word
         r >> 5 = row r may be returned; "auto" then scans."""
@@ -745,8 +759,10 @@ class Index:
 
     ``dtype`` is the storage of the normalised rows: ``"float32"``, ``"float16"``, ``"bfloat16"``
     or ``"float8_e4m3fn"`` (alias ``"f8"``: one byte per element, each element of the direction
-    rounded to 3 mantissa bits; exact scans only, so ``mode="mfma"`` and ``filter="i8"`` raise
-    ``ValueError`` on it and ``"auto"`` scans).
+    rounded to 3 mantissa bits).  A float8 index scans by default (``mode="mfma"`` raises
+    ``ValueError``, ``"auto"`` scans); ``filter="f8"`` gives it the batched search on the
+    block-scaled fp8 MFMA (cosine, dimensions up to 768), with unchanged results.
+    ``filter="i8"`` raises on it, ``filter="f8"`` on every other dtype.
 
     ``upsert(vectors)`` accepts ``(id, values)``, ``(id, values, metadata)``
     tuples or ``{"id", "values", "metadata"}`` dicts and overwrites existing
@@ -763,7 +779,7 @@ class Index:
     same vectors.  Capacity grows on demand (doubling), as a Pinecone index
     has no fixed size.
 
-    Two things are called "filter" here.  The constructor's ``filter="native" | "i8"`` is
+    Two things are called "filter" here.  The constructor's ``filter="native" | "i8" | "f8"`` is
     the kind of filter GEMM the batched search runs (``DeviceIndex.set_filter``); it never
     changes a result.  ``query(..., filter={...})`` / ``query_batch(..., filter={...})`` is
     Pinecone's metadata filter (``metafilter``): only vectors whose metadata satisfies it can
@@ -781,8 +797,10 @@ class Index:
             raise ValueError(f"unknown filter {filter!r} (expected one of {sorted(_lib.FILTERS)})")
         if metric != "cosine" and filter != "native":
             raise ValueError(f"filter={filter!r} serves the batched MFMA search, which is cosine-only (metric={metric!r})")
-        if _lib.is_f8(dtype) and filter != "native":
-            raise ValueError(f"filter={filter!r} serves the batched MFMA search, which a float8 index does not have")
+        if _lib.is_f8(dtype) and filter == "i8":
+            raise ValueError("filter='i8' is not available on a float8 index (its batched search is filter='f8')")
+        if filter == "f8" and not _lib.is_f8(dtype):
+            raise ValueError(f"filter='f8' reads stored float8 rows: it needs dtype='f8' (dtype={dtype!r})")
         if devices is None:
             devices = [device] * int(shards or 1)
         self.name = name
@@ -1100,17 +1118,28 @@ class Index:
             res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter))
         return [{"matches": m, "namespace": ""} for m in res]
 
-    def _masked_mode(self, mode: str, nq: int, n: int, eligible: int) -> str:
+    def _masked_mode(self, mode: str, nq: int, n: int, eligible: int, k: int = 10) -> str:
         """The library's "auto" scans whenever a mask is given (it does not know the eligible
         share); this layer does, and asks for MFMA when the unmasked conditions hold (>= 8
-        queries, >= 64k rows per shard, an f16/bf16 index or the int8 filter copy) and the share
-        reaches MASKED_MFMA_MIN_SHARE."""
+        queries, >= 64k rows per shard, an f16/bf16 index or the int8 filter copy; a float8
+        index with the "f8" filter has the library's own corner for that kind, in passes of the
+        masked scan) and the share reaches MASKED_MFMA_MIN_SHARE."""
         if mode != "auto":
             return mode
-        if self.metric != "cosine" or _lib.is_f8(self._set.dtype):  # the batched MFMA path: cosine, not float8
+        if self.metric != "cosine":  # the batched MFMA path is cosine-only
             return "scan"
-        mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter == "i8"
-        if mfma_ok and nq >= 8 and n // self._set.n >= 65536 and eligible >= MASKED_MFMA_MIN_SHARE * n:
+        per_shard = n // self._set.n
+        if _lib.is_f8(self._set.dtype):
+            if self._set.filter != "f8":
+                return "scan"
+            ld = self._set.ld
+            qb = 1 if k > 64 else 4 if ld <= 256 else 2 if ld <= 512 else 1  # the masked scan's queries per pass
+            passes = -(-nq // qb)
+            size_ok = (passes >= 16 and per_shard >= 131072) or (passes >= 8 and per_shard * ld >= 1 << 28)
+        else:
+            mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter == "i8"
+            size_ok = mfma_ok and nq >= 8 and per_shard >= 65536
+        if size_ok and eligible >= MASKED_MFMA_MIN_SHARE * n:
             return "mfma"
         return "scan"
 
@@ -1126,7 +1155,7 @@ class Index:
         else:
             if mode not in _lib.SEARCH_MODES:
                 raise ValueError(f"unknown search mode {mode!r}")
-            scores, rows = self._set.search(q, k, n, mode=self._masked_mode(mode, q.shape[0], n, bitmap[1]),
+            scores, rows = self._set.search(q, k, n, mode=self._masked_mode(mode, q.shape[0], n, bitmap[1], k),
                                             mask=bitmap[0])
         scores = scores.cpu().numpy()
         if self.metric == "euclidean":  # the library's -||q - v||^2 (descending) as Pinecone's squared distance

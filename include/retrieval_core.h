@@ -43,8 +43,10 @@ extern "C" {
 #define RC_BF16 2
 /* float8: each element is the OCP e4m3fn byte (round to nearest even) of x̂_c · 2⁸, the stored
  * value is decode(byte) · 2⁻⁸ (3 mantissa bits; |x̂_c| <= 1, so nothing saturates, and elements
- * down to 2⁻¹⁴ stay normal).  One byte per element, ld = round_up(dim, 256).  Exact scans only:
- * RC_SEARCH_MFMA and RC_FILTER_I8 are RC_ERR_UNSUPPORTED on it, RC_SEARCH_AUTO scans. */
+ * down to 2⁻¹⁴ stay normal).  One byte per element, ld = round_up(dim, 256).  It scans exactly
+ * by default: RC_SEARCH_MFMA is RC_ERR_UNSUPPORTED and RC_SEARCH_AUTO scans until its own filter
+ * is switched on, rc_index_set_filter(RC_FILTER_F8) (cosine, ld 256 / 512 / 768), which gives it
+ * the batched search with unchanged results.  RC_FILTER_I8 is RC_ERR_UNSUPPORTED on it. */
 #define RC_F8 3
 
 /* Pillow resampling filters (PIL.Image.Resampling values) */
@@ -186,11 +188,30 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
  *                      bound, and candidates are rescored exactly on the stored rows.
  *                      Row widths (dim rounded up to 128) 256, 512 or 768; makes
  *                      RC_SEARCH_MFMA available on f32 indexes too.
- * Enabling quantises every row (synchronous on `stream`). */
+ *                      Enabling quantises every row (synchronous on `stream`).
+ *   RC_FILTER_F8     — an RC_F8 index only: the filter GEMM reads the stored e4m3
+ *                      rows with the block-scaled fp8 MFMA (twice the f16 rate, half
+ *                      the row bytes), the query held as two e4m3 terms; candidates
+ *                      are rescored exactly on the stored rows, so RC_SEARCH_MFMA
+ *                      returns the scan's rows and score bits.  It allocates nothing;
+ *                      RC_FILTER_NATIVE switches it off.  With it RC_SEARCH_MFMA is
+ *                      available and RC_SEARCH_AUTO takes the batched path under its
+ *                      usual conditions.  RC_ERR_UNSUPPORTED on an index that is not
+ *                      RC_F8, not cosine, or of a row width (dim rounded up to 256)
+ *                      other than 256, 512 or 768. */
 #define RC_FILTER_NATIVE 0
 #define RC_FILTER_I8 1
+#define RC_FILTER_F8 2
 int rc_index_set_filter(rc_index *h, int kind, void *stream);
 int rc_index_get_filter(const rc_index *h, int *kind);
+/* What the RC_FILTER_F8 filter computes (a diagnostic: no reference counterpart).  Runs the
+ * filter's query preparation and its kernel's own K loop over the local rows
+ * [row0, row0 + n) (row0 a multiple of 128) and writes the filter scores s' — the two-term
+ * e4m3 query against the stored rows, before any threshold — to out_scores (device f32
+ * [nq][n]) and each query's bound on |s' − exact score| to out_eps (device f32 [nq]).
+ * queries: device f32 [nq][dim].  RC_ERR_UNSUPPORTED unless the filter kind is RC_FILTER_F8. */
+int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t row0, int64_t n, float *out_scores,
+                           float *out_eps, void *stream);
 
 /* replaces the metric= argument of pc.create_index — ingesting/utils.py:29-36 (the
  * reference asks for "cosine"; Pinecone also offers "dotproduct" and "euclidean").
@@ -214,8 +235,9 @@ int rc_index_get_filter(const rc_index *h, int *kind);
  * the same bits.  All-zero vectors and queries stay rejected by the host layer.
  * The batched MFMA path is cosine-only (its candidate threshold is a bound in cosine
  * space): on a non-cosine index RC_SEARCH_AUTO scans, RC_SEARCH_MFMA and
- * rc_index_set_filter(RC_FILTER_I8) are RC_ERR_UNSUPPORTED, and so is a non-cosine
- * metric on an index that holds the int8 copy.  An unknown metric is RC_ERR_INVALID. */
+ * rc_index_set_filter(RC_FILTER_I8 / RC_FILTER_F8) are RC_ERR_UNSUPPORTED, and so is a
+ * non-cosine metric on an index whose filter is not RC_FILTER_NATIVE.  An unknown metric is
+ * RC_ERR_INVALID. */
 #define RC_METRIC_COSINE 0
 #define RC_METRIC_DOT 1
 #define RC_METRIC_EUCLIDEAN 2
@@ -310,7 +332,7 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
  * RC_FILTER_NATIVE on every shard). */
 int rc_sharded_set_filter(rc_sharded *h, int kind);
 /* rc_index_set_metric on every shard; the metric is validated against every shard
- * before any is set (an unknown metric, or a shard with the int8 copy, changes none). */
+ * before any is set (an unknown metric, or a shard whose filter is not RC_FILTER_NATIVE, changes none). */
 int rc_sharded_set_metric(rc_sharded *h, int metric);
 
 /* ------------------------------------------------------------------------
