@@ -45,8 +45,8 @@ def is_f8(dtype: str) -> bool:
     return DTYPES.get(dtype) == RC_F8
 
 
-RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8 = 0, 1, 2
-FILTERS = {"native": RC_FILTER_NATIVE, "i8": RC_FILTER_I8, "f8": RC_FILTER_F8}
+RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8, RC_FILTER_METRIC = 0, 1, 2, 3
+FILTERS = {"native": RC_FILTER_NATIVE, "i8": RC_FILTER_I8, "f8": RC_FILTER_F8, "metric": RC_FILTER_METRIC}
 RC_METRIC_COSINE, RC_METRIC_DOT, RC_METRIC_EUCLIDEAN = 0, 1, 2
 METRICS = {"cosine": RC_METRIC_COSINE, "dotproduct": RC_METRIC_DOT, "euclidean": RC_METRIC_EUCLIDEAN}  # Pinecone's names
 

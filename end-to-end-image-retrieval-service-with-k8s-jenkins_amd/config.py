@@ -26,8 +26,9 @@ class Config:
     # storage of the index rows: "float32", "float16", "bfloat16" or "float8_e4m3fn" ("f8": exact scans only)
     INDEX_DTYPE = os.getenv("RC_INDEX_DTYPE", "float32")
     INDEX_CAPACITY = int(os.getenv("RC_INDEX_CAPACITY", str(1 << 20)))  # initial rows; grows on demand
-    # batched-search filter kind: "native", "i8" (int8 copy of the rows; dims up to 768) or "f8"
-    # (a float8 index's own filter on its stored rows; dims up to 768)
+    # batched-search filter kind: "native", "i8" (int8 copy of the rows; dims up to 768), "f8"
+    # (a float8 index's own filter on its stored rows; dims up to 768) or "metric" (an f16 / bf16
+    # index: the batched search under INDEX_METRIC dotproduct / euclidean too)
     INDEX_FILTER = os.getenv("RC_INDEX_FILTER", "native")
     # Pinecone's create_index(metric=...): "cosine" (the reference's), "dotproduct" or "euclidean"
     INDEX_METRIC = os.getenv("RC_INDEX_METRIC", "cosine")

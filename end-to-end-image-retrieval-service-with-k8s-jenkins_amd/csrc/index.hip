@@ -393,6 +393,25 @@ constexpr int kF8BatchMinPasses = 16;
 constexpr int64_t kF8BatchMinRows = 131072;
 constexpr int kF8BatchMinPassesLarge = 8;                     // ... with at least
 constexpr int64_t kF8BatchMinBytesLarge = int64_t(1) << 28;  // this many bytes of rows
+// The metric filter (RC_FILTER_METRIC under dotproduct / euclidean) competes with a scan of one
+// query per pass, but at kBatchMinQueries the batched path is behind it up to 131 072 rows (f16,
+// top-10, wall ms per call, scan / batched, tools/metric_filter_micro.py, profiles/metric_filter/;
+// dotproduct; the euclidean batched search is up to 12 % slower, its scan the same):
+//   rows x width      8 queries        16 queries
+//    65 536 x 256   0.196 / 0.263    0.377 / 0.337
+//    65 536 x 512   0.233 / 0.295    0.454 / 0.369
+//    65 536 x 768   0.322 / 0.332    0.632 / 0.410
+//   131 072 x 256   0.199 / 0.287    0.385 / 0.369
+//   131 072 x 512   0.247 / 0.321    0.481 / 0.397
+//   131 072 x 768   0.355 / 0.373    0.701 / 0.460
+//   262 144 x 256   0.247 / 0.331    0.479 / 0.422
+//   262 144 x 512   0.447 / 0.370    0.872 / 0.448
+//   262 144 x 768   0.644 / 0.467    1.273 / 0.561
+// 16 queries are ahead everywhere from kBatchMinRows (1.00-2.3x, both metrics); 8 queries from 2^28
+// bytes of rows (1.18-1.39x; 9 to 15 queries were not measured and take the 8-query rule).
+constexpr int kMetricBatchMinQueries = 16;
+constexpr int kMetricBatchMinQueriesLarge = 8;                    // ... with at least
+constexpr int64_t kMetricBatchMinBytesLarge = int64_t(1) << 28;  // this many bytes of rows
 
 // Every global row a shard can report must fit the 32-bit row word of the top-k
 // keys (merge_lists_kernel) below the all-ones value: row_base + (cap - 1) * stride < 2^32 - 1.
@@ -558,6 +577,8 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
     p.rsx = h->rsx;
     p.rex = h->rex;
     p.mask = mask;
+    p.metric = h->metric;  // non-cosine (RC_FILTER_METRIC): the filter and rescore kernels' metric forms
+    p.norms = h->norms;
     if (h->gtimer.enabled) h->gtimer.create();
     batched_search(p, h->bws, s, h->gtimer.enabled ? &h->gtimer : nullptr);
     int nblk = (int)std::min<int64_t>(h->bws.fb_blocks, std::max<int64_t>(1, (n_rows + 511) / 512));
@@ -568,6 +589,13 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
     a.flags = h->bws.flags;
     a.grid_y = std::min(nq, FB_QSTRIDE);
     a.mask = mask;
+    if (h->metric != RC_METRIC_COSINE) {  // the metric fallback kernel (scan_metric.h): raw queries, as every metric scan
+        a.metric = h->metric;
+        a.norms = h->norms;
+        a.qraw = queries;
+        a.dim = h->dim;
+        a.nq_real = nq;
+    }
     launch_scan(h, a);
     launch_merge_partials(h, h->bws.fb_partial, h->bws.flags, nblk, nq, nq, k, scores, out_rows, s);
 }
@@ -834,8 +862,8 @@ int rc_index_reserve(rc_index *h, int max_nq, int max_k) {
 int rc_index_set_filter(rc_index *h, int kind, void *stream) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_I8 || kind == RC_FILTER_F8, RC_ERR_INVALID,
-                   "filter must be RC_FILTER_NATIVE, RC_FILTER_I8 or RC_FILTER_F8");
+        RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_I8 || kind == RC_FILTER_F8 || kind == RC_FILTER_METRIC,
+                   RC_ERR_INVALID, "filter must be RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8 or RC_FILTER_METRIC");
         std::lock_guard<std::mutex> lk(h->mu);
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
@@ -843,6 +871,14 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
         if (kind == RC_FILTER_NATIVE) {
             RC_HIP(hipDeviceSynchronize());  // no search may still read the copy
             free_filter(h);
+            return;
+        }
+        if (kind == RC_FILTER_METRIC) {  // allocates nothing: the native filter kernels and their metric forms
+            RC_REQUIRE(h->dtype == RC_F16 || h->dtype == RC_BF16, RC_ERR_UNSUPPORTED,
+                       "the metric filter's GEMM reads stored f16 / bf16 rows: it needs an f16 or bf16 index");
+            RC_HIP(hipDeviceSynchronize());
+            free_filter(h);  // an int8 copy goes, as on a switch to RC_FILTER_NATIVE
+            h->filter = RC_FILTER_METRIC;
             return;
         }
         if (kind == RC_FILTER_F8) {  // allocates nothing: the filter GEMM reads the stored rows
@@ -892,8 +928,8 @@ int rc_index_set_metric(rc_index *h, int metric) {
         RC_REQUIRE(metric == RC_METRIC_COSINE || metric == RC_METRIC_DOT || metric == RC_METRIC_EUCLIDEAN, RC_ERR_INVALID,
                    "metric must be RC_METRIC_COSINE, RC_METRIC_DOT or RC_METRIC_EUCLIDEAN");
         std::lock_guard<std::mutex> lk(h->mu);
-        RC_REQUIRE(metric == RC_METRIC_COSINE || h->filter == RC_FILTER_NATIVE, RC_ERR_UNSUPPORTED,
-                   "a non-cosine metric on an index with the int8 filter copy or the float8 filter (the batched MFMA search is cosine-only)");
+        RC_REQUIRE(metric == RC_METRIC_COSINE || h->filter == RC_FILTER_NATIVE || h->filter == RC_FILTER_METRIC, RC_ERR_UNSUPPORTED,
+                   "a non-cosine metric on an index with the int8 filter copy or the float8 filter (those filters are cosine-only)");
         h->metric = metric;  // no device call: searches already enqueued took the metric they were launched with
     });
 }
@@ -1016,17 +1052,19 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
         std::lock_guard<std::mutex> lk(h->mu);
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
-        // the batched path's candidate threshold is a bound in cosine space: a non-cosine index
-        // scans (AUTO) and refuses MFMA, whatever it holds
-        RC_REQUIRE(mode != RC_SEARCH_MFMA || h->metric == RC_METRIC_COSINE, RC_ERR_UNSUPPORTED,
-                   "batched MFMA search is cosine-only (this index scores by dotproduct or euclidean)");
+        // without RC_FILTER_METRIC the batched path's candidate threshold is a bound in cosine space:
+        // a non-cosine index scans (AUTO) and refuses MFMA, whatever it holds.  With it the filter
+        // bounds the metric's own score (search_mfma.hip) on the f16 / bf16 rows it was set on.
+        const bool metric_ok = h->metric == RC_METRIC_COSINE || h->filter == RC_FILTER_METRIC;
+        RC_REQUIRE(mode != RC_SEARCH_MFMA || metric_ok, RC_ERR_UNSUPPORTED,
+                   "batched MFMA search is cosine-only without RC_FILTER_METRIC (this index scores by dotproduct or euclidean)");
         if (n_rows == 0) {  // an empty shard answers (-inf, -1) in every mode
             empty_search(nq, k, scores, out_rows, s);
             return;
         }
         // (a float8 index scans unless its own filter is switched on: RC_FILTER_F8)
-        const bool mfma_ok = h->metric == RC_METRIC_COSINE && ((h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr ||
-                                                               h->filter == RC_FILTER_F8);
+        const bool mfma_ok = metric_ok && ((h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr ||
+                                           h->filter == RC_FILTER_F8);
         RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
                    "batched MFMA search needs an f16/bf16 index, the int8 filter copy, or a float8 index with RC_FILTER_F8");
         // with a mask AUTO scans: only the caller knows the eligible share, and a selective mask
@@ -1038,6 +1076,9 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
             auto_mfma = (passes >= kF8BatchMinPasses && n_rows >= kF8BatchMinRows) ||
                         (passes >= kF8BatchMinPassesLarge && n_rows * h->ld >= kF8BatchMinBytesLarge);
         }
+        if (h->filter == RC_FILTER_METRIC && h->metric != RC_METRIC_COSINE)  // its own corner (see kMetricBatchMinQueries); f16 / bf16 rows
+            auto_mfma = (nq >= kMetricBatchMinQueries && n_rows >= kBatchMinRows) ||
+                        (nq >= kMetricBatchMinQueriesLarge && n_rows * h->ld * 2 >= kMetricBatchMinBytesLarge);
         const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && mask == nullptr && mfma_ok && auto_mfma);
         if (!use_mfma) {
             scan_search(h, queries, nq, n_rows, k, mask, scores, out_rows, s);

@@ -267,7 +267,8 @@ struct ScanArgs {
     const uint32_t *mask = nullptr;
     // Scoring rule (rc_index_set_metric).  Not RC_METRIC_COSINE: the metric kernels
     // (launch_scan_metric), which read norms [n_rows] and need raw queries (qraw), one per pass
-    // (qb = 1), and no flags.
+    // (qb = 1).  With flags (f16 / bf16 rows only): the metric batched search's exact fallback,
+    // grid.y striding over the flagged queries as above, each normalised from qraw.
     int metric = RC_METRIC_COSINE;
     const float *norms = nullptr;
 };
@@ -376,6 +377,7 @@ struct BatchWs {
     int *flags = nullptr;       // [nq_cap] 1 = candidate overflow, exact fallback needed
     float *sq = nullptr;        // [nq_cap] int8 filter: query scale (q̃ = sq · q8)
     float *aq = nullptr;        // [nq_cap] int8 filter: coefficient of a row's residual norm in the bound
+    float *mcoef = nullptr;     // [nq_cap][4] metric filter: (eps, alpha, beta, gamma) of each query (metric_coef)
     int *ovf = nullptr;         // overflowed queries since the last timing read (device counter)
     int fb_blocks = 0;               // blocks of the fallback scan: FB_BUDGET_BYTES / (nq_cap * k_cap * 8), clamped
     uint64_t *fb_partial = nullptr;  // [fb_blocks][nq_cap][k_cap] partial keys of the exact fallback scan
@@ -405,6 +407,10 @@ struct BatchPlan {
     const uint32_t *mask = nullptr;
     // float8 index with rc_index_set_filter(RC_FILTER_F8): the filter GEMM reads the stored e4m3 rows
     bool f8_filter = false;
+    // RC_FILTER_METRIC under a non-cosine metric: the native filter kernels' metric forms, which
+    // bound each row's metric score and read norms [n_rows]; the keys carry metric scores
+    int metric = RC_METRIC_COSINE;
+    const float *norms = nullptr;
 };
 
 // The int8 filter keeps a row's scale and residual norm at a tile-transposed slot:

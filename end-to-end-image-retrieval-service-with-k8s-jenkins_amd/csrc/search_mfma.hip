@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "index_common.h"
+#include "rescore.h"
 
 namespace rc {
 
@@ -84,6 +85,44 @@ __global__ __launch_bounds__(64) void prepare_queries_kernel(const float *__rest
     }
 }
 
+// The metric filter's preparation (RC_FILTER_METRIC under dotproduct / euclidean): qn, qh, eps
+// and thr exactly as above, plus the query's metric constants mcoef[qi] = (eps, alpha, beta,
+// gamma).  (alpha, beta, gamma) = metric_coef(metric, wave_sum_sq): the metric scan's own sum of
+// squares (same lane partition, same butterfly) and its own rule, so the rescored keys have the
+// scan's bits.  One wave per query: the sum is wave-uniform, as metric_coef's readfirstlane needs.
+template <typename T>
+__global__ __launch_bounds__(64) void prepare_queries_metric_kernel(const float *__restrict__ q, int nq, int dim, int64_t ld,
+                                                                   int metric, float *__restrict__ qn, T *__restrict__ qh,
+                                                                   float *__restrict__ eps, float *__restrict__ thr,
+                                                                   float *__restrict__ mcoef) {
+    const int lane = threadIdx.x;
+    const int qi = blockIdx.x;
+    const bool valid = qi < nq;
+    const float *src = q + (int64_t)(valid ? qi : 0) * dim;
+    const float ss = wave_sum_sq(src, dim, lane, valid);
+    const float inv = inv_norm_of(ss);  // wave_inv_norm's value
+    const MetricCoef mc = metric_coef(metric, ss);
+    float err = 0.f;
+    for (int c = lane; c < ld; c += 64) {
+        const float v = RC_UNIT_ELEM(src, c, dim, inv, valid);
+        const T h = Elem<T>::cast(v);
+        const float d = v - Elem<T>::load(&h, 0);
+        err = fmaf(d, d, err);
+        if (valid) qn[(int64_t)qi * ld + c] = v;
+        qh[(int64_t)qi * ld + c] = h;
+    }
+    err = wave_sum(err);
+    if (lane == 0) {
+        const float e = 1.01f * sqrtf(err) + 6.5e-5f;
+        eps[qi] = e;
+        thr[qi] = valid ? -INFINITY : INFINITY;
+        mcoef[4 * qi + 0] = e;
+        mcoef[4 * qi + 1] = mc.alpha;
+        mcoef[4 * qi + 2] = mc.beta;
+        mcoef[4 * qi + 3] = mc.gamma;
+    }
+}
+
 // ------------------------------------------------------- filter GEMM -------
 struct FilterArgs {
     const void *rows;  // [>= roundup(r_end, 256)][ld]
@@ -126,6 +165,61 @@ __device__ __forceinline__ void append_candidate(const FilterArgs &a, int q, int
     if ((int)pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = (uint32_t)row;
 }
 
+// ---------------------------------------- metric epilogue (RC_FILTER_METRIC) --
+// Under dotproduct / euclidean the two native filter kernels below have a METRIC form: the same
+// GEMM, and an epilogue that bounds the row's METRIC score instead of testing the cosine.  (The
+// int8 and float8 filters have no such form: they stay cosine-only.)
+//
+// s' is the filter GEMM's accumulator for (query q, row r), c the exact cosine the scan and
+// rescore_kernel compute in f32 (RC_ROW_FMA16 + sum16), and |s' - c| <= eps[q] (the header's
+// bound, prepare_queries_kernel's eps).  With n = norms[r] and (alpha, beta, gamma) the query's
+// metric_coef constants, the filter keeps (q, r) iff
+//     u = metric_score(mc, ĉ, n) >= thr[q],     ĉ = s' + eps[q]   (one f32 add)
+// where under a metric thr[q] is the running k-th best EXACT metric score itself (-inf until k
+// rows are held), with no eps subtracted (rescore_candidates).
+// Exact, because u >= the row's exact score s = metric_score(mc, c, n), bit for bit:
+//   * ĉ >= c.  The real number s' + eps is >= c; rounding to nearest is monotone and c is an f32,
+//     so fl(s' + eps) >= fl(c) = c: the add's rounding cannot take ĉ below c.
+//   * t(x) = fmaf(alpha, x, -(beta·n)) is non-decreasing in x for alpha >= 0 (alpha is ‖q‖ or
+//     2‖q‖): the exact alpha·x - fl(beta·n) is, and a correctly rounded FMA is a monotone
+//     function of its exact value.  The addend fl(beta·n) is the same f32 on both sides.
+//   * s(t) = fmaf(n, t, -gamma) is non-decreasing in t for n >= 0 (a norm), likewise.
+//   So ĉ >= c gives u = s(t(ĉ)) >= s(t(c)) = s: no second slack term.  The running k-th best only
+//   rises, so every row of the final top-k has s >= thr[q] at its stage, hence u >= thr[q]; rows
+//   tied with the k-th score pass because the test is >=.
+// The per-row arithmetic is metric_score itself (one copy, index_common.h), so the three roundings
+// are the scan's.  In these epilogues a lane owns one query and four consecutive rows per
+// accumulator: the constants are per lane, loaded as prepared (metric_coef assumes a wave-uniform
+// query and is not called here), and a lane's four norms are one aligned 16-byte load.
+// norms holds `capacity` floats, not the padded row count, and the last row tile reaches past
+// r_end: the norm index is clamped to r_end - 1 (as the metric scan loads its norms under the
+// rows' clamp).  A row >= r_end then gets some u, which can only defeat the wave-uniform
+// early-out: the append still tests row < r_end.
+// The epilogues overwrite the accumulators with u and then run the cosine epilogue's own test on
+// them (the maximum of u as the wave-uniform early-out, then u >= thr per row): no second copy of
+// the tile in registers.  The norm loads sit in the epilogue itself, so each tile's epilogue waits
+// for the row DMA in flight before it (vector-memory loads return in order); DESIGN.md, "Metric
+// filter", has what that costs against the cosine launch.
+struct FilterMetric {
+    const float *norms;  // [>= r_end]
+    const float *mcoef;  // [nqb*256][4]: eps, alpha, beta, gamma
+};
+
+// norms of a row tile's rows o .. o + 3 (o a multiple of 4): tn = the norm of the tile's first row
+// (wave-uniform), left >= 1 = how many of the tile's rows are below r_end; indices clamped to
+// left - 1.  Offsets in 32 bits against the uniform base: one address register per load.
+__device__ __forceinline__ f32x4_t load_norms4(const float *__restrict__ tn, int o, int left) {
+    if (o + 4 <= left) return *reinterpret_cast<const f32x4_t *>(tn + o);
+    f32x4_t v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = tn[min(o + j, left - 1)];
+    return v;
+}
+// u of the comment above: k4 =(eps, alpha, beta, gamma) of the lane's query
+__device__ __forceinline__ float metric_upper(const f32x4_t &k4, float sp, float n) {
+    return metric_score(MetricCoef{k4[1], k4[2], k4[3]}, sp + k4[0], n);
+}
+
 // 256x256x64 tile, 512 threads = 8 waves in two groups (G0 = waves 0-3 own
 // query rows 0-127, G1 = waves 4-7 rows 128-255; wave w and w+4 share a SIMD).
 // Each wave owns 128 queries x 64 index rows as 4 quadrants of 64x32.  The
@@ -138,156 +232,18 @@ __device__ __forceinline__ void append_candidate(const FilterArgs &a, int q, int
 // reads LDS.  MFMA roles: A operand = index rows, B operand = queries, so a
 // lane's accumulator holds 4 consecutive ROWS of one query: the epilogue tests
 // one per-lane threshold against 16 values at a time.
+// The body is filter_gemm_body.inc, included in the cosine kernel and in its METRIC form: one copy
+// of the text, and the cosine kernel keeps the instructions it had.
 template <typename T>
 __global__ __launch_bounds__(512, 1) void filter_gemm_kernel(FilterArgs a) {
-    using Op = MfmaOp<T>;
-    using v8 = typename Op::v8;
-    constexpr int BK = 64;
-    constexpr int A_BYTES = SB_TILE * BK * 2, STAGE = 2 * A_BYTES;
-    __shared__ __attribute__((aligned(16))) uint8_t smem[2 * STAGE];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave >> 2, wc = wave & 3;
-    const int g = lane >> 4, li = lane & 15;
-
-    const FilterBlock fb(a, SB_TILE);
-    const int qb = fb.qb;
-    const int64_t rt0 = fb.rt0, rt1 = fb.rt1;
-    if (rt0 >= rt1) return;  // block-uniform
-    const int nkt = a.nkt;
-    const int64_t ld = a.ld;
-    const int64_t nsteps = (rt1 - rt0) * nkt;
-    const uint16_t *Ag = (const uint16_t *)a.qh + (int64_t)qb * SB_TILE * ld;
-    const uint16_t *Rg = (const uint16_t *)a.rows + (a.r_begin + rt0 * SB_TILE) * ld;
-
-    // 64 pieces of 1 KB per step (queries: 0-31, rows: 32-63); wave w owns pieces w + 8 i.
-    auto stage4 = [&](int buf, int64_t step, int i0) {
-        uint8_t *base = smem + buf * STAGE;
-        const int64_t rt = step / nkt;
-        const int k0 = (int)(step - rt * nkt) * BK;
-        const uint16_t *Wg = Rg + rt * SB_TILE * ld;
-#pragma unroll
-        for (int i = i0; i < i0 + 4; ++i) {
-            const int piece = wave + 8 * i;
-            const bool is_q = i < 4;
-            const int r = (is_q ? piece : piece - 32) * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((r >> 1) & 7);
-            const uint16_t *src = (is_q ? Ag : Wg) + (int64_t)r * ld + k0 + c * 8;
-            __builtin_amdgcn_global_load_lds((const void *)src, (lds_void *)(base + piece * 1024), 16, 0, 0);
-        }
-    };
-    auto bar = [] {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-
-    // thresholds of this lane's 8 query rows: q = qb*256 + grp*128 + mq*64 + mi*16 + li
-    float thr[2][4];
-#pragma unroll
-    for (int mq = 0; mq < 2; ++mq)
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) thr[mq][mi] = a.thr[qb * SB_TILE + grp * 128 + mq * 64 + mi * 16 + li];
-
-    f32x4_t acc[2][2][4][2];
-    auto zero_acc = [&] {
-#pragma unroll
-        for (int a0 = 0; a0 < 2; ++a0)
-#pragma unroll
-            for (int a1 = 0; a1 < 2; ++a1)
-#pragma unroll
-                for (int a2 = 0; a2 < 4; ++a2)
-#pragma unroll
-                    for (int a3 = 0; a3 < 2; ++a3) acc[a0][a1][a2][a3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    };
-    zero_acc();
-
-    stage4(0, 0, 0);
-    stage4(0, 0, 4);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    bar();
-    if (grp == 1) bar();  // stagger: G1 one segment behind
-
-    v8 af[4][2], wf[2][2];  // queries [mi][s], rows [ni][s]
-    for (int64_t step = 0; step < nsteps; ++step) {
-        const int cur = (int)(step & 1);
-        const uint8_t *As = smem + cur * STAGE;
-        const uint8_t *Ws = As + A_BYTES;
-        const bool more = step + 1 < nsteps;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int mq = p >> 1;
-            const int nq = (p == 1 || p == 2);
-            if (p == 0 || p == 2) {
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        const int r = grp * 128 + mq * 64 + mi * 16 + li;
-                        const int c = s * 4 + g;
-                        af[mi][s] = *reinterpret_cast<const v8 *>(As + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-                    }
-            }
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const int r = wc * 64 + nq * 32 + ni * 16 + li;
-                    const int c = s * 4 + g;
-                    wf[ni][s] = *reinterpret_cast<const v8 *>(Ws + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-                }
-            if (more && p < 2) stage4(cur ^ 1, step + 1, p * 4);
-            if (p == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            bar();
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni)
-                        acc[mq][nq][mi][ni] = Op::mma(wf[ni][s], af[mi][s], acc[mq][nq][mi][ni]);
-            __builtin_amdgcn_s_setprio(0);
-            bar();
-        }
-
-        if ((step + 1) % nkt == 0) {
-            // ---- epilogue of row tile rt: lane holds S[q][r .. r+3] for 8 q x 4 r-groups
-            const int64_t rt = rt0 + step / nkt;
-            const int64_t rbase = a.r_begin + rt * SB_TILE + wc * 64 + 4 * g;
-#pragma unroll
-            for (int mq = 0; mq < 2; ++mq)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi) {
-                    const float t = thr[mq][mi];
-                    float m = -INFINITY;
-#pragma unroll
-                    for (int nq = 0; nq < 2; ++nq)
-#pragma unroll
-                        for (int ni = 0; ni < 2; ++ni) {
-                            const f32x4_t v = acc[mq][nq][mi][ni];
-                            m = fmaxf(m, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-                        }
-                    if (__ballot(m >= t) == 0) continue;  // wave-uniform: the common case
-                    if (m >= t) {
-                        const int q = qb * SB_TILE + grp * 128 + mq * 64 + mi * 16 + li;
-#pragma unroll
-                        for (int nq = 0; nq < 2; ++nq)
-#pragma unroll
-                            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) {
-                                    const int64_t row = rbase + nq * 32 + ni * 16 + j;
-                                    if (acc[mq][nq][mi][ni][j] >= t && row < a.r_end) append_candidate(a, q, row);
-                                }
-                    }
-                }
-            zero_acc();
-        }
-    }
-    if (grp == 0) bar();  // balance the stagger barrier
+    constexpr bool METRIC = false;
+    [[maybe_unused]] const FilterMetric fm{};
+#include "filter_gemm_body.inc"
+}
+template <typename T>
+__global__ __launch_bounds__(512, 1) void filter_gemm_metric_kernel(FilterArgs a, FilterMetric fm) {
+    constexpr bool METRIC = true;
+#include "filter_gemm_body.inc"
 }
 
 // Query-stationary filter GEMM (ld = 64·NKT <= 512).  The filter GEMM above
@@ -315,167 +271,19 @@ constexpr int QS_QT = 2, QS_RT = 128, QS_NS = 8;  // queries/16 per wave, rows p
 // ABL (A/B diagnostics, diagnostic builds only; 0 in production): bit0 no DMA in the
 // loop, bit1 no MFMA, bit2 no fragment reads (MFMAs on the query registers), bit3 no
 // epilogue.
+// The body is filter_qs_body.inc (as filter_gemm_body.inc); the METRIC form's epilogue loads the
+// tile's norms itself.
 template <typename T, int NKT, int ABL = 0>  // 256 queries per block
 __global__ __launch_bounds__(512, 1) void filter_qs_kernel(FilterArgs a) {
-    constexpr int QS_WAVES = 16 / QS_QT;
-    constexpr int RF = QS_RT / 16;
-    using Op = MfmaOp<T>;
-    using v8 = typename Op::v8;
-    constexpr int STEP_BYTES = QS_RT * 128;  // 16 KB at QT = 2
-    __shared__ __attribute__((aligned(16))) uint8_t smem[QS_NS * STEP_BYTES];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 4, li = lane & 15;
-
-    const FilterBlock fb(a, QS_RT);
-    const int qb = fb.qb;
-    const int64_t rt0 = fb.rt0, rt1 = fb.rt1;
-    if (rt0 >= rt1) return;  // block-uniform
-    const int64_t ld = a.ld;
-    const int ntiles = (int)(rt1 - rt0);  // per-block counters in 32 bits: uniform SALU compares
-    const int nsteps = ntiles * NKT;
-    const uint16_t *Rg = (const uint16_t *)a.rows + (a.r_begin + rt0 * QS_RT) * ld;
-
-    // this lane's query fragments for the whole K: qf[qt][kk], kk = 32-wide k chunk
-    v8 qf[QS_QT][2 * NKT];
-    const int q0 = qb * SB_TILE + wave * 16 * QS_QT;
-#pragma unroll
-    for (int qt = 0; qt < QS_QT; ++qt)
-#pragma unroll
-        for (int kk = 0; kk < 2 * NKT; ++kk)
-            qf[qt][kk] = *reinterpret_cast<const v8 *>((const uint16_t *)a.qh + (int64_t)(q0 + qt * 16 + li) * ld +
-                                                       kk * 32 + g * 8);
-    float thr[QS_QT];
-#pragma unroll
-    for (int qt = 0; qt < QS_QT; ++qt) thr[qt] = a.thr[q0 + qt * 16 + li];
-    // consume the query loads here, so the compiler's vmcnt waits for them sit
-    // before the K loop instead of inside it (where they would drain the DMA ring)
-#pragma unroll
-    for (int qt = 0; qt < QS_QT; ++qt) {
-        asm volatile("" ::"v"(thr[qt]));
-#pragma unroll
-        for (int kk = 0; kk < 2 * NKT; ++kk) asm volatile("" ::"v"(qf[qt][kk]));
-    }
-
-    // step t = (tile, k-step): 2·RF pieces of 1 KB (8 rows x 128 B); wave w issues pieces w + QS_WAVES·i.
-    constexpr int PPW = 2 * RF / QS_WAVES;
-    uint32_t loff[PPW];  // byte offset of this lane's 16 B within the step's rows
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int r = (wave + QS_WAVES * i) * 8 + (lane >> 3);
-        loff[i] = (uint32_t)(r * (int)ld + (((lane & 7) ^ ((r >> 1) & 7)) << 3)) * 2u;
-    }
-    auto issue = [&](int t) {
-        const int tile = t / NKT;
-        const int ks = (int)(t - tile * NKT);
-        uint8_t *base = smem + (int)(t % QS_NS) * STEP_BYTES;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(Rg + (int64_t)tile * QS_RT * ld + ks * 64), (short)0, 0x7fffffff, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            // (the builtin's operands kept non-dependent: a template-dependent operand defers
-            // its target check to instantiation, where the host pass drops the kernel's stub)
-            lds_void *dst = (lds_void *)(base + (wave + QS_WAVES * i) * 1024);
-            const uint32_t off = loff[i];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, off, 0, 0, 0);
-        }
-    };
-    // one barrier per SPS = 2 k-steps (nsteps is a multiple): steps t..t+SPS-1 land
-    // together, steps t+NS-SPS..t+NS-1 go into the slots freed by t-SPS..t-1; NS - SPS
-    // steps in flight
-    constexpr int SPS = 2;
-    for (int t = 0; t < min(QS_NS - SPS, nsteps); ++t) issue(t);
-
-    f32x4_t acc[RF][QS_QT];
-    for (int tile = 0; tile < ntiles; ++tile) {
-#pragma unroll
-        for (int rf = 0; rf < RF; ++rf)
-#pragma unroll
-            for (int qt = 0; qt < QS_QT; ++qt)
-                acc[rf][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kp = 0; kp < NKT / SPS; ++kp) {
-            const int t = tile * NKT + SPS * kp;
-            // steps t..t+SPS-1 landed: the NS - 2·SPS younger steps (PPW DMAs each) may be in flight
-            static_assert(NKT % SPS == 0 && (QS_NS - 2 * SPS) * PPW < 64, "whole sync groups; vmcnt is 6 bits");
-            if (t + QS_NS - SPS - 1 < nsteps) {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((QS_NS - 2 * SPS) * PPW) : "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // every wave's DMA of t..t+SPS-1 landed; slots of t-SPS..t-1 are free
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int j = QS_NS - SPS; j < QS_NS; ++j)
-                if (!(ABL & 1) && t + j < nsteps) issue(t + j);
-            // groups of 4 row fragments, (k half kl, k sub-chunk sh, row quarter rh): 4 reads,
-            // then their 4·QT MFMAs with counted lgkmcnt waits.  Row r = 16 rf + li: its
-            // swizzle (r >> 1) & 7 = (li >> 1) & 7 does not depend on rf.  The SIMD
-            // partner wave's MFMAs cover the read latency.
-            constexpr int RH = RF / 4, NG = SPS * 2 * RH;
-            auto frag_ptr = [&](int gi) {
-                const int kl = gi / (2 * RH), sh = (gi / RH) % 2, rh = gi % RH;
-                return smem + ((t + kl) % QS_NS) * STEP_BYTES + li * 128 + (((sh * 4 + g) ^ ((li >> 1) & 7)) << 4) +
-                       rh * 4 * 2048;
-            };
-            auto load_group = [&](int gi, v8 *dst) {
-                const uint8_t *Sr = frag_ptr(gi);
-                const int ks = SPS * kp + gi / (2 * RH), sh = (gi / RH) % 2;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    dst[i] = (ABL & 4) ? qf[i & 1][(ks * 2 + sh + i) % (2 * NKT)]
-                                       : *reinterpret_cast<const v8 *>(Sr + i * 2048);
-            };
-#pragma unroll
-            for (int gi = 0; gi < NG; ++gi) {
-                const int ks = SPS * kp + gi / (2 * RH), sh = (gi / RH) % 2, rh = gi % RH;
-                v8 cur[4];
-                load_group(gi, cur);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int qt = 0; qt < QS_QT; ++qt)
-                        if constexpr (ABL & 2)
-                            asm volatile("" ::"v"(cur[i]));
-                        else
-                            acc[rh * 4 + i][qt] = Op::mma(cur[i], qf[qt][ks * 2 + sh], acc[rh * 4 + i][qt]);
-                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-            }
-        }
-        // ---- epilogue of row tile rt0 + tile: candidates s' >= thr[q]
-        const int64_t rbase = a.r_begin + (rt0 + tile) * QS_RT + 4 * g;
-        if constexpr (ABL & 8) {  // diagnostics: no epilogue (accumulators kept live)
-#pragma unroll
-            for (int rf = 0; rf < RF; ++rf)
-#pragma unroll
-                for (int qt = 0; qt < QS_QT; ++qt) asm volatile("" ::"v"(acc[rf][qt]));
-            continue;
-        }
-#pragma unroll
-        for (int qt = 0; qt < QS_QT; ++qt) {
-            const float th = thr[qt];
-            float m = -INFINITY;
-#pragma unroll
-            for (int rf = 0; rf < RF; ++rf) {
-                const f32x4_t v = acc[rf][qt];
-                m = fmaxf(m, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-            }
-            if (__ballot(m >= th) == 0) continue;  // wave-uniform: the common case
-            if (m >= th) {
-                const int q = q0 + qt * 16 + li;
-#pragma unroll
-                for (int rf = 0; rf < RF; ++rf)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int64_t row = rbase + rf * 16 + j;
-                        if (acc[rf][qt][j] >= th && row < a.r_end) append_candidate(a, q, row);
-                    }
-            }
-        }
-    }
+    constexpr bool METRIC = false;
+    [[maybe_unused]] const FilterMetric fm{};
+#include "filter_qs_body.inc"
+}
+template <typename T, int NKT>
+__global__ __launch_bounds__(512, 1) void filter_qs_metric_kernel(FilterArgs a, FilterMetric fm) {
+    constexpr bool METRIC = true;
+    constexpr int ABL = 0;
+#include "filter_qs_body.inc"
 }
 
 // ------------------------------------------------ int8 filter (optional) --
@@ -1086,112 +894,17 @@ __global__ __launch_bounds__(512, 1) void filter_f8_kernel(FilterF8Args fa) {
 }
 
 // ------------------------------------------------------- exact rescoring --
-// One block per query.  Candidates are scored exactly as scan_topk_kernel
-// scores a row (RC_ROW_FMA16 + sum16: 16 lanes per row, 16-B chunks, f32 FMA in chunk
-// order, DPP reduction), merged with the running top-k keys, and the threshold for the
-// next stage is set.  Overflow (more candidates than cap) is flagged for the
-// host's exact fallback; the counter is reset for the next stage.
-//
-// MASKED (rc_index_search_masked; `mask` as in ScanArgs): a candidate whose bit is clear is
-// scored but not pushed; the filter kernels are untouched.  Why that is exact: the running
-// list then holds eligible rows only, so thr[q] is -inf or (kth best exact score among the
-// ELIGIBLE rows seen so far) - eps[q], a lower bound of the final masked kth best minus eps;
-// by the header's argument every eligible row of the masked top-k has s' >= thr[q] at its
-// stage, passes the filter, and is rescored here.  Ineligible rows only take candidate slots:
-// thr rises more slowly than in an unmasked search (it stays -inf until k eligible rows were
-// seen), so a selective mask overflows sooner.  An overflowed query is flagged exactly as
-// before — n counts every appended candidate, eligible or not, so a list that lost entries
-// is never trusted — and the fallback is the MASKED scan (index.hip), whose lists the
-// unchanged merge writes over this kernel's output.  Candidate rows are < r_end <= n_rows
-// (every filter epilogue tests that), so mask[row >> 5] stays inside the bitmap.
-template <typename T, int NCH, int CAP, bool MASKED>
-__global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows, int64_t ld, const float *__restrict__ qn,
-                                                     int k, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ cand,
-                                                     int cap, uint64_t *__restrict__ keys, const float *__restrict__ eps,
-                                                     float *__restrict__ thr, int *__restrict__ flags,
-                                                     int *__restrict__ ovf_total, int final_pass, int64_t row_base,
-                                                     int64_t row_stride, float *__restrict__ out_scores,
-                                                     int64_t *__restrict__ out_rows, const uint32_t *__restrict__ mask) {
-    constexpr int EPC = RowShape<T, NCH>::EPC;
-    constexpr int CPL = RowShape<T, NCH>::CPL;
-    constexpr int U = 2;
-    __shared__ uint64_t lds[4][CAP];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int sub = lane & 15, rg = lane >> 4;
-    const int qi = blockIdx.x;
-
-    float q[1][CPL][EPC];
-#pragma unroll
-    for (int i = 0; i < CPL; ++i)
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            q[0][i][e] = qn[(int64_t)qi * ld + (sub + 16 * i) * EPC + e];
-            if constexpr (sizeof(T) == 1) q[0][i][e] *= query_unscale<T>();  // as scan_rows: the scan's bits
-        }
-
-    const uint32_t n = cnt[qi];
-    const int nn = (int)min<uint32_t>(n, (uint32_t)cap);
-    const uint32_t *cl = cand + (int64_t)qi * cap;
-    const uint4 *base4 = reinterpret_cast<const uint4 *>(rows);
-    const int64_t ld4 = ld / EPC;
-
-    WaveTopK<CAP> tk;
-    tk.init(as_lds(&lds[wave][0]), k);
-    if (wave == 0) {  // the running top-k of the earlier stages
-        for (int j = 0; j < k; j += 64) {
-            const uint64_t key = (j + lane < k) ? keys[(int64_t)qi * k + j + lane] : KEY_EMPTY;
-            tk.reserve(64);
-            tk.push(key != KEY_EMPTY, key);
-        }
-    }
-    for (int j0 = wave * 4 * U; j0 < nn; j0 += 16 * U) {
-        uint4 x[U][CPL];
-        uint32_t rr[U];
-        [[maybe_unused]] uint32_t mw[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * 4 + rg;
-            rr[u] = cl[j < nn ? j : 0];
-            if constexpr (MASKED) mw[u] = mask[rr[u] >> 5];
-#pragma unroll
-            for (int i = 0; i < CPL; ++i) x[u][i] = base4[(int64_t)rr[u] * ld4 + sub + 16 * i];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * 4 + rg;
-            float acc[1];
-            RC_ROW_FMA16(T, 1, CPL, EPC, x[u], q, acc);
-            const float s = sum16(acc[0]);
-            tk.reserve(4);
-            if constexpr (MASKED) tk.push(sub == 0 && j < nn && ((mw[u] >> (rr[u] & 31u)) & 1u) != 0u, make_key(s, rr[u]));
-            else tk.push(sub == 0 && j < nn, make_key(s, rr[u]));
-        }
-    }
-    tk.compact();
-    __syncthreads();
-    if (wave == 0) {
-        RC_FOLD_WAVE_LISTS(&lds[w][0], tk, k, lane);
-        for (int j = lane; j < k; j += 64) {
-            const uint64_t key = tk.buf[j];
-            keys[(int64_t)qi * k + j] = key;
-            if (final_pass) {
-                RC_EMIT_KEY(key, row_base, row_stride, out_scores[(int64_t)qi * k + j], out_rows[(int64_t)qi * k + j]);
-            }
-        }
-        if (lane == 0) {
-            thr[qi] = tk.count >= k ? key_score(tk.buf[k - 1]) - eps[qi] : -INFINITY;
-            if (n > (uint32_t)cap && flags[qi] == 0) {
-                flags[qi] = 1;
-                atomicAdd(ovf_total, 1);
-            }
-            cnt[qi] = 0;
-        }
-    }
-}
+// rescore_kernel and its metric form are in rescore.h; the metric kernels are instantiated in
+// rescore_metric_{f16,bf16}.hip, not here.
+extern template void launch_rescore_metric<f16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
+extern template void launch_rescore_metric<bf16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
 
 // ------------------------------------------------------------------ host ---
 template <typename T>
 void launch_rescore(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
+    if constexpr (sizeof(T) == 2) {  // the metric filter's dtypes: f16 / bf16
+        if (p.metric != RC_METRIC_COSINE) return launch_rescore_metric<T>(p, ws, final_pass, s);
+    }
     // (float8 rows: the even widths up to 768, what the float8 filter serves)
     const bool ok = with_nch<(sizeof(T) == 1 ? 6 : 16), T>(p.nch, [&](auto nch) {
         with_topk_cap(topk_cap(p.k), [&](auto cap) {
@@ -1263,14 +976,32 @@ void run_stages(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *tim
 template <typename T>
 void run_batched(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
     const int nq_pad = (p.nq + SB_TILE - 1) / SB_TILE * SB_TILE;
-    hipLaunchKernelGGL(prepare_queries_kernel<T>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn,
-                       (T *)ws.qh, ws.eps, ws.thr);
+    const bool metric = p.metric != RC_METRIC_COSINE;  // the METRIC forms of the same kernels (RC_FILTER_METRIC)
+    if (metric)
+        hipLaunchKernelGGL(prepare_queries_metric_kernel<T>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, p.metric,
+                           ws.qn, (T *)ws.qh, ws.eps, ws.thr, ws.mcoef);
+    else
+        hipLaunchKernelGGL(prepare_queries_kernel<T>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn,
+                           (T *)ws.qh, ws.eps, ws.thr);
     RC_LAUNCH_CHECK();
     auto filter = [&](int64_t c0, int64_t c1, int64_t nchunk, int nqb) {
         const int64_t rt_total = (c1 - c0 + SB_TILE - 1) / SB_TILE;
         const int64_t tpc = (rt_total + nchunk - 1) / nchunk;
         FilterArgs fa{p.rows, ws.qh, p.ld, (int)(p.ld / 64), c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap};
         const int nkt = (int)(p.ld / 64);
+        if (metric) {
+            const FilterMetric fm{p.norms, ws.mcoef};
+            if (nkt == 2 || nkt == 4 || nkt == 8) {
+                fa.tiles_per_chunk = ((c1 - c0 + QS_RT - 1) / QS_RT + nchunk - 1) / nchunk;
+                const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
+                if (nkt == 8) hipLaunchKernelGGL((filter_qs_metric_kernel<T, 8>), gr, bl, 0, s, fa, fm);
+                else if (nkt == 4) hipLaunchKernelGGL((filter_qs_metric_kernel<T, 4>), gr, bl, 0, s, fa, fm);
+                else hipLaunchKernelGGL((filter_qs_metric_kernel<T, 2>), gr, bl, 0, s, fa, fm);
+            } else {
+                hipLaunchKernelGGL(filter_gemm_metric_kernel<T>, dim3((unsigned)(nchunk * nqb)), dim3(512), 0, s, fa, fm);
+            }
+            return;
+        }
         if (nkt == 2 || nkt == 4 || nkt == 8) {
             fa.tiles_per_chunk = ((c1 - c0 + QS_RT - 1) / QS_RT + nchunk - 1) / nchunk;
             const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
@@ -1371,6 +1102,9 @@ void filter_scores_f8(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, 
 void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
     RC_REQUIRE(p.ld % 64 == 0, RC_ERR_UNSUPPORTED, "batched search needs ld % 64 == 0");
     RC_REQUIRE(p.n_rows > 0, RC_ERR_INVALID, "batched search over an empty range");
+    if (p.metric != RC_METRIC_COSINE)  // the native kernels' METRIC forms only: the int8 and float8 filters are cosine-only
+        RC_REQUIRE((p.dtype == RC_F16 || p.dtype == RC_BF16) && !p.f8_filter && p.rows8 == nullptr && p.norms != nullptr,
+                   RC_ERR_UNSUPPORTED, "batched MFMA search under a non-cosine metric needs an f16 or bf16 index with RC_FILTER_METRIC");
     if (p.f8_filter) {
         RC_REQUIRE(p.dtype == RC_F8 && f8_filter_supported(p.ld), RC_ERR_UNSUPPORTED,
                    "float8 filter needs a float8 index of ld 256, 512 or 768");
@@ -1407,6 +1141,7 @@ void BatchWs::ensure(int nq, int k, int64_t ld, int dtype_bytes) {
     flags = (int *)dmalloc((size_t)nq_cap * sizeof(int));
     sq = (float *)dmalloc((size_t)nq_cap * sizeof(float));
     aq = (float *)dmalloc((size_t)nq_cap * sizeof(float));
+    mcoef = (float *)dmalloc((size_t)nq_cap * 4 * sizeof(float));
     ovf = (int *)dmalloc(sizeof(int));
     RC_HIP(hipMemset(ovf, 0, sizeof(int)));
     // the fallback scan's partial lists are sized by a memory budget, not by the row count:
@@ -1418,7 +1153,7 @@ void BatchWs::ensure(int nq, int k, int64_t ld, int dtype_bytes) {
 
 void BatchWs::release() {
     for (void *p : {(void *)qn, qh, (void *)eps, (void *)thr, (void *)cnt, (void *)cand, (void *)keys, (void *)flags, (void *)sq,
-                    (void *)aq, (void *)ovf, (void *)fb_partial})
+                    (void *)aq, (void *)mcoef, (void *)ovf, (void *)fb_partial})
         dfree(p);
     *this = BatchWs{};
 }

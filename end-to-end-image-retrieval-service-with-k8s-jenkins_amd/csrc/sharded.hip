@@ -546,10 +546,19 @@ int rc_sharded_set_filter(rc_sharded *h, int kind) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
         std::lock_guard<std::mutex> lk(h->mu);
+        // the kind every shard has now (they are set together: shard 0 speaks for all): a refused
+        // switch away from RC_FILTER_METRIC (to the int8 or float8 filter under a non-cosine metric)
+        // must leave it in place, or the index would lose its batched search.  Only that kind is put
+        // back: it allocates nothing, so restoring it cannot fail.  A previous int8 copy was freed by
+        // the shards that did switch and is not rebuilt here (it may be what there was no room for):
+        // from RC_FILTER_I8 / RC_FILTER_F8 a failure ends at RC_FILTER_NATIVE, as before.
+        int prev = RC_FILTER_NATIVE;
+        if (h->n > 0) check_status(rc_index_get_filter(h->shard[0], &prev));
+        const int back = prev == RC_FILTER_METRIC ? RC_FILTER_METRIC : RC_FILTER_NATIVE;
         try {
             for (int s = 0; s < h->n; ++s) check_status(rc_index_set_filter(h->shard[s], kind, h->st[s]));
         } catch (...) {  // all or nothing: a failed shard (e.g. no room for the int8 copy) rolls every shard back
-            for (int s = 0; s < h->n; ++s) (void)rc_index_set_filter(h->shard[s], RC_FILTER_NATIVE, h->st[s]);
+            for (int s = 0; s < h->n; ++s) (void)rc_index_set_filter(h->shard[s], back, h->st[s]);
             throw;
         }
     });
@@ -565,8 +574,8 @@ int rc_sharded_set_metric(rc_sharded *h, int metric) {
         for (int s = 0; s < h->n && metric != RC_METRIC_COSINE; ++s) {
             int kind = RC_FILTER_NATIVE;
             check_status(rc_index_get_filter(h->shard[s], &kind));
-            RC_REQUIRE(kind == RC_FILTER_NATIVE, RC_ERR_UNSUPPORTED,
-                       "a non-cosine metric on an index with the int8 filter copy or the float8 filter (the batched MFMA search is cosine-only)");
+            RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_METRIC, RC_ERR_UNSUPPORTED,
+                       "a non-cosine metric on an index with the int8 filter copy or the float8 filter (those filters are cosine-only)");
         }
         for (int s = 0; s < h->n; ++s) check_status(rc_index_set_metric(h->shard[s], metric));
     });

@@ -124,8 +124,11 @@ class DeviceIndex:
     def set_filter(self, kind: str, stream=None) -> None:
         """Filter kind of the batched search (rc_index_set_filter): "native" (the filter GEMM
         reads the stored f16/bf16 rows), "i8" (an int8 copy of every row, int8 MFMA at twice the
-        f16 rate) or "f8" (a float8 index only: the block-scaled fp8 MFMA on the stored rows, no
-        copy; it is what gives a float8 index ``mode="mfma"``).  Results never change —
+        f16 rate), "f8" (a float8 index only: the block-scaled fp8 MFMA on the stored rows, no
+        copy; it is what gives a float8 index ``mode="mfma"``) or "metric" (an f16/bf16 index
+        only: "native" under cosine, and under dotproduct / euclidean the same filter GEMM with
+        a bound on the metric's own score, which is what gives a non-cosine index
+        ``mode="mfma"``; no copy).  "i8" and "f8" are cosine-only.  Results never change —
         candidates are rescored exactly on the stored rows."""
         if kind not in _lib.FILTERS:
             raise ValueError(f"unknown filter {kind!r} (expected one of {sorted(_lib.FILTERS)})")
@@ -198,8 +201,9 @@ class DeviceIndex:
         said otherwise): (scores f32 [nq,k] descending, global rows i64 [nq,k]).
 
         ``mode``: "scan" (HBM-bound streaming scan), "mfma" (batched filter GEMM +
-        exact rescoring, f16/bf16 index, cosine only) or "auto" (MFMA for >= 8 queries; a
-        float8 index scans and refuses "mfma" unless its filter is "f8").
+        exact rescoring, f16/bf16 index; under dotproduct / euclidean only with the "metric"
+        filter) or "auto" (MFMA for >= 8 queries; a float8 index scans and refuses "mfma" unless
+        its filter is "f8", a non-cosine index unless its filter is "metric").
         ``mask``: optional row-eligibility bitmap over the LOCAL rows (rc_index_search_masked):
         an int32 / uint32 tensor of ceil(n_rows / 32) words on this device, bit r & 31 of word
         r >> 5 = row r may be returned; "auto" then scans."""
@@ -753,9 +757,11 @@ class Index:
     every search sorts descending; ``query`` / ``query_batch`` report ``max(0.0, -s)``).  The
     metric is a scoring rule over unchanged storage: ``upsert``, ``fetch``, ``delete``,
     ``query(id=...)`` and metadata filters work alike under all three, and ``save`` / ``load``
-    keep it.  The batched MFMA search is cosine-only: a non-cosine index always scans,
-    ``mode="mfma"`` and ``filter="i8"`` raise ``ValueError`` on it.  All-zero vectors and
-    queries are rejected under every metric.
+    keep it.  By default the batched MFMA search is cosine-only: a non-cosine index scans,
+    ``mode="mfma"`` and ``filter="i8"`` raise ``ValueError`` on it.  ``filter="metric"`` (an
+    f16/bf16 index) gives it the batched search — ``mode="mfma"``, and ``"auto"`` under the
+    usual conditions — with the scan's ids and score bits.  All-zero vectors and queries are
+    rejected under every metric.
 
     ``dtype`` is the storage of the normalised rows: ``"float32"``, ``"float16"``, ``"bfloat16"``
     or ``"float8_e4m3fn"`` (alias ``"f8"``: one byte per element, each element of the direction
@@ -779,7 +785,7 @@ class Index:
     same vectors.  Capacity grows on demand (doubling), as a Pinecone index
     has no fixed size.
 
-    Two things are called "filter" here.  The constructor's ``filter="native" | "i8" | "f8"`` is
+    Two things are called "filter" here.  The constructor's ``filter="native" | "i8" | "f8" | "metric"`` is
     the kind of filter GEMM the batched search runs (``DeviceIndex.set_filter``); it never
     changes a result.  ``query(..., filter={...})`` / ``query_batch(..., filter={...})`` is
     Pinecone's metadata filter (``metafilter``): only vectors whose metadata satisfies it can
@@ -795,8 +801,10 @@ class Index:
             raise ValueError(f"unknown metric {metric!r} (expected one of {sorted(_lib.METRICS)})")
         if filter not in _lib.FILTERS:
             raise ValueError(f"unknown filter {filter!r} (expected one of {sorted(_lib.FILTERS)})")
-        if metric != "cosine" and filter != "native":
-            raise ValueError(f"filter={filter!r} serves the batched MFMA search, which is cosine-only (metric={metric!r})")
+        if metric != "cosine" and filter not in ("native", "metric"):
+            raise ValueError(f"filter={filter!r} is cosine-only (metric={metric!r}); filter='metric' serves the other metrics")
+        if filter == "metric" and (_lib.is_f8(dtype) or dtype in ("float32", "f32")):
+            raise ValueError(f"filter='metric' reads stored f16 / bf16 rows: it needs dtype float16 or bfloat16 (dtype={dtype!r})")
         if _lib.is_f8(dtype) and filter == "i8":
             raise ValueError("filter='i8' is not available on a float8 index (its batched search is filter='f8')")
         if filter == "f8" and not _lib.is_f8(dtype):
@@ -1123,10 +1131,15 @@ class Index:
         share); this layer does, and asks for MFMA when the unmasked conditions hold (>= 8
         queries, >= 64k rows per shard, an f16/bf16 index or the int8 filter copy; a float8
         index with the "f8" filter has the library's own corner for that kind, in passes of the
-        masked scan) and the share reaches MASKED_MFMA_MIN_SHARE."""
+        masked scan) and the share reaches MASKED_MFMA_MIN_SHARE.  A non-cosine index scans unless
+        its filter is "metric"; then the size rule is that filter's own (>= 16 queries, or >= 8
+        over >= 2^28 bytes of rows per shard: measured unmasked, where 8 queries over fewer rows
+        are behind the scan) and the share is the same constant (measured for cosine; under a
+        metric it is unmeasured, and conservative: the competing masked scan takes one query per
+        pass there)."""
         if mode != "auto":
             return mode
-        if self.metric != "cosine":  # the batched MFMA path is cosine-only
+        if self.metric != "cosine" and self._set.filter != "metric":  # no batched path for this index
             return "scan"
         per_shard = n // self._set.n
         if _lib.is_f8(self._set.dtype):
@@ -1136,6 +1149,8 @@ class Index:
             qb = 1 if k > 64 else 4 if ld <= 256 else 2 if ld <= 512 else 1  # the masked scan's queries per pass
             passes = -(-nq // qb)
             size_ok = (passes >= 16 and per_shard >= 131072) or (passes >= 8 and per_shard * ld >= 1 << 28)
+        elif self.metric != "cosine":  # the "metric" filter's corner, as the library's unmasked "auto"
+            size_ok = per_shard >= 65536 and (nq >= 16 or (nq >= 8 and per_shard * self._set.ld * 2 >= 1 << 28))
         else:
             mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter == "i8"
             size_ok = mfma_ok and nq >= 8 and per_shard >= 65536

@@ -198,10 +198,24 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
  *                      available and RC_SEARCH_AUTO takes the batched path under its
  *                      usual conditions.  RC_ERR_UNSUPPORTED on an index that is not
  *                      RC_F8, not cosine, or of a row width (dim rounded up to 256)
- *                      other than 256, 512 or 768. */
+ *                      other than 256, 512 or 768.
+ *   RC_FILTER_METRIC — an RC_F16 / RC_BF16 index only (RC_ERR_UNSUPPORTED on any other):
+ *                      the batched search under every metric.  Under RC_METRIC_COSINE it
+ *                      is RC_FILTER_NATIVE: the same kernels, the same bits.  Under
+ *                      RC_METRIC_DOT / RC_METRIC_EUCLIDEAN the same filter GEMM over the
+ *                      stored rows bounds each row's METRIC score from above (from the
+ *                      GEMM's value, its error bound and the row's norm) and keeps the
+ *                      rows whose bound reaches the query's running k-th best metric
+ *                      score; candidates are rescored exactly by the metric's rule, so
+ *                      RC_SEARCH_MFMA returns the scan's rows and score bits, and
+ *                      RC_SEARCH_AUTO takes the batched path under its usual
+ *                      conditions.  It allocates nothing (switching to it from
+ *                      RC_FILTER_I8 frees the int8 copy); all three metrics may be set
+ *                      on it, in any order. */
 #define RC_FILTER_NATIVE 0
 #define RC_FILTER_I8 1
 #define RC_FILTER_F8 2
+#define RC_FILTER_METRIC 3
 int rc_index_set_filter(rc_index *h, int kind, void *stream);
 int rc_index_get_filter(const rc_index *h, int *kind);
 /* What the RC_FILTER_F8 filter computes (a diagnostic: no reference counterpart).  Runs the
@@ -233,10 +247,13 @@ int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t ro
  * (qn, 0, 0) for RC_METRIC_DOT and (2 qn, 1, ss) for RC_METRIC_EUCLIDEAN.  It is a
  * function of the row and the query alone: every search path and a sharded index give
  * the same bits.  All-zero vectors and queries stay rejected by the host layer.
- * The batched MFMA path is cosine-only (its candidate threshold is a bound in cosine
- * space): on a non-cosine index RC_SEARCH_AUTO scans, RC_SEARCH_MFMA and
- * rc_index_set_filter(RC_FILTER_I8 / RC_FILTER_F8) are RC_ERR_UNSUPPORTED, and so is a
- * non-cosine metric on an index whose filter is not RC_FILTER_NATIVE.  An unknown metric is
+ * The batched MFMA path serves a non-cosine metric only through RC_FILTER_METRIC (an
+ * f16 / bf16 index), whose filter bounds the metric's own score per row.  With any other
+ * filter kind its candidate threshold is a bound in cosine space: on a non-cosine index
+ * with RC_FILTER_NATIVE RC_SEARCH_AUTO scans and RC_SEARCH_MFMA is RC_ERR_UNSUPPORTED;
+ * rc_index_set_filter(RC_FILTER_I8 / RC_FILTER_F8) on a non-cosine index is
+ * RC_ERR_UNSUPPORTED (those two filters are cosine-only), and so is a non-cosine metric
+ * on an index whose filter is RC_FILTER_I8 or RC_FILTER_F8.  An unknown metric is
  * RC_ERR_INVALID. */
 #define RC_METRIC_COSINE 0
 #define RC_METRIC_DOT 1
@@ -329,10 +346,10 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
                                  int with_values, const uint32_t *mask, float *scores, int64_t *out_rows,
                                  float *values);
 /* rc_index_set_filter on every shard; all or nothing (a failure restores
- * RC_FILTER_NATIVE on every shard). */
+ * RC_FILTER_NATIVE on every shard, or RC_FILTER_METRIC if that was the kind before). */
 int rc_sharded_set_filter(rc_sharded *h, int kind);
 /* rc_index_set_metric on every shard; the metric is validated against every shard
- * before any is set (an unknown metric, or a shard whose filter is not RC_FILTER_NATIVE, changes none). */
+ * before any is set (an unknown metric, or a shard whose filter is neither RC_FILTER_NATIVE nor RC_FILTER_METRIC under a non-cosine metric, changes none). */
 int rc_sharded_set_metric(rc_sharded *h, int metric);
 
 /* ------------------------------------------------------------------------
