@@ -163,6 +163,7 @@ SIGNATURES = {
     "rc_model_timing_read": (C.c_int, [_vp, _i32, _pd, _pi64, _pd]),
     "rc_model_timing_reset": (C.c_int, [_vp]),
     "rc_gemm_bf16": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "rc_attention_bf16": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "rc_jpeg_probe": (C.c_int, [C.c_char_p, _i64, C.POINTER(JpegInfo)]),
     "rc_jpeg_decode_coefficients": (C.c_int, [C.c_char_p, _i64, _vp, _vp]),
     "rc_jpeg_decoder_create": (C.c_int, [_i32, _i32, _i64, C.POINTER(_vp)]),

@@ -424,6 +424,41 @@ void layernorm(rc_model *m, const float *x, const float *g, const float *b, uint
     m->timers[T_LN].end(t, s, (double)M * m->cfg.hidden * 6.0);
 }
 
+// The attention launches, shared by the model (encode, last_layer_cls) and the kernel-level
+// entry rc_attention_bf16, so the parity tests run the product's launch arithmetic.
+// qkv [images·tokens][3·heads·64] bf16 (Q | K | V columns), scale = 1 / sqrt(head dim).
+enum AttnKind { ATTN_FULL = 0, ATTN_FULL_RT = 1, ATTN_CLS = 2 };
+
+// fewer (image, head) items than CUs: each item's query tiles split over 4 blocks (a lone image:
+// 48 blocks)
+int attention_qsplit(int items, int ncu) { return items < ncu ? 4 : 1; }
+
+// ATTN_FULL: out [images·tokens][heads·64], attention_v2_kernel<197> at 197 tokens and <0> (the
+// token count at run time) otherwise; ATTN_FULL_RT: <0> at any count.  ATTN_CLS: out
+// [images][heads·64] for query row 0 of each image (attention_cls_kernel), read from qkv or, with
+// q_cls, from compact [images][heads·64] rows; qsplit is not used.
+void launch_attention(int kind, const uint16_t *qkv, const uint16_t *q_cls, uint16_t *out, int images, int tokens, int heads,
+                      float scale, int qsplit, hipStream_t s) {
+    const int items = images * heads;
+    const float scale_log2e = scale * 1.4426950408889634f;
+    if (kind == ATTN_CLS) {
+        RC_REQUIRE(tokens >= 1 && tokens <= ATT_CLS_ROWS, RC_ERR_INVALID, "CLS attention: tokens must be 1 .. 256");
+        hipLaunchKernelGGL(attention_cls_kernel, dim3((items + 3) / 4), dim3(256), 0, s, qkv, out, tokens, heads, items,
+                           scale_log2e, q_cls);
+    } else {
+        RC_REQUIRE(tokens >= 1 && tokens <= ATT2_ROWS, RC_ERR_INVALID, "attention: tokens must be 1 .. 208");
+        RC_REQUIRE(qsplit == 1 || qsplit == 4, RC_ERR_INVALID, "attention: qsplit must be 1 or 4");
+        if (kind == ATTN_FULL && tokens == 197) {
+            hipLaunchKernelGGL(attention_v2_kernel<197>, dim3(items * qsplit), dim3(256), 0, s, qkv, out, tokens, heads,
+                               scale_log2e, qsplit);
+        } else {
+            hipLaunchKernelGGL(attention_v2_kernel<0>, dim3(items * qsplit), dim3(256), 0, s, qkv, out, tokens, heads,
+                               scale_log2e, qsplit);
+        }
+    }
+    RC_LAUNCH_CHECK();
+}
+
 // Last encoder layer after its QKV GEMM, for the CLS rows only (see
 // attention_cls_kernel): gather the n CLS rows of the residual stream into
 // cls_hidden[i0 ..], CLS-query attention, then O-proj (+residual), LN2, fc1+GELU
@@ -452,9 +487,7 @@ void last_layer_cls(rc_model *m, const Layer &L, int i0, int n, const uint16_t *
     }
     const int ta = m->timers[T_ATTN].begin(s);
     const int items = n * c.heads;
-    hipLaunchKernelGGL(attention_cls_kernel, dim3((items + 3) / 4), dim3(256), 0, s, qkv, ac, T, c.heads, items,
-                       scale * 1.4426950408889634f, q_cls ? qc : nullptr);
-    RC_LAUNCH_CHECK();
+    launch_attention(ATTN_CLS, qkv, q_cls ? qc : nullptr, ac, n, T, c.heads, scale, 1, s);
     m->timers[T_ATTN].end(ta, s, 4.0 * items * (double)T * (H / c.heads));
     GemmArgs o{ac, L.w_o, L.b_o, n, H, H, nullptr, hc, nullptr, 1};
     if (m->ln_fold) {  // LN2 folded into fc1, as in the other layers
@@ -559,17 +592,7 @@ void encode(rc_model *m, const uint8_t *images, int i0, int n, float *raw, float
         }
         if (!fuse) {
             const int ta = m->timers[T_ATTN].begin(s);
-            const int items = n * c.heads;
-            // fewer items than CUs: each item's query tiles split over 4 blocks (a lone image: 48 blocks)
-            const int qsplit = items < m->ncu ? 4 : 1;
-            if (T == 197) {
-                hipLaunchKernelGGL(attention_v2_kernel<197>, dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
-                                   scale * 1.4426950408889634f, qsplit);
-            } else {
-                hipLaunchKernelGGL(attention_v2_kernel<0>, dim3(items * qsplit), dim3(256), 0, s, qkv, attn, T, c.heads,
-                                   scale * 1.4426950408889634f, qsplit);
-            }
-            RC_LAUNCH_CHECK();
+            launch_attention(ATTN_FULL, qkv, nullptr, attn, n, T, c.heads, scale, attention_qsplit(n * c.heads, m->ncu), s);
             m->timers[T_ATTN].end(ta, s, 4.0 * n * c.heads * (double)T * T * (H / c.heads));
         }
         {
@@ -1049,5 +1072,29 @@ extern "C" int rc_gemm_bf16(int epi, int variant, const uint16_t *A, const uint1
                 break;
             default: throw Error(RC_ERR_INVALID, "unknown epilogue");
         }
+    });
+}
+
+extern "C" int rc_attention_bf16(int kind, const uint16_t *qkv, const uint16_t *q_cls, uint16_t *out, int images, int tokens,
+                                 int heads, int qsplit, void *stream) {
+    return guard([&] {
+        // everything refused here is refused before any device call
+        RC_REQUIRE(kind == ATTN_FULL || kind == ATTN_FULL_RT || kind == ATTN_CLS, RC_ERR_INVALID,
+                   "attention kind: 0 full, 1 full with the token count at run time, 2 CLS query only");
+        RC_REQUIRE(qkv && out, RC_ERR_INVALID, "null qkv or out");
+        RC_REQUIRE(images >= 1 && heads >= 1, RC_ERR_INVALID, "images and heads must be >= 1");
+        const int max_tokens = kind == ATTN_CLS ? ATT_CLS_ROWS : ATT2_ROWS;
+        RC_REQUIRE(tokens >= 1 && tokens <= max_tokens, RC_ERR_INVALID,
+                   "tokens must be 1 .. " + std::to_string(max_tokens) + " for this attention kind");
+        RC_REQUIRE(qsplit == 0 || qsplit == 1 || qsplit == 4, RC_ERR_INVALID, "qsplit must be 0 (the model's choice), 1 or 4");
+        RC_REQUIRE((int64_t)images * heads * 4 <= INT32_MAX, RC_ERR_INVALID, "images x heads too large");
+        if (qsplit == 0 && kind != ATTN_CLS) {
+            int device = 0, ncu = 0;
+            RC_HIP(hipGetDevice(&device));
+            RC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+            qsplit = attention_qsplit(images * heads, ncu);
+        }
+        const float scale = 1.0f / std::sqrt(64.0f);  // head dim 64, as encode()
+        launch_attention(kind, qkv, q_cls, out, images, tokens, heads, scale, qsplit == 0 ? 1 : qsplit, (hipStream_t)stream);
     });
 }

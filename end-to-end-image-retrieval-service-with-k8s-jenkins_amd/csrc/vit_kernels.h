@@ -581,10 +581,11 @@ __global__ __launch_bounds__(192) void gather_cls_kernel(const float *__restrict
 // P·V: 8 lanes per V row, 8 rows per load instruction (see below).
 // q != null: the CLS query rows come compact ([images][H], the last layer's Q computed
 // for the CLS rows only) instead of from qkv.
+constexpr int ATT_CLS_ROWS = 256;  // keys: four per lane, one f32 score each in LDS
 __global__ __launch_bounds__(256) void attention_cls_kernel(const uint16_t *__restrict__ qkv, uint16_t *__restrict__ out,
                                                            int tokens, int heads, int items, float scale_log2e,
                                                            const uint16_t *__restrict__ qc) {
-    constexpr int HD = 64, MAXT = 256;
+    constexpr int HD = 64, MAXT = ATT_CLS_ROWS;
     __shared__ float ps[4][MAXT];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int item = blockIdx.x * 4 + w;

@@ -453,6 +453,21 @@ int rc_model_timing_reset(rc_model *m);
 int rc_gemm_bf16(int epi, int variant, const uint16_t *A, const uint16_t *W, const float *bias, int M, int N, int K,
                  void *out, const float *pos, int tokens, void *stream);
 
+/* Kernel-level entry to the attention kernels (parity tests; inside rc_embed this is the eager
+ * attention of modeling_vit_msn.py:161-186), launched by the launcher the model uses.
+ * qkv [images·tokens][3·heads·64] bf16 with Q | K | V columns as the model lays them out, head
+ * dim 64, scale log2(e)/8 folded into exp2.  out = softmax(Q·Kᵀ/8)·V per (image, head), bf16.
+ * kind 0: full attention as rc_embed launches it (the 197-token instantiation at tokens == 197,
+ * the runtime-token-count one otherwise), out [images·tokens][heads·64]; kind 1: the same with
+ * the runtime-token-count instantiation at any count; kind 2: the CLS query only (the last
+ * layer), out [images][heads·64], the queries from q_cls (compact [images][heads·64]) or, when
+ * q_cls is null, from row 0 of each image in qkv.  qsplit (full kinds): blocks per (image,
+ * head), 1 or 4, or 0 for the model's choice (4 below one item per compute unit).  tokens:
+ * 1 .. 208 (full kinds), 1 .. 256 (kind 2).  Anything else, null qkv / out and images or
+ * heads < 1 are RC_ERR_INVALID before any device call.  Pointers must be 16-byte aligned. */
+int rc_attention_bf16(int kind, const uint16_t *qkv, const uint16_t *q_cls, uint16_t *out, int images, int tokens,
+                      int heads, int qsplit, void *stream);
+
 /* Index-side timing of the dominant search kernel (scan), same conventions. */
 int rc_index_timing(rc_index *h, int enable);
 int rc_index_timing_read(rc_index *h, double *total_ms, int64_t *launches, double *bytes);

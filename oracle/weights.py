@@ -63,12 +63,19 @@ def _std_for(name: str) -> tuple[float, float]:
     return 0.0, 0.02  # biases, cls token, position embeddings
 
 
-def seeded_vit_msn_weights(seed: int = 1907, num_layers: int = LAYERS) -> dict[str, np.ndarray]:
+def seeded_vit_msn_weights(seed: int = 1907, num_layers: int = LAYERS, image_size: int = IMAGE) -> dict[str, np.ndarray]:
+    """``image_size`` below 224 (a multiple of 16): the same tensors with the position embeddings
+    cut to the first ``(image_size / 16)² + 1`` rows, for a model built at that input size."""
     rng = np.random.Generator(np.random.PCG64(seed))
     out = {}
     for name, shape in vit_msn_shapes(num_layers):
         mean, std = _std_for(name)
         out[name] = (rng.standard_normal(shape, dtype=np.float32) * np.float32(std) + np.float32(mean)).astype(np.float32)
+    if image_size != IMAGE:
+        if image_size % PATCH or not 0 < image_size <= IMAGE:
+            raise ValueError(f"image_size must be a multiple of {PATCH} up to {IMAGE}")
+        tokens = (image_size // PATCH) ** 2 + 1
+        out["embeddings.position_embeddings"] = np.ascontiguousarray(out["embeddings.position_embeddings"][:, :tokens])
     return out
 
 

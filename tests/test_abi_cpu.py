@@ -63,6 +63,37 @@ def test_invalid_arguments_rejected_before_any_device_call(lib):
     assert lib.rc_model_create(0, ctypes.byref(cfg), ctypes.byref(m)) == L.RC_ERR_UNSUPPORTED
 
 
+def test_attention_entry_is_exported_and_bound(lib):
+    raw = ctypes.CDLL(import_pkg("_lib").LIB_PATH)
+    assert hasattr(raw, "rc_attention_bf16")
+    assert "rc_attention_bf16" in declared_functions()
+    assert "rc_attention_bf16" in import_pkg("_lib").SIGNATURES
+    assert lib.rc_attention_bf16.argtypes is not None and len(lib.rc_attention_bf16.argtypes) == 9
+
+
+@pytest.mark.parametrize("kind,tokens,qsplit,null_qkv,what", [
+    (0, 0, 0, False, b"tokens"),
+    (0, 209, 0, False, b"tokens"),      # the full kernels hold 13 key tiles of 16
+    (1, 209, 0, False, b"tokens"),
+    (2, 257, 0, False, b"tokens"),      # the CLS kernel's score buffer holds 256
+    (0, 197, 3, False, b"qsplit"),
+    (0, 197, 0, True, b"null"),
+    (3, 197, 0, False, b"kind"),
+])
+def test_attention_entry_refuses_bad_arguments_before_any_device_call(lib, kind, tokens, qsplit, null_qkv, what):
+    """rc_attention_bf16 validates before it touches HIP: RC_ERR_INVALID on a host without a GPU
+    (the pointers are never dereferenced)."""
+    L = import_pkg("_lib")
+    buf = (ctypes.c_uint16 * 16)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    st = lib.rc_attention_bf16(kind, None if null_qkv else p, None, p, 1, tokens, 12, qsplit, None)
+    assert st == L.RC_ERR_INVALID
+    assert what in lib.rc_last_error()
+    assert lib.rc_attention_bf16(0, p, None, p, 0, 197, 12, 0, None) == L.RC_ERR_INVALID  # images < 1
+    assert lib.rc_attention_bf16(0, p, None, p, 1, 197, 0, 0, None) == L.RC_ERR_INVALID   # heads < 1
+    assert lib.rc_attention_bf16(0, p, None, None, 1, 197, 12, 0, None) == L.RC_ERR_INVALID  # null out
+
+
 def test_check_maps_status_to_exceptions(lib):
     L = import_pkg("_lib")
     h = ctypes.c_void_p()
