@@ -27,8 +27,8 @@ RC_ERR_STATE = 5
 
 RC_F32, RC_F16, RC_BF16, RC_F8 = 0, 1, 2, 3
 RC_TOPK_MAX = 256
-RC_SEARCH_AUTO, RC_SEARCH_SCAN, RC_SEARCH_MFMA = 0, 1, 2
-SEARCH_MODES = {"auto": RC_SEARCH_AUTO, "scan": RC_SEARCH_SCAN, "mfma": RC_SEARCH_MFMA}
+RC_SEARCH_AUTO, RC_SEARCH_SCAN, RC_SEARCH_MFMA, RC_SEARCH_MFMA_MASKED = 0, 1, 2, 3
+SEARCH_MODES = {"auto": RC_SEARCH_AUTO, "scan": RC_SEARCH_SCAN, "mfma": RC_SEARCH_MFMA, "mfma_masked": RC_SEARCH_MFMA_MASKED}
 DTYPES = {"float32": RC_F32, "f32": RC_F32, "float16": RC_F16, "f16": RC_F16, "bfloat16": RC_BF16, "bf16": RC_BF16,
           "float8_e4m3fn": RC_F8, "f8": RC_F8}
 DTYPE_BYTES = {RC_F32: 4, RC_F16: 2, RC_BF16: 2, RC_F8: 1}

@@ -1,6 +1,7 @@
 // filter_gemm_body.inc — the body of filter_gemm_kernel<T> and filter_gemm_metric_kernel<T>
 // (search_mfma.hip), included inside each kernel's braces.  In scope: T, the kernel argument
-// `FilterArgs a`, `constexpr bool METRIC` and (METRIC) `FilterMetric fm`.  Text inclusion, not a
+// `FilterArgs a`, `constexpr bool METRIC` and (METRIC) `FilterMetric fm`, `constexpr bool MASKED` and
+// (MASKED) `const uint32_t *mask` (filter_gemm_masked_kernel<T, METRIC>).  Text inclusion, not a
 // device function: as a function taking the arguments by reference the cosine kernel's registers
 // and schedule change; this way it compiles to the instructions it had as the only copy.  (A
 // `bool METRIC = false` template parameter on the kernel itself would read better, but the
@@ -68,6 +69,10 @@
                     for (int a3 = 0; a3 < 2; ++a3) acc[a0][a1][a2][a3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     };
     zero_acc();
+    // MASKED: the bitmap words of this wave's 64 rows of the current row tile (wave-uniform: scalar
+    // registers), loaded one tile ahead of the epilogue that reads them
+    [[maybe_unused]] uint32_t mw[2];
+    if constexpr (MASKED) load_mask_words(mask, a.r_begin + rt0 * SB_TILE + wc * 64, a.r_end, mw);
 
     stage4(0, 0, 0);
     stage4(0, 0, 4);
@@ -123,61 +128,78 @@
             // ---- epilogue of row tile rt: lane holds S[q][r .. r+3] for 8 q x 4 r-groups
             const int64_t rt = rt0 + step / nkt;
             const int64_t rbase = a.r_begin + rt * SB_TILE + wc * 64 + 4 * g;
-            if constexpr (METRIC) {  // u >= thr[q] (the metric epilogue's comment in search_mfma.hip)
-                const int64_t tile_row = a.r_begin + rt * SB_TILE;  // wave-uniform
-                const float *tn = fm.norms + tile_row;
-                const int left = (int)min<int64_t>(a.r_end - tile_row, (int64_t)SB_TILE);
-                f32x4_t nv[2][2];
+            // MASKED: none of the wave's 64 rows is eligible: no epilogue (wave-uniform)
+            if (!MASKED || (mw[0] | mw[1]) != 0u) {
+                if constexpr (METRIC) {  // u >= thr[q] (the metric epilogue's comment in search_mfma.hip)
+                    const int64_t tile_row = a.r_begin + rt * SB_TILE;  // wave-uniform
+                    const float *tn = fm.norms + tile_row;
+                    const int left = (int)min<int64_t>(a.r_end - tile_row, (int64_t)SB_TILE);
+                    f32x4_t nv[2][2];
 #pragma unroll
-                for (int nq = 0; nq < 2; ++nq)
+                    for (int nq = 0; nq < 2; ++nq)
 #pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) nv[nq][ni] = load_norms4(tn, wc * 64 + 4 * g + nq * 32 + ni * 16, left);
-                // in place: the accumulators become u, and the test below (its maximum as the
-                // wave-uniform early-out, then per row) is the cosine epilogue's own code on them —
-                // no second copy of the values in registers
+                        for (int ni = 0; ni < 2; ++ni) nv[nq][ni] = load_norms4(tn, wc * 64 + 4 * g + nq * 32 + ni * 16, left);
+                    // in place: the accumulators become u, and the test below (its maximum as the
+                    // wave-uniform early-out, then per row) is the cosine epilogue's own code on them —
+                    // no second copy of the values in registers
 #pragma unroll
-                for (int mq = 0; mq < 2; ++mq)
+                    for (int mq = 0; mq < 2; ++mq)
 #pragma unroll
-                    for (int mi = 0; mi < 4; ++mi) {
-                        const int q = qb * SB_TILE + grp * 128 + mq * 64 + mi * 16 + li;
-                        const f32x4_t k4 = *reinterpret_cast<const f32x4_t *>(fm.mcoef + 4 * q);
+                        for (int mi = 0; mi < 4; ++mi) {
+                            const int q = qb * SB_TILE + grp * 128 + mq * 64 + mi * 16 + li;
+                            const f32x4_t k4 = *reinterpret_cast<const f32x4_t *>(fm.mcoef + 4 * q);
 #pragma unroll
-                        for (int nq = 0; nq < 2; ++nq)
+                            for (int nq = 0; nq < 2; ++nq)
 #pragma unroll
-                            for (int ni = 0; ni < 2; ++ni)
+                                for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-                                for (int j = 0; j < 4; ++j)
-                                    acc[mq][nq][mi][ni][j] = metric_upper(k4, acc[mq][nq][mi][ni][j], nv[nq][ni][j]);
-                        if (mi % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // at most 2 queries' constants (8 registers) in flight
-                    }
-            }
-#pragma unroll
-            for (int mq = 0; mq < 2; ++mq)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi) {
-                    const float t = thr[mq][mi];
-                    float m = -INFINITY;
+                                    for (int j = 0; j < 4; ++j)
+                                        acc[mq][nq][mi][ni][j] = metric_upper(k4, acc[mq][nq][mi][ni][j], nv[nq][ni][j]);
+                            if (mi % 2 == 1) __builtin_amdgcn_sched_barrier(0);  // at most 2 queries' constants (8 registers) in flight
+                        }
+                }
+                if constexpr (MASKED) {  // ineligible rows leave the test: mask_ineligible4's comment
 #pragma unroll
                     for (int nq = 0; nq < 2; ++nq)
 #pragma unroll
                         for (int ni = 0; ni < 2; ++ni) {
-                            const f32x4_t v = acc[mq][nq][mi][ni];
-                            m = fmaxf(m, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+                            const uint32_t e = mw[nq] >> (ni * 16 + 4 * g);  // rows wc·64 + nq·32 + ni·16 + 4g + j: bit j
+#pragma unroll
+                            for (int mq = 0; mq < 2; ++mq)
+#pragma unroll
+                                for (int mi = 0; mi < 4; ++mi) acc[mq][nq][mi][ni] = mask_ineligible4(acc[mq][nq][mi][ni], e);
                         }
-                    if (__ballot(m >= t) == 0) continue;  // wave-uniform: the common case
-                    if (m >= t) {
-                        const int q = qb * SB_TILE + grp * 128 + mq * 64 + mi * 16 + li;
+                }
+#pragma unroll
+                for (int mq = 0; mq < 2; ++mq)
+#pragma unroll
+                    for (int mi = 0; mi < 4; ++mi) {
+                        const float t = thr[mq][mi];
+                        float m = -INFINITY;
 #pragma unroll
                         for (int nq = 0; nq < 2; ++nq)
 #pragma unroll
-                            for (int ni = 0; ni < 2; ++ni)
+                            for (int ni = 0; ni < 2; ++ni) {
+                                const f32x4_t v = acc[mq][nq][mi][ni];
+                                m = fmaxf(m, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+                            }
+                        if (__ballot(m >= t) == 0) continue;  // wave-uniform: the common case
+                        if (m >= t) {
+                            const int q = qb * SB_TILE + grp * 128 + mq * 64 + mi * 16 + li;
 #pragma unroll
-                                for (int j = 0; j < 4; ++j) {
-                                    const int64_t row = rbase + nq * 32 + ni * 16 + j;
-                                    if (acc[mq][nq][mi][ni][j] >= t && row < a.r_end) append_candidate(a, q, row);
-                                }
+                            for (int nq = 0; nq < 2; ++nq)
+#pragma unroll
+                                for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j) {
+                                        const int64_t row = rbase + nq * 32 + ni * 16 + j;
+                                        if (acc[mq][nq][mi][ni][j] >= t && row < a.r_end) append_candidate(a, q, row);
+                                    }
+                        }
                     }
-                }
+            }
+            if constexpr (MASKED)
+                load_mask_words(mask, a.r_begin + min(rt + 1, rt1 - 1) * SB_TILE + wc * 64, a.r_end, mw);
             zero_acc();
         }
     }

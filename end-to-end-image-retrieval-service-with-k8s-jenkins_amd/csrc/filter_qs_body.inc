@@ -1,7 +1,8 @@
 // filter_qs_body.inc — the body of filter_qs_kernel<T, NKT, ABL> and filter_qs_metric_kernel<T, NKT>
 // (search_mfma.hip), included inside each kernel's braces.  In scope: T, NKT, ABL, the kernel
-// argument `FilterArgs a`, `constexpr bool METRIC` and (METRIC) `FilterMetric fm`.  Text inclusion,
-// not a device function, for the reason given in filter_gemm_body.inc.
+// argument `FilterArgs a`, `constexpr bool METRIC` and (METRIC) `FilterMetric fm`, `constexpr bool
+// MASKED` and (MASKED) `const uint32_t *mask` (filter_qs_masked_kernel<T, NKT, METRIC>).  Text
+// inclusion, not a device function, for the reason given in filter_gemm_body.inc.
     constexpr int QS_WAVES = 16 / QS_QT;
     constexpr int RF = QS_RT / 16;
     using Op = MfmaOp<T>;
@@ -88,6 +89,10 @@
 
     f32x4_t acc[RF][QS_QT];
     for (int tile = 0; tile < ntiles; ++tile) {
+        // MASKED: the tile's bitmap words (wave-uniform: scalar registers, none of the lane's own),
+        // loaded here so that their latency runs under the tile's K loop
+        [[maybe_unused]] uint32_t mw[QS_RT / 32];
+        if constexpr (MASKED) load_mask_words(mask, a.r_begin + (rt0 + tile) * QS_RT, a.r_end, mw);
 #pragma unroll
         for (int rf = 0; rf < RF; ++rf)
 #pragma unroll
@@ -145,6 +150,12 @@
             }
         }
         // ---- epilogue of row tile rt0 + tile: candidates s' >= thr[q]
+        if constexpr (MASKED) {  // no eligible row in the tile: no epilogue (wave-uniform)
+            uint32_t any = 0u;
+#pragma unroll
+            for (int i = 0; i < QS_RT / 32; ++i) any |= mw[i];
+            if (any == 0u) continue;
+        }
         [[maybe_unused]] int lq = li, gq = g;  // METRIC: li and g again, from v_mbcnt
         if constexpr (METRIC) {
             int ln;
@@ -153,6 +164,12 @@
             gq = ln >> 4;
         }
         const int64_t rbase = a.r_begin + (rt0 + tile) * QS_RT + 4 * gq;
+        // MASKED: ineligible rows of acc[rf][.] leave the test below (mask_ineligible4's comment)
+        [[maybe_unused]] auto mask_rows = [&](int rf) __attribute__((always_inline)) {
+            const uint32_t e = mw[rf >> 1] >> ((rf & 1) * 16 + 4 * gq);  // rows 16 rf + 4 g + j: bit j
+#pragma unroll
+            for (int qt = 0; qt < QS_QT; ++qt) acc[rf][qt] = mask_ineligible4(acc[rf][qt], e);
+        };
         if constexpr (ABL & 8) {  // diagnostics: no epilogue (accumulators kept live)
 #pragma unroll
             for (int rf = 0; rf < RF; ++rf)
@@ -180,8 +197,13 @@
                 for (int qt = 0; qt < QS_QT; ++qt)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) acc[rf][qt][j] = metric_upper(k4[qt], acc[rf][qt][j], nv[j]);
+                if constexpr (MASKED) mask_rows(rf);  // here, under the same barriers: the NKT 8 form has no register for more
                 if (rf % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // at most four norm loads (16 registers) in flight
             }
+        }
+        if constexpr (MASKED && !METRIC) {
+#pragma unroll
+            for (int rf = 0; rf < RF; ++rf) mask_rows(rf);
         }
 #pragma unroll
         for (int qt = 0; qt < QS_QT; ++qt) {

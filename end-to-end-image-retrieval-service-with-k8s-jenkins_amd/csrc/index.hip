@@ -567,9 +567,10 @@ int batch_query_bytes(const rc_index *h) { return h->dtype == RC_F8 ? 2 : (int)d
 // path's normalised queries (wave_inv_norm / RC_UNIT_ELEM, the scan's own normalisation),
 // and merge_partials_kernel over the flagged queries' partial lists.
 // With a mask the rescoring drops ineligible candidates (search_mfma.hip) and the
-// fallback is the masked scan; the merge is the same.
+// fallback is the masked scan; the merge is the same.  mask_filter (RC_SEARCH_MFMA_MASKED): the
+// filter kernels apply the mask as well, in their MASKED forms.
 void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
-                          float *scores, int64_t *out_rows, hipStream_t s) {
+                          bool mask_filter, float *scores, int64_t *out_rows, hipStream_t s) {
     h->bws.ensure(nq, k, h->ld, batch_query_bytes(h));
     BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, n_rows, h->row_base, h->row_stride, queries, nq, k, scores, out_rows};
     p.f8_filter = h->filter == RC_FILTER_F8;
@@ -577,6 +578,7 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
     p.rsx = h->rsx;
     p.rex = h->rex;
     p.mask = mask;
+    p.mask_filter = mask_filter && mask != nullptr;
     p.metric = h->metric;  // non-cosine (RC_FILTER_METRIC): the filter and rescore kernels' metric forms
     p.norms = h->norms;
     if (h->gtimer.enabled) h->gtimer.create();
@@ -1045,8 +1047,12 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
         RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
         RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
         RC_REQUIRE(n_rows >= 0 && n_rows <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
-        RC_REQUIRE(mode == RC_SEARCH_AUTO || mode == RC_SEARCH_SCAN || mode == RC_SEARCH_MFMA, RC_ERR_INVALID,
-                   "unknown search mode");
+        RC_REQUIRE(mode == RC_SEARCH_AUTO || mode == RC_SEARCH_SCAN || mode == RC_SEARCH_MFMA || mode == RC_SEARCH_MFMA_MASKED,
+                   RC_ERR_INVALID, "unknown search mode");
+        // RC_SEARCH_MFMA_MASKED is RC_SEARCH_MFMA (refused where it is, with its errors; the same path
+        // without a mask) whose filter kernels read the mask too
+        const bool mask_filter = mode == RC_SEARCH_MFMA_MASKED;
+        if (mask_filter) mode = RC_SEARCH_MFMA;
         if (nq == 0) return;
         RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
         std::lock_guard<std::mutex> lk(h->mu);
@@ -1084,7 +1090,7 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
             scan_search(h, queries, nq, n_rows, k, mask, scores, out_rows, s);
             return;
         }
-        batched_search_exact(h, queries, nq, n_rows, k, mask, scores, out_rows, s);
+        batched_search_exact(h, queries, nq, n_rows, k, mask, mask_filter, scores, out_rows, s);
     });
 }
 

@@ -405,6 +405,8 @@ struct BatchPlan {
     const float *rex = nullptr;     // [cap_pad] ||x̂ - x̃||₂ (rounded up), at i8_slot(row)
     // row-eligibility bitmap over the local rows (ScanArgs::mask), or null: applied in rescore_kernel
     const uint32_t *mask = nullptr;
+    // RC_SEARCH_MFMA_MASKED (mask != null): the filter kernels' MASKED forms apply the bitmap too
+    bool mask_filter = false;
     // float8 index with rc_index_set_filter(RC_FILTER_F8): the filter GEMM reads the stored e4m3 rows
     bool f8_filter = false;
     // RC_FILTER_METRIC under a non-cosine metric: the native filter kernels' metric forms, which

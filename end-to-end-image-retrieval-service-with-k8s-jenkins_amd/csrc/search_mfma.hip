@@ -141,6 +141,15 @@ struct FilterArgs {
     const float *rsx = nullptr, *rex = nullptr, *sq = nullptr, *aq = nullptr;
 };
 
+// The int8 and float8 kernels take MASKED as a template parameter; their MASKED forms get the bitmap
+// beside the arguments, and the unmasked forms keep the kernel arguments they had.
+struct FilterArgsMasked {
+    FilterArgs a;
+    const uint32_t *mask;  // [ceil(r_end / 32)], over the local rows (BatchPlan::mask)
+};
+__device__ __forceinline__ const FilterArgs &filter_args(const FilterArgs &a) { return a; }
+__device__ __forceinline__ const FilterArgs &filter_args(const FilterArgsMasked &m) { return m.a; }
+
 // Block → (query block, row chunk), for tiles of RT rows: blocks b and b+8 share an XCD; the nqb
 // blocks of one chunk are consecutive on one XCD, so each row tile is read from HBM once and
 // served to the other query blocks from that XCD's L2.  The block's row tiles are [rt0, rt1)
@@ -163,6 +172,56 @@ struct FilterBlock {
 __device__ __forceinline__ void append_candidate(const FilterArgs &a, int q, int64_t row) {
     const uint32_t pos = atomicAdd(&a.cnt[q], 1u);
     if ((int)pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = (uint32_t)row;
+}
+
+// -------------------------------------- MASKED epilogues (RC_SEARCH_MFMA_MASKED) --
+// Every filter kernel has a MASKED form (a compile-time form, as scan_rows_q's and rescore_kernel's:
+// the unmasked kernels keep their instructions).  It reads the row-eligibility bitmap over the LOCAL
+// rows that rescore_kernel<.., MASKED> reads (bit r & 31 of word r >> 5) and appends (q, row) iff
+// the kernel's own test passes AND the row's bit is set.
+// Why it stays exact: the unmasked argument (the header's, the metric epilogue's, the int8 and float8
+// bounds) restricted to the eligible rows.  The result is the top-k of the eligible rows.  thr[q] comes
+// from rescore_kernel, which under a mask merges eligible rows only: it is the k-th best exact score
+// of the ELIGIBLE rows seen so far (minus eps[q]; -inf while fewer than k were seen), a lower bound of
+// the final k-th best eligible score, and it only rises.  An eligible row of the final top-k therefore
+// passes the kernel's test at its stage as before, and its bit is set: it is appended.  Ineligible
+// rows were never part of the result; leaving them out only shortens the lists, so a stage collects
+// ≈ k·(g - 1) candidates whatever the eligible share, where the unmasked filter under a mask collects
+// 1 / share times as many ("Masked search").  A clustered mask can still overflow a
+// stage: the flagged queries take the masked scan on the device, as before.
+// A row tile starts at a multiple of 64 rows, so its bits are whole words at a wave-uniform address:
+// scalar loads into scalar registers, issued a tile (or a K loop) ahead of the epilogue that reads
+// them.  A tile without an eligible row skips its epilogue on a wave-uniform branch (its loads and
+// MFMAs stay: they are one flattened pipeline).
+//
+// NW words of the 32·NW rows from `first_row` (a multiple of 64).  The bitmap holds ceil(r_end / 32)
+// words and the last tile reaches past r_end: the index is clamped to the last word (a read past the
+// bitmap is a fault) and a word wholly past r_end reads as 0.  Bits at or past r_end inside the last
+// word may be set: the epilogues keep their row < r_end test.
+template <int NW>
+__device__ __forceinline__ void load_mask_words(const uint32_t *__restrict__ mask, int64_t first_row, int64_t r_end,
+                                                uint32_t (&w)[NW]) {
+    // Through the constant address space (the bitmap does not change while a search runs): only
+    // there does the compiler load a uniform address with the scalar unit.  As a global load the
+    // words were vector registers held across the K loop, and the NKT 8 forms spilled.
+    typedef const __attribute__((address_space(4))) uint32_t *const_words;
+    const const_words cm = (const_words)mask;
+    const int64_t w0 = first_row >> 5, wl = (r_end - 1) >> 5;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const uint32_t v = cm[min(w0 + i, wl)];
+        w[i] = w0 + i <= wl ? v : 0u;
+    }
+}
+// A lane's four consecutive rows of one f32 accumulator, their eligibility in bits 0-3 of e: the
+// ineligible ones become NaN ahead of the epilogue's maximum, so both levels of its early-out see
+// eligible rows only.  NaN and not -inf: while thr[q] is still -inf, -inf >= thr holds and the row
+// would be appended; NaN fails every >=, and fmaxf returns its other operand, so the maximum runs
+// over the eligible rows (-inf when the lane has none).
+__device__ __forceinline__ f32x4_t mask_ineligible4(f32x4_t v, uint32_t e) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (e >> j) & 1u ? v[j] : __builtin_nanf("");
+    return v;
 }
 
 // ---------------------------------------- metric epilogue (RC_FILTER_METRIC) --
@@ -236,13 +295,21 @@ __device__ __forceinline__ float metric_upper(const f32x4_t &k4, float sp, float
 // of the text, and the cosine kernel keeps the instructions it had.
 template <typename T>
 __global__ __launch_bounds__(512, 1) void filter_gemm_kernel(FilterArgs a) {
-    constexpr bool METRIC = false;
+    constexpr bool METRIC = false, MASKED = false;
     [[maybe_unused]] const FilterMetric fm{};
+    [[maybe_unused]] const uint32_t *const mask = nullptr;
 #include "filter_gemm_body.inc"
 }
 template <typename T>
 __global__ __launch_bounds__(512, 1) void filter_gemm_metric_kernel(FilterArgs a, FilterMetric fm) {
-    constexpr bool METRIC = true;
+    constexpr bool METRIC = true, MASKED = false;
+    [[maybe_unused]] const uint32_t *const mask = nullptr;
+#include "filter_gemm_body.inc"
+}
+// the MASKED form of both (new kernels, so a template parameter costs no existing symbol; cosine: fm unused)
+template <typename T, bool METRIC>
+__global__ __launch_bounds__(512, 1) void filter_gemm_masked_kernel(FilterArgs a, FilterMetric fm, const uint32_t *mask) {
+    constexpr bool MASKED = true;
 #include "filter_gemm_body.inc"
 }
 
@@ -275,13 +342,22 @@ constexpr int QS_QT = 2, QS_RT = 128, QS_NS = 8;  // queries/16 per wave, rows p
 // tile's norms itself.
 template <typename T, int NKT, int ABL = 0>  // 256 queries per block
 __global__ __launch_bounds__(512, 1) void filter_qs_kernel(FilterArgs a) {
-    constexpr bool METRIC = false;
+    constexpr bool METRIC = false, MASKED = false;
     [[maybe_unused]] const FilterMetric fm{};
+    [[maybe_unused]] const uint32_t *const mask = nullptr;
 #include "filter_qs_body.inc"
 }
 template <typename T, int NKT>
 __global__ __launch_bounds__(512, 1) void filter_qs_metric_kernel(FilterArgs a, FilterMetric fm) {
-    constexpr bool METRIC = true;
+    constexpr bool METRIC = true, MASKED = false;
+    constexpr int ABL = 0;
+    [[maybe_unused]] const uint32_t *const mask = nullptr;
+#include "filter_qs_body.inc"
+}
+// the MASKED form of both (as filter_gemm_masked_kernel)
+template <typename T, int NKT, bool METRIC>
+__global__ __launch_bounds__(512, 1) void filter_qs_masked_kernel(FilterArgs a, FilterMetric fm, const uint32_t *mask) {
+    constexpr bool MASKED = true;
     constexpr int ABL = 0;
 #include "filter_qs_body.inc"
 }
@@ -365,9 +441,16 @@ __device__ __forceinline__ void lds_write_u32(uint32_t *p, uint32_t v) {
 }
 
 // AUX: cache-policy bits of the row DMA (0; 2 = nontemporal: diagnostic builds' A/B)
-template <int NKT, int RT, int AUX = 0>
-__global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
+// MASKED (the MASKED epilogues' comment above): here a lane holds ONE row per accumulator, row
+// 16·rf + li of the tile, so its eligibility is one bit per rf (em).  The accumulators are integers:
+// an ineligible row's become INT_MIN ahead of the gate's maximum, and since a huge negative value
+// still passes v >= thr while thr is -inf, the append tests the row's bit as well.
+template <int NKT, int RT, int AUX = 0, bool MASKED = false>
+__global__ __launch_bounds__(512, 1) void filter_i8_kernel(std::conditional_t<MASKED, FilterArgsMasked, FilterArgs> am) {
     typedef int i32x4_t __attribute__((ext_vector_type(4)));
+    const FilterArgs &a = filter_args(am);
+    [[maybe_unused]] const uint32_t *mask = nullptr;
+    if constexpr (MASKED) mask = am.mask;
     constexpr int QT = QS_QT, WAVES = 16 / QS_QT, RF = RT / 16, RH = RF / 4;
     constexpr int STEP_BYTES = RT * 128;
     constexpr int SPS = 2, SXL = 2 * RH;
@@ -477,6 +560,8 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
 
     i32x4_t acc[RF][QT];
     for (int tile = 0; tile < ntiles; ++tile) {
+        [[maybe_unused]] uint32_t mw[RT / 32];  // MASKED: the tile's bitmap words, loaded under its K loop
+        if constexpr (MASKED) load_mask_words(mask, row0 + (int64_t)tile * RT, a.r_end, mw);
 #pragma unroll
         for (int rf = 0; rf < RF; ++rf)
 #pragma unroll
@@ -535,6 +620,25 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
             }
         }
         // ---- epilogue: keep (q, row) iff sq·(sx·D) + ex·aq >= thr[q]
+        [[maybe_unused]] uint32_t em = 0u;  // MASKED: bit rf = row 16 rf + li of the tile is eligible
+        if constexpr (MASKED) {
+            uint32_t any = 0u;
+#pragma unroll
+            for (int i = 0; i < RT / 32; ++i) any |= mw[i];
+            if (any == 0u) {  // no eligible row in the tile: no epilogue (wave-uniform)
+                load_scales(min(tile + 1, ntiles - 1));  // as at the tile's end: the same wait counts on every path
+                continue;
+            }
+#pragma unroll
+            for (int rf = 0; rf < RF; ++rf) {
+                const bool el = ((mw[rf >> 1] >> ((rf & 1) * 16 + li)) & 1u) != 0u;
+                em |= (uint32_t)el << rf;
+#pragma unroll
+                for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[rf][qt][j] = el ? acc[rf][qt][j] : INT_MIN;
+            }
+        }
         float sx[RF], ex[RF];
 #pragma unroll
         for (int rf = 0; rf < RF; ++rf) {
@@ -566,6 +670,7 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
                 hq[qt][j] = fmaf(exm, aq[qt][j], sq[qt][j] * m) >= thr[qt][j];
                 hit |= hq[qt][j];
             }
+        if constexpr (MASKED) hit = hit && em != 0u;
         if (__ballot(hit) != 0 && hit) {
             const int64_t rbase = row0 + (int64_t)tile * RT + li;
 #pragma unroll
@@ -580,7 +685,7 @@ __global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterArgs a) {
                     for (int rf = 0; rf < RF; ++rf) {
                         const int64_t row = rbase + rf * 16;
                         const float v = fmaf(ex[rf], aq[qt][j], sq[qt][j] * (sx[rf] * (float)acc[rf][qt][j]));
-                        if (v >= thr[qt][j] && row < a.r_end) {
+                        if (v >= thr[qt][j] && (!MASKED || ((em >> rf) & 1u) != 0u) && row < a.r_end) {
                             const int ql = q - qb * SB_TILE;
                             const uint32_t p = lds_add_rtn_u32(&lcnt[ql], 1u);
                             if (p < (uint32_t)I8_SL) {
@@ -677,6 +782,12 @@ struct FilterF8Args {
     float *dump;          // DUMP: s' of queries [0, dump_nq) x rows [r_begin, r_end), [dump_nq][r_end - r_begin]
     int dump_nq;
 };
+struct FilterF8ArgsMasked {  // the MASKED form's (as FilterArgsMasked)
+    FilterF8Args f;
+    const uint32_t *mask;
+};
+__device__ __forceinline__ const FilterF8Args &filter_args(const FilterF8Args &f) { return f; }
+__device__ __forceinline__ const FilterF8Args &filter_args(const FilterF8ArgsMasked &m) { return m.f; }
 
 // Query-stationary, as filter_qs_kernel / filter_i8_kernel: same FilterBlock mapping, 8 waves, the
 // same LDS ring of RT rows x 128 B per step filled by buffer-descriptor DMA, every ring step issued
@@ -714,8 +825,14 @@ __device__ __forceinline__ f32x4_t mfma_f8_scaled(i32x8_t row, i32x8_t query, f3
                                                             qscale * 0x01010101);
 }
 
-template <int NKT, int RT, int TERMS, int QT, bool DUMP = false>
-__global__ __launch_bounds__(512, 1) void filter_f8_kernel(FilterF8Args fa) {
+// MASKED (the MASKED epilogues' comment above): rows and accumulators as filter_qs_kernel's, so the
+// same 4-bit fields.  No MASKED DUMP form.
+template <int NKT, int RT, int TERMS, int QT, bool DUMP = false, bool MASKED = false>
+__global__ __launch_bounds__(512, 1) void filter_f8_kernel(std::conditional_t<MASKED, FilterF8ArgsMasked, FilterF8Args> fam) {
+    static_assert(!(DUMP && MASKED), "the DUMP form has no mask");
+    const FilterF8Args &fa = filter_args(fam);
+    [[maybe_unused]] const uint32_t *mask = nullptr;
+    if constexpr (MASKED) mask = fam.mask;
     constexpr int WAVES = 8, QPB = WAVES * 16 * QT, RF = RT / 16, RH = RF / 4;
     constexpr int STEP_BYTES = RT * 128;
     constexpr int NS = QS_NS * 128 / RT;  // ring steps: 128 KB of rows either way
@@ -796,6 +913,8 @@ __global__ __launch_bounds__(512, 1) void filter_f8_kernel(FilterF8Args fa) {
 
     f32x4_t acc[RF][QT];
     for (int tile = 0; tile < ntiles; ++tile) {
+        [[maybe_unused]] uint32_t mw[RT / 32];  // MASKED: the tile's bitmap words, loaded under its K loop
+        if constexpr (MASKED) load_mask_words(mask, row0 + (int64_t)tile * RT, a.r_end, mw);
 #pragma unroll
         for (int rf = 0; rf < RF; ++rf)
 #pragma unroll
@@ -870,6 +989,18 @@ __global__ __launch_bounds__(512, 1) void filter_f8_kernel(FilterF8Args fa) {
             continue;
         }
         // ---- epilogue of the tile: candidates s' >= thr[q]
+        if constexpr (MASKED) {
+            uint32_t any = 0u;
+#pragma unroll
+            for (int i = 0; i < RT / 32; ++i) any |= mw[i];
+            if (any == 0u) continue;  // no eligible row in the tile: no epilogue (wave-uniform)
+#pragma unroll
+            for (int rf = 0; rf < RF; ++rf) {
+                const uint32_t e = mw[rf >> 1] >> ((rf & 1) * 16 + 4 * g);  // rows 16 rf + 4 g + j: bit j
+#pragma unroll
+                for (int qt = 0; qt < QT; ++qt) acc[rf][qt] = mask_ineligible4(acc[rf][qt], e);
+            }
+        }
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const float th = thr[qt];
@@ -989,6 +1120,25 @@ void run_batched(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *ti
         const int64_t tpc = (rt_total + nchunk - 1) / nchunk;
         FilterArgs fa{p.rows, ws.qh, p.ld, (int)(p.ld / 64), c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap};
         const int nkt = (int)(p.ld / 64);
+        if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED: the MASKED forms (cosine: fm is not read)
+            const FilterMetric fm{p.norms, ws.mcoef};
+            auto launch = [&](auto m) {
+                constexpr bool M = decltype(m)::value;
+                if (nkt == 2 || nkt == 4 || nkt == 8) {
+                    fa.tiles_per_chunk = ((c1 - c0 + QS_RT - 1) / QS_RT + nchunk - 1) / nchunk;
+                    const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
+                    if (nkt == 8) hipLaunchKernelGGL((filter_qs_masked_kernel<T, 8, M>), gr, bl, 0, s, fa, fm, p.mask);
+                    else if (nkt == 4) hipLaunchKernelGGL((filter_qs_masked_kernel<T, 4, M>), gr, bl, 0, s, fa, fm, p.mask);
+                    else hipLaunchKernelGGL((filter_qs_masked_kernel<T, 2, M>), gr, bl, 0, s, fa, fm, p.mask);
+                } else {
+                    hipLaunchKernelGGL((filter_gemm_masked_kernel<T, M>), dim3((unsigned)(nchunk * nqb)), dim3(512), 0, s, fa, fm,
+                                       p.mask);
+                }
+            };
+            if (metric) launch(std::true_type{});
+            else launch(std::false_type{});
+            return;
+        }
         if (metric) {
             const FilterMetric fm{p.norms, ws.mcoef};
             if (nkt == 2 || nkt == 4 || nkt == 8) {
@@ -1036,6 +1186,13 @@ void run_batched_i8(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
         fa.sq = ws.sq;
         fa.aq = ws.aq;
         const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
+        if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED
+            const FilterArgsMasked fm{fa, p.mask};
+            if (nkt == 4) hipLaunchKernelGGL((filter_i8_kernel<4, 128, 0, true>), gr, bl, 0, s, fm);
+            else if (nkt == 6) hipLaunchKernelGGL((filter_i8_kernel<6, 64, 0, true>), gr, bl, 0, s, fm);
+            else hipLaunchKernelGGL((filter_i8_kernel<2, 128, 0, true>), gr, bl, 0, s, fm);
+            return;
+        }
 #if defined(RC_GEMM_ABLATION)
         if (nkt == 4 && g_diag_filter_aux == 2) {
             hipLaunchKernelGGL((filter_i8_kernel<4, 128, 2>), gr, bl, 0, s, fa);
@@ -1065,6 +1222,15 @@ void launch_filter_f8(const BatchPlan &p, const BatchWs &ws, int nq_pad, int64_t
     FilterF8Args fa{FilterArgs{p.rows, ws.qh, p.ld, nkt, c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
                     (const uint8_t *)ws.qh + (int64_t)nq_pad * p.ld, dump, p.nq};
     const dim3 gr((unsigned)(nchunk * nqb)), bl(512);
+    if constexpr (!DUMP) {
+        if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED
+            const FilterF8ArgsMasked fm{fa, p.mask};
+            if (nkt == 4) hipLaunchKernelGGL((filter_f8_kernel<4, 64, F8_TERMS, QS_QT, false, true>), gr, bl, 0, s, fm);
+            else if (nkt == 6) hipLaunchKernelGGL((filter_f8_kernel<6, 64, F8_TERMS, 1, false, true>), gr, bl, 0, s, fm);
+            else hipLaunchKernelGGL((filter_f8_kernel<2, 128, F8_TERMS, QS_QT, false, true>), gr, bl, 0, s, fm);
+            return;
+        }
+    }
     if (nkt == 4) hipLaunchKernelGGL((filter_f8_kernel<4, 64, F8_TERMS, QS_QT, DUMP>), gr, bl, 0, s, fa);
     else if (nkt == 6) hipLaunchKernelGGL((filter_f8_kernel<6, 64, F8_TERMS, 1, DUMP>), gr, bl, 0, s, fa);
     else hipLaunchKernelGGL((filter_f8_kernel<2, 128, F8_TERMS, QS_QT, DUMP>), gr, bl, 0, s, fa);

@@ -35,6 +35,35 @@ from ._lib import check, ptr, stream_ptr
 # share 0.5 with no fallback, level with it at 0.1 (every query falls back) and 4.8x slower at
 # 0.01.  0.5 is the lowest measured share at which MFMA wins without falling back.
 MASKED_MFMA_MIN_SHARE = 0.5
+# Below that share "auto" asks for "mfma_masked" (the mask inside the filter GEMM: candidates per
+# stage no longer grow with 1 / share) inside the box that was measured, and scans outside it.
+# Source: tools/masked_search_micro.py --part maskfilter on an MI355X (records appended to
+# profiles/masked_search/masked_search_micro.jsonl; DESIGN.md, "Masked search"): "mfma_masked"
+# against the masked scan, f16 x 512, uniformly random masks at shares 0.25 / 0.1 / 0.01 / 0.001,
+# top-10 and top-100, 16 / 32 / 64 / 256 queries over 65,536 and 1M rows, 32 / 256 queries over 16M.
+# The bar is 2x, not 1x: the host does not know how clustered a mask is, a clustered mask makes the
+# scan up to 2x cheaper at equal share, and it saves the filter GEMM nothing.
+#   MASK_FILTER_MIN_QUERIES  up to 1M rows every measured cell from 32 queries on is at least 3.16x
+#       ahead (the lowest: 32 x top-100 at share 0.25 over 65,536 rows).  At 16 queries the cells lie
+#       between 1.98x and 4.08x, one under the bar and four within 10 % of it: 16-31 queries scan.
+#   MASK_FILTER_MIN_SHARE    the most selective share measured; below it nothing was measured.
+#   MASK_FILTER_MIN_ROWS / MASK_FILTER_MAX_ROWS  the smallest and largest measured rows per shard
+#       (the smallest is also the unmasked "auto" bound); larger shards scan until they are measured.
+#   MASK_FILTER_LARGE_ROWS, MASK_FILTER_LARGE_MIN_QUERIES, MASK_FILTER_LARGE_MIN_SHARE  the filter
+#       GEMM reads every row whatever the share, while the masked scan skips 8-row groups without an
+#       eligible row, so over many rows a very selective mask favours the scan: over 16M rows 32
+#       queries are 6.5x-17x ahead at shares 0.25 and 0.1, but 1.9x-2.3x at 0.01 and level at 0.001;
+#       256 queries stay at least 6.26x ahead down to 0.001.  Above 1M rows per shard (the largest
+#       size whose every cell from 32 queries clears the bar) the rule therefore wants 256 queries
+#       or a share of at least 0.1; 64 queries were not measured over 16M rows and count as 32.
+# k does not enter: top-10 and top-100 were measured in every cell, and the rule holds for both.
+MASK_FILTER_MIN_QUERIES = 32
+MASK_FILTER_MIN_SHARE = 0.001
+MASK_FILTER_MIN_ROWS = 65536
+MASK_FILTER_MAX_ROWS = 16_000_000
+MASK_FILTER_LARGE_ROWS = 1_000_000
+MASK_FILTER_LARGE_MIN_QUERIES = 256
+MASK_FILTER_LARGE_MIN_SHARE = 0.1
 BITMAP_CACHE_ENTRIES = 8
 
 
@@ -206,7 +235,11 @@ class DeviceIndex:
         its filter is "f8", a non-cosine index unless its filter is "metric").
         ``mask``: optional row-eligibility bitmap over the LOCAL rows (rc_index_search_masked):
         an int32 / uint32 tensor of ceil(n_rows / 32) words on this device, bit r & 31 of word
-        r >> 5 = row r may be returned; "auto" then scans."""
+        r >> 5 = row r may be returned; "auto" then scans.  "mfma" with a mask keeps the filter
+        GEMM as it is and drops ineligible candidates when rescoring (fast while at least half
+        of the rows are eligible); "mfma_masked" applies the mask inside the filter GEMM as
+        well, so a selective mask no longer overflows the candidate lists.  It is refused
+        where "mfma" is, and without a mask it is "mfma"."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
         q = self._vecs(queries)
@@ -699,7 +732,9 @@ class ShardSet:
     def search(self, queries: torch.Tensor, k: int, n_rows: int, mode: str = "auto", stream=None, mask=None):
         """Exact top-k over global rows [0, n_rows) by the index's metric: (scores f32 [nq,k]
         descending, rows i64 [nq,k]) on the leader.
-        ``mask``: an optional HOST uint32 bitmap over the global rows (rc_sharded_search_masked)."""
+        ``mask``: an optional HOST uint32 bitmap over the global rows (rc_sharded_search_masked);
+        ``mode="mfma_masked"`` runs every shard's filter GEMM under its part of the mask
+        (``DeviceIndex.search``)."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
         if queries.dim() == 1:
@@ -1112,8 +1147,10 @@ class Index:
                     include_metadata: bool = False, mode: str = "auto", filter: dict | None = None) -> list[dict]:
         """Batched form of ``query`` (f16/bf16 shards run the MFMA path for >= 8 queries).
         ``filter``: one metadata filter for the whole batch (see ``query``); with ``mode="auto"``
-        a filtered batch takes the MFMA path only at an eligible share of at least
-        ``MASKED_MFMA_MIN_SHARE``."""
+        a filtered batch takes the MFMA path at an eligible share of at least
+        ``MASKED_MFMA_MIN_SHARE``, and below it the MFMA path with the mask inside the filter
+        GEMM (``mode="mfma_masked"``) where ``_masked_mode``'s measured rule allows; otherwise
+        the masked scan."""
         if top_k < 1 or top_k > _lib.RC_TOPK_MAX:
             raise ValueError(f"top_k must be in [1, {_lib.RC_TOPK_MAX}]")
         if isinstance(vectors, torch.Tensor):
@@ -1136,7 +1173,13 @@ class Index:
         over >= 2^28 bytes of rows per shard: measured unmasked, where 8 queries over fewer rows
         are behind the scan) and the share is the same constant (measured for cosine; under a
         metric it is unmeasured, and conservative: the competing masked scan takes one query per
-        pass there)."""
+        pass there).  Below that share a cosine f16/bf16 index with the native filter gets
+        "mfma_masked" (the mask inside the filter GEMM) for >= MASK_FILTER_MIN_QUERIES queries, a
+        share >= MASK_FILTER_MIN_SHARE and MASK_FILTER_MIN_ROWS .. MASK_FILTER_MAX_ROWS rows per
+        shard, and above MASK_FILTER_LARGE_ROWS rows per shard only for >=
+        MASK_FILTER_LARGE_MIN_QUERIES queries or a share >= MASK_FILTER_LARGE_MIN_SHARE: where it
+        measured at least 2x ahead of the masked scan (f16; bf16 runs the same kernels at the
+        same MFMA rate).  Everything else scans."""
         if mode != "auto":
             return mode
         if self.metric != "cosine" and self._set.filter != "metric":  # no batched path for this index
@@ -1156,6 +1199,17 @@ class Index:
             size_ok = mfma_ok and nq >= 8 and per_shard >= 65536
         if size_ok and eligible >= MASKED_MFMA_MIN_SHARE * n:
             return "mfma"
+        # below that share: the mask inside the filter GEMM, where it was measured 2x ahead of the
+        # masked scan (the MASK_FILTER_* constants' comment).  Measured on a cosine f16 index with
+        # the native filter: the int8 / float8 filters and the metric forms have tested MASKED
+        # kernels and no timing, so they scan.
+        native_cosine = self.metric == "cosine" and self._set.filter in ("native", "metric") and not _lib.is_f8(self._set.dtype)
+        in_box = (nq >= MASK_FILTER_MIN_QUERIES and MASK_FILTER_MIN_ROWS <= per_shard <= MASK_FILTER_MAX_ROWS and
+                  eligible >= MASK_FILTER_MIN_SHARE * n)
+        if per_shard > MASK_FILTER_LARGE_ROWS:
+            in_box = in_box and (nq >= MASK_FILTER_LARGE_MIN_QUERIES or eligible >= MASK_FILTER_LARGE_MIN_SHARE * n)
+        if size_ok and native_cosine and in_box:
+            return "mfma_masked"
         return "scan"
 
     def _query_locked(self, q: torch.Tensor, k: int, include_values: bool, include_metadata: bool,

@@ -160,6 +160,7 @@ int rc_index_search(rc_index *h, const float *queries, int nq, int64_t n_rows, i
 #define RC_SEARCH_AUTO 0
 #define RC_SEARCH_SCAN 1
 #define RC_SEARCH_MFMA 2
+#define RC_SEARCH_MFMA_MASKED 3 /* rc_index_search_masked: RC_SEARCH_MFMA with the mask inside the filter GEMM */
 int rc_index_search_ex(rc_index *h, const float *queries, int nq, int64_t n_rows, int k,
                        float *scores, int64_t *out_rows, int mode, void *stream);
 
@@ -174,7 +175,11 @@ int rc_index_search_ex(rc_index *h, const float *queries, int nq, int64_t n_rows
  * with no eligible row is valid).  Modes: RC_SEARCH_SCAN skips the row loads of
  * every 8-row group (16-row on an RC_F8 index) without an eligible row; RC_SEARCH_MFMA keeps the filter GEMM
  * as it is and drops ineligible candidates when rescoring (overflowed queries fall
- * back to the masked scan on the device); RC_SEARCH_AUTO with a mask scans. */
+ * back to the masked scan on the device); RC_SEARCH_MFMA_MASKED also applies the mask in
+ * the filter GEMM's epilogue, so the candidate lists hold eligible rows only and a
+ * selective mask no longer overflows them (a clustered one still can, and falls back);
+ * it is refused exactly where RC_SEARCH_MFMA is and equals it without a mask;
+ * RC_SEARCH_AUTO with a mask scans. */
 int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_rows, int k,
                            const uint32_t *mask, float *scores, int64_t *out_rows, int mode, void *stream);
 

@@ -1,4 +1,4 @@
-"""Masked (metadata-filtered) search timings on one GPU.  Three parts, each a child process of its
+"""Masked (metadata-filtered) search timings on one GPU.  Four parts, each a child process of its
 own under its own time limit (a part that fails or runs out of time ends the run):
 
   scan    the masked scan against the unmasked scan of the same build, interleaved: 1M x 512 f32
@@ -8,7 +8,14 @@ own under its own time limit (a part that fails or runs out of time ends the run
           e.g. the parent commit's), alternating fresh processes;
   mfma    the masked MFMA path against the masked multi-query scan: 1M x 512 f16, 256 queries x
           top-100, shares 1.0 / 0.5 / 0.1 (and 0.35, 0.25, 0.01) — the crossover behind
-          index.MASKED_MFMA_MIN_SHARE.
+          index.MASKED_MFMA_MIN_SHARE;
+  maskfilter  the mask inside the filter GEMM (mode "mfma_masked") against the masked scan and
+          against "mfma" (mask at rescoring only), interleaved, results compared bit for bit in every
+          row.  "table": 1M x 512 f16, 256 queries x top-100, shares 1.0 ... 0.001 random and 0.1 /
+          0.01 clustered, with the queries that fell back.  "grid": "mfma_masked" against the masked
+          scan at 16 / 32 / 64 / 256 queries x top-10 / top-100, shares 0.25 ... 0.001, over the
+          first 65,536, 1M and 16M rows of one index (--grid-rows; 32 and 256 queries only past
+          1M rows) — what index.Index._masked_mode's rule below MASKED_MFMA_MIN_SHARE is read from.
 
 Every line printed is one JSON record; --out appends them to a file as well.
 Times: "wall_ms" is a host clock around REPS calls ending in a device synchronise, per call;
@@ -27,7 +34,7 @@ sys.path.insert(0, REPO)
 PKG = "end-to-end-image-retrieval-service-with-k8s-jenkins_amd"
 ROWS, DIM = 1_000_000, 512
 SHARES = (1.0, 0.5, 0.1, 0.01, 0.001)
-LIMITS = {"scan": 420, "parent": 480, "mfma": 300}  # seconds per part
+LIMITS = {"scan": 420, "parent": 480, "mfma": 300, "maskfilter": 420}  # seconds per part
 
 
 def emit(rec, out):
@@ -170,20 +177,70 @@ def part_mfma(args):
     d.close()
 
 
+def part_maskfilter(args):
+    import torch
+
+    M = importlib.import_module(f"{PKG}.index")
+    grid_rows = [int(r) for r in args.grid_rows.split(",")]
+    cap = max([ROWS] + grid_rows)
+    d = M.DeviceIndex(DIM, dtype="float16", capacity=cap)
+    d.fill_random(4, 0, cap)
+    Qall = torch.randn(256, DIM, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
+    d.timing(True)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+
+    def cell(what, rows, nq, k, share, kind, modes):
+        mask, eligible = make_mask(rows, share, kind, 9, d.device)
+        Q = Qall[:nq]
+        fns = {m: (lambda m=m: d.search(Q, k, rows, mode=m, mask=mask)) for m in modes}
+        ref = fns["scan"]()
+        torch.cuda.synchronize()
+        rec = {"part": "maskfilter", "what": what, "dtype": "float16", "rows": rows, "dim": DIM, "nq": nq, "k": k,
+               "share": share, "kind": kind, "eligible": eligible}
+        for m in modes[1:]:  # bit equality with the masked scan, and the queries that fell back in one call
+            d.gemm_timing_read()
+            got = fns[m]()
+            torch.cuda.synchronize()
+            rec[m + "_equals_scan"] = bool(torch.equal(ref[0].view(torch.int32), got[0].view(torch.int32)) and
+                                           torch.equal(ref[1], got[1]))
+            rec[m + "_fallback_queries"] = d.gemm_timing_read()[3]
+        wall = {m: [] for m in modes}
+        for _ in range(args.rounds):  # interleaved: scan, mfma, mfma_masked, scan, ...
+            for m in modes:
+                wall[m].append(timed(d, fns[m], 2 if m == "scan" else 4)[0])
+        for m in modes:
+            rec[m + "_ms_per_batch"] = med(wall[m])
+            rec[m + "_minmax"] = [min(wall[m]), max(wall[m])]
+        rec["scan_over_mfma_masked"] = rec["scan_ms_per_batch"] / rec["mfma_masked_ms_per_batch"]
+        emit(rec, args.out)
+
+    for share, kind in [(1.0, "random"), (0.5, "random"), (0.35, "random"), (0.25, "random"), (0.1, "random"),
+                        (0.01, "random"), (0.001, "random"), (0.1, "clustered"), (0.01, "clustered")]:
+        cell("table", ROWS, 256, 100, share, kind, ["scan", "mfma", "mfma_masked"])
+    for rows in grid_rows:
+        for nq in ((16, 32, 64, 256) if rows <= ROWS else (32, 256)):
+            for k in (10, 100):
+                for share in (0.25, 0.1, 0.01, 0.001):
+                    cell("grid", rows, nq, k, share, "random", ["scan", "mfma_masked"])
+    d.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=["scan", "parent", "parent-child", "mfma"], default=None,
+    ap.add_argument("--part", choices=["scan", "parent", "parent-child", "mfma", "maskfilter"], default=None,
                     help="run one part in this process (default: every part, each in a child process with a time limit)")
-    ap.add_argument("--parts", default="scan,parent,mfma")
+    ap.add_argument("--parts", default="scan,parent,mfma,maskfilter")
     ap.add_argument("--parent-lib", default=None, help="another build of libretrieval_core.so to compare the unmasked scan with")
     ap.add_argument("--out", default=None, help="append the JSON records to this file")
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--alternations", type=int, default=2)
     ap.add_argument("--label", default="this")
+    ap.add_argument("--grid-rows", default="65536,1000000,16000000", help="maskfilter: the grid's row counts")
     args = ap.parse_args()
     if args.part is not None:
-        {"scan": part_scan, "parent": part_parent, "parent-child": part_parent_child, "mfma": part_mfma}[args.part](args)
+        {"scan": part_scan, "parent": part_parent, "parent-child": part_parent_child, "mfma": part_mfma,
+         "maskfilter": part_maskfilter}[args.part](args)
         return
     for part in args.parts.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--part", part, "--reps", str(args.reps), "--rounds", str(args.rounds),
@@ -192,6 +249,8 @@ def main():
             cmd += ["--parent-lib", args.parent_lib]
         if args.out:
             cmd += ["--out", args.out]
+        if part == "maskfilter":
+            cmd += ["--grid-rows", args.grid_rows]
         subprocess.run(cmd, check=True, timeout=LIMITS[part])  # a failed or overrunning part ends the run
 
 
