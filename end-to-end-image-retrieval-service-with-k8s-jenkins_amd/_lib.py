@@ -27,6 +27,7 @@ RC_ERR_STATE = 5
 
 RC_F32, RC_F16, RC_BF16, RC_F8 = 0, 1, 2, 3
 RC_TOPK_MAX = 256
+RC_PAGE_ROWS = 256  # local rows per shard in one page of a paged row pool (retrieval_core.h)
 RC_SEARCH_AUTO, RC_SEARCH_SCAN, RC_SEARCH_MFMA, RC_SEARCH_MFMA_MASKED = 0, 1, 2, 3
 SEARCH_MODES = {"auto": RC_SEARCH_AUTO, "scan": RC_SEARCH_SCAN, "mfma": RC_SEARCH_MFMA, "mfma_masked": RC_SEARCH_MFMA_MASKED}
 DTYPES = {"float32": RC_F32, "f32": RC_F32, "float16": RC_F16, "f16": RC_F16, "bfloat16": RC_BF16, "bf16": RC_BF16,
@@ -145,6 +146,11 @@ SIGNATURES = {
     "rc_sharded_query_host": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "rc_sharded_search_masked": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
     "rc_sharded_query_host_masked": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rc_index_pages_set": (C.c_int, [_vp, _i32, _vp, _i32, _vp]),
+    "rc_index_search_pages": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "rc_sharded_pages_set": (C.c_int, [_vp, _i32, _vp, _i32]),
+    "rc_sharded_search_pages": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "rc_sharded_query_host_pages": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rc_index_timing": (C.c_int, [_vp, _i32]),
     "rc_index_timing_read": (C.c_int, [_vp, _pd, _pi64, _pd]),
     "rc_model_create": (C.c_int, [_i32, C.POINTER(VitConfig), C.POINTER(_vp)]),

@@ -21,7 +21,7 @@
 #include <cstring>
 #include <vector>
 
-#include "index_common.h"
+#include "paged.h"
 
 namespace rc {
 
@@ -341,6 +341,17 @@ __global__ __launch_bounds__(256) void empty_result_kernel(int64_t n, float *__r
     rows[i] = -1;
 }
 
+// Paged value gather (rc_sharded_query_host_pages): the local row of each position through a
+// slot's page table; an empty slot (position < 0) stays negative, which fetch_kernel answers
+// with NaN values.  n_pos bounds the table entries read.
+__global__ __launch_bounds__(256) void pages_rows_kernel(const int64_t *__restrict__ pos, int64_t n, const int32_t *__restrict__ pages,
+                                                        int64_t n_pos, int64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = pos[i];
+    out[i] = (p < 0 || p >= n_pos) ? -1 : (int64_t)pages[p / RC_PAGE_ROWS] * RC_PAGE_ROWS + p % RC_PAGE_ROWS;
+}
+
 }  // namespace rc
 
 // ================================================================= host ====
@@ -373,6 +384,14 @@ struct rc_index {
     BatchWs bws;         // batched MFMA search workspace (search_mfma.hip)
     KernelTimer timer;   // scan_topk_kernel launches (bytes)
     KernelTimer gtimer;  // the batched search's filter launches, whichever filter kernel (flops)
+    // page tables (rc_index_pages_set), by slot: one device allocation each, doubled when it grows
+    struct PageTable {
+        int32_t *dev = nullptr;
+        int n_pages = 0, cap = 0;
+    };
+    std::vector<PageTable> tables;
+    int64_t *pg_rows = nullptr;  // [pg_rows_cap] local rows of a paged value gather
+    int64_t pg_rows_cap = 0;
 };
 
 namespace {
@@ -506,6 +525,14 @@ void launch_scan(rc_index *h, const ScanArgs &a) {
     dispatch_dtype(h->dtype, [&](auto t) { rc::launch_scan<decltype(t)>(a); });
 }
 
+void launch_scan_paged(rc_index *h, const ScanArgs &a, const int32_t *pages) {
+    const PagedScanArgs p{a, pages};
+    dispatch_dtype(h->dtype, [&](auto t) {
+        if (a.metric != RC_METRIC_COSINE) rc::launch_scan_paged_metric<decltype(t)>(p);
+        else rc::launch_scan_paged<decltype(t)>(p);
+    });
+}
+
 // Top-k over nlist sorted partial lists per query, one block per query: past MERGE_HEADS_MIN lists
 // through the lists' heads (merge_heads_kernel), else over every key (merge_partials_kernel).  The
 // same keys either way.
@@ -524,8 +551,11 @@ void launch_merge_partials(rc_index *h, const uint64_t *partial, const int *flag
 }
 
 // mask (optional): the row-eligibility bitmap of rc_index_search_masked; the masked scan kernels.
+// pages (optional): a slot's page table (rc_index_search_pages); n_rows, the blocks' ranges, the
+// mask and the returned rows are then positions, and the paged scan kernels run over the same
+// block shape, so the partial lists are those of a dense index of the positions.
 void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask, float *scores,
-                 int64_t *out_rows, hipStream_t s) {
+                 int64_t *out_rows, hipStream_t s, const int32_t *pages = nullptr) {
     // queries per scan pass: a power of two the kernel is instantiated for (1, 2, 4)
     int qb = 1;
     while (qb * 2 <= std::min(nq, scan_max_qb(h->nch, k, mask != nullptr, h->metric))) qb *= 2;
@@ -552,7 +582,8 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
         a.mask = mask;
         a.metric = h->metric;  // non-cosine: the metric kernels, which also read the norms
         a.norms = h->norms;
-        launch_scan(h, a);
+        if (pages != nullptr) launch_scan_paged(h, a, pages);
+        else launch_scan(h, a);
         h->timer.end(slot, s, bytes);
     }
     launch_merge_partials(h, h->partial, nullptr, nblk, nq, nq_pad, k, scores, out_rows, s);
@@ -694,6 +725,34 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
     dispatch_dtype(h->dtype, [&](auto t) { launch_query1<decltype(t)>(a, s); });
     return true;
 }
+
+// The table of a slot, or an error (caller holds h->mu).
+static const rc_index::PageTable &page_table(const rc_index *h, int slot) {
+    RC_REQUIRE(slot >= 0 && slot < (int)h->tables.size() && h->tables[slot].n_pages > 0, RC_ERR_INVALID,
+               "unknown slot (no page table was set for it)");
+    return h->tables[slot];
+}
+
+// Internal (sharded.hip, rc_sharded_query_host_pages): the values of the positions pos[0..n)
+// (device; < 0 = empty: NaN) of a slot, as rc_index_fetch gives them, on stream `s`.
+void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos, int64_t n, float *out, hipStream_t s) {
+    if (n == 0) return;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const rc_index::PageTable &t = page_table(h, slot);
+    RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+    DeviceScope ds(h->device);
+    if (n > h->pg_rows_cap) {
+        RC_HIP(hipDeviceSynchronize());  // no gather may still read the old list
+        dfree(h->pg_rows);
+        h->pg_rows = nullptr;
+        h->pg_rows_cap = 0;
+        h->pg_rows = (int64_t *)dmalloc((size_t)n * sizeof(int64_t));
+        h->pg_rows_cap = n;
+    }
+    hipLaunchKernelGGL(pages_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pos, n, t.dev, n_pos, h->pg_rows);
+    RC_LAUNCH_CHECK();
+    dispatch_dtype(h->dtype, [&](auto tt) { launch_fetch<decltype(tt)>(h, h->pg_rows, n, out, false, s); });
+}
 }  // namespace rc
 
 extern "C" {
@@ -756,6 +815,8 @@ int rc_index_destroy(rc_index *h) {
         dfree(h->qn);
         dfree(h->partial);
         if (h->q1_done != nullptr) (void)hipHostFree(h->q1_done);
+        for (auto &t : h->tables) dfree(t.dev);
+        dfree(h->pg_rows);
         delete h;
     });
 }
@@ -1091,6 +1152,62 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
             return;
         }
         batched_search_exact(h, queries, nq, n_rows, k, mask, mask_filter, scores, out_rows, s);
+    });
+}
+
+int rc_index_pages_set(rc_index *h, int slot, const int32_t *pages_host, int n_pages, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(slot >= 0 && slot < RC_PAGE_SLOTS_MAX, RC_ERR_INVALID, "slot must be in [0, RC_PAGE_SLOTS_MAX)");
+        RC_REQUIRE(n_pages >= 0, RC_ERR_INVALID, "negative page count");
+        RC_REQUIRE(n_pages == 0 || pages_host != nullptr, RC_ERR_INVALID, "null page list");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const int64_t limit = h->capacity / RC_PAGE_ROWS;  // whole pages inside the rows and the norms
+        for (int i = 0; i < n_pages; ++i)
+            RC_REQUIRE(pages_host[i] >= 0 && pages_host[i] < limit, RC_ERR_INVALID, "page at or past capacity / RC_PAGE_ROWS");
+        if (n_pages == 0 && slot >= (int)h->tables.size()) return;
+        DeviceScope ds(h->device);
+        hipStream_t s = (hipStream_t)stream;
+        RC_HIP(hipDeviceSynchronize());  // no search may still read the table
+        if (slot >= (int)h->tables.size()) h->tables.resize((size_t)slot + 1);
+        rc_index::PageTable &t = h->tables[slot];
+        if (n_pages == 0) {
+            dfree(t.dev);
+            t = rc_index::PageTable{};
+            return;
+        }
+        if (n_pages > t.cap) {
+            const int cap2 = std::max(std::max(16, n_pages), 2 * t.cap);
+            int32_t *dev = (int32_t *)dmalloc((size_t)cap2 * sizeof(int32_t));
+            dfree(t.dev);
+            t.dev = dev;
+            t.cap = cap2;
+            t.n_pages = 0;
+        }
+        RC_HIP(hipMemcpyAsync(t.dev, pages_host, (size_t)n_pages * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RC_HIP(hipStreamSynchronize(s));  // the host list may be reused; later searches on any stream see the table
+        t.n_pages = n_pages;
+    });
+}
+
+int rc_index_search_pages(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
+                          float *scores, int64_t *out_rows, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
+        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const rc_index::PageTable &t = page_table(h, slot);
+        RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+        if (nq == 0) return;
+        DeviceScope ds(h->device);
+        hipStream_t s = (hipStream_t)stream;
+        if (n_pos == 0) {  // this shard holds none of the slot's positions
+            empty_search(nq, k, scores, out_rows, s);
+            return;
+        }
+        scan_search(h, queries, nq, n_pos, k, mask, scores, out_rows, s, t.dev);
     });
 }
 

@@ -33,6 +33,7 @@ void index_move_rows(rc_index *from, const int64_t *src_idx, rc_index *to, const
 bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int with_values, float *out_scores,
                   int64_t *out_rows, float *out_values, hipStream_t s, volatile unsigned **done = nullptr,
                   unsigned *seq = nullptr);
+void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos, int64_t n, float *out, hipStream_t s);
 
 // Wait for query1's completion word instead of the stream: the word is stored after the results
 // (system-scope release), so the host can read them the moment it changes, without the
@@ -121,6 +122,9 @@ struct rc_sharded {
     int64_t qh_bytes = 0;
     uint8_t *qh = nullptr;  // pinned
     uint8_t *qd = nullptr;  // leader device
+    // page tables (rc_sharded_pages_set), by slot: the host copy of the list every shard holds
+    // on its device (one page number = the same local rows on every shard); empty = no table
+    std::vector<std::vector<int32_t>> tables;
 };
 
 namespace {
@@ -760,6 +764,9 @@ int rc_sharded_move_rows(rc_sharded *h, const int64_t *src_rows, const int64_t *
 
 namespace {
 
+void query_host_checked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, int with_values,
+                        const uint32_t *mask, float *scores, int64_t *out_rows, float *values, int slot);
+
 // rc_sharded_fetch's body (caller holds h->mu)
 void fetch_locked(rc_sharded *h, const int64_t *rows, int64_t n, float *out, int stored) {
         std::vector<int64_t> cnt(h->n, 0);
@@ -802,14 +809,21 @@ void fetch_locked(rc_sharded *h, const int64_t *rows, int64_t n, float *out, int
 // rc_sharded_search's body (caller holds h->mu; device buffers on the leader, stream = leader stream)
 // mask (optional): HOST bitmap over the global rows; staged per shard first, and the call then
 // returns only once the staged words were copied (the next call may overwrite them).
+// slot >= 0 (rc_sharded_search_pages): n_rows, the mask and the returned rows are positions of
+// that slot; position i is on shard i % n as its position i / n, exactly as global rows are, so
+// the split of the mask, the shards' row maps and the merge are the ones of the dense search.
 void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
-                   int mode, void *stream, const uint32_t *mask = nullptr) {
+                   int mode, void *stream, const uint32_t *mask = nullptr, int slot = -1) {
         hipStream_t ls = (hipStream_t)stream;
         const bool masked = mask != nullptr;
         if (masked) stage_mask(h, mask, n_rows, ls);
+        auto shard_search = [&](int s, const float *q, int64_t n_local, float *so, int64_t *ro, void *st) {
+            const uint32_t *m = masked ? h->mk_d[s] : nullptr;
+            return slot >= 0 ? rc_index_search_pages(h->shard[s], q, nq, slot, n_local, k, m, so, ro, st)
+                             : rc_index_search_masked(h->shard[s], q, nq, n_local, k, m, so, ro, mode, st);
+        };
         if (h->n == 1) {
-            check_status(rc_index_search_masked(h->shard[0], queries, nq, n_rows, k, masked ? h->mk_d[0] : nullptr, scores,
-                                                out_rows, mode, stream));
+            check_status(shard_search(0, queries, n_rows, scores, out_rows, stream));
             if (masked) {
                 fence_mask_single(h, ls);
                 wait_mask(h);
@@ -833,8 +847,7 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
             }
             float *so = local ? h->g_s + s * slice : h->s_loc[s];
             int64_t *ro = local ? h->g_r + s * slice : h->r_loc[s];
-            check_status(rc_index_search_masked(h->shard[s], q, nq, shard_rows(h, s, n_rows), k,
-                                                masked ? h->mk_d[s] : nullptr, so, ro, mode, h->st[s]));
+            check_status(shard_search(s, q, shard_rows(h, s, n_rows), so, ro, h->st[s]));
             if (!local) {
                 RC_HIP(hipMemcpyPeerAsync(h->g_s + s * slice, h->dev[0], so, h->dev[s], slice * sizeof(float), h->st[s]));
                 RC_HIP(hipMemcpyPeerAsync(h->g_r + s * slice, h->dev[0], ro, h->dev[s], slice * sizeof(int64_t), h->st[s]));
@@ -895,6 +908,27 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
         RC_REQUIRE(n_rows >= 0 && n_rows <= h->cap * h->n, RC_ERR_INVALID, "n_rows out of range");
         if (nq == 0) return;
         RC_REQUIRE(queries && scores && out_rows && (!with_values || values), RC_ERR_INVALID, "null buffer");
+        query_host_checked(h, queries, nq, n_rows, k, with_values, mask, scores, out_rows, values, -1);
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+// The table of a slot and the range of n_pos it covers, or an error (caller holds h->mu).
+const std::vector<int32_t> &page_list(const rc_sharded *h, int slot, int64_t n_pos) {
+    RC_REQUIRE(slot >= 0 && slot < (int)h->tables.size() && !h->tables[slot].empty(), RC_ERR_INVALID,
+               "unknown slot (no page table was set for it)");
+    const std::vector<int32_t> &L = h->tables[slot];
+    RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)L.size() * RC_PAGE_ROWS * h->n, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+    return L;
+}
+
+// rc_sharded_query_host_masked's body after its argument checks; slot >= 0:
+// rc_sharded_query_host_pages (n_rows and out_rows are positions of that slot).
+void query_host_checked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, int with_values,
+                        const uint32_t *mask, float *scores, int64_t *out_rows, float *values, int slot) {
         const int64_t nk = (int64_t)nq * k;
         if (n_rows == 0) {  // an empty index: empty lists, no device work
             std::fill(scores, scores + nk, -INFINITY);
@@ -902,13 +936,14 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
             return;
         }
         std::lock_guard<std::mutex> lk(h->mu);
+        if (slot >= 0) (void)page_list(h, slot, n_rows);  // under the lock, before any device call
         // one shard: the matched rows' values are gathered on the device and come back in the
         // same copy as the lists; several shards: values through the staged fetch afterwards
         const bool dev_values = with_values && h->n == 1;
         const QueryLayout L = query_layout(h, nq, k, dev_values);
         ensure_query(h, L.total);
         DeviceScope dl(h->dev[0]);
-        if (h->n == 1 && nq == 1 && mask == nullptr) {
+        if (slot < 0 && h->n == 1 && nq == 1 && mask == nullptr) {
             // the request path: one launch pair (query in the kernel arguments, results written
             // straight into the pinned block), no copies; the host polls the completion word
             float *hs = (float *)(h->qh + L.sc);
@@ -929,8 +964,11 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
         RC_HIP(hipMemcpyAsync(h->qd + L.q, h->qh + L.q, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, h->qs));
         float *dsc = (float *)(h->qd + L.sc);
         int64_t *drw = (int64_t *)(h->qd + L.rw);
-        search_locked(h, (const float *)(h->qd + L.q), nq, n_rows, k, dsc, drw, RC_SEARCH_AUTO, h->qs, mask);
-        if (dev_values) check_status(rc_index_fetch(h->shard[0], drw, nk, (float *)(h->qd + L.val), h->qs));
+        search_locked(h, (const float *)(h->qd + L.q), nq, n_rows, k, dsc, drw, RC_SEARCH_AUTO, h->qs, mask, slot);
+        if (dev_values) {
+            if (slot >= 0) index_fetch_pages(h->shard[0], slot, n_rows, drw, nk, (float *)(h->qd + L.val), h->qs);
+            else check_status(rc_index_fetch(h->shard[0], drw, nk, (float *)(h->qd + L.val), h->qs));
+        }
         RC_HIP(hipMemcpyAsync(h->qh + L.sc, h->qd + L.sc, (size_t)(L.total - L.sc), hipMemcpyDeviceToHost, h->qs));
         RC_HIP(hipStreamSynchronize(h->qs));
         std::memcpy(scores, h->qh + L.sc, (size_t)nk * sizeof(float));
@@ -942,7 +980,12 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
             std::vector<int64_t> at;
             for (int64_t i = 0; i < nk; ++i)
                 if (out_rows[i] >= 0) {
-                    live.push_back(out_rows[i]);
+                    int64_t g = out_rows[i];
+                    if (slot >= 0) {  // position -> global row through the slot's pages
+                        const int64_t span = (int64_t)RC_PAGE_ROWS * h->n;
+                        g = (int64_t)h->tables[slot][g / span] * span + g % span;
+                    }
+                    live.push_back(g);
                     at.push_back(i);
                 } else {
                     std::fill(values + i * h->dim, values + (i + 1) * h->dim, NAN);
@@ -954,6 +997,59 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
                     std::memcpy(values + at[j] * h->dim, tmp.data() + j * h->dim, (size_t)h->dim * sizeof(float));
             }
         }
+}
+
+}  // namespace
+
+extern "C" {
+
+int rc_sharded_pages_set(rc_sharded *h, int slot, const int32_t *pages_host, int n_pages) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(slot >= 0 && slot < RC_PAGE_SLOTS_MAX, RC_ERR_INVALID, "slot must be in [0, RC_PAGE_SLOTS_MAX)");
+        RC_REQUIRE(n_pages >= 0, RC_ERR_INVALID, "negative page count");
+        RC_REQUIRE(n_pages == 0 || pages_host != nullptr, RC_ERR_INVALID, "null page list");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const int64_t limit = h->cap / RC_PAGE_ROWS;
+        for (int i = 0; i < n_pages; ++i)
+            RC_REQUIRE(pages_host[i] >= 0 && pages_host[i] < limit, RC_ERR_INVALID,
+                       "page at or past capacity_per_shard / RC_PAGE_ROWS");
+        if (n_pages == 0 && slot >= (int)h->tables.size()) return;
+        if (slot >= (int)h->tables.size()) h->tables.resize((size_t)slot + 1);
+        h->tables[slot].clear();  // a failure below leaves the slot unknown, never half installed
+        for (int s = 0; s < h->n; ++s) check_status(rc_index_pages_set(h->shard[s], slot, pages_host, n_pages, h->st[s]));
+        h->tables[slot].assign(pages_host, pages_host + n_pages);
+    });
+}
+
+int rc_sharded_search_pages(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
+                            float *scores, int64_t *out_rows, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
+        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        (void)page_list(h, slot, n_pos);
+        if (nq == 0) return;
+        search_locked(h, queries, nq, n_pos, k, scores, out_rows, RC_SEARCH_SCAN, stream, mask, slot);
+    });
+}
+
+int rc_sharded_query_host_pages(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, int with_values,
+                                const uint32_t *mask, float *scores, int64_t *out_rows, float *values) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
+        RC_REQUIRE(nq == 0 || (queries && scores && out_rows && (!with_values || values)), RC_ERR_INVALID, "null buffer");
+        RC_REQUIRE(slot >= 0 && slot < RC_PAGE_SLOTS_MAX && n_pos >= 0, RC_ERR_INVALID, "slot or n_pos out of range");
+        if (nq == 0 || n_pos == 0) {
+            std::lock_guard<std::mutex> lk(h->mu);
+            (void)page_list(h, slot, n_pos);
+            if (nq == 0) return;
+        }
+        query_host_checked(h, queries, nq, n_pos, k, with_values, mask, scores, out_rows, values, slot);
     });
 }
 

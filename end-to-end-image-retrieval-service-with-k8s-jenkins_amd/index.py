@@ -23,7 +23,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 import torch
 
-from . import _lib, compaction, metafilter
+from . import _lib, compaction, metafilter, pages
 from ._lib import check, ptr, stream_ptr
 
 # query_batch(filter=..., mode="auto") takes the batched MFMA path when the unmasked conditions
@@ -258,6 +258,29 @@ class DeviceIndex:
         mask = mask.to(device=self.device).contiguous()
         check(self.lib.rc_index_search_masked(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(mask), ptr(scores),
                                               ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
+        return scores, rows
+
+    def set_pages(self, slot: int, page_list, stream=None) -> None:
+        """Install or replace slot's page table (rc_index_pages_set; an empty list frees it):
+        position p of the slot lives at local row ``page_list[p // 256] * 256 + p % 256``."""
+        arr = np.ascontiguousarray(page_list, dtype=np.int32).reshape(-1)
+        check(self.lib.rc_index_pages_set(self.handle, int(slot), arr.ctypes.data if arr.size else None, int(arr.size),
+                                          stream_ptr(stream)))
+
+    def search_pages(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None):
+        """``search(mode="scan")`` over positions [0, n_pos) of a slot (rc_index_search_pages): the
+        rows returned are ``row_base + position * row_stride``.  ``mask``: an optional device
+        bitmap over the positions, as ``search`` takes one over the rows."""
+        q = self._vecs(queries)
+        nq = q.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        if mask is not None:
+            if mask.dtype not in (torch.int32, torch.uint32) or mask.numel() < (int(n_pos) + 31) // 32:
+                raise ValueError("mask must hold ceil(n_pos / 32) 32-bit words")
+            mask = mask.to(device=self.device).contiguous()
+        check(self.lib.rc_index_search_pages(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), ptr(mask), ptr(scores),
+                                             ptr(rows), stream_ptr(stream)))
         return scores, rows
 
     def export_rows(self, row0: int, n: int, stream=None):
@@ -752,6 +775,74 @@ class ShardSet:
                                                     ptr(scores), ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
+    # ------------------------------------------------------------------ page tables --
+    # A slot is one vector set (a namespace) inside this ShardSet's rows: an ordered list of
+    # pages (``pages``: RC_PAGE_ROWS local rows on every shard each) holding positions [0, n_pos).
+    # Rows are written, fetched and moved by global row as ever; only the searches go through
+    # the table, and they return POSITIONS (retrieval_core.h, "Page tables").
+    def set_pages(self, slot: int, page_list) -> None:
+        """Install or replace slot's page table on every shard (rc_sharded_pages_set); an empty
+        list frees it.  Waits for the devices: call it when the set gains or loses a page."""
+        arr = np.ascontiguousarray(page_list, dtype=np.int32).reshape(-1)
+        check(self.lib.rc_sharded_pages_set(self.handle, int(slot), arr.ctypes.data if arr.size else None, int(arr.size)))
+
+    def search_pages(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None):
+        """``search(mode="scan")`` over the positions [0, n_pos) of a slot: (scores, positions),
+        bit-identical to a dense ShardSet of as many shards holding the slot's vectors in
+        position order.  ``mask``: an optional HOST uint32 bitmap over the positions."""
+        if queries.dim() == 1:
+            queries = queries[None]
+        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        nq = q.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        m = None if mask is None else self._host_mask(mask, n_pos)
+        check(self.lib.rc_sharded_search_pages(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k),
+                                               None if m is None else m.ctypes.data, ptr(scores), ptr(rows), stream_ptr(stream)))
+        return scores, rows
+
+    def query_host_pages(self, q: np.ndarray, k: int, slot: int, n_pos: int, with_values: bool, mask=None):
+        """``query_host`` over the positions [0, n_pos) of a slot (rc_sharded_query_host_pages):
+        host (scores, positions, values or None), new arrays."""
+        nq = int(q.shape[0])
+        sc = np.empty((nq, k), np.float32)
+        rw = np.empty((nq, k), np.int64)
+        val = np.empty((nq, k, self.dim), np.float32) if with_values else None
+        m = None if mask is None else self._host_mask(mask, n_pos)
+        check(self.lib.rc_sharded_query_host_pages(self.handle, q.ctypes.data, nq, int(slot), int(n_pos), int(k),
+                                                   1 if with_values else 0, None if m is None else m.ctypes.data,
+                                                   sc.ctypes.data, rw.ctypes.data, None if val is None else val.ctypes.data))
+        return sc, rw, val
+
+    def export_run(self, row0: int, n: int):
+        """Raw stored rows and norms of the global rows [row0, row0 + n), ``row0`` a multiple of
+        the shard count (a run of pages): each shard's part is one contiguous block."""
+        if row0 % self.n:
+            raise ValueError("row0 must be a multiple of the shard count")
+        el = _lib.dtype_bytes(self.dtype)
+        rows = np.zeros((n, self.ld * el), dtype=np.uint8)
+        norms = np.zeros((n,), dtype=np.float32)
+        for s in range(self.n):
+            m = self.shard_rows(s, n)
+            if m == 0:
+                continue
+            r, nr = self._shards[s].export_rows(row0 // self.n, m)
+            torch.cuda.synchronize(self._shards[s].device)
+            rows[s::self.n] = r.cpu().numpy()
+            norms[s::self.n] = nr.cpu().numpy()
+        return rows, norms
+
+    def import_run(self, row0: int, rows, norms) -> None:
+        """Inverse of ``export_run``."""
+        if row0 % self.n:
+            raise ValueError("row0 must be a multiple of the shard count")
+        for s in range(self.n):
+            if self.shard_rows(s, len(norms)) == 0:
+                continue
+            self._shards[s].import_rows(row0 // self.n, torch.from_numpy(np.ascontiguousarray(rows[s::self.n])),
+                                        torch.from_numpy(np.ascontiguousarray(norms[s::self.n])))
+            torch.cuda.synchronize(self._shards[s].device)
+
     # raw stored rows in GLOBAL row order (the snapshot layout, independent of the shard count)
     def export_rows(self, n_rows: int):
         import numpy as np
@@ -777,6 +868,39 @@ class ShardSet:
             self._shards[s].import_rows(0, torch.from_numpy(rows[s::self.n].copy()),
                                         torch.from_numpy(norms[s::self.n].copy()))
             torch.cuda.synchronize(self._shards[s].device)
+
+
+def _namespace_name(namespace) -> str:
+    """``None`` is the default namespace ``""``; anything but a string is refused."""
+    if namespace is None:
+        return ""
+    if not isinstance(namespace, str):
+        raise ValueError("namespace must be a string")
+    return namespace
+
+
+# the pool of the named namespaces starts at this many pages per shard and doubles on demand
+POOL_INITIAL_PAGES = 4
+
+
+class _Namespace:
+    """Host state of one named namespace: what ``Index`` itself keeps for ``""`` (under the same
+    attribute names, so the helpers that take a state serve both), plus its place in the pool —
+    the ordered page list and the slot of its device-resident page table.  An id's position is
+    its index in ``_ids``; ``pages.position_to_row`` gives the pool row."""
+
+    __slots__ = ("name", "slot", "pages", "_ids", "_rows", "_meta", "_gen", "_recent", "_bitmaps")
+
+    def __init__(self, name: str, slot: int):
+        self.name = name
+        self.slot = slot
+        self.pages: list[int] = []
+        self._ids: list[str] = []
+        self._rows: dict[str, int] = {}  # id -> position
+        self._meta: dict[str, dict] = {}
+        self._gen = 0
+        self._recent: tuple[int, dict[str, np.ndarray]] = (-1, {})
+        self._bitmaps: dict[tuple[str, int], tuple[np.ndarray, int]] = {}
 
 
 class Index:
@@ -827,6 +951,19 @@ class Index:
     be returned, and the restriction happens inside the exact search (a row-eligibility
     bitmap the masked scan takes), so the top-k of the eligible vectors is exact however
     selective the filter is.
+
+    ``namespace=`` on ``upsert`` / ``upsert_tensor`` / ``query`` / ``query_batch`` / ``fetch`` /
+    ``delete`` names an independent vector set, as in Pinecone: ids are unique per namespace,
+    a query or fetch sees its own namespace only, and ``delete_all`` empties one namespace.
+    ``""`` (or ``None``) is the default namespace, stored and searched exactly as an index
+    without namespaces.  Every named namespace lives in one second ``ShardSet``, the pool
+    (same dimension, dtype, metric and devices; made by the first upsert into a named
+    namespace, grown by doubling), which hands its rows out in pages (``pages``); a query
+    there is the exact scan over the namespace's own pages (``ShardSet.search_pages``), so it
+    costs what the namespace holds, not what the pool holds, and gives the scores, order and
+    ties of an index holding that namespace alone.  A namespace exists while it holds a
+    vector.  In a named namespace ``query_batch`` takes ``mode="auto"`` or ``"scan"``
+    (``"mfma"`` / ``"mfma_masked"`` raise ``ValueError``: no batched search over pages).
     """
 
     def __init__(self, name: str, dimension: int = 768, metric: str = "cosine", dtype: str = "float32",
@@ -866,10 +1003,22 @@ class Index:
         # metadata-filter bitmaps, most recently used last: (canonical filter JSON, _gen) ->
         # (bitmap, eligible count); any upsert or delete bumps _gen, so stale entries can never be hit
         self._bitmaps: dict[tuple[str, int], tuple[np.ndarray, int]] = {}
+        # named namespaces: their states by name, the pool they share (None until the first
+        # upsert into one), the pool's page allocator and the page-table slots in use
+        self._ns: dict[str, _Namespace] = {}
+        self._pool: ShardSet | None = None
+        self._alloc = pages.PageAllocator()
+        self._free_slots: list[int] = []
+        self._next_slot = 0
 
     @property
     def shard_set(self) -> ShardSet:
         return self._set
+
+    @property
+    def pool(self) -> "ShardSet | None":
+        """The ShardSet holding every named namespace (None before the first one)."""
+        return self._pool
 
     @property
     def dtype(self) -> str:
@@ -889,6 +1038,8 @@ class Index:
 
     def close(self) -> None:
         self._set.close()
+        if self._pool is not None:
+            self._pool.close()
 
     def _normalize_items(self, vectors: Iterable) -> list[tuple[str, list[float], dict]]:
         items: dict[str, tuple[str, list[float], dict]] = {}
@@ -921,23 +1072,28 @@ class Index:
         self._set.grow(per)
 
     def upsert(self, vectors: Sequence, namespace: str = "") -> dict:
+        namespace = _namespace_name(namespace)
         items = self._normalize_items(vectors)
         if not items:
             return {"upserted_count": 0}
         vecs = torch.tensor([it[1] for it in items], dtype=torch.float32)
         with self._mu:
-            self._upsert_locked(items, vecs)
+            if namespace:
+                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_rows(vecs, rows))
+            else:
+                self._upsert_locked(items, vecs)
         return {"upserted_count": len(items)}
 
-    def upsert_tensor(self, ids: Sequence[str], vecs, metadata: Sequence[dict] | None = None) -> dict:
+    def upsert_tensor(self, ids: Sequence[str], vecs, metadata: Sequence[dict] | None = None, namespace: str = "") -> dict:
         """Batched upsert of device-resident vectors (the ingest path: embeddings never leave HBM).
 
         ``vecs``: f32 [len(ids), dimension] on a GPU, or a list of parts ``(positions,
         tensor)`` — the vectors of ``ids[positions]`` on whatever GPU produced them (an
         ``EmbedderPool`` batch): each goes straight to its shard's GPU.  Same semantics as
         ``upsert`` (overwrite by id, last occurrence wins)."""
+        namespace = _namespace_name(namespace)
         if isinstance(vecs, (list, tuple)):
-            return self._upsert_parts(ids, vecs, metadata)
+            return self._upsert_parts(ids, vecs, metadata, namespace)
         if vecs.dim() != 2 or vecs.shape[0] != len(ids) or vecs.shape[1] != self.dimension:
             raise ValueError("vecs must be [len(ids), dimension]")
         metadata = list(metadata) if metadata is not None else [{}] * len(ids)
@@ -956,10 +1112,13 @@ class Index:
         if not bool(nonzero):
             raise ValueError("Dense vectors must contain at least one non-zero value for the cosine metric")
         with self._mu:
-            self._upsert_locked(items, vecs)
+            if namespace:
+                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_rows(vecs, rows))
+            else:
+                self._upsert_locked(items, vecs)
         return {"upserted_count": len(items)}
 
-    def _upsert_parts(self, ids, parts, metadata) -> dict:
+    def _upsert_parts(self, ids, parts, metadata, namespace: str = "") -> dict:
         metadata = list(metadata) if metadata is not None else [{}] * len(ids)
         if len(metadata) != len(ids):
             raise ValueError("metadata and ids differ in length")
@@ -982,8 +1141,7 @@ class Index:
             if t.shape[0] and not bool((t != 0).any(dim=1).all()):
                 raise ValueError("Dense vectors must contain at least one non-zero value for the cosine metric")
         items = [(ids[i], None, dict(metadata[i] or {})) for i in keep]
-        with self._mu:
-            rows = self._plan_rows(items)
+        def split(rows):  # the parts as ShardSet.upsert_parts takes them: (global rows, vectors)
             sel = [[] for _ in parts]  # per part: (offset, global row) of the kept positions
             for i, r in zip(keep, rows):
                 pi, o = where[i]
@@ -995,9 +1153,123 @@ class Index:
                 offs = torch.tensor([o for o, _ in lst], dtype=torch.int64)
                 v = t if len(lst) == t.shape[0] and offs.tolist() == list(range(t.shape[0])) else t[offs.to(t.device)]
                 out.append((torch.tensor([r for _, r in lst], dtype=torch.int64), v))
-            self._device_write(self._set.upsert_parts, out)
-            self._commit_rows(items, rows)
+            return out
+
+        with self._mu:
+            if namespace:
+                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_parts(split(rows)))
+            else:
+                rows = self._plan_rows(items)
+                self._device_write(self._set.upsert_parts, split(rows))
+                self._commit_rows(items, rows)
         return {"upserted_count": len(items)}
+
+    # ------------------------------------------------------------ named namespaces --
+    def _ensure_pool(self) -> ShardSet:
+        if self._pool is None:
+            per = POOL_INITIAL_PAGES * pages.PAGE_ROWS
+            self._pool = ShardSet(self.dimension, dtype=self._set.dtype, capacity_per_shard=per,
+                                  devices=list(self._set.devices), metric=self.metric)
+            self._alloc.set_capacity(per // pages.PAGE_ROWS)
+        return self._pool
+
+    def _take_pages(self, count: int) -> list[int]:
+        """``count`` pool pages, growing the pool (doubling, ``rc_sharded_grow``) if it is short."""
+        pool = self._ensure_pool()
+        if self._alloc.pages_short(count):
+            per = self._alloc.capacity_needed(count, pool.capacity_per_shard)
+            pool.grow(per)
+            self._alloc.set_capacity(pool.capacity_per_shard // pages.PAGE_ROWS)
+        return self._alloc.alloc(count)
+
+    def _ns_rows(self, ns: _Namespace, positions, page_list=None) -> list[int]:
+        """Pool rows of a namespace's positions."""
+        sp = pages.span(self._set.n)
+        pl = ns.pages if page_list is None else page_list
+        return [pl[p // sp] * sp + p % sp for p in positions]
+
+    def _ns_upsert_locked(self, name: str, items, write) -> None:
+        """``_upsert_locked`` in a named namespace: positions for the items (an existing id keeps
+        its position), the pages the new length needs, the device write ``write(pool, pool
+        rows)``, the page table if it gained a page, then the host maps.  If the write raises
+        nothing is registered and the new pages go back to the free list; a namespace made by
+        this call never comes to exist."""
+        ns = self._ns.get(name)
+        fresh = ns is None
+        if fresh:
+            ns = _Namespace(name, self._free_slots.pop() if self._free_slots else self._next_slot)
+        pos, nxt = [], len(ns._ids)
+        for vid, _, _ in items:
+            p = ns._rows.get(vid)
+            if p is None:
+                p, nxt = nxt, nxt + 1
+            pos.append(p)
+        gained = self._take_pages(pages.pages_for(nxt, self._set.n) - len(ns.pages))
+        page_list = ns.pages + gained
+        try:
+            write(self._pool, self._ns_rows(ns, pos, page_list))
+            if gained:
+                self._pool.set_pages(ns.slot, page_list)
+        except BaseException:
+            ns._gen += 1
+            self._alloc.free(gained)
+            if fresh:
+                self._free_slots.append(ns.slot)
+            elif gained:  # the table may be half replaced: back to the list the host holds
+                self._pool.set_pages(ns.slot, ns.pages)
+            raise
+        ns.pages = page_list
+        if fresh:
+            self._ns[name] = ns
+            if ns.slot == self._next_slot:
+                self._next_slot += 1
+        for (vid, _, md), p in zip(items, pos):
+            if vid not in ns._rows:
+                ns._rows[vid] = p
+                ns._ids.append(vid)
+            ns._meta[vid] = md
+        ns._gen += 1
+
+    def _ns_drop_locked(self, ns: _Namespace) -> None:
+        """The namespace holds nothing any more: its pages, its table and its slot are free."""
+        self._pool.set_pages(ns.slot, [])
+        self._alloc.free(ns.pages)
+        self._free_slots.append(ns.slot)
+        del self._ns[ns.name]
+
+    def _ns_delete_rows_locked(self, ns: _Namespace, positions: list[int]) -> None:
+        """``_delete_rows_locked`` on a namespace's positions (distinct, ascending): the same
+        plan (position i is on shard i % n, as a global row is), the moves on pool rows, the
+        host maps, then the pages past the new length go back to the free list."""
+        if not positions:
+            return
+        n = len(ns._ids)
+        src, dst = compaction.plan_compaction(n, positions, self._set.n)
+        if src:
+            try:
+                self._pool.move_rows(self._ns_rows(ns, src), self._ns_rows(ns, dst))
+            except BaseException:
+                ns._gen += 1
+                raise
+        ids = ns._ids
+        for p in positions:
+            vid = ids[p]
+            del ns._rows[vid]
+            ns._meta.pop(vid, None)
+        for s, d in zip(src, dst):
+            vid = ids[s]
+            ids[d] = vid
+            ns._rows[vid] = d
+        del ids[n - len(positions):]
+        ns._gen += 1
+        if not ids:
+            self._ns_drop_locked(ns)
+            return
+        keep = pages.pages_for(len(ids), self._set.n)
+        if keep < len(ns.pages):
+            gone, ns.pages = ns.pages[keep:], ns.pages[:keep]
+            self._pool.set_pages(ns.slot, ns.pages)
+            self._alloc.free(gone)
 
     def _plan_rows(self, items) -> list[int]:
         """Row of each (deduplicated) item: its existing row, or the next free rows; grows the
@@ -1053,10 +1325,10 @@ class Index:
         write into rows of ids being deleted), but the ids being deleted may now hold another
         vector's values.  The cached values and bitmaps are invalidated and the error is
         re-raised; repeat the call."""
-        self._delete(ids, delete_all, filter)
+        self._delete(ids, delete_all, filter, namespace)
         return {}
 
-    def _delete(self, ids, delete_all, flt) -> int:
+    def _delete(self, ids, delete_all, flt, namespace: str = "") -> int:
         """``delete``'s body; returns how many vectors were removed (Pinecone's call reports
         nothing; the package's ``/delete_images`` route answers with the count)."""
         if flt is not None and not isinstance(flt, dict):
@@ -1065,6 +1337,24 @@ class Index:
             raise ValueError("ids must be a list of ids, not one string")
         if (ids is not None) + bool(delete_all) + bool(flt) != 1:
             raise ValueError("delete needs exactly one of ids, delete_all=True or a non-empty filter")
+        namespace = _namespace_name(namespace)
+        if namespace:
+            with self._mu:
+                ns = self._ns.get(namespace)
+                if ns is None:  # nothing there: Pinecone's delete in an unknown namespace is a no-op
+                    return 0
+                if delete_all:
+                    n = len(ns._ids)
+                    self._ns_drop_locked(ns)
+                    return n
+                if ids is not None:
+                    pos = sorted({ns._rows[i] for i in ids if i in ns._rows})
+                else:
+                    bitmap, eligible = self._bitmap_locked(flt, ns)
+                    bits = np.unpackbits(bitmap.view(np.uint8), bitorder="little")[:len(ns._ids)]
+                    pos = np.flatnonzero(bits).tolist() if eligible else []
+                self._ns_delete_rows_locked(ns, pos)
+                return len(pos)
         with self._mu:
             if delete_all:
                 n = len(self._ids)
@@ -1101,24 +1391,28 @@ class Index:
         del ids[n - len(rows):]
         self._gen += 1
 
-    def _bitmap_locked(self, flt) -> tuple[np.ndarray, int] | None:
+    def _bitmap_locked(self, flt, st=None) -> tuple[np.ndarray, int] | None:
         """The row-eligibility bitmap of a metadata filter and its eligible count (None for no
-        filter: ``None`` or ``{}``).  Cached per (canonical filter, generation)."""
+        filter: ``None`` or ``{}``).  Cached per (canonical filter, generation).  ``st``: a named
+        namespace's state (the bitmap is then over its positions, the cache its own)."""
+        if st is None:
+            st = self
         if flt is None:
             return None
         if not isinstance(flt, dict):
             raise ValueError("filter must be a dict (Pinecone metadata filter) or None")
         if not flt:
             return None
-        key = (metafilter.canonical(flt), self._gen)
-        hit = self._bitmaps.pop(key, None)
+        key = (metafilter.canonical(flt), st._gen)
+        cache = st._bitmaps
+        hit = cache.pop(key, None)
         if hit is None:
-            hit = metafilter.build_bitmap(metafilter.compile_filter(flt), self._ids, self._meta)
-            for old in [k for k in self._bitmaps if k[1] != self._gen]:
-                del self._bitmaps[old]
-            while len(self._bitmaps) >= BITMAP_CACHE_ENTRIES:
-                del self._bitmaps[next(iter(self._bitmaps))]  # least recently used
-        self._bitmaps[key] = hit  # (re)inserted last = most recently used
+            hit = metafilter.build_bitmap(metafilter.compile_filter(flt), st._ids, st._meta)
+            for old in [k for k in cache if k[1] != st._gen]:
+                del cache[old]
+            while len(cache) >= BITMAP_CACHE_ENTRIES:
+                del cache[next(iter(cache))]  # least recently used
+        cache[key] = hit  # (re)inserted last = most recently used
         return hit
 
     def query(self, vector=None, top_k: int = 10, include_values: bool = False, include_metadata: bool = False,
@@ -1132,6 +1426,21 @@ class Index:
         top_k = int(top_k)
         if top_k > _lib.RC_TOPK_MAX:
             raise ValueError(f"top_k must be <= {_lib.RC_TOPK_MAX}")
+        namespace = _namespace_name(namespace)
+        if namespace:
+            with self._mu:
+                ns = self._ns.get(namespace)
+                if ns is None:  # no such namespace: no device work
+                    return {"matches": [], "namespace": namespace}
+                if vector is None:
+                    p = ns._rows.get(id)
+                    if p is None:
+                        return {"matches": [], "namespace": namespace}
+                    vector = self._pool.fetch_rows(self._ns_rows(ns, [p]))[0]
+                q = _as_vector_np(vector, self.dimension)
+                bm = self._bitmap_locked(filter, ns)
+                res = self._query_host_locked(q, top_k, include_values, include_metadata, bm, ns)[0]
+            return {"matches": res, "namespace": namespace}
         with self._mu:
             if vector is None:
                 r = self._rows.get(id)
@@ -1144,13 +1453,15 @@ class Index:
         return {"matches": res, "namespace": namespace}
 
     def query_batch(self, vectors, top_k: int = 10, include_values: bool = False,
-                    include_metadata: bool = False, mode: str = "auto", filter: dict | None = None) -> list[dict]:
+                    include_metadata: bool = False, mode: str = "auto", filter: dict | None = None,
+                    namespace: str = "") -> list[dict]:
         """Batched form of ``query`` (f16/bf16 shards run the MFMA path for >= 8 queries).
         ``filter``: one metadata filter for the whole batch (see ``query``); with ``mode="auto"``
         a filtered batch takes the MFMA path at an eligible share of at least
         ``MASKED_MFMA_MIN_SHARE``, and below it the MFMA path with the mask inside the filter
         GEMM (``mode="mfma_masked"``) where ``_masked_mode``'s measured rule allows; otherwise
-        the masked scan."""
+        the masked scan.  ``namespace``: a named namespace scans its own pages (``mode`` "auto" or
+        "scan" there; "mfma" / "mfma_masked" raise ``ValueError``)."""
         if top_k < 1 or top_k > _lib.RC_TOPK_MAX:
             raise ValueError(f"top_k must be in [1, {_lib.RC_TOPK_MAX}]")
         if isinstance(vectors, torch.Tensor):
@@ -1159,6 +1470,20 @@ class Index:
                 raise ValueError("queries must be [n, dimension]")
         else:
             q = torch.tensor([_as_vector(v, self.dimension) for v in vectors], dtype=torch.float32)
+        namespace = _namespace_name(namespace)
+        if namespace:
+            if mode not in _lib.SEARCH_MODES:
+                raise ValueError(f"unknown search mode {mode!r}")
+            if mode not in ("auto", "scan"):
+                raise ValueError(f"mode={mode!r} is not available in a named namespace: there is no batched MFMA search "
+                                 "over pages (use 'auto' or 'scan')")
+            with self._mu:
+                ns = self._ns.get(namespace)
+                if ns is None:
+                    res = [[] for _ in range(q.shape[0])]
+                else:
+                    res = self._query_locked(q, top_k, include_values, include_metadata, "scan", self._bitmap_locked(filter, ns), ns)
+            return [{"matches": m, "namespace": namespace} for m in res]
         with self._mu:
             res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter))
         return [{"matches": m, "namespace": ""} for m in res]
@@ -1213,14 +1538,19 @@ class Index:
         return "scan"
 
     def _query_locked(self, q: torch.Tensor, k: int, include_values: bool, include_metadata: bool,
-                      mode: str = "auto", bitmap=None) -> list[list[dict]]:
-        n = len(self._ids)
+                      mode: str = "auto", bitmap=None, ns: _Namespace | None = None) -> list[list[dict]]:
+        """``ns``: a named namespace's state — the paged scan over its pages; the rows that come
+        back are its positions, mapped to pool rows where values are fetched."""
+        st = self if ns is None else ns
+        n = len(st._ids)
         if n == 0 or q.shape[0] == 0:
             return [[] for _ in range(q.shape[0])]
-        if bitmap is None:
-            scores, rows = self._set.search(q, k, n, mode=mode)
-        elif bitmap[1] == 0:  # nothing is eligible: no device work
+        if bitmap is not None and bitmap[1] == 0:  # nothing is eligible: no device work
             return [[] for _ in range(q.shape[0])]
+        if ns is not None:
+            scores, rows = self._pool.search_pages(q, k, ns.slot, n, mask=None if bitmap is None else bitmap[0])
+        elif bitmap is None:
+            scores, rows = self._set.search(q, k, n, mode=mode)
         else:
             if mode not in _lib.SEARCH_MODES:
                 raise ValueError(f"unknown search mode {mode!r}")
@@ -1235,35 +1565,45 @@ class Index:
         recent: dict[str, np.ndarray] = {}
         for sq, rq in zip(scores, rows):
             sel = [(s, r) for s, r in zip(sq, rq) if r >= 0]
-            vals = self._set.fetch_rows([r for _, r in sel]).numpy() if include_values and sel else None
+            vals = None
+            if include_values and sel:
+                if ns is None:
+                    vals = self._set.fetch_rows([r for _, r in sel]).numpy()
+                else:
+                    vals = self._pool.fetch_rows(self._ns_rows(ns, [r for _, r in sel])).numpy()
             if vals is not None:
-                recent.update((self._ids[r], v) for (_, r), v in zip(sel, vals))
+                recent.update((st._ids[r], v) for (_, r), v in zip(sel, vals))
             matches = []
             for j, (s, r) in enumerate(sel):
-                vid = self._ids[r]
+                vid = st._ids[r]
                 m = Record(vals[j], id=vid, score=float(s)) if include_values else {"id": vid, "score": float(s)}
                 if include_metadata:
-                    dict.__setitem__(m, "metadata", dict(self._meta.get(vid, {})))
+                    dict.__setitem__(m, "metadata", dict(st._meta.get(vid, {})))
                 matches.append(m)
             out.append(matches)
         if include_values:
-            self._recent = (self._gen, recent)
+            st._recent = (st._gen, recent)
         return out
 
     def _query_host_locked(self, q: np.ndarray, k: int, include_values: bool, include_metadata: bool,
-                           bitmap=None) -> list[list[dict]]:
+                           bitmap=None, ns: _Namespace | None = None) -> list[list[dict]]:
         """The request path (a query or a few): ``ShardSet.query_host``, one library call, the
-        lists and (include_values) the matched rows' values come back together."""
-        n = len(self._ids)
+        lists and (include_values) the matched rows' values come back together.  ``ns``: a named
+        namespace's state (``ShardSet.query_host_pages`` on the pool; the rows are positions)."""
+        st = self if ns is None else ns
+        n = len(st._ids)
         if n == 0 or (bitmap is not None and bitmap[1] == 0):  # (a filter nothing satisfies: no device work)
             return [[] for _ in range(q.shape[0])]
-        if bitmap is None:
+        if ns is not None:
+            sc, rw, val = self._pool.query_host_pages(q, k, ns.slot, n, include_values,
+                                                      mask=None if bitmap is None else bitmap[0])
+        elif bitmap is None:
             sc, rw, val = self._set.query_host(q, k, n, include_values)
         else:
             sc, rw, val = self._set.query_host(q, k, n, include_values, mask=bitmap[0])
         out = []
         recent: dict[str, np.ndarray] = {}
-        ids, meta = self._ids, self._meta
+        ids, meta = st._ids, st._meta
         for qi in range(q.shape[0]):
             rows = rw[qi].tolist()
             live = k - rows.count(-1)  # the lists are sorted: empty slots (-1) come last
@@ -1290,22 +1630,30 @@ class Index:
                         m["metadata"] = dict(meta.get(m["id"], {}))
             out.append(matches)
         if include_values:
-            self._recent = (self._gen, recent)
+            st._recent = (st._gen, recent)
         return out
 
     def fetch(self, ids: Sequence[str], namespace: str = "") -> dict:
+        namespace = _namespace_name(namespace)
         with self._mu:
-            found = [(i, self._rows[i]) for i in ids if i in self._rows]
+            # a named namespace has its own ids, rows (positions) and cache of recently queried
+            # values: nothing fetched in one namespace can be served in another
+            st = self._ns.get(namespace) if namespace else self
             vectors = {}
-            gen, recent = self._recent
-            if found and gen == self._gen and all(i in recent for i, _ in found):
+            if st is None:
+                return {"vectors": vectors, "namespace": namespace}
+            found = [(i, st._rows[i]) for i in ids if i in st._rows]
+            gen, recent = st._recent
+            if found and gen == st._gen and all(i in recent for i, _ in found):
                 vals = [recent[i] for i, _ in found]  # fetched by the query just before: no second device read
-            elif found:
+            elif found and st is self:
                 vals = self._set.fetch_rows([r for _, r in found]).numpy()
+            elif found:
+                vals = self._pool.fetch_rows(self._ns_rows(st, [r for _, r in found])).numpy()
             if found:
                 for (vid, _), v in zip(found, vals):
                     rec = Record(v, id=vid)  # "values" becomes a list when read (retriever/main.py reads metadata)
-                    dict.__setitem__(rec, "metadata", dict(self._meta.get(vid, {})))
+                    dict.__setitem__(rec, "metadata", dict(st._meta.get(vid, {})))
                     vectors[vid] = rec
         return {"vectors": vectors, "namespace": namespace}
 
@@ -1314,8 +1662,13 @@ class Index:
     # name, ingesting/utils.py:23-38); the in-HBM index is saved to a directory:
     # manifest.json (name, dimension, dtype, ids in row order, metadata) +
     # rows.npy (raw stored bytes in GLOBAL row order, exactly what search scores;
-    # independent of the shard count) + norms.npy.
+    # independent of the shard count) + norms.npy.  That is format 1, and what an index without
+    # named namespaces writes.  With named namespaces the manifest is format 2: it also lists
+    # them ("namespaces": name, count, ids in position order, metadata) and each has its own
+    # ns<i>_rows.npy / ns<i>_norms.npy, raw stored rows in POSITION order — independent of the
+    # pages the namespace happened to hold and of the shard count.
     SNAPSHOT_FORMAT = 1
+    SNAPSHOT_FORMAT_NAMESPACES = 2
 
     def save(self, path: str) -> None:
         import numpy as np
@@ -1326,10 +1679,25 @@ class Index:
             rows, norms = self._set.export_rows(n)
             np.save(os.path.join(path, "rows.npy"), rows)
             np.save(os.path.join(path, "norms.npy"), norms)
-            manifest = {"format": self.SNAPSHOT_FORMAT, "name": self.name, "dimension": self.dimension,
+            spaces = []
+            for i, ns in enumerate(self._ns.values()):
+                cnt = len(ns._ids)
+                el = _lib.dtype_bytes(self._set.dtype)
+                nrows = np.zeros((cnt, self._set.ld * el), dtype=np.uint8)
+                nnorms = np.zeros((cnt,), dtype=np.float32)
+                for pos0, row0, m in pages.row_runs(ns.pages, cnt, self._set.n):  # runs of consecutive pages: one export each
+                    nrows[pos0:pos0 + m], nnorms[pos0:pos0 + m] = self._pool.export_run(row0, m)
+                np.save(os.path.join(path, f"ns{i}_rows.npy"), nrows)
+                np.save(os.path.join(path, f"ns{i}_norms.npy"), nnorms)
+                spaces.append({"name": ns.name, "count": cnt, "ids": list(ns._ids),
+                               "metadata": {v: ns._meta.get(v, {}) for v in ns._ids}})
+            manifest = {"format": self.SNAPSHOT_FORMAT_NAMESPACES if spaces else self.SNAPSHOT_FORMAT,
+                        "name": self.name, "dimension": self.dimension,
                         "metric": self.metric, "dtype": self._set.dtype, "ld": self._set.ld, "count": n,
                         "capacity": self._set.capacity, "filter": self._set.filter,
                         "ids": list(self._ids), "metadata": {i: self._meta.get(i, {}) for i in self._ids}}
+            if spaces:
+                manifest["namespaces"] = spaces
             tmp = os.path.join(path, "manifest.json.tmp")
             with open(tmp, "w") as f:
                 json.dump(manifest, f)
@@ -1342,7 +1710,7 @@ class Index:
 
         with open(os.path.join(path, "manifest.json")) as f:
             man = json.load(f)
-        if man.get("format") != cls.SNAPSHOT_FORMAT:
+        if man.get("format") not in (cls.SNAPSHOT_FORMAT, cls.SNAPSHOT_FORMAT_NAMESPACES):
             raise ValueError(f"unsupported snapshot format {man.get('format')!r}")
         n = int(man["count"])
         idx = cls(man["name"], dimension=man["dimension"], metric=man["metric"], dtype=man["dtype"],
@@ -1359,9 +1727,31 @@ class Index:
         idx._ids = list(man["ids"])
         idx._rows = {vid: r for r, vid in enumerate(idx._ids)}
         idx._meta = {vid: dict(man["metadata"].get(vid, {})) for vid in idx._ids}
+        for i, sp in enumerate(man.get("namespaces", [])):
+            cnt = int(sp["count"])
+            nrows = np.load(os.path.join(path, f"ns{i}_rows.npy"), allow_pickle=False)
+            nnorms = np.load(os.path.join(path, f"ns{i}_norms.npy"), allow_pickle=False)
+            if nrows.shape[0] != cnt or nnorms.shape[0] != cnt or len(sp["ids"]) != cnt or not sp["name"] or cnt == 0:
+                raise ValueError("snapshot files disagree on a namespace")
+            items = [(vid, None, dict(sp["metadata"].get(vid, {}))) for vid in sp["ids"]]
+
+            def write(pool, rows, nrows=nrows, nnorms=nnorms):  # rows: the pool rows of positions 0 .. cnt - 1
+                r0 = 0
+                while r0 < len(rows):  # runs of consecutive pool rows (whole pages but the last)
+                    r1 = r0 + 1
+                    while r1 < len(rows) and rows[r1] == rows[r1 - 1] + 1:
+                        r1 += 1
+                    pool.import_run(rows[r0], nrows[r0:r1], nnorms[r0:r1])
+                    r0 = r1
+
+            with idx._mu:
+                idx._ns_upsert_locked(sp["name"], items, write)
         return idx
 
     def describe_index_stats(self) -> dict:
+        with self._mu:
+            spaces = {"": {"vector_count": len(self._ids)}}
+            spaces.update((name, {"vector_count": len(ns._ids)}) for name, ns in self._ns.items())
         return {"dimension": self.dimension, "index_fullness": len(self._ids) / self._set.capacity,
-                "total_vector_count": len(self._ids), "namespaces": {"": {"vector_count": len(self._ids)}},
+                "total_vector_count": sum(v["vector_count"] for v in spaces.values()), "namespaces": spaces,
                 "shards": self._set.n}

@@ -57,6 +57,17 @@ def validate_extension(filename: str | None) -> str:
     return ext
 
 
+def form_namespace(field) -> str:
+    """The optional ``namespace`` form field as text ("" when absent)."""
+    if field is None:
+        return ""
+    raw = field.data if hasattr(field, "data") else field
+    try:
+        return raw.decode("utf-8") if isinstance(raw, (bytes, bytearray)) else str(raw)
+    except UnicodeDecodeError:
+        raise HTTPException(status_code=400, detail="Invalid namespace.")
+
+
 def _prepare(files: Sequence[tuple]):
     """Extension checks, then the validation decode (ingesting/main.py:111-119) of every file:
     (names, blobs, content types, extensions, decoded images).  Raises the reference's 400s."""
@@ -100,7 +111,7 @@ def _embed_for(embedder, images, index):
     return raw
 
 
-def _finish(prep, index, storage: StorageHook, id_factory: Callable[[], str]) -> list[dict]:
+def _finish(prep, index, storage: StorageHook, id_factory: Callable[[], str], namespace: str = "") -> list[dict]:
     """Embed the decoded batch, then ids, storage hook and ONE upsert (ingesting/main.py:124-168)."""
     from ..embedding import main as emb
 
@@ -115,23 +126,28 @@ def _finish(prep, index, storage: StorageHook, id_factory: Callable[[], str]) ->
     for p, data, ct, name in zip(paths, blobs, ctypes_, names):
         storage.upload(p, data, ct)
         urls.append(storage.signed_url(p, name))
-    index.upsert_tensor(ids, vecs, [{"gcs_path": p, "filename": n} for p, n in zip(paths, names)])
+    meta = [{"gcs_path": p, "filename": n} for p, n in zip(paths, names)]
+    if namespace:
+        index.upsert_tensor(ids, vecs, meta, namespace=namespace)
+    else:
+        index.upsert_tensor(ids, vecs, meta)
     return [{"message": "Successfully!", "file_id": fid, "gcs_path": p, "signed_url": u}
             for fid, p, u in zip(ids, paths, urls)]
 
 
 def ingest_many(files: Sequence[tuple], index, storage: StorageHook | None = None,
-                id_factory: Callable[[], str] | None = None) -> list[dict]:
+                id_factory: Callable[[], str] | None = None, namespace: str = "") -> list[dict]:
     """files: ``(filename, bytes[, content_type])`` per image → one response dict per image.
 
     Every image is validated before anything is embedded or stored (a bad file
     fails the whole call with the reference's 400, and nothing is ingested).
-    ``index`` may be a zero-argument callable (opened only once the batch is valid)."""
-    return _finish(_prepare(files), index, storage or StorageHook(), id_factory or (lambda: str(uuid.uuid4())))
+    ``index`` may be a zero-argument callable (opened only once the batch is valid).
+    ``namespace``: the index namespace the images go into (``""`` = the default one)."""
+    return _finish(_prepare(files), index, storage or StorageHook(), id_factory or (lambda: str(uuid.uuid4())), namespace)
 
 
 def ingest_stream(batches: Iterable[Sequence[tuple]], index, storage: StorageHook | None = None,
-                  id_factory: Callable[[], str] | None = None) -> Iterator[list[dict]]:
+                  id_factory: Callable[[], str] | None = None, namespace: str = "") -> Iterator[list[dict]]:
     """Bulk ingest: ``ingest_many`` over a stream of upload batches, pipelined.  Batch i+1 is
     validated and decoded (host Huffman on a worker thread, GPU reconstruction on a side
     stream) while the GPU embeds batch i and the host upserts it; yields each batch's
@@ -157,7 +173,7 @@ def ingest_stream(batches: Iterable[Sequence[tuple]], index, storage: StorageHoo
 
     it = iter(batches)
     with _short_gil_switch():
-        yield from _pipeline(it, prepare, main, index, storage, id_factory)
+        yield from _pipeline(it, prepare, main, index, storage, id_factory, namespace)
 
 
 _switch_lock = threading.Lock()
@@ -188,7 +204,7 @@ def _short_gil_switch():
                 sys.setswitchinterval(_switch_saved)
 
 
-def _pipeline(it, prepare, main, index, storage, id_factory):
+def _pipeline(it, prepare, main, index, storage, id_factory, namespace=""):
     """ingest_stream's loop: the worker prepares batch i+1 while this thread finishes batch i."""
     import concurrent.futures as cf
 
@@ -208,11 +224,12 @@ def _pipeline(it, prepare, main, index, storage, id_factory):
                     im.record_stream(main)
             if opened is None:
                 opened = index() if callable(index) else index
-            yield _finish(prep, opened, storage, id_factory)
+            yield _finish(prep, opened, storage, id_factory, namespace)
 
 
 def push_one(filename: str, data: bytes, index, content_type: str | None = None, storage: StorageHook | None = None,
-             feature_fn: Callable[[bytes], list] | None = None, id_factory: Callable[[], str] | None = None) -> dict:
+             feature_fn: Callable[[bytes], list] | None = None, id_factory: Callable[[], str] | None = None,
+             namespace: str = "") -> dict:
     """The single-image ``/push_image`` flow (ingesting/main.py:101-168), step for step:
     ext check → validation decode → feature vector (``feature_fn``, default the in-process
     embed; the reference POSTs to /embed) → uuid → storage hook → ``index.upsert``.
@@ -235,5 +252,9 @@ def push_one(filename: str, data: bytes, index, content_type: str | None = None,
     storage.upload(gcs_path, data, content_type)
     signed_url = storage.signed_url(gcs_path, filename)
     index = index() if callable(index) else index
-    index.upsert([(file_id, feature, {"gcs_path": gcs_path, "filename": filename})])
+    vectors = [(file_id, feature, {"gcs_path": gcs_path, "filename": filename})]
+    if namespace:
+        index.upsert(vectors, namespace=namespace)
+    else:
+        index.upsert(vectors)
     return {"message": "Successfully!", "file_id": file_id, "gcs_path": gcs_path, "signed_url": signed_url}

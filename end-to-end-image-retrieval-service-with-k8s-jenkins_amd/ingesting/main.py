@@ -8,6 +8,9 @@ Contract kept (``ingesting/main.py:91-168``):
   POST /push_images  (batched form) repeated ``files`` → one such dict per image (ingesting.core.ingest_many)
   POST /delete_images JSON ``{"ids": [...]}`` → {"deleted_count": ids that existed}; 422 without a list ``ids``
                      (no reference counterpart: ``Index.delete``)
+  /push_image and /push_images take an optional form field ``namespace``, /delete_images an optional
+  JSON key ``"namespace"`` (a string; 422 otherwise): the index namespace written to or deleted from
+  (absent = the default one)
 
 ``get_feature_vector`` is a module-level name, as in the reference (whose tests
 monkeypatch ``ingesting.main.get_feature_vector``); by default it embeds in
@@ -67,15 +70,18 @@ async def push_image(request: Request):
     if f is None:
         raise _missing_file("file")
     return core.push_one(f.filename, f.data, index, content_type=f.content_type, storage=storage,
-                         feature_fn=_feature_fn(request))
+                         feature_fn=_feature_fn(request), namespace=core.form_namespace(form.get("namespace")))
 
 
 @app.post("/push_images")
 async def push_images(request: Request):
-    parts = parse_form_all(await request.body(), request.headers.get("content-type", "")).get("files")
+    form = parse_form_all(await request.body(), request.headers.get("content-type", ""))
+    parts = form.get("files")
     if not parts:
         raise _missing_file("files")
-    return core.ingest_many([(f.filename, f.data, f.content_type) for f in parts], index, storage=storage)
+    ns = form.get("namespace")
+    return core.ingest_many([(f.filename, f.data, f.content_type) for f in parts], index, storage=storage,
+                            namespace=core.form_namespace(ns[-1] if ns else None))
 
 
 @app.post("/delete_images")
@@ -91,5 +97,11 @@ async def delete_images(request: Request):
     if not isinstance(ids, list) or not all(isinstance(i, str) for i in ids):
         raise RequestValidationError([{"type": "list_type", "loc": ("body", "ids"), "msg": "Input should be a list of ids",
                                        "input": None}])
+    namespace = body.get("namespace", "")
+    if not isinstance(namespace, str):
+        raise RequestValidationError([{"type": "string_type", "loc": ("body", "namespace"), "msg": "Input should be a string",
+                                       "input": None}])
     # Index.delete is Pinecone's call and returns {}; its body reports how many ids existed
-    return {"deleted_count": index()._delete(ids, False, None) if ids else 0}
+    if not ids:
+        return {"deleted_count": 0}
+    return {"deleted_count": index()._delete(ids, False, None, namespace) if namespace else index()._delete(ids, False, None)}

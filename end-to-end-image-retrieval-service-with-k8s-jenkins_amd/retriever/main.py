@@ -8,7 +8,9 @@ Contract kept (``retriever/main.py:94-169``):
                       image."; 422 without ``file``; an optional form field ``filter`` (a JSON
                       object, Pinecone's metadata-filter language, see ``metafilter``) restricts
                       the search to matching vectors — 400 "Invalid filter." if it is not JSON,
-                      not an object, or not a valid filter (not in the reference)
+                      not an object, or not a valid filter (not in the reference); an optional
+                      form field ``namespace`` searches that namespace of the index (absent =
+                      the default one; one that holds nothing answers [])
 
 Flow as in the reference: validation decode (``:111-117``; folded into the in-process embed,
 which validates with the same 400 body before the model runs) → ``get_feature_vector``
@@ -27,7 +29,7 @@ from fastapi.exceptions import RequestValidationError
 from PIL import Image, UnidentifiedImageError
 
 from ..config import Config
-from ..ingesting.core import StorageHook
+from ..ingesting.core import StorageHook, form_namespace
 from ..ingesting.utils import embed_locally, get_index
 from ..ingesting.utils import get_feature_vector as _remote_feature_vector
 from ..metafilter import compile_filter
@@ -84,6 +86,7 @@ async def search_image(request: Request):
         raise RequestValidationError([{"type": "missing", "loc": ("body", "file"), "msg": "Field required",
                                        "input": None}])
     flt = _parse_filter(form.get("filter"))
+    namespace = form_namespace(form.get("namespace"))
     feature_fn = _feature_fn(request)
     if not getattr(feature_fn, "validates_image", False):
         try:
@@ -94,13 +97,13 @@ async def search_image(request: Request):
     # the model runs — a GPU-decodable JPEG is decoded once (on the GPU) instead of twice
     feature = feature_fn(f.data)
     ix = index()
-    if flt is None:  # no filter field: the reference's call, unchanged
+    if flt is None and not namespace:  # neither field: the reference's call, unchanged
         match_ids = search(ix, feature, top_k=Config.TOP_K)
     else:
-        match_ids = search(ix, feature, top_k=Config.TOP_K, filter=flt)
+        match_ids = search(ix, feature, top_k=Config.TOP_K, filter=flt, namespace=namespace)
     if not match_ids:
         return []
-    response = ix.fetch(ids=match_ids)
+    response = ix.fetch(ids=match_ids, namespace=namespace) if namespace else ix.fetch(ids=match_ids)
     images_url = []
     for match_id in match_ids:
         if len(images_url) == Config.TOP_K:

@@ -358,6 +358,49 @@ int rc_sharded_set_filter(rc_sharded *h, int kind);
 int rc_sharded_set_metric(rc_sharded *h, int metric);
 
 /* ------------------------------------------------------------------------
+ * Page tables: several independent vector sets (namespaces) in one index's rows.
+ *
+ * A slot names one set.  Its vectors are dense in POSITION space [0, n_pos); the
+ * rows are handed out in pages of RC_PAGE_ROWS local rows per shard, and the slot's
+ * page table lists its pages in position order.  On one rc_index, position p lives
+ * at local row pages[p / RC_PAGE_ROWS] * RC_PAGE_ROWS + p % RC_PAGE_ROWS.  On an
+ * rc_sharded handle of S shards one page number means local rows
+ * [RC_PAGE_ROWS p, RC_PAGE_ROWS (p + 1)) on EVERY shard, i.e. global rows
+ * [RC_PAGE_ROWS S p, RC_PAGE_ROWS S (p + 1)): position i lives at global row
+ * pages[i / (RC_PAGE_ROWS S)] * RC_PAGE_ROWS S + i % (RC_PAGE_ROWS S), on shard
+ * i % S, as that shard's position i / S.  Rows are written, read and moved by global
+ * row through the calls above; only the searches below go through the table.
+ *
+ * A paged search scores positions [0, n_pos) and returns POSITIONS: scores, positions
+ * and tie order are bit-identical to a dense index of S shards holding the same
+ * vectors in position order, searched with RC_SEARCH_SCAN (the scan kernels' paged
+ * form; the same merges).  Rows of the last page at or past n_pos are never scored.
+ * mask: a bitmap over positions (as rc_index_search_masked / rc_sharded_search_masked
+ * over rows), or NULL.  There is no batched MFMA search over pages.
+ *
+ * rc_*_pages_set installs or replaces a slot's table (n_pages = 0 frees it): a
+ * device-resident int32 array per shard, one allocation per slot and shard, doubled
+ * when it grows.  It waits for the device, so call it when a set gains or loses a
+ * page, not per query.  Every argument is checked before any device call: a slot
+ * outside [0, RC_PAGE_SLOTS_MAX) or without a table, n_pos beyond the table's
+ * pages, a page at or past capacity / RC_PAGE_ROWS, k outside [1, RC_TOPK_MAX] and
+ * NULL buffers return RC_ERR_INVALID. */
+#define RC_PAGE_ROWS 256
+#define RC_PAGE_SLOTS_MAX 1048576
+int rc_index_pages_set(rc_index *h, int slot, const int32_t *pages_host, int n_pages, void *stream);
+int rc_index_search_pages(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                          const uint32_t *mask, float *scores, int64_t *out_rows, void *stream);
+int rc_sharded_pages_set(rc_sharded *h, int slot, const int32_t *pages_host, int n_pages);
+int rc_sharded_search_pages(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                            const uint32_t *mask, float *scores, int64_t *out_rows, void *stream);
+/* rc_sharded_query_host_masked over a slot: host in, host out, one H2D copy, the paged
+ * search, the matched positions' values (gathered through the table), one D2H copy,
+ * one synchronisation.  out_rows are positions. */
+int rc_sharded_query_host_pages(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                                int with_values, const uint32_t *mask, float *scores, int64_t *out_rows,
+                                float *values);
+
+/* ------------------------------------------------------------------------
  * ViT-MSN image embedding.  Replaces the /embed compute path —
  * embedding/main.py:97-114: PIL decode (stays on host) → ViTImageProcessor
  * (resize, rescale, normalize) → ViTMSNModel → last_hidden_state[:, 0, :].
