@@ -148,6 +148,8 @@ SIGNATURES = {
     "rc_sharded_query_host_masked": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rc_index_pages_set": (C.c_int, [_vp, _i32, _vp, _i32, _vp]),
     "rc_index_search_pages": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "rc_index_search_pages_ex": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "rc_sharded_search_pages_ex": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
     "rc_sharded_pages_set": (C.c_int, [_vp, _i32, _vp, _i32]),
     "rc_sharded_search_pages": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
     "rc_sharded_query_host_pages": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),

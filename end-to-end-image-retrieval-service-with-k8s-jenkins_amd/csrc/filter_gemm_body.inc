@@ -1,7 +1,9 @@
 // filter_gemm_body.inc — the body of filter_gemm_kernel<T> and filter_gemm_metric_kernel<T>
 // (search_mfma.hip), included inside each kernel's braces.  In scope: T, the kernel argument
 // `FilterArgs a`, `constexpr bool METRIC` and (METRIC) `FilterMetric fm`, `constexpr bool MASKED` and
-// (MASKED) `const uint32_t *mask` (filter_gemm_masked_kernel<T, METRIC>).  Text inclusion, not a
+// (MASKED) `const uint32_t *mask` (filter_gemm_masked_kernel<T, METRIC>), `constexpr bool PAGED` and
+// (PAGED) `const int32_t *pages` (filter_gemm_paged_kernel, search_mfma_paged.hip; filter_mfma.h,
+// "PAGED forms").  Text inclusion, not a
 // device function: as a function taking the arguments by reference the cosine kernel's registers
 // and schedule change; this way it compiles to the instructions it had as the only copy.  (A
 // `bool METRIC = false` template parameter on the kernel itself would read better, but the
@@ -26,7 +28,15 @@
     const int64_t ld = a.ld;
     const int64_t nsteps = (rt1 - rt0) * nkt;
     const uint16_t *Ag = (const uint16_t *)a.qh + (int64_t)qb * SB_TILE * ld;
-    const uint16_t *Rg = (const uint16_t *)a.rows + (a.r_begin + rt0 * SB_TILE) * ld;
+    // PAGED: Rg is the pool's first row; a tile is one whole page, found in stage4
+    const uint16_t *Rg = (const uint16_t *)a.rows + (PAGED ? (int64_t)0 : (a.r_begin + rt0 * SB_TILE) * ld);
+    // PAGED: the page of the tile being staged (pg_cur) and of the tile after it (pg_ahead, loaded a
+    // tile ahead of the loads that need it); pg_epi is the page of the tile whose epilogue comes next
+    // (METRIC: its norms), loaded where mw is.  Wave-uniform scalar loads (load_page).
+    [[maybe_unused]] const int64_t pos0 = a.r_begin + rt0 * SB_TILE;
+    [[maybe_unused]] int32_t pg_cur = 0, pg_ahead = 0, pg_epi = 0;
+    if constexpr (PAGED) pg_ahead = load_page(pages, pos0);
+    if constexpr (PAGED && METRIC) pg_epi = load_page(pages, pos0);
 
     // 64 pieces of 1 KB per step (queries: 0-31, rows: 32-63); wave w owns pieces w + 8 i.
     auto stage4 = [&](int buf, int64_t step, int i0) {
@@ -34,6 +44,15 @@
         const int64_t rt = step / nkt;
         const int k0 = (int)(step - rt * nkt) * BK;
         const uint16_t *Wg = Rg + rt * SB_TILE * ld;
+        if constexpr (PAGED) {
+            if (i0 == 4) {  // the call that stages the rows; steps come in order, a tile's first takes the page over
+                if (k0 == 0) {
+                    pg_cur = pg_ahead;
+                    pg_ahead = load_page(pages, pos0 + min(rt + 1, rt1 - rt0 - 1) * SB_TILE);
+                }
+                Wg = Rg + (int64_t)pg_cur * RC_PAGE_ROWS * ld;
+            }
+        }
 #pragma unroll
         for (int i = i0; i < i0 + 4; ++i) {
             const int piece = wave + 8 * i;
@@ -132,7 +151,8 @@
             if (!MASKED || (mw[0] | mw[1]) != 0u) {
                 if constexpr (METRIC) {  // u >= thr[q] (the metric epilogue's comment in search_mfma.hip)
                     const int64_t tile_row = a.r_begin + rt * SB_TILE;  // wave-uniform
-                    const float *tn = fm.norms + tile_row;
+                    // (PAGED: the norms sit beside the rows, in the tile's page; `left` stays in positions)
+                    const float *tn = fm.norms + (PAGED ? (int64_t)pg_epi * RC_PAGE_ROWS : tile_row);
                     const int left = (int)min<int64_t>(a.r_end - tile_row, (int64_t)SB_TILE);
                     f32x4_t nv[2][2];
 #pragma unroll
@@ -200,6 +220,7 @@
             }
             if constexpr (MASKED)
                 load_mask_words(mask, a.r_begin + min(rt + 1, rt1 - 1) * SB_TILE + wc * 64, a.r_end, mw);
+            if constexpr (PAGED && METRIC) pg_epi = load_page(pages, a.r_begin + min(rt + 1, rt1 - 1) * SB_TILE);
             zero_acc();
         }
     }

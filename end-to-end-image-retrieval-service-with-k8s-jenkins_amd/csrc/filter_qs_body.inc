@@ -1,8 +1,10 @@
 // filter_qs_body.inc — the body of filter_qs_kernel<T, NKT, ABL> and filter_qs_metric_kernel<T, NKT>
 // (search_mfma.hip), included inside each kernel's braces.  In scope: T, NKT, ABL, the kernel
 // argument `FilterArgs a`, `constexpr bool METRIC` and (METRIC) `FilterMetric fm`, `constexpr bool
-// MASKED` and (MASKED) `const uint32_t *mask` (filter_qs_masked_kernel<T, NKT, METRIC>).  Text
-// inclusion, not a device function, for the reason given in filter_gemm_body.inc.
+// MASKED` and (MASKED) `const uint32_t *mask` (filter_qs_masked_kernel<T, NKT, METRIC>), `constexpr
+// bool PAGED` and (PAGED) `const int32_t *pages` (filter_qs_paged_kernel, search_mfma_paged.hip;
+// filter_mfma.h, "PAGED forms").  Text inclusion, not a device function, for the reason given in
+// filter_gemm_body.inc.
     constexpr int QS_WAVES = 16 / QS_QT;
     constexpr int RF = QS_RT / 16;
     using Op = MfmaOp<T>;
@@ -21,7 +23,8 @@
     const int64_t ld = a.ld;
     const int ntiles = (int)(rt1 - rt0);  // per-block counters in 32 bits: uniform SALU compares
     const int nsteps = ntiles * NKT;
-    const uint16_t *Rg = (const uint16_t *)a.rows + (a.r_begin + rt0 * QS_RT) * ld;
+    // PAGED: Rg is the pool's first row; a tile's rows are found through its page (`issue`)
+    const uint16_t *Rg = (const uint16_t *)a.rows + (PAGED ? (int64_t)0 : (a.r_begin + rt0 * QS_RT) * ld);
 
     // this lane's query fragments for the whole K: qf[qt][kk], kk = 32-wide k chunk
     v8 qf[QS_QT][2 * NKT];
@@ -60,12 +63,26 @@
         const int r = (wave + QS_WAVES * i) * 8 + (lane >> 3);
         loff[i] = (uint32_t)(r * (int)ld + (((lane & 7) ^ ((r >> 1) & 7)) << 3)) * 2u;
     }
+    // PAGED: the page of the tile whose steps are being issued (pg_cur) and of the tile after it
+    // (pg_ahead, loaded when the tile before it starts: a whole tile of steps ahead of the descriptor
+    // that needs it).  Wave-uniform scalar loads (load_page): scalar registers, no VGPR.
+    [[maybe_unused]] const int64_t pos0 = a.r_begin + rt0 * QS_RT;  // the block's first position
+    [[maybe_unused]] int32_t pg_cur = 0, pg_ahead = 0;
+    if constexpr (PAGED) pg_ahead = load_page(pages, pos0);
     auto issue = [&](int t) {
         const int tile = t / NKT;
         const int ks = (int)(t - tile * NKT);
         uint8_t *base = smem + (int)(t % QS_NS) * STEP_BYTES;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(Rg + (int64_t)tile * QS_RT * ld + ks * 64), (short)0, 0x7fffffff, 0x00020000);
+        const uint16_t *src = Rg + (int64_t)tile * QS_RT * ld + ks * 64;
+        if constexpr (PAGED) {
+            if (ks == 0) {  // steps are issued in order: a tile's first step takes the page over
+                pg_cur = pg_ahead;
+                pg_ahead = load_page(pages, pos0 + (int64_t)min(tile + 1, ntiles - 1) * QS_RT);
+            }
+            const int in_page = ((int)(pos0 & (RC_PAGE_ROWS - 1)) + tile * QS_RT) & (RC_PAGE_ROWS - 1);
+            src = Rg + ((int64_t)pg_cur * RC_PAGE_ROWS + in_page) * ld + ks * 64;
+        }
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)src, (short)0, 0x7fffffff, 0x00020000);
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
             // (the builtin's operands kept non-dependent: a template-dependent operand defers
@@ -93,6 +110,8 @@
         // loaded here so that their latency runs under the tile's K loop
         [[maybe_unused]] uint32_t mw[QS_RT / 32];
         if constexpr (MASKED) load_mask_words(mask, a.r_begin + (rt0 + tile) * QS_RT, a.r_end, mw);
+        [[maybe_unused]] int32_t pg_epi = 0;  // PAGED METRIC: this tile's page, for its norms (as mw: a scalar register)
+        if constexpr (PAGED && METRIC) pg_epi = load_page(pages, a.r_begin + (rt0 + tile) * QS_RT);
 #pragma unroll
         for (int rf = 0; rf < RF; ++rf)
 #pragma unroll
@@ -183,7 +202,8 @@
             // moves up among the tile's last MFMAs, where the row fragments are still live.
             __builtin_amdgcn_sched_barrier(0);
             const int64_t tile_row = a.r_begin + (rt0 + tile) * QS_RT;  // wave-uniform
-            const float *tn = fm.norms + tile_row;
+            // (PAGED: the norms sit beside the rows, at the tile's local row; `left` stays in positions)
+            const float *tn = fm.norms + (PAGED ? (int64_t)pg_epi * RC_PAGE_ROWS + (tile_row & (RC_PAGE_ROWS - 1)) : tile_row);
             const int left = (int)min<int64_t>(a.r_end - tile_row, (int64_t)QS_RT);
 #pragma unroll
             for (int qt = 0; qt < QS_QT; ++qt) thr[qt] = a.thr[q0 + qt * 16 + lq];

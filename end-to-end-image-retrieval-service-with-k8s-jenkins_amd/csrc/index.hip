@@ -431,6 +431,23 @@ constexpr int64_t kF8BatchMinBytesLarge = int64_t(1) << 28;  // this many bytes 
 constexpr int kMetricBatchMinQueries = 16;
 constexpr int kMetricBatchMinQueriesLarge = 8;                    // ... with at least
 constexpr int64_t kMetricBatchMinBytesLarge = int64_t(1) << 28;  // this many bytes of rows
+// The batched search over pages (rc_index_search_pages_ex) competes with the paged scan of the same
+// slot (f16 x 512 on a shuffled page list in a 4M-row pool, wall ms per call, median of 5 interleaved
+// rounds, paged MFMA / paged scan, tools/paged_batched_micro.py, profiles/paged_batched/; DESIGN.md,
+// "Namespaces", row (d) has [min, max] and the dense floor):
+//   positions     16 x top-10     16 x top-100    64 x top-10     64 x top-100    1024 x top-10    1024 x top-100
+//      65 536   0.380 / 0.361   0.582 / 0.529   0.524 / 1.402   0.823 / 2.047   0.681 / 23.58    1.040 / 33.78
+//     262 144   0.496 / 0.550   0.687 / 0.754   0.724 / 2.140   0.986 / 3.032   1.081 / 35.64    1.394 / 48.34
+//   1 048 576   0.669 / 1.830   1.020 / 2.208   0.887 / 7.331   1.434 / 8.718   1.755 / 117.1    2.587 / 139.1
+// 16 queries over 65 536 positions are behind the scan (its 8 two-query passes are cheaper than the
+// staged path's fixed cost); every other measured cell is ahead with its [min, max] wholly below the
+// scan's.  RC_SEARCH_AUTO without a mask takes the batched path from the smallest measured corners
+// that are: 64 queries from 65 536 positions, 16 queries from 262 144.  17 to 63 queries below
+// 262 144 positions were not measured and scan.
+constexpr int kPagedBatchMinQueries = 64;
+constexpr int64_t kPagedBatchMinPositions = 65536;
+constexpr int kPagedBatchMinQueriesLarge = 16;               // ... or with at least
+constexpr int64_t kPagedBatchMinPositionsLarge = 262144;    // this many positions on this shard
 
 // Every global row a shard can report must fit the 32-bit row word of the top-k
 // keys (merge_lists_kernel) below the all-ones value: row_base + (cap - 1) * stride < 2^32 - 1.
@@ -600,8 +617,12 @@ int batch_query_bytes(const rc_index *h) { return h->dtype == RC_F8 ? 2 : (int)d
 // With a mask the rescoring drops ineligible candidates (search_mfma.hip) and the
 // fallback is the masked scan; the merge is the same.  mask_filter (RC_SEARCH_MFMA_MASKED): the
 // filter kernels apply the mask as well, in their MASKED forms.
+// pages (optional): a slot's page table (rc_index_search_pages_ex); n_rows, the mask and the returned
+// rows are then positions, the filter and rescore kernels their PAGED forms (search_mfma_paged.hip),
+// and the fallback the paged scan's fallback form (scan_paged.h), each query normalised from the raw
+// queries as every paged scan does.
 void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
-                          bool mask_filter, float *scores, int64_t *out_rows, hipStream_t s) {
+                          bool mask_filter, float *scores, int64_t *out_rows, hipStream_t s, const int32_t *pages = nullptr) {
     h->bws.ensure(nq, k, h->ld, batch_query_bytes(h));
     BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, n_rows, h->row_base, h->row_stride, queries, nq, k, scores, out_rows};
     p.f8_filter = h->filter == RC_FILTER_F8;
@@ -612,6 +633,7 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
     p.mask_filter = mask_filter && mask != nullptr;
     p.metric = h->metric;  // non-cosine (RC_FILTER_METRIC): the filter and rescore kernels' metric forms
     p.norms = h->norms;
+    p.pages = pages;
     if (h->gtimer.enabled) h->gtimer.create();
     batched_search(p, h->bws, s, h->gtimer.enabled ? &h->gtimer : nullptr);
     int nblk = (int)std::min<int64_t>(h->bws.fb_blocks, std::max<int64_t>(1, (n_rows + 511) / 512));
@@ -622,14 +644,15 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
     a.flags = h->bws.flags;
     a.grid_y = std::min(nq, FB_QSTRIDE);
     a.mask = mask;
-    if (h->metric != RC_METRIC_COSINE) {  // the metric fallback kernel (scan_metric.h): raw queries, as every metric scan
-        a.metric = h->metric;
+    if (h->metric != RC_METRIC_COSINE || pages != nullptr) {  // the metric fallback kernel (scan_metric.h) and the paged
+        a.metric = h->metric;                                 // ones (scan_paged.h): raw queries, as every such scan
         a.norms = h->norms;
         a.qraw = queries;
         a.dim = h->dim;
         a.nq_real = nq;
     }
-    launch_scan(h, a);
+    if (pages != nullptr) launch_scan_paged(h, a, pages);
+    else launch_scan(h, a);
     launch_merge_partials(h, h->bws.fb_partial, h->bws.flags, nblk, nq, nq, k, scores, out_rows, s);
 }
 
@@ -1192,22 +1215,51 @@ int rc_index_pages_set(rc_index *h, int slot, const int32_t *pages_host, int n_p
 
 int rc_index_search_pages(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
                           float *scores, int64_t *out_rows, void *stream) {
+    return rc_index_search_pages_ex(h, queries, nq, slot, n_pos, k, mask, scores, out_rows, RC_SEARCH_SCAN, stream);
+}
+
+int rc_index_search_pages_ex(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
+                             float *scores, int64_t *out_rows, int mode, void *stream) {
     return guard([&] {
+        RC_REQUIRE(mode == RC_SEARCH_AUTO || mode == RC_SEARCH_SCAN || mode == RC_SEARCH_MFMA || mode == RC_SEARCH_MFMA_MASKED,
+                   RC_ERR_INVALID, "unknown search mode");
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
         RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
         RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
         RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
+        const bool mask_filter = mode == RC_SEARCH_MFMA_MASKED;  // without a mask it is RC_SEARCH_MFMA
+        if (mask_filter) mode = RC_SEARCH_MFMA;
         std::lock_guard<std::mutex> lk(h->mu);
         const rc_index::PageTable &t = page_table(h, slot);
         RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
         if (nq == 0) return;
+        // refused where rc_index_search_ex refuses the mode, and on the int8 and float8 filters, which
+        // have no paged form: the paged kernels are the native f16 / bf16 ones, cosine or RC_FILTER_METRIC
+        const bool metric_ok = h->metric == RC_METRIC_COSINE || h->filter == RC_FILTER_METRIC;
+        RC_REQUIRE(mode != RC_SEARCH_MFMA || metric_ok, RC_ERR_UNSUPPORTED,
+                   "batched MFMA search is cosine-only without RC_FILTER_METRIC (this index scores by dotproduct or euclidean)");
+        const bool mfma_ok = metric_ok && (h->dtype == RC_F16 || h->dtype == RC_BF16) && h->rows8 == nullptr &&
+                             (h->filter == RC_FILTER_NATIVE || h->filter == RC_FILTER_METRIC);
+        RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
+                   "batched MFMA search over pages needs an f16/bf16 index with the native or the metric filter");
+        RC_REQUIRE(mode != RC_SEARCH_MFMA || paged_filter_supported(h->ld, h->metric != RC_METRIC_COSINE, mask_filter && mask != nullptr),
+                   RC_ERR_UNSUPPORTED,
+                   "RC_SEARCH_MFMA_MASKED over pages is not available under a non-cosine metric at row width 512 (use RC_SEARCH_MFMA)");
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
         if (n_pos == 0) {  // this shard holds none of the slot's positions
             empty_search(nq, k, scores, out_rows, s);
             return;
         }
-        scan_search(h, queries, nq, n_pos, k, mask, scores, out_rows, s, t.dev);
+        // with a mask AUTO scans (as rc_index_search_masked, and the masked paged forms are unmeasured)
+        const bool auto_mfma = (nq >= kPagedBatchMinQueries && n_pos >= kPagedBatchMinPositions) ||
+                               (nq >= kPagedBatchMinQueriesLarge && n_pos >= kPagedBatchMinPositionsLarge);
+        const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && mask == nullptr && mfma_ok && auto_mfma);
+        if (!use_mfma) {
+            scan_search(h, queries, nq, n_pos, k, mask, scores, out_rows, s, t.dev);
+            return;
+        }
+        batched_search_exact(h, queries, nq, n_pos, k, mask, mask_filter, scores, out_rows, s, t.dev);
     });
 }
 

@@ -413,6 +413,10 @@ struct BatchPlan {
     // bound each row's metric score and read norms [n_rows]; the keys carry metric scores
     int metric = RC_METRIC_COSINE;
     const float *norms = nullptr;
+    // a slot's page table (rc_index_search_pages_ex), or null: n_rows, the mask, the candidates and
+    // the returned rows are then POSITIONS of that table, and the kernels are the PAGED forms
+    // (search_mfma_paged.hip; f16 / bf16 rows, native or metric filter)
+    const int32_t *pages = nullptr;
 };
 
 // The int8 filter keeps a row's scale and residual norm at a tile-transposed slot:
@@ -423,6 +427,8 @@ __host__ __device__ __forceinline__ int64_t i8_slot(int64_t row) {
 }
 bool i8_filter_supported(int64_t ld);  // row widths filter_i8_kernel is instantiated for
 bool f8_filter_supported(int64_t ld);  // ... and filter_f8_kernel
+// the paged native filter kernels (search_mfma_paged.hip): every form but ld 512 with METRIC and MASKED
+bool paged_filter_supported(int64_t ld, bool metric, bool mask_filter);
 
 // Enqueue the staged filter-GEMM / rescore search on `s` (no host sync).
 void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer);

@@ -9,7 +9,8 @@ namespace rc {
 // The contiguous scan's arguments read in position space (n_rows = the positions [0, n_pos) of
 // this shard; rows_per_block, mask and the keys are over positions), plus the device-resident
 // page table: ceil(n_pos / RC_PAGE_ROWS) int32 page numbers, each below capacity / RC_PAGE_ROWS.
-// Raw queries only (qraw; qn and flags are not used).
+// Raw queries only (qraw; qn is not used).  With flags (f16 / bf16 rows): the paged batched
+// search's exact fallback, grid.y striding over the flagged queries as in ScanArgs.
 struct PagedScanArgs {
     ScanArgs scan;
     const int32_t *pages;

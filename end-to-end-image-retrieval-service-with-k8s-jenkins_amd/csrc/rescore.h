@@ -1,7 +1,8 @@
 // rescore.h — the batched search's exact rescoring (search_mfma.hip's stages): the device code of
 // rescore_kernel and of its metric form, and the metric form's launch.  Included by
-// search_mfma.hip, which instantiates the cosine kernels, and by rescore_metric_{f16,bf16}.hip,
-// which instantiate launch_rescore_metric<T> for one storage dtype each: the metric kernels (96
+// search_mfma.hip, which instantiates the cosine kernels, by rescore_metric_{f16,bf16}.hip,
+// which instantiate launch_rescore_metric<T> for one storage dtype each, and by
+// rescore_paged_{f16,bf16}.hip, which do the same for the page-table form (launch_rescore_paged<T>): the metric kernels (96
 // instantiations) compile in two translation units of their own, in parallel with the rest.
 #pragma once
 
@@ -47,8 +48,9 @@ __global__ __launch_bounds__(256) void rescore_kernel(const T *__restrict__ rows
                                                      int *__restrict__ ovf_total, int final_pass, int64_t row_base,
                                                      int64_t row_stride, float *__restrict__ out_scores,
                                                      int64_t *__restrict__ out_rows, const uint32_t *__restrict__ mask) {
-    constexpr bool METRIC = false;
+    constexpr bool METRIC = false, PAGED = false;
     [[maybe_unused]] const float *const norms = nullptr, *const mcoef = nullptr;  // the metric form's arguments
+    [[maybe_unused]] const int32_t *const pages = nullptr;                        // the paged form's
 #include "rescore_body.inc"
 }
 template <typename T, int NCH, int CAP, bool MASKED>
@@ -59,8 +61,9 @@ __global__ __launch_bounds__(256) void rescore_metric_kernel(const T *__restrict
                                                             int64_t row_base, int64_t row_stride, float *__restrict__ out_scores,
                                                             int64_t *__restrict__ out_rows, const uint32_t *__restrict__ mask,
                                                             const float *__restrict__ norms, const float *__restrict__ mcoef) {
-    constexpr bool METRIC = true;
+    constexpr bool METRIC = true, PAGED = false;
     [[maybe_unused]] const float *const eps = nullptr;  // the cosine form's argument: thr takes no slack here
+    [[maybe_unused]] const int32_t *const pages = nullptr;
 #include "rescore_body.inc"
 }
 
@@ -79,6 +82,49 @@ void launch_rescore_metric(const BatchPlan &p, const BatchWs &ws, int final_pass
             };
             if (p.mask != nullptr) launch(std::true_type{});
             else launch(std::false_type{});
+        });
+    });
+    if (!ok) throw Error(RC_ERR_UNSUPPORTED, "unsupported row width");
+    RC_LAUNCH_CHECK();
+}
+
+// The page-table form of both (BatchPlan::pages, a named namespace's batched search): one kernel,
+// METRIC a template parameter (a new symbol either way).  `rows` and `norms` are the pool's, `cand`
+// holds positions, `mask` is over positions and the keys carry positions, so RC_EMIT_KEY yields
+// row_base + p·row_stride as the paged scan's merge does; eps is unused under METRIC, norms and
+// mcoef without it.  Instantiated in rescore_paged_{f16,bf16}.hip.
+template <typename T, int NCH, int CAP, bool MASKED, bool METRIC>
+__global__ __launch_bounds__(256) void rescore_paged_kernel(const T *__restrict__ rows, int64_t ld, const float *__restrict__ qn,
+                                                           int k, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ cand,
+                                                           int cap, uint64_t *__restrict__ keys, const float *__restrict__ eps,
+                                                           float *__restrict__ thr, int *__restrict__ flags,
+                                                           int *__restrict__ ovf_total, int final_pass, int64_t row_base,
+                                                           int64_t row_stride, float *__restrict__ out_scores,
+                                                           int64_t *__restrict__ out_rows, const uint32_t *__restrict__ mask,
+                                                           const float *__restrict__ norms, const float *__restrict__ mcoef,
+                                                           const int32_t *__restrict__ pages) {
+    constexpr bool PAGED = true;
+#include "rescore_body.inc"
+}
+
+template <typename T>
+void launch_rescore_paged(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
+    static_assert(sizeof(T) == 2, "the paged batched search serves f16 / bf16 rows");
+    const bool ok = with_nch<16, T>(p.nch, [&](auto nch) {
+        with_topk_cap(topk_cap(p.k), [&](auto cap) {
+            auto launch = [&](auto masked, auto metric) {
+                hipLaunchKernelGGL((rescore_paged_kernel<T, decltype(nch)::value, decltype(cap)::value, decltype(masked)::value,
+                                                         decltype(metric)::value>),
+                                   dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn, p.k, ws.cnt, ws.cand, ws.cap, ws.keys,
+                                   ws.eps, ws.thr, ws.flags, ws.ovf, final_pass, p.row_base, p.row_stride, p.out_scores, p.out_rows,
+                                   p.mask, p.norms, ws.mcoef, p.pages);
+            };
+            auto with_mask = [&](auto metric) {
+                if (p.mask != nullptr) launch(std::true_type{}, metric);
+                else launch(std::false_type{}, metric);
+            };
+            if (p.metric != RC_METRIC_COSINE) with_mask(std::true_type{});
+            else with_mask(std::false_type{});
         });
     });
     if (!ok) throw Error(RC_ERR_UNSUPPORTED, "unsupported row width");

@@ -1,7 +1,10 @@
 // rescore_body.inc — the body of rescore_kernel and rescore_metric_kernel (rescore.h), included
 // inside each kernel's braces.  In scope: T, NCH, CAP, MASKED, the kernels' arguments (each kernel
-// declares the ones only the other takes as null constants) and `constexpr bool METRIC`.  Text
-// inclusion, not a device function: the cosine kernels keep the instructions they had.
+// declares the ones only the other takes as null constants), `constexpr bool METRIC`, and
+// `constexpr bool PAGED` with (PAGED) `const int32_t *pages` (rescore_paged_kernel: the candidates,
+// the mask bits and the keys are POSITIONS of a page table, and only the row and norm address goes
+// through it, as scan_paged.h's scan).  Text inclusion, not a device function: the cosine kernels
+// keep the instructions they had.
     constexpr int EPC = RowShape<T, NCH>::EPC;
     constexpr int CPL = RowShape<T, NCH>::CPL;
     constexpr int U = 2;
@@ -40,6 +43,7 @@
     for (int j0 = wave * 4 * U; j0 < nn; j0 += 16 * U) {
         uint4 x[U][CPL];
         uint32_t rr[U];
+        [[maybe_unused]] uint32_t lr[U];  // PAGED: the local row of position rr[u]
         [[maybe_unused]] uint32_t mw[U];
         [[maybe_unused]] float nrm[U];
 #pragma unroll
@@ -47,6 +51,13 @@
             const int j = j0 + u * 4 + rg;
             rr[u] = cl[j < nn ? j : 0];
             if constexpr (MASKED) mw[u] = mask[rr[u] >> 5];
+            if constexpr (PAGED) {  // a candidate position is < r_end <= n_pos: inside the table
+                lr[u] = (uint32_t)pages[rr[u] / RC_PAGE_ROWS] * RC_PAGE_ROWS + rr[u] % RC_PAGE_ROWS;
+                if constexpr (METRIC) nrm[u] = norms[lr[u]];
+#pragma unroll
+                for (int i = 0; i < CPL; ++i) x[u][i] = base4[(int64_t)lr[u] * ld4 + sub + 16 * i];
+                continue;
+            }
             if constexpr (METRIC) nrm[u] = norms[rr[u]];  // a candidate row is < r_end <= n_rows
 #pragma unroll
             for (int i = 0; i < CPL; ++i) x[u][i] = base4[(int64_t)rr[u] * ld4 + sub + 16 * i];

@@ -163,6 +163,70 @@ __global__ __launch_bounds__(256, (scan_min_waves<T, NCH, QB, CAP>())) void scan
                                                        norms, mc);
 }
 
+// The exact fallback of the paged batched search (search_mfma_paged.hip; f16 / bf16 rows, the
+// dtypes that search serves), as scan_topk_kernel's fallback branch and scan_topk_metric_fallback_kernel:
+// block (b, y) scans its position range for the queries y, y + gridDim.y, ... whose candidate list
+// overflowed (flags: a block-uniform early exit for the others), one query per pass, each
+// normalised from the raw queries exactly as the kernel above does (so the keys are the paged
+// scan's, bit for bit); partial is [nblk][nq_total][k], merged by the existing merge under the flags.
+template <typename T, int NCH, int CAP, bool MASKED, bool METRIC>
+__global__ __launch_bounds__(256) void scan_topk_paged_fallback_kernel(
+    const T *__restrict__ rows, const float *__restrict__ norms, int64_t ld, int64_t n_pos, int64_t rows_per_block,
+    const int32_t *__restrict__ pages, int nq_total, int k, uint64_t *__restrict__ partial, const int *__restrict__ flags,
+    const float *__restrict__ qraw, int dim, const uint32_t *__restrict__ mask, int metric) {
+    constexpr int EPC = RowShape<T, NCH>::EPC;
+    constexpr int CPL = RowShape<T, NCH>::CPL;
+    const int lane = threadIdx.x & 63, sub = lane & 15;
+    for (int qf = blockIdx.y; qf < nq_total; qf += gridDim.y) {
+        if (!flags[qf]) continue;  // block-uniform
+        float q[1][CPL][EPC];
+        [[maybe_unused]] MetricCoef mc{};
+        const float *src = qraw + (int64_t)qf * dim;
+        float inv;
+        if constexpr (METRIC) {
+            const float ss = wave_sum_sq(src, dim, lane, true);
+            inv = inv_norm_of(ss);
+            mc = metric_coef(metric, ss);
+        } else {
+            inv = wave_inv_norm(src, dim, lane, true);
+        }
+#pragma unroll
+        for (int i = 0; i < CPL; ++i)
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) q[0][i][e] = RC_UNIT_ELEM(src, (sub + 16 * i) * EPC + e, dim, inv, true);
+        scan_rows_q_paged<T, NCH, 1, CAP, MASKED, METRIC>(rows, ld, n_pos, rows_per_block, pages, q, qf, nq_total, k, partial, mask,
+                                                          norms, mc);
+        __syncthreads();  // the next query reuses the LDS lists
+    }
+}
+
+// the fallback launch of both launchers below: grid.y strides over the queries
+template <typename T, bool METRIC>
+void launch_scan_paged_fallback(const PagedScanArgs &p) {
+    const ScanArgs &a = p.scan;
+    if constexpr (sizeof(T) == 2) {
+        if (a.qb != 1 || a.nq_real != a.nq_total || (METRIC && a.norms == nullptr))
+            throw Error(RC_ERR_INVALID, "internal: the paged fallback scan takes unpadded raw queries, one per pass");
+        const dim3 grid(a.nblk, a.grid_y);
+        const bool ok = with_nch<16, T>(a.nch, [&](auto nch) {
+            with_topk_cap(topk_cap(a.k), [&](auto cap) {
+                constexpr int NCH = decltype(nch)::value, CAP = decltype(cap)::value;
+                auto launch = [&](auto masked) {
+                    hipLaunchKernelGGL((scan_topk_paged_fallback_kernel<T, NCH, CAP, decltype(masked)::value, METRIC>), grid,
+                                       dim3(256), 0, a.stream, (const T *)a.rows, a.norms, a.ld, a.n_rows, a.rows_per_block, p.pages,
+                                       a.nq_total, a.k, a.partial, a.flags, a.qraw, a.dim, a.mask, a.metric);
+                };
+                if (a.mask != nullptr) launch(std::true_type{});
+                else launch(std::false_type{});
+            });
+        });
+        if (!ok) throw Error(RC_ERR_UNSUPPORTED, "unsupported row width");
+        RC_LAUNCH_CHECK();
+    } else {
+        throw Error(RC_ERR_INVALID, "internal: the paged fallback scan serves f16 / bf16 rows");
+    }
+}
+
 template <typename T, int NCH, int QB, int CAP, bool MASKED, bool METRIC>
 void launch_scan_paged_one(const PagedScanArgs &p) {
     const ScanArgs &a = p.scan;
@@ -172,8 +236,8 @@ void launch_scan_paged_one(const PagedScanArgs &p) {
 }
 
 inline void check_paged_args(const PagedScanArgs &p) {
-    if (p.pages == nullptr || p.scan.qraw == nullptr || p.scan.flags != nullptr)
-        throw Error(RC_ERR_INVALID, "internal: a paged scan takes a page table and raw queries, and has no fallback mode");
+    if (p.pages == nullptr || p.scan.qraw == nullptr)
+        throw Error(RC_ERR_INVALID, "internal: a paged scan takes a page table and raw queries");
 }
 
 // The instantiations of the contiguous scan (launch_scan_qb): multi-query passes up to CAP 256,
@@ -197,6 +261,7 @@ template <typename T>
 void launch_scan_paged(const PagedScanArgs &p) {
     check_paged_args(p);
     const ScanArgs &a = p.scan;
+    if (a.flags != nullptr) return launch_scan_paged_fallback<T, false>(p);  // the paged batched search's exact fallback
     const bool ok = with_nch<16, T>(a.nch, [&](auto nch) {
         constexpr int NCH = decltype(nch)::value;
         if constexpr (NCH <= 2) {  // queries per pass: scan_max_qb's register budget
@@ -215,6 +280,7 @@ template <typename T>
 void launch_scan_paged_metric(const PagedScanArgs &p) {
     check_paged_args(p);
     const ScanArgs &a = p.scan;
+    if (a.flags != nullptr) return launch_scan_paged_fallback<T, true>(p);
     if (a.norms == nullptr || a.qb != 1) throw Error(RC_ERR_INVALID, "internal: a metric scan takes one query per pass and the norms");
     const bool ok = with_nch<16, T>(a.nch, [&](auto nch) {
         with_topk_cap(topk_cap(a.k), [&](auto cap) {

@@ -31,29 +31,11 @@
 #include <algorithm>
 #include <vector>
 
+#include "filter_mfma.h"
 #include "index_common.h"
 #include "rescore.h"
 
 namespace rc {
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <typename T> struct MfmaOp;
-template <> struct MfmaOp<f16_t> {
-    typedef _Float16 v8 __attribute__((ext_vector_type(8)));
-    static __device__ __forceinline__ f32x4_t mma(v8 a, v8 b, f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct MfmaOp<bf16_t> {
-    typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-    static __device__ __forceinline__ f32x4_t mma(v8 a, v8 b, f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-
-constexpr int SB_TILE = 256;  // queries per query block = rows per row tile
 
 // ------------------------------------------------------ query preparation --
 // One wave per query slot q < nq_pad: qn = q/||q|| (f32, the exact rescoring
@@ -123,24 +105,6 @@ __global__ __launch_bounds__(64) void prepare_queries_metric_kernel(const float 
     }
 }
 
-// ------------------------------------------------------- filter GEMM -------
-struct FilterArgs {
-    const void *rows;  // [>= roundup(r_end, 256)][ld]
-    const void *qh;    // [nqb*256][ld]
-    int64_t ld;
-    int nkt;           // ld / 64
-    int64_t r_begin;   // multiple of 256
-    int64_t r_end;
-    int64_t tiles_per_chunk;
-    int nqb;
-    const float *thr;  // [nqb*256]
-    uint32_t *cnt;     // [nqb*256]
-    uint32_t *cand;    // [nqb*256][cap]
-    int cap;
-    // int8 filter only (filter_i8_kernel): per-row sx / ex at i8_slot(row), per-query sq / aq
-    const float *rsx = nullptr, *rex = nullptr, *sq = nullptr, *aq = nullptr;
-};
-
 // The int8 and float8 kernels take MASKED as a template parameter; their MASKED forms get the bitmap
 // beside the arguments, and the unmasked forms keep the kernel arguments they had.
 struct FilterArgsMasked {
@@ -149,135 +113,6 @@ struct FilterArgsMasked {
 };
 __device__ __forceinline__ const FilterArgs &filter_args(const FilterArgs &a) { return a; }
 __device__ __forceinline__ const FilterArgs &filter_args(const FilterArgsMasked &m) { return m.a; }
-
-// Block → (query block, row chunk), for tiles of RT rows: blocks b and b+8 share an XCD; the nqb
-// blocks of one chunk are consecutive on one XCD, so each row tile is read from HBM once and
-// served to the other query blocks from that XCD's L2.  The block's row tiles are [rt0, rt1)
-// (none: rt0 >= rt1, a block-uniform early return for the caller).
-struct FilterBlock {
-    int qb;
-    int64_t rt0, rt1;
-    __device__ __forceinline__ FilterBlock(const FilterArgs &a, int RT) {
-        const int b = blockIdx.x, xcd = b & 7, jx = b >> 3;
-        qb = jx % a.nqb;
-        const int64_t chunk = (int64_t)(jx / a.nqb) * 8 + xcd;
-        const int64_t rt_total = (a.r_end - a.r_begin + RT - 1) / RT;
-        rt0 = chunk * a.tiles_per_chunk;
-        rt1 = min(rt_total, rt0 + a.tiles_per_chunk);
-    }
-};
-
-// Row `row` passed query q's filter: append it to q's candidate list (the count keeps running
-// past cap: rescore_kernel reads an overflow from it).
-__device__ __forceinline__ void append_candidate(const FilterArgs &a, int q, int64_t row) {
-    const uint32_t pos = atomicAdd(&a.cnt[q], 1u);
-    if ((int)pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = (uint32_t)row;
-}
-
-// -------------------------------------- MASKED epilogues (RC_SEARCH_MFMA_MASKED) --
-// Every filter kernel has a MASKED form (a compile-time form, as scan_rows_q's and rescore_kernel's:
-// the unmasked kernels keep their instructions).  It reads the row-eligibility bitmap over the LOCAL
-// rows that rescore_kernel<.., MASKED> reads (bit r & 31 of word r >> 5) and appends (q, row) iff
-// the kernel's own test passes AND the row's bit is set.
-// Why it stays exact: the unmasked argument (the header's, the metric epilogue's, the int8 and float8
-// bounds) restricted to the eligible rows.  The result is the top-k of the eligible rows.  thr[q] comes
-// from rescore_kernel, which under a mask merges eligible rows only: it is the k-th best exact score
-// of the ELIGIBLE rows seen so far (minus eps[q]; -inf while fewer than k were seen), a lower bound of
-// the final k-th best eligible score, and it only rises.  An eligible row of the final top-k therefore
-// passes the kernel's test at its stage as before, and its bit is set: it is appended.  Ineligible
-// rows were never part of the result; leaving them out only shortens the lists, so a stage collects
-// ≈ k·(g - 1) candidates whatever the eligible share, where the unmasked filter under a mask collects
-// 1 / share times as many ("Masked search").  A clustered mask can still overflow a
-// stage: the flagged queries take the masked scan on the device, as before.
-// A row tile starts at a multiple of 64 rows, so its bits are whole words at a wave-uniform address:
-// scalar loads into scalar registers, issued a tile (or a K loop) ahead of the epilogue that reads
-// them.  A tile without an eligible row skips its epilogue on a wave-uniform branch (its loads and
-// MFMAs stay: they are one flattened pipeline).
-//
-// NW words of the 32·NW rows from `first_row` (a multiple of 64).  The bitmap holds ceil(r_end / 32)
-// words and the last tile reaches past r_end: the index is clamped to the last word (a read past the
-// bitmap is a fault) and a word wholly past r_end reads as 0.  Bits at or past r_end inside the last
-// word may be set: the epilogues keep their row < r_end test.
-template <int NW>
-__device__ __forceinline__ void load_mask_words(const uint32_t *__restrict__ mask, int64_t first_row, int64_t r_end,
-                                                uint32_t (&w)[NW]) {
-    // Through the constant address space (the bitmap does not change while a search runs): only
-    // there does the compiler load a uniform address with the scalar unit.  As a global load the
-    // words were vector registers held across the K loop, and the NKT 8 forms spilled.
-    typedef const __attribute__((address_space(4))) uint32_t *const_words;
-    const const_words cm = (const_words)mask;
-    const int64_t w0 = first_row >> 5, wl = (r_end - 1) >> 5;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        const uint32_t v = cm[min(w0 + i, wl)];
-        w[i] = w0 + i <= wl ? v : 0u;
-    }
-}
-// A lane's four consecutive rows of one f32 accumulator, their eligibility in bits 0-3 of e: the
-// ineligible ones become NaN ahead of the epilogue's maximum, so both levels of its early-out see
-// eligible rows only.  NaN and not -inf: while thr[q] is still -inf, -inf >= thr holds and the row
-// would be appended; NaN fails every >=, and fmaxf returns its other operand, so the maximum runs
-// over the eligible rows (-inf when the lane has none).
-__device__ __forceinline__ f32x4_t mask_ineligible4(f32x4_t v, uint32_t e) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (e >> j) & 1u ? v[j] : __builtin_nanf("");
-    return v;
-}
-
-// ---------------------------------------- metric epilogue (RC_FILTER_METRIC) --
-// Under dotproduct / euclidean the two native filter kernels below have a METRIC form: the same
-// GEMM, and an epilogue that bounds the row's METRIC score instead of testing the cosine.  (The
-// int8 and float8 filters have no such form: they stay cosine-only.)
-//
-// s' is the filter GEMM's accumulator for (query q, row r), c the exact cosine the scan and
-// rescore_kernel compute in f32 (RC_ROW_FMA16 + sum16), and |s' - c| <= eps[q] (the header's
-// bound, prepare_queries_kernel's eps).  With n = norms[r] and (alpha, beta, gamma) the query's
-// metric_coef constants, the filter keeps (q, r) iff
-//     u = metric_score(mc, ĉ, n) >= thr[q],     ĉ = s' + eps[q]   (one f32 add)
-// where under a metric thr[q] is the running k-th best EXACT metric score itself (-inf until k
-// rows are held), with no eps subtracted (rescore_candidates).
-// Exact, because u >= the row's exact score s = metric_score(mc, c, n), bit for bit:
-//   * ĉ >= c.  The real number s' + eps is >= c; rounding to nearest is monotone and c is an f32,
-//     so fl(s' + eps) >= fl(c) = c: the add's rounding cannot take ĉ below c.
-//   * t(x) = fmaf(alpha, x, -(beta·n)) is non-decreasing in x for alpha >= 0 (alpha is ‖q‖ or
-//     2‖q‖): the exact alpha·x - fl(beta·n) is, and a correctly rounded FMA is a monotone
-//     function of its exact value.  The addend fl(beta·n) is the same f32 on both sides.
-//   * s(t) = fmaf(n, t, -gamma) is non-decreasing in t for n >= 0 (a norm), likewise.
-//   So ĉ >= c gives u = s(t(ĉ)) >= s(t(c)) = s: no second slack term.  The running k-th best only
-//   rises, so every row of the final top-k has s >= thr[q] at its stage, hence u >= thr[q]; rows
-//   tied with the k-th score pass because the test is >=.
-// The per-row arithmetic is metric_score itself (one copy, index_common.h), so the three roundings
-// are the scan's.  In these epilogues a lane owns one query and four consecutive rows per
-// accumulator: the constants are per lane, loaded as prepared (metric_coef assumes a wave-uniform
-// query and is not called here), and a lane's four norms are one aligned 16-byte load.
-// norms holds `capacity` floats, not the padded row count, and the last row tile reaches past
-// r_end: the norm index is clamped to r_end - 1 (as the metric scan loads its norms under the
-// rows' clamp).  A row >= r_end then gets some u, which can only defeat the wave-uniform
-// early-out: the append still tests row < r_end.
-// The epilogues overwrite the accumulators with u and then run the cosine epilogue's own test on
-// them (the maximum of u as the wave-uniform early-out, then u >= thr per row): no second copy of
-// the tile in registers.  The norm loads sit in the epilogue itself, so each tile's epilogue waits
-// for the row DMA in flight before it (vector-memory loads return in order); DESIGN.md, "Metric
-// filter", has what that costs against the cosine launch.
-struct FilterMetric {
-    const float *norms;  // [>= r_end]
-    const float *mcoef;  // [nqb*256][4]: eps, alpha, beta, gamma
-};
-
-// norms of a row tile's rows o .. o + 3 (o a multiple of 4): tn = the norm of the tile's first row
-// (wave-uniform), left >= 1 = how many of the tile's rows are below r_end; indices clamped to
-// left - 1.  Offsets in 32 bits against the uniform base: one address register per load.
-__device__ __forceinline__ f32x4_t load_norms4(const float *__restrict__ tn, int o, int left) {
-    if (o + 4 <= left) return *reinterpret_cast<const f32x4_t *>(tn + o);
-    f32x4_t v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = tn[min(o + j, left - 1)];
-    return v;
-}
-// u of the comment above: k4 =(eps, alpha, beta, gamma) of the lane's query
-__device__ __forceinline__ float metric_upper(const f32x4_t &k4, float sp, float n) {
-    return metric_score(MetricCoef{k4[1], k4[2], k4[3]}, sp + k4[0], n);
-}
 
 // 256x256x64 tile, 512 threads = 8 waves in two groups (G0 = waves 0-3 own
 // query rows 0-127, G1 = waves 4-7 rows 128-255; wave w and w+4 share a SIMD).
@@ -298,18 +133,21 @@ __global__ __launch_bounds__(512, 1) void filter_gemm_kernel(FilterArgs a) {
     constexpr bool METRIC = false, MASKED = false;
     [[maybe_unused]] const FilterMetric fm{};
     [[maybe_unused]] const uint32_t *const mask = nullptr;
+    RC_FILTER_NOT_PAGED
 #include "filter_gemm_body.inc"
 }
 template <typename T>
 __global__ __launch_bounds__(512, 1) void filter_gemm_metric_kernel(FilterArgs a, FilterMetric fm) {
     constexpr bool METRIC = true, MASKED = false;
     [[maybe_unused]] const uint32_t *const mask = nullptr;
+    RC_FILTER_NOT_PAGED
 #include "filter_gemm_body.inc"
 }
 // the MASKED form of both (new kernels, so a template parameter costs no existing symbol; cosine: fm unused)
 template <typename T, bool METRIC>
 __global__ __launch_bounds__(512, 1) void filter_gemm_masked_kernel(FilterArgs a, FilterMetric fm, const uint32_t *mask) {
     constexpr bool MASKED = true;
+    RC_FILTER_NOT_PAGED
 #include "filter_gemm_body.inc"
 }
 
@@ -333,7 +171,7 @@ __global__ __launch_bounds__(512, 1) void filter_gemm_masked_kernel(FilterArgs a
 // its latency.  (A 4-wave form with 64 queries per wave pinned in AGPRs and
 // inline-asm MFMAs was measured against it in round 2 — within 1 %, behind after
 // the 2-GB sub-launches — and removed.)
-constexpr int QS_QT = 2, QS_RT = 128, QS_NS = 8;  // queries/16 per wave, rows per tile, LDS ring steps
+// (QS_QT, QS_RT, QS_NS: filter_mfma.h)
 
 // ABL (A/B diagnostics, diagnostic builds only; 0 in production): bit0 no DMA in the
 // loop, bit1 no MFMA, bit2 no fragment reads (MFMAs on the query registers), bit3 no
@@ -345,6 +183,7 @@ __global__ __launch_bounds__(512, 1) void filter_qs_kernel(FilterArgs a) {
     constexpr bool METRIC = false, MASKED = false;
     [[maybe_unused]] const FilterMetric fm{};
     [[maybe_unused]] const uint32_t *const mask = nullptr;
+    RC_FILTER_NOT_PAGED
 #include "filter_qs_body.inc"
 }
 template <typename T, int NKT>
@@ -352,6 +191,7 @@ __global__ __launch_bounds__(512, 1) void filter_qs_metric_kernel(FilterArgs a, 
     constexpr bool METRIC = true, MASKED = false;
     constexpr int ABL = 0;
     [[maybe_unused]] const uint32_t *const mask = nullptr;
+    RC_FILTER_NOT_PAGED
 #include "filter_qs_body.inc"
 }
 // the MASKED form of both (as filter_gemm_masked_kernel)
@@ -359,6 +199,7 @@ template <typename T, int NKT, bool METRIC>
 __global__ __launch_bounds__(512, 1) void filter_qs_masked_kernel(FilterArgs a, FilterMetric fm, const uint32_t *mask) {
     constexpr bool MASKED = true;
     constexpr int ABL = 0;
+    RC_FILTER_NOT_PAGED
 #include "filter_qs_body.inc"
 }
 
@@ -1029,11 +870,15 @@ __global__ __launch_bounds__(512, 1) void filter_f8_kernel(std::conditional_t<MA
 // rescore_metric_{f16,bf16}.hip, not here.
 extern template void launch_rescore_metric<f16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
 extern template void launch_rescore_metric<bf16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
+// ... and the page-table form of both (BatchPlan::pages) in rescore_paged_{f16,bf16}.hip
+extern template void launch_rescore_paged<f16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
+extern template void launch_rescore_paged<bf16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
 
 // ------------------------------------------------------------------ host ---
 template <typename T>
 void launch_rescore(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
     if constexpr (sizeof(T) == 2) {  // the metric filter's dtypes: f16 / bf16
+        if (p.pages != nullptr) return launch_rescore_paged<T>(p, ws, final_pass, s);  // candidates are positions
         if (p.metric != RC_METRIC_COSINE) return launch_rescore_metric<T>(p, ws, final_pass, s);
     }
     // (float8 rows: the even widths up to 768, what the float8 filter serves)
@@ -1120,6 +965,7 @@ void run_batched(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *ti
         const int64_t tpc = (rt_total + nchunk - 1) / nchunk;
         FilterArgs fa{p.rows, ws.qh, p.ld, (int)(p.ld / 64), c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap};
         const int nkt = (int)(p.ld / 64);
+        if (p.pages != nullptr) return launch_filter_paged<T>(p, ws, fa, nchunk, nqb, s);  // the PAGED forms (search_mfma_paged.hip)
         if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED: the MASKED forms (cosine: fm is not read)
             const FilterMetric fm{p.norms, ws.mcoef};
             auto launch = [&](auto m) {
@@ -1268,6 +1114,9 @@ void filter_scores_f8(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, 
 void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
     RC_REQUIRE(p.ld % 64 == 0, RC_ERR_UNSUPPORTED, "batched search needs ld % 64 == 0");
     RC_REQUIRE(p.n_rows > 0, RC_ERR_INVALID, "batched search over an empty range");
+    if (p.pages != nullptr)  // the int8 and float8 filters have no paged form
+        RC_REQUIRE((p.dtype == RC_F16 || p.dtype == RC_BF16) && !p.f8_filter && p.rows8 == nullptr, RC_ERR_UNSUPPORTED,
+                   "batched MFMA search over pages needs an f16 or bf16 index with the native or the metric filter");
     if (p.metric != RC_METRIC_COSINE)  // the native kernels' METRIC forms only: the int8 and float8 filters are cosine-only
         RC_REQUIRE((p.dtype == RC_F16 || p.dtype == RC_BF16) && !p.f8_filter && p.rows8 == nullptr && p.norms != nullptr,
                    RC_ERR_UNSUPPORTED, "batched MFMA search under a non-cosine metric needs an f16 or bf16 index with RC_FILTER_METRIC");

@@ -819,7 +819,7 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
         if (masked) stage_mask(h, mask, n_rows, ls);
         auto shard_search = [&](int s, const float *q, int64_t n_local, float *so, int64_t *ro, void *st) {
             const uint32_t *m = masked ? h->mk_d[s] : nullptr;
-            return slot >= 0 ? rc_index_search_pages(h->shard[s], q, nq, slot, n_local, k, m, so, ro, st)
+            return slot >= 0 ? rc_index_search_pages_ex(h->shard[s], q, nq, slot, n_local, k, m, so, ro, mode, st)
                              : rc_index_search_masked(h->shard[s], q, nq, n_local, k, m, so, ro, mode, st);
         };
         if (h->n == 1) {
@@ -964,7 +964,8 @@ void query_host_checked(rc_sharded *h, const float *queries, int nq, int64_t n_r
         RC_HIP(hipMemcpyAsync(h->qd + L.q, h->qh + L.q, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, h->qs));
         float *dsc = (float *)(h->qd + L.sc);
         int64_t *drw = (int64_t *)(h->qd + L.rw);
-        search_locked(h, (const float *)(h->qd + L.q), nq, n_rows, k, dsc, drw, RC_SEARCH_AUTO, h->qs, mask, slot);
+        search_locked(h, (const float *)(h->qd + L.q), nq, n_rows, k, dsc, drw, slot >= 0 ? RC_SEARCH_SCAN : RC_SEARCH_AUTO, h->qs, mask,
+                      slot);  // a slot scans, as before the paged batched search
         if (dev_values) {
             if (slot >= 0) index_fetch_pages(h->shard[0], slot, n_rows, drw, nk, (float *)(h->qd + L.val), h->qs);
             else check_status(rc_index_fetch(h->shard[0], drw, nk, (float *)(h->qd + L.val), h->qs));
@@ -1024,7 +1025,14 @@ int rc_sharded_pages_set(rc_sharded *h, int slot, const int32_t *pages_host, int
 
 int rc_sharded_search_pages(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
                             float *scores, int64_t *out_rows, void *stream) {
+    return rc_sharded_search_pages_ex(h, queries, nq, slot, n_pos, k, mask, scores, out_rows, RC_SEARCH_SCAN, stream);
+}
+
+int rc_sharded_search_pages_ex(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
+                               float *scores, int64_t *out_rows, int mode, void *stream) {
     return guard([&] {
+        RC_REQUIRE(mode == RC_SEARCH_AUTO || mode == RC_SEARCH_SCAN || mode == RC_SEARCH_MFMA || mode == RC_SEARCH_MFMA_MASKED,
+                   RC_ERR_INVALID, "unknown search mode");
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
         RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
         RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
@@ -1032,7 +1040,7 @@ int rc_sharded_search_pages(rc_sharded *h, const float *queries, int nq, int slo
         std::lock_guard<std::mutex> lk(h->mu);
         (void)page_list(h, slot, n_pos);
         if (nq == 0) return;
-        search_locked(h, queries, nq, n_pos, k, scores, out_rows, RC_SEARCH_SCAN, stream, mask, slot);
+        search_locked(h, queries, nq, n_pos, k, scores, out_rows, mode, stream, mask, slot);  // every shard takes the mode
     });
 }
 

@@ -267,10 +267,16 @@ class DeviceIndex:
         check(self.lib.rc_index_pages_set(self.handle, int(slot), arr.ctypes.data if arr.size else None, int(arr.size),
                                           stream_ptr(stream)))
 
-    def search_pages(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None):
-        """``search(mode="scan")`` over positions [0, n_pos) of a slot (rc_index_search_pages): the
-        rows returned are ``row_base + position * row_stride``.  ``mask``: an optional device
-        bitmap over the positions, as ``search`` takes one over the rows."""
+    def search_pages(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None, mode: str = "scan"):
+        """``search`` over positions [0, n_pos) of a slot (rc_index_search_pages_ex): the rows
+        returned are ``row_base + position * row_stride``.  ``mask``: an optional device bitmap
+        over the positions, as ``search`` takes one over the rows.  ``mode``: "scan" (default),
+        "mfma" / "mfma_masked" (the batched MFMA search over the slot's pages: an f16/bf16 index
+        with the native or the "metric" filter, else the library's unsupported error; the scan's
+        bits) or "auto" (scans with a mask; without one the batched search where it is available,
+        from 64 queries over 65536 positions or 16 queries over 262144)."""
+        if mode not in _lib.SEARCH_MODES:
+            raise ValueError(f"unknown search mode {mode!r}")
         q = self._vecs(queries)
         nq = q.shape[0]
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
@@ -279,8 +285,8 @@ class DeviceIndex:
             if mask.dtype not in (torch.int32, torch.uint32) or mask.numel() < (int(n_pos) + 31) // 32:
                 raise ValueError("mask must hold ceil(n_pos / 32) 32-bit words")
             mask = mask.to(device=self.device).contiguous()
-        check(self.lib.rc_index_search_pages(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), ptr(mask), ptr(scores),
-                                             ptr(rows), stream_ptr(stream)))
+        check(self.lib.rc_index_search_pages_ex(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), ptr(mask), ptr(scores),
+                                                ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
     def export_rows(self, row0: int, n: int, stream=None):
@@ -786,10 +792,13 @@ class ShardSet:
         arr = np.ascontiguousarray(page_list, dtype=np.int32).reshape(-1)
         check(self.lib.rc_sharded_pages_set(self.handle, int(slot), arr.ctypes.data if arr.size else None, int(arr.size)))
 
-    def search_pages(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None):
-        """``search(mode="scan")`` over the positions [0, n_pos) of a slot: (scores, positions),
-        bit-identical to a dense ShardSet of as many shards holding the slot's vectors in
-        position order.  ``mask``: an optional HOST uint32 bitmap over the positions."""
+    def search_pages(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None, mode: str = "scan"):
+        """``search`` over the positions [0, n_pos) of a slot: (scores, positions), bit-identical
+        to a dense ShardSet of as many shards holding the slot's vectors in position order.
+        ``mask``: an optional HOST uint32 bitmap over the positions.  ``mode``: as
+        ``DeviceIndex.search_pages``; every shard takes it (rc_sharded_search_pages_ex)."""
+        if mode not in _lib.SEARCH_MODES:
+            raise ValueError(f"unknown search mode {mode!r}")
         if queries.dim() == 1:
             queries = queries[None]
         q = queries.to(device=self.device, dtype=torch.float32).contiguous()
@@ -797,8 +806,9 @@ class ShardSet:
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         m = None if mask is None else self._host_mask(mask, n_pos)
-        check(self.lib.rc_sharded_search_pages(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k),
-                                               None if m is None else m.ctypes.data, ptr(scores), ptr(rows), stream_ptr(stream)))
+        check(self.lib.rc_sharded_search_pages_ex(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k),
+                                                  None if m is None else m.ctypes.data, ptr(scores), ptr(rows),
+                                                  _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
     def query_host_pages(self, q: np.ndarray, k: int, slot: int, n_pos: int, with_values: bool, mask=None):
@@ -963,12 +973,24 @@ class Index:
     costs what the namespace holds, not what the pool holds, and gives the scores, order and
     ties of an index holding that namespace alone.  A namespace exists while it holds a
     vector.  In a named namespace ``query_batch`` takes ``mode="auto"`` or ``"scan"``
-    (``"mfma"`` / ``"mfma_masked"`` raise ``ValueError``: no batched search over pages).
+    (``"mfma"`` / ``"mfma_masked"`` raise ``ValueError``) unless the index was made with
+    ``paged_search="mfma"``: then ``query_batch`` there takes all four modes and hands them to
+    the batched MFMA search over the namespace's pages (``ShardSet.search_pages(mode=...)``;
+    ``"auto"`` scans under a metadata filter and otherwise follows the library's measured
+    rule), with the scan's ids and score bits.  That needs an f16/bf16 index with
+    ``filter="native"`` or ``"metric"`` (the pool gets the metric filter when the index has it);
+    anything else raises ``ValueError`` at construction.  ``paged_search="scan"`` (default)
+    changes nothing; ``query`` always scans.
     """
 
     def __init__(self, name: str, dimension: int = 768, metric: str = "cosine", dtype: str = "float32",
                  capacity: int = 1 << 20, device=None, shards: int | None = None, devices=None,
-                 filter: str = "native"):
+                 filter: str = "native", paged_search: str = "scan"):
+        if paged_search not in ("scan", "mfma"):
+            raise ValueError(f"unknown paged_search {paged_search!r} (expected 'scan' or 'mfma')")
+        if paged_search == "mfma" and (_lib.is_f8(dtype) or dtype in ("float32", "f32") or filter in ("i8", "f8")):
+            raise ValueError("paged_search='mfma' runs the native f16 / bf16 kernels over pages: it needs dtype float16 or "
+                             f"bfloat16 and filter 'native' or 'metric' (dtype={dtype!r}, filter={filter!r})")
         if metric not in _lib.METRICS:
             raise ValueError(f"unknown metric {metric!r} (expected one of {sorted(_lib.METRICS)})")
         if filter not in _lib.FILTERS:
@@ -986,6 +1008,7 @@ class Index:
         self.name = name
         self.dimension = int(dimension)
         self.metric = metric
+        self.paged_search = paged_search
         n = len(devices)
         self._set = ShardSet(self.dimension, dtype=dtype, capacity_per_shard=max(1, -(-int(capacity) // n)),
                              devices=devices, metric=metric)
@@ -1170,6 +1193,8 @@ class Index:
             per = POOL_INITIAL_PAGES * pages.PAGE_ROWS
             self._pool = ShardSet(self.dimension, dtype=self._set.dtype, capacity_per_shard=per,
                                   devices=list(self._set.devices), metric=self.metric)
+            if self.paged_search == "mfma" and self._set.filter == "metric":  # else the pool stays native
+                self._pool.set_filter("metric")
             self._alloc.set_capacity(per // pages.PAGE_ROWS)
         return self._pool
 
@@ -1461,7 +1486,10 @@ class Index:
         ``MASKED_MFMA_MIN_SHARE``, and below it the MFMA path with the mask inside the filter
         GEMM (``mode="mfma_masked"``) where ``_masked_mode``'s measured rule allows; otherwise
         the masked scan.  ``namespace``: a named namespace scans its own pages (``mode`` "auto" or
-        "scan" there; "mfma" / "mfma_masked" raise ``ValueError``)."""
+        "scan" there; "mfma" / "mfma_masked" raise ``ValueError``), unless the index has
+        ``paged_search="mfma"``: then all four modes go down to the batched MFMA search over the
+        namespace's pages ("auto" scans under a metadata filter, and otherwise follows the
+        library's rule)."""
         if top_k < 1 or top_k > _lib.RC_TOPK_MAX:
             raise ValueError(f"top_k must be in [1, {_lib.RC_TOPK_MAX}]")
         if isinstance(vectors, torch.Tensor):
@@ -1474,15 +1502,17 @@ class Index:
         if namespace:
             if mode not in _lib.SEARCH_MODES:
                 raise ValueError(f"unknown search mode {mode!r}")
-            if mode not in ("auto", "scan"):
-                raise ValueError(f"mode={mode!r} is not available in a named namespace: there is no batched MFMA search "
-                                 "over pages (use 'auto' or 'scan')")
+            if self.paged_search != "mfma":
+                if mode not in ("auto", "scan"):
+                    raise ValueError(f"mode={mode!r} is not available in a named namespace of this index (use 'auto' or "
+                                     "'scan'): the batched MFMA search over pages is enabled with Index(..., paged_search='mfma')")
+                mode = "scan"
             with self._mu:
                 ns = self._ns.get(namespace)
                 if ns is None:
                     res = [[] for _ in range(q.shape[0])]
                 else:
-                    res = self._query_locked(q, top_k, include_values, include_metadata, "scan", self._bitmap_locked(filter, ns), ns)
+                    res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter, ns), ns)
             return [{"matches": m, "namespace": namespace} for m in res]
         with self._mu:
             res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter))
@@ -1539,8 +1569,9 @@ class Index:
 
     def _query_locked(self, q: torch.Tensor, k: int, include_values: bool, include_metadata: bool,
                       mode: str = "auto", bitmap=None, ns: _Namespace | None = None) -> list[list[dict]]:
-        """``ns``: a named namespace's state — the paged scan over its pages; the rows that come
-        back are its positions, mapped to pool rows where values are fetched."""
+        """``ns``: a named namespace's state — the paged search over its pages (``mode`` as
+        ``query_batch`` resolved it: "scan" unless the index has ``paged_search="mfma"``); the rows
+        that come back are its positions, mapped to pool rows where values are fetched."""
         st = self if ns is None else ns
         n = len(st._ids)
         if n == 0 or q.shape[0] == 0:
@@ -1548,7 +1579,8 @@ class Index:
         if bitmap is not None and bitmap[1] == 0:  # nothing is eligible: no device work
             return [[] for _ in range(q.shape[0])]
         if ns is not None:
-            scores, rows = self._pool.search_pages(q, k, ns.slot, n, mask=None if bitmap is None else bitmap[0])
+            # (under a metadata filter the library's "auto" scans: the masked paged forms are unmeasured)
+            scores, rows = self._pool.search_pages(q, k, ns.slot, n, mask=None if bitmap is None else bitmap[0], mode=mode)
         elif bitmap is None:
             scores, rows = self._set.search(q, k, n, mode=mode)
         else:
@@ -1705,7 +1737,7 @@ class Index:
 
     @classmethod
     def load(cls, path: str, capacity: int | None = None, device=None, shards: int | None = None,
-             devices=None, filter: str | None = None) -> "Index":
+             devices=None, filter: str | None = None, paged_search: str = "scan") -> "Index":
         import numpy as np
 
         with open(os.path.join(path, "manifest.json")) as f:
@@ -1715,7 +1747,7 @@ class Index:
         n = int(man["count"])
         idx = cls(man["name"], dimension=man["dimension"], metric=man["metric"], dtype=man["dtype"],
                   capacity=max(int(capacity or man.get("capacity", 0)), n, 1), device=device, shards=shards,
-                  devices=devices, filter=filter or man.get("filter", "native"))
+                  devices=devices, filter=filter or man.get("filter", "native"), paged_search=paged_search)
         if idx._set.ld != man["ld"]:
             raise ValueError("snapshot row layout does not match this build")
         rows = np.load(os.path.join(path, "rows.npy"), allow_pickle=False)

@@ -376,7 +376,21 @@ int rc_sharded_set_metric(rc_sharded *h, int metric);
  * vectors in position order, searched with RC_SEARCH_SCAN (the scan kernels' paged
  * form; the same merges).  Rows of the last page at or past n_pos are never scored.
  * mask: a bitmap over positions (as rc_index_search_masked / rc_sharded_search_masked
- * over rows), or NULL.  There is no batched MFMA search over pages.
+ * over rows), or NULL.
+ *
+ * rc_*_search_pages_ex takes a search mode, one of RC_SEARCH_*, as rc_index_search_masked
+ * does; rc_*_search_pages is RC_SEARCH_SCAN.  RC_SEARCH_MFMA / RC_SEARCH_MFMA_MASKED run
+ * the batched MFMA search over the slot's pages (the page-table forms of the native
+ * f16 / bf16 filter, rescore and fallback kernels; cosine, or dotproduct / euclidean with
+ * RC_FILTER_METRIC): the same bits as RC_SEARCH_SCAN, ties included.  They return
+ * RC_ERR_UNSUPPORTED where rc_index_search_ex refuses them and on an index whose filter
+ * is RC_FILTER_I8 or RC_FILTER_F8, which have no paged form.  RC_SEARCH_MFMA_MASKED
+ * without a mask is RC_SEARCH_MFMA; with one it is refused (RC_ERR_UNSUPPORTED) under a
+ * non-cosine metric at row width 512, the one form that is not built.  RC_SEARCH_AUTO scans with a mask, and without one
+ * takes the batched search where it is available and measured ahead of the paged scan:
+ * from 64 queries over 65536 positions per shard, or 16 queries over 262144 (DESIGN.md,
+ * "Namespaces").  An unknown mode is RC_ERR_INVALID.  Queries
+ * whose candidates overflow count in rc_index_gemm_timing_read's fallbacks.
  *
  * rc_*_pages_set installs or replaces a slot's table (n_pages = 0 frees it): a
  * device-resident int32 array per shard, one allocation per slot and shard, doubled
@@ -390,9 +404,13 @@ int rc_sharded_set_metric(rc_sharded *h, int metric);
 int rc_index_pages_set(rc_index *h, int slot, const int32_t *pages_host, int n_pages, void *stream);
 int rc_index_search_pages(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
                           const uint32_t *mask, float *scores, int64_t *out_rows, void *stream);
+int rc_index_search_pages_ex(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                             const uint32_t *mask, float *scores, int64_t *out_rows, int mode, void *stream);
 int rc_sharded_pages_set(rc_sharded *h, int slot, const int32_t *pages_host, int n_pages);
 int rc_sharded_search_pages(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
                             const uint32_t *mask, float *scores, int64_t *out_rows, void *stream);
+int rc_sharded_search_pages_ex(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                               const uint32_t *mask, float *scores, int64_t *out_rows, int mode, void *stream);
 /* rc_sharded_query_host_masked over a slot: host in, host out, one H2D copy, the paged
  * search, the matched positions' values (gathered through the table), one D2H copy,
  * one synchronisation.  out_rows are positions. */
