@@ -153,6 +153,9 @@ SIGNATURES = {
     "rc_sharded_pages_set": (C.c_int, [_vp, _i32, _vp, _i32]),
     "rc_sharded_search_pages": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
     "rc_sharded_query_host_pages": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rc_meta_write": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "rc_meta_move": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp]),
+    "rc_meta_eval": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
     "rc_index_timing": (C.c_int, [_vp, _i32]),
     "rc_index_timing_read": (C.c_int, [_vp, _pd, _pi64, _pd]),
     "rc_model_create": (C.c_int, [_i32, C.POINTER(VitConfig), C.POINTER(_vp)]),

@@ -10,6 +10,11 @@ from __future__ import annotations
 import os
 
 
+def comma_list(text: str) -> list[str]:
+    """The non-empty, stripped entries of a comma-separated setting."""
+    return [f.strip() for f in text.split(",") if f.strip()]
+
+
 class Config:
     # reference: Config for Pinecone (INPUT_RESOLUTION is the embedding dimension)
     INDEX_NAME = "mlops1-project"
@@ -32,6 +37,9 @@ class Config:
     INDEX_FILTER = os.getenv("RC_INDEX_FILTER", "native")
     # Pinecone's create_index(metric=...): "cosine" (the reference's), "dotproduct" or "euclidean"
     INDEX_METRIC = os.getenv("RC_INDEX_METRIC", "cosine")
+    # metadata fields kept as device columns (Index(metadata_config={"indexed": [...]})): a comma
+    # list of field names; empty (the default) = none, metadata filters are evaluated on the host
+    INDEX_METADATA_FIELDS = comma_list(os.getenv("RC_INDEX_METADATA_FIELDS", ""))
     # index shards: RC_INDEX_DEVICES = "all" (one shard per visible GPU) or a comma list
     # of device ordinals ("0,1,2,3"); otherwise RC_INDEX_SHARDS shards on the current GPU
     INDEX_DEVICES = os.getenv("RC_INDEX_DEVICES", "")

@@ -23,7 +23,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 import torch
 
-from . import _lib, compaction, metafilter, pages
+from . import _lib, compaction, metacolumns, metafilter, pages
 from ._lib import check, ptr, stream_ptr
 
 # query_batch(filter=..., mode="auto") takes the batched MFMA path when the unmasked conditions
@@ -981,11 +981,23 @@ class Index:
     ``filter="native"`` or ``"metric"`` (the pool gets the metric filter when the index has it);
     anything else raises ``ValueError`` at construction.  ``paged_search="scan"`` (default)
     changes nothing; ``query`` always scans.
+
+    ``metadata_config={"indexed": ["field", ...]}`` (Pinecone's pod-index knob; default ``None``)
+    keeps the named metadata fields as typed columns on the leader device (``metacolumns``: 9
+    bytes per row and field), and a metadata filter over those fields becomes its bitmap in one
+    kernel (``rc_meta_eval``) instead of a Python pass over every row.  Results never change:
+    the bitmap is bit-identical to ``metafilter.build_bitmap``'s, and a filter that names another
+    field, a field holding a value without a column encoding (a list, ``None``, ...: the field is
+    demoted for the life of the object) or an operand without one is evaluated on the host as
+    before.  ``metadata_index_stats()`` reports which path ran.  Anything but a dict with exactly
+    the key ``"indexed"`` and a list of distinct non-empty names not starting with ``$`` raises
+    ``ValueError``.
     """
 
     def __init__(self, name: str, dimension: int = 768, metric: str = "cosine", dtype: str = "float32",
                  capacity: int = 1 << 20, device=None, shards: int | None = None, devices=None,
-                 filter: str = "native", paged_search: str = "scan"):
+                 filter: str = "native", paged_search: str = "scan", metadata_config: dict | None = None):
+        indexed = metacolumns.validate_config(metadata_config)
         if paged_search not in ("scan", "mfma"):
             raise ValueError(f"unknown paged_search {paged_search!r} (expected 'scan' or 'mfma')")
         if paged_search == "mfma" and (_lib.is_f8(dtype) or dtype in ("float32", "f32") or filter in ("i8", "f8")):
@@ -1033,6 +1045,12 @@ class Index:
         self._alloc = pages.PageAllocator()
         self._free_slots: list[int] = []
         self._next_slot = 0
+        # metadata columns (metadata_config): the host state both column sets share, the default
+        # namespace's set (by global row) and the pool's (by pool row, made with the pool)
+        self.metadata_config = None if indexed is None else {"indexed": list(indexed)}
+        self._fields = None if indexed is None else metacolumns.FieldIndex(indexed)
+        self._cols = metacolumns.Columns(len(indexed), self._set.capacity, self._set.device) if indexed else None
+        self._pool_cols: "metacolumns.Columns | None" = None
 
     @property
     def shard_set(self) -> ShardSet:
@@ -1184,6 +1202,7 @@ class Index:
             else:
                 rows = self._plan_rows(items)
                 self._device_write(self._set.upsert_parts, split(rows))
+                self._device_write(self._columns_write, self._cols, self._set, rows, items)
                 self._commit_rows(items, rows)
         return {"upserted_count": len(items)}
 
@@ -1196,6 +1215,8 @@ class Index:
             if self.paged_search == "mfma" and self._set.filter == "metric":  # else the pool stays native
                 self._pool.set_filter("metric")
             self._alloc.set_capacity(per // pages.PAGE_ROWS)
+            if self._cols is not None:  # the pool's metadata columns, by pool row; they grow with it
+                self._pool_cols = metacolumns.Columns(self._cols.n_fields, self._pool.capacity, self._pool.device)
         return self._pool
 
     def _take_pages(self, count: int) -> list[int]:
@@ -1232,7 +1253,9 @@ class Index:
         gained = self._take_pages(pages.pages_for(nxt, self._set.n) - len(ns.pages))
         page_list = ns.pages + gained
         try:
-            write(self._pool, self._ns_rows(ns, pos, page_list))
+            rows = self._ns_rows(ns, pos, page_list)
+            write(self._pool, rows)
+            self._columns_write(self._pool_cols, self._pool, rows, items)
             if gained:
                 self._pool.set_pages(ns.slot, page_list)
         except BaseException:
@@ -1273,6 +1296,7 @@ class Index:
         if src:
             try:
                 self._pool.move_rows(self._ns_rows(ns, src), self._ns_rows(ns, dst))
+                self._columns_move(self._pool_cols, self._ns_rows(ns, src), self._ns_rows(ns, dst))
             except BaseException:
                 ns._gen += 1
                 raise
@@ -1326,10 +1350,49 @@ class Index:
             self._gen += 1
             raise
 
+    def _columns_write(self, cols, owner: ShardSet, rows, items) -> None:
+        """The metadata columns of the rows an upsert just wrote: ALL fields of every row (tag 0
+        where a field is absent), so a reused row shows nothing of its former owner.  After the
+        vector write, before the host maps are committed.  If it raises, the columns are marked
+        invalid — every filter then takes the host path, a stale column never makes a bitmap —
+        and the error propagates like a failed vector write."""
+        fx = self._fields
+        if cols is None or not fx.valid:
+            return
+        try:
+            cols.ensure(owner.capacity)  # the vectors' capacity: the columns grow with it
+            tags, vals = fx.encode([md for _, _, md in items])
+            cols.write(rows, tags, vals)
+        except BaseException:
+            fx.valid = False
+            raise
+
+    def _columns_move(self, cols, src, dst) -> None:
+        """The columns follow a compaction's (src, dst) plan (after ``move_rows`` succeeded)."""
+        fx = self._fields
+        if cols is None or not fx.valid:
+            return
+        try:
+            cols.move(src, dst)
+        except BaseException:
+            fx.valid = False
+            raise
+
+    def metadata_index_stats(self) -> dict:
+        """``{"indexed": the configured fields, "device": those still evaluated on the device,
+        "demoted": {field: reason}, "valid": whether the device columns are in use, "device_evals" /
+        "host_evals": bitmap cache misses by the path that built the bitmap}``.  Without
+        ``metadata_config``: no fields, not valid, and both counters stay 0."""
+        with self._mu:
+            if self._fields is None:
+                return {"indexed": [], "device": [], "demoted": {}, "valid": False, "device_evals": 0, "host_evals": 0}
+            return self._fields.stats()
+
     def _upsert_locked(self, items, vecs: torch.Tensor) -> None:
         # device write first: if it raises, no id is registered (no zero rows behind live ids)
         rows = self._plan_rows(items)
         self._device_write(self._set.upsert_rows, vecs, rows)
+        self._device_write(self._columns_write, self._cols, self._set, rows, items)
         self._commit_rows(items, rows)
 
     def delete(self, ids: Sequence[str] | None = None, delete_all: bool = False, namespace: str = "",
@@ -1404,6 +1467,7 @@ class Index:
         src, dst = compaction.plan_compaction(n, rows, self._set.n)
         if src:
             self._device_write(self._set.move_rows, src, dst)
+            self._device_write(self._columns_move, self._cols, src, dst)
         ids = self._ids
         for r in rows:
             vid = ids[r]
@@ -1432,13 +1496,36 @@ class Index:
         cache = st._bitmaps
         hit = cache.pop(key, None)
         if hit is None:
-            hit = metafilter.build_bitmap(metafilter.compile_filter(flt), st._ids, st._meta)
+            hit = self._build_bitmap_locked(flt, st)
             for old in [k for k in cache if k[1] != st._gen]:
                 del cache[old]
             while len(cache) >= BITMAP_CACHE_ENTRIES:
                 del cache[next(iter(cache))]  # least recently used
         cache[key] = hit  # (re)inserted last = most recently used
         return hit
+
+    def _build_bitmap_locked(self, flt, st) -> tuple[np.ndarray, int]:
+        """A bitmap cache miss.  With valid metadata columns and a filter that compiles to a
+        program over them (``metacolumns.compile_program``), ``rc_meta_eval`` on the leader's
+        current stream and one copy back; otherwise — and always without ``metadata_config`` —
+        ``metafilter.build_bitmap`` over the host's metadata.  The two give the same bits."""
+        pred = metafilter.compile_filter(flt)
+        fx = self._fields
+        if fx is None:
+            return metafilter.build_bitmap(pred, st._ids, st._meta)
+        n = len(st._ids)
+        cols = self._cols if st is self else self._pool_cols
+        if cols is not None and fx.valid and n >= metacolumns.DEVICE_MIN_ROWS:
+            program = fx.program(flt)
+            if program is not None:
+                if st is self:
+                    hit = cols.eval(program, n)
+                else:
+                    hit = cols.eval(program, n, pages=st.pages, span=pages.span(self._set.n))
+                fx.device_evals += 1
+                return hit
+        fx.host_evals += 1
+        return metafilter.build_bitmap(pred, st._ids, st._meta)
 
     def query(self, vector=None, top_k: int = 10, include_values: bool = False, include_metadata: bool = False,
               id: str | None = None, namespace: str = "", filter: dict | None = None, **_: Any) -> dict:
@@ -1730,6 +1817,8 @@ class Index:
                         "ids": list(self._ids), "metadata": {i: self._meta.get(i, {}) for i in self._ids}}
             if spaces:
                 manifest["namespaces"] = spaces
+            if self.metadata_config is not None:  # only then: every other manifest stays byte for byte what it was
+                manifest["metadata_config"] = {"indexed": list(self.metadata_config["indexed"])}
             tmp = os.path.join(path, "manifest.json.tmp")
             with open(tmp, "w") as f:
                 json.dump(manifest, f)
@@ -1737,7 +1826,10 @@ class Index:
 
     @classmethod
     def load(cls, path: str, capacity: int | None = None, device=None, shards: int | None = None,
-             devices=None, filter: str | None = None, paged_search: str = "scan") -> "Index":
+             devices=None, filter: str | None = None, paged_search: str = "scan",
+             metadata_config: dict | None = None) -> "Index":
+        """``metadata_config=None`` means the snapshot's own (none, if it was saved without one);
+        the columns and string dictionaries are rebuilt from the loaded metadata."""
         import numpy as np
 
         with open(os.path.join(path, "manifest.json")) as f:
@@ -1747,7 +1839,8 @@ class Index:
         n = int(man["count"])
         idx = cls(man["name"], dimension=man["dimension"], metric=man["metric"], dtype=man["dtype"],
                   capacity=max(int(capacity or man.get("capacity", 0)), n, 1), device=device, shards=shards,
-                  devices=devices, filter=filter or man.get("filter", "native"), paged_search=paged_search)
+                  devices=devices, filter=filter or man.get("filter", "native"), paged_search=paged_search,
+                  metadata_config=metadata_config if metadata_config is not None else man.get("metadata_config"))
         if idx._set.ld != man["ld"]:
             raise ValueError("snapshot row layout does not match this build")
         rows = np.load(os.path.join(path, "rows.npy"), allow_pickle=False)
@@ -1759,6 +1852,9 @@ class Index:
         idx._ids = list(man["ids"])
         idx._rows = {vid: r for r, vid in enumerate(idx._ids)}
         idx._meta = {vid: dict(man["metadata"].get(vid, {})) for vid in idx._ids}
+        if n:
+            with idx._mu:
+                idx._columns_write(idx._cols, idx._set, list(range(n)), [(vid, None, idx._meta[vid]) for vid in idx._ids])
         for i, sp in enumerate(man.get("namespaces", [])):
             cnt = int(sp["count"])
             nrows = np.load(os.path.join(path, f"ns{i}_rows.npy"), allow_pickle=False)

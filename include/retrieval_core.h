@@ -419,6 +419,86 @@ int rc_sharded_query_host_pages(rc_sharded *h, const float *queries, int nq, int
                                 float *values);
 
 /* ------------------------------------------------------------------------
+ * Metadata columns: the indexed metadata fields of an index's rows as typed
+ * columns in device memory, and the kernel that turns a metadata filter
+ * (index.query(filter=...)) into the row-eligibility bitmap the masked searches
+ * take.  Stateless: the caller owns every buffer (the host layer keeps them as
+ * torch tensors) and the three calls only enqueue work on `stream`.
+ *
+ * Layout, F = n_fields fields over `capacity` rows, field-major:
+ *   tags  uint8 [F, capacity]   RC_META_TAG_* of field f of row r at tags[f * capacity + r]
+ *   vals  int64 [F, capacity]   NUMBER: the float64 bits; BOOL: 0 / 1; STRING: the string's
+ *                               code in the host's dictionary of that field; ABSENT: unused
+ *
+ * rc_meta_write scatters n rows: field f of device row rows[i] becomes
+ * (in_tags[f * n + i], in_vals[f * n + i]) for EVERY f, so a reused row keeps nothing
+ * of its former owner.  rows must be distinct.  rc_meta_move copies all fields of row
+ * src_rows[i] to row dst_rows[i] (the two lists disjoint, as rc_index_move_rows).
+ * rows, src_rows, dst_rows, in_tags and in_vals are DEVICE buffers; a row outside
+ * [0, capacity) is skipped by the kernel, never written.
+ *
+ * rc_meta_eval evaluates a postfix program at positions [0, n) and writes
+ * out_words uint32 [ceil(n / 32)] (bit p & 31 of word p >> 5 = position p satisfies the
+ * program; bits at or past n clear — rc_index_search_masked's layout) and *out_count
+ * (how many do), both DEVICE buffers.  Without a page list position p is row p; with
+ * one (pages_host, HOST int32 [n_pages], span a multiple of 256) it is row
+ * pages[p / span] * span + p % span: a namespace's page list over the pool's global
+ * rows, span = RC_PAGE_ROWS * shards.
+ *
+ * The program is HOST int64 [2 * n_instr], two words per instruction:
+ *   word 0 = op | field << 8 | operand tag << 16 | k << 32,  word 1 = operand val.
+ * A leaf (RC_META_EQ .. RC_META_NOT_EXISTS) pushes one boolean computed from field
+ * `field` of the row and the operand; RC_META_TRUE / RC_META_FALSE push a constant;
+ * RC_META_AND / RC_META_OR replace the top k entries by their conjunction /
+ * disjunction.  The result is the one entry left at the end.  Comparison rules:
+ *   EQ   the tags are equal and the values are: NUMBER compares as IEEE float64 (so
+ *        -0.0 equals 0.0 and a NaN equals nothing, itself included), BOOL and STRING as
+ *        integers.  An absent field equals nothing.  NE is the negation of EQ.
+ *   GT GE LT LE   both tags are NUMBER and the float64 comparison holds; else false.
+ *   EXISTS / NOT_EXISTS   the row's tag is not / is RC_META_TAG_ABSENT.
+ * Limits: n_fields <= RC_META_MAX_FIELDS, n_instr <= RC_META_MAX_INSTR, stack depth
+ * <= RC_META_MAX_STACK (the lane's stack is one 64-bit register).
+ *
+ * workspace: DEVICE scratch of at least 16 * n_instr + 4 * n_pages bytes, 16-byte
+ * aligned; the call uploads the checked program and page list there.  program_host and
+ * pages_host must stay valid until `stream` has passed the call.
+ *
+ * Every check runs before any device call and returns RC_ERR_INVALID: NULL buffers,
+ * n beyond the capacity (or beyond n_pages * span), a page at or past capacity / span,
+ * a span that is not a positive multiple of 256, a small or misaligned workspace, and a
+ * malformed program (unknown op, field >= n_fields, an operand tag that is no value's,
+ * a combinator that takes more entries than the stack holds, a stack deeper than
+ * RC_META_MAX_STACK, anything but one entry left).  A program that passes cannot make
+ * the kernel read outside the columns. */
+#define RC_META_TAG_ABSENT 0
+#define RC_META_TAG_NUMBER 1
+#define RC_META_TAG_BOOL 2
+#define RC_META_TAG_STRING 3
+#define RC_META_EQ 0
+#define RC_META_NE 1
+#define RC_META_GT 2
+#define RC_META_GE 3
+#define RC_META_LT 4
+#define RC_META_LE 5
+#define RC_META_EXISTS 6
+#define RC_META_NOT_EXISTS 7
+#define RC_META_TRUE 8
+#define RC_META_FALSE 9
+#define RC_META_AND 10
+#define RC_META_OR 11
+#define RC_META_MAX_FIELDS 64
+#define RC_META_MAX_INSTR 512
+#define RC_META_MAX_STACK 64
+int rc_meta_write(uint8_t *tags, int64_t *vals, int n_fields, int64_t capacity, const int64_t *rows,
+                  const uint8_t *in_tags, const int64_t *in_vals, int64_t n, void *stream);
+int rc_meta_move(uint8_t *tags, int64_t *vals, int n_fields, int64_t capacity, const int64_t *src_rows,
+                 const int64_t *dst_rows, int64_t n, void *stream);
+int rc_meta_eval(const uint8_t *tags, const int64_t *vals, int n_fields, int64_t capacity,
+                 const int64_t *program_host, int n_instr, const int32_t *pages_host, int n_pages, int span,
+                 int64_t n, void *workspace, int64_t workspace_bytes, uint32_t *out_words, uint32_t *out_count,
+                 void *stream);
+
+/* ------------------------------------------------------------------------
  * ViT-MSN image embedding.  Replaces the /embed compute path —
  * embedding/main.py:97-114: PIL decode (stays on host) → ViTImageProcessor
  * (resize, rescale, normalize) → ViTMSNModel → last_hidden_state[:, 0, :].
