@@ -40,6 +40,9 @@ class Config:
     # metadata fields kept as device columns (Index(metadata_config={"indexed": [...]})): a comma
     # list of field names; empty (the default) = none, metadata filters are evaluated on the host
     INDEX_METADATA_FIELDS = comma_list(os.getenv("RC_INDEX_METADATA_FIELDS", ""))
+    # largest top_k a query may ask for (Index(max_top_k=...)): 256 (the default) to 10000; above
+    # 256 a query runs the deep top-k search
+    INDEX_MAX_TOP_K = int(os.getenv("RC_INDEX_MAX_TOP_K", "256"))
     # index shards: RC_INDEX_DEVICES = "all" (one shard per visible GPU) or a comma list
     # of device ordinals ("0,1,2,3"); otherwise RC_INDEX_SHARDS shards on the current GPU
     INDEX_DEVICES = os.getenv("RC_INDEX_DEVICES", "")

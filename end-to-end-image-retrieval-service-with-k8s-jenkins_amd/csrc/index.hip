@@ -21,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "deep.h"
 #include "paged.h"
 
 namespace rc {
@@ -392,6 +393,10 @@ struct rc_index {
     std::vector<PageTable> tables;
     int64_t *pg_rows = nullptr;  // [pg_rows_cap] local rows of a paged value gather
     int64_t pg_rows_cap = 0;
+    // deep top-k (rc_index_search_deep): the score arrays of the queries in flight and the selection's workspace
+    float *dscores = nullptr;  // [dscores_cap]
+    int64_t dscores_cap = 0;
+    DeepSel dsel;
 };
 
 namespace {
@@ -662,6 +667,54 @@ void empty_search(int nq, int k, float *scores, int64_t *out_rows, hipStream_t s
     RC_LAUNCH_CHECK();
 }
 
+// The deep top-k's score pass (deep_scores.h) over scan_search's block shape: the f32 score of nq
+// raw queries against rows (pages: positions) [0, n), out[q * n + r].  n >= 1.
+void deep_score_pass(rc_index *h, const float *queries, int nq, int64_t n, const int32_t *pages, float *out, hipStream_t s) {
+    int nblk = (int)std::min<int64_t>(kMaxBlocks, std::max<int64_t>(1, (n + 511) / 512));
+    const int round_blocks = 4 * h->ncu;
+    if (nblk > round_blocks) nblk = nblk / round_blocks * round_blocks;
+    int64_t rpb = (n + nblk - 1) / nblk;
+    rpb = std::max<int64_t>(32, (rpb + 31) / 32 * 32);
+    nblk = (int)std::max<int64_t>(1, (n + rpb - 1) / rpb);
+    const DeepScoreArgs a{h->rows, h->norms, h->ld, h->nch, h->dim, n, rpb, nblk, queries, nq, h->metric, pages, out, s};
+    dispatch_dtype(h->dtype, [&](auto t) { launch_deep_scores<decltype(t)>(a); });
+}
+
+// rc_index_search_deep's body (caller holds h->mu, the device is current): the k best of rows
+// (pages: positions) [0, n) per query, in chunks of deep_chunk_queries() queries: the chunk's
+// score pass, then every selection round over its scores.  out_keys (sharded.hip: [nq][k] keys
+// carrying global rows) or, when it is null, scores / out_rows through the emit kernel.
+void deep_search_locked(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, const int32_t *pages,
+                        uint64_t *out_keys, float *scores, int64_t *out_rows, hipStream_t s) {
+    if (n == 0) {  // an empty shard: every slot is empty
+        if (out_keys != nullptr) RC_HIP(hipMemsetAsync(out_keys, 0xff, (size_t)nq * k * sizeof(uint64_t), s));
+        else empty_search(nq, k, scores, out_rows, s);
+        return;
+    }
+    const int qc = deep_chunk_queries(nq, n);
+    if ((int64_t)qc * n > h->dscores_cap) {
+        dfree(h->dscores);
+        h->dscores = nullptr;
+        h->dscores_cap = 0;
+        h->dscores = (float *)dmalloc((size_t)qc * n * sizeof(float));
+        h->dscores_cap = (int64_t)qc * n;
+    }
+    h->dsel.ensure(qc, out_keys != nullptr ? 0 : (int64_t)qc * k);
+    for (int q0 = 0; q0 < nq; q0 += qc) {
+        const int m = std::min(qc, nq - q0);
+        deep_score_pass(h, queries + (int64_t)q0 * h->dim, m, n, pages, h->dscores, s);
+        DeepStream st;
+        st.scores = h->dscores;
+        st.n = n;
+        st.row_base = h->row_base;
+        st.row_stride = h->row_stride;
+        st.mask = mask;
+        uint64_t *ko = out_keys != nullptr ? out_keys + (int64_t)q0 * k : h->dsel.keys;
+        deep_select_rounds(st, h->dsel, m, k, ko, s);
+        if (out_keys == nullptr) deep_emit(ko, (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, s);
+    }
+}
+
 }  // namespace
 
 namespace rc {
@@ -776,6 +829,25 @@ void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos,
     RC_LAUNCH_CHECK();
     dispatch_dtype(h->dtype, [&](auto tt) { launch_fetch<decltype(tt)>(h, h->pg_rows, n, out, false, s); });
 }
+
+// Internal (sharded.hip, rc_sharded_search_deep): a shard's own deep top-k as keys [nq][k] that
+// carry global rows (slot >= 0: global positions of that slot over [0, n) local positions),
+// KEY_EMPTY past the eligible rows, on stream `s`.  mask: device bitmap over the local rows /
+// positions, or null.  The caller has checked nq, k and the buffers.
+void index_search_deep_keys(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, int slot,
+                            uint64_t *out_keys, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int32_t *pages = nullptr;
+    if (slot >= 0) {
+        const rc_index::PageTable &t = page_table(h, slot);
+        RC_REQUIRE(n >= 0 && n <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+        pages = t.dev;
+    } else {
+        RC_REQUIRE(n >= 0 && n <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
+    }
+    DeviceScope ds(h->device);
+    deep_search_locked(h, queries, nq, n, k, mask, pages, out_keys, nullptr, nullptr, s);
+}
 }  // namespace rc
 
 extern "C" {
@@ -840,6 +912,8 @@ int rc_index_destroy(rc_index *h) {
         if (h->q1_done != nullptr) (void)hipHostFree(h->q1_done);
         for (auto &t : h->tables) dfree(t.dev);
         dfree(h->pg_rows);
+        dfree(h->dscores);
+        h->dsel.release();
         delete h;
     });
 }
@@ -1260,6 +1334,62 @@ int rc_index_search_pages_ex(rc_index *h, const float *queries, int nq, int slot
             return;
         }
         batched_search_exact(h, queries, nq, n_pos, k, mask, mask_filter, scores, out_rows, s, t.dev);
+    });
+}
+
+int rc_index_search_deep(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask, float *scores,
+                         int64_t *out_rows, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
+        RC_REQUIRE(n_rows >= 0 && n_rows <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
+        if (nq == 0) return;
+        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        DeviceScope ds(h->device);
+        deep_search_locked(h, queries, nq, n_rows, k, mask, nullptr, nullptr, scores, out_rows, (hipStream_t)stream);
+    });
+}
+
+int rc_index_search_pages_deep(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
+                               float *scores, int64_t *out_rows, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
+        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const rc_index::PageTable &t = page_table(h, slot);
+        RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+        if (nq == 0) return;
+        DeviceScope ds(h->device);
+        deep_search_locked(h, queries, nq, n_pos, k, mask, t.dev, nullptr, scores, out_rows, (hipStream_t)stream);
+    });
+}
+
+int rc_index_scores(rc_index *h, const float *query, int64_t n_rows, float *out_scores, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(n_rows >= 0 && n_rows <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
+        if (n_rows == 0) return;
+        RC_REQUIRE(query && out_scores, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        DeviceScope ds(h->device);
+        deep_score_pass(h, query, 1, n_rows, nullptr, out_scores, (hipStream_t)stream);
+    });
+}
+
+int rc_index_scores_pages(rc_index *h, const float *query, int slot, int64_t n_pos, float *out_scores, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(n_pos == 0 || (query && out_scores), RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const rc_index::PageTable &t = page_table(h, slot);
+        RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+        if (n_pos == 0) return;
+        DeviceScope ds(h->device);
+        deep_score_pass(h, query, 1, n_pos, t.dev, out_scores, (hipStream_t)stream);
     });
 }
 

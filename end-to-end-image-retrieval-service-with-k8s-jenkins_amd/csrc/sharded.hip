@@ -23,6 +23,7 @@
 #include <cstring>
 #include <vector>
 
+#include "deep.h"
 #include "index_common.h"
 
 namespace rc {
@@ -34,6 +35,8 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
                   int64_t *out_rows, float *out_values, hipStream_t s, volatile unsigned **done = nullptr,
                   unsigned *seq = nullptr);
 void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos, int64_t n, float *out, hipStream_t s);
+void index_search_deep_keys(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, int slot,
+                            uint64_t *out_keys, hipStream_t s);
 
 // Wait for query1's completion word instead of the stream: the word is stored after the results
 // (system-scope release), so the host can read them the moment it changes, without the
@@ -125,6 +128,15 @@ struct rc_sharded {
     // page tables (rc_sharded_pages_set), by slot: the host copy of the list every shard holds
     // on its device (one page number = the same local rows on every shard); empty = no table
     std::vector<std::vector<int32_t>> tables;
+    // deep top-k (rc_sharded_search_deep), several shards: a shard s > 0 keeps a query copy and its
+    // own k keys per query on its device, the leader the gathered lists [n][dnq_cap x dk_cap
+    // entries used as [n][nq][k]] and the workspace of its selection over them
+    int dnq_cap = 0;
+    int64_t dkeys_cap = 0;              // keys per shard: nq * k of the largest call
+    std::vector<float *> dq;            // [dnq_cap][dim]
+    std::vector<uint64_t *> dk_loc;     // [dkeys_cap]
+    uint64_t *dg_keys = nullptr;        // leader [n][dkeys_cap]
+    DeepSel dsel;
 };
 
 namespace {
@@ -163,6 +175,40 @@ void ensure_search(rc_sharded *h, int nq, int k) {
     h->g_r = (int64_t *)dmalloc((size_t)h->n * nq2 * k2 * sizeof(int64_t));
     h->nq_cap = nq2;
     h->k_cap = k2;
+}
+
+void free_deep(rc_sharded *h) {
+    for (int s = 0; s < h->n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        dfree(h->dq[s]);
+        dfree(h->dk_loc[s]);
+        h->dq[s] = nullptr;
+        h->dk_loc[s] = nullptr;
+    }
+    DeviceScope dl(h->dev[0]);
+    dfree(h->dg_keys);
+    h->dg_keys = nullptr;
+    h->dnq_cap = 0;
+    h->dkeys_cap = 0;
+}
+
+// Room for a deep search of nq queries x k keys over several shards.  Every shard past the leader
+// gets its buffers whether or not it is remote now (rc_sharded_force_remote changes that later).
+void ensure_deep(rc_sharded *h, int nq, int k) {
+    const int64_t nk = (int64_t)nq * k;
+    if (nq <= h->dnq_cap && nk <= h->dkeys_cap) return;
+    const int nq2 = std::max(nq, h->dnq_cap);
+    const int64_t nk2 = std::max(nk, h->dkeys_cap);
+    free_deep(h);
+    for (int s = 1; s < h->n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        h->dq[s] = (float *)dmalloc((size_t)nq2 * h->dim * sizeof(float));
+        h->dk_loc[s] = (uint64_t *)dmalloc((size_t)nk2 * sizeof(uint64_t));
+    }
+    DeviceScope dl(h->dev[0]);
+    h->dg_keys = (uint64_t *)dmalloc((size_t)h->n * nk2 * sizeof(uint64_t));
+    h->dnq_cap = nq2;
+    h->dkeys_cap = nk2;
 }
 
 void free_staging(rc_sharded *h) {
@@ -405,6 +451,11 @@ void destroy(rc_sharded *h) {
     free_staging(h);
     free_move(h);
     free_mask(h);
+    free_deep(h);
+    {
+        DeviceScope dl(h->dev[0]);
+        h->dsel.release();
+    }
     if (h->qs) {
         free_query(h);
         DeviceScope dl(h->dev[0]);
@@ -472,6 +523,8 @@ int rc_sharded_create(int n_shards, const int *devices, int dim, int dtype, int6
         h->mk_h.assign(n_shards, nullptr);
         h->mk_d.assign(n_shards, nullptr);
         h->ev_mask.assign(n_shards, nullptr);
+        h->dq.assign(n_shards, nullptr);
+        h->dk_loc.assign(n_shards, nullptr);
         try {
             for (int s = 0; s < n_shards; ++s) {
                 check_status(rc_index_create(h->dev[s], dim, dtype, capacity_per_shard, s, &h->shard[s]));
@@ -860,9 +913,82 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
         if (masked) wait_mask(h);
 }
 
+// rc_sharded_search_deep's body (caller holds h->mu; device buffers on the leader, stream = leader
+// stream), as search_locked: the mask is a HOST bitmap over the global rows (slot >= 0: positions)
+// staged per shard.  Each shard selects its own k keys (global rows) with no traffic per round;
+// the leader gathers the n lists and runs the same rounds over those n x k keys.  A key's order
+// does not depend on the shard that held the row, so the result is that of one index.
+void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
+                        void *stream, const uint32_t *mask, int slot) {
+    hipStream_t ls = (hipStream_t)stream;
+    const bool masked = mask != nullptr;
+    if (masked) stage_mask(h, mask, n_rows, ls);
+    if (h->n == 1) {
+        const uint32_t *m = masked ? h->mk_d[0] : nullptr;
+        check_status(slot >= 0 ? rc_index_search_pages_deep(h->shard[0], queries, nq, slot, n_rows, k, m, scores, out_rows, stream)
+                               : rc_index_search_deep(h->shard[0], queries, nq, n_rows, k, m, scores, out_rows, stream));
+        if (masked) {
+            fence_mask_single(h, ls);
+            wait_mask(h);
+        }
+        return;
+    }
+    ensure_deep(h, nq, k);
+    const int64_t slice = (int64_t)nq * k;
+    {
+        DeviceScope dl(h->dev[0]);
+        for (int s = 0; s < h->n; ++s) RC_HIP(hipEventRecord(h->ev_start[s], ls));
+    }
+    for (int s = 0; s < h->n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        RC_HIP(hipStreamWaitEvent(h->st[s], h->ev_start[s], 0));
+        const bool local = !h->remote[s];
+        const float *q = queries;
+        if (!local) {
+            RC_HIP(hipMemcpyPeerAsync(h->dq[s], h->dev[s], queries, h->dev[0], (size_t)nq * h->dim * sizeof(float), h->st[s]));
+            q = h->dq[s];
+        }
+        uint64_t *ko = local ? h->dg_keys + s * slice : h->dk_loc[s];
+        index_search_deep_keys(h->shard[s], q, nq, shard_rows(h, s, n_rows), k, masked ? h->mk_d[s] : nullptr, slot, ko, h->st[s]);
+        if (!local)
+            RC_HIP(hipMemcpyPeerAsync(h->dg_keys + s * slice, h->dev[0], ko, h->dev[s], (size_t)slice * sizeof(uint64_t), h->st[s]));
+        RC_HIP(hipEventRecord(h->ev_done[s], h->st[s]));
+    }
+    DeviceScope dl(h->dev[0]);
+    for (int s = 0; s < h->n; ++s) RC_HIP(hipStreamWaitEvent(ls, h->ev_done[s], 0));
+    const int qc = deep_chunk_queries(nq, (int64_t)h->n * k);
+    h->dsel.ensure(qc, (int64_t)qc * k);
+    for (int q0 = 0; q0 < nq; q0 += qc) {
+        const int m = std::min(qc, nq - q0);
+        DeepStream st;
+        st.keys = h->dg_keys;  // list s of query q at [(s * nq + q) * k]
+        st.n = (int64_t)h->n * k;
+        st.klist = k;
+        st.nq_total = nq;
+        st.q0 = q0;
+        deep_select_rounds(st, h->dsel, m, k, h->dsel.keys, ls);
+        deep_emit(h->dsel.keys, (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, ls);
+    }
+    if (masked) wait_mask(h);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rc_sharded_search_deep(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask, float *scores,
+                           int64_t *out_rows, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
+        RC_REQUIRE(n_rows >= 0 && n_rows <= h->cap * h->n, RC_ERR_INVALID, "n_rows out of range");
+        if (nq == 0) return;
+        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        search_deep_locked(h, queries, nq, n_rows, k, scores, out_rows, stream, mask, -1);
+    });
+}
 
 int rc_sharded_fetch(rc_sharded *h, const int64_t *rows, int64_t n, float *out, int stored) {
     return guard([&] {
@@ -1041,6 +1167,20 @@ int rc_sharded_search_pages_ex(rc_sharded *h, const float *queries, int nq, int 
         (void)page_list(h, slot, n_pos);
         if (nq == 0) return;
         search_locked(h, queries, nq, n_pos, k, scores, out_rows, mode, stream, mask, slot);  // every shard takes the mode
+    });
+}
+
+int rc_sharded_search_pages_deep(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
+                                 float *scores, int64_t *out_rows, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
+        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        (void)page_list(h, slot, n_pos);
+        if (nq == 0) return;
+        search_deep_locked(h, queries, nq, n_pos, k, scores, out_rows, stream, mask, slot);
     });
 }
 

@@ -289,6 +289,53 @@ class DeviceIndex:
                                                 ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
+    def _device_mask(self, mask, n: int):
+        if mask is None:
+            return None
+        if mask.dtype not in (torch.int32, torch.uint32) or mask.numel() < (int(n) + 31) // 32:
+            raise ValueError("mask must hold ceil(n / 32) 32-bit words")
+        return mask.to(device=self.device).contiguous()
+
+    def search_deep(self, queries: torch.Tensor, k: int, n_rows: int, stream=None, mask=None):
+        """Exact top-k for ``k`` up to 10000 (rc_index_search_deep): one pass over the rows that
+        keeps every row's score, then ``ceil(k / 256)`` selection rounds over the scores.  The
+        scores, rows and tie order of ``search(mode="scan")`` continued past 256; slots past the
+        eligible rows are ``(-inf, -1)``.  ``mask``: as ``search`` (a device bitmap over the
+        local rows).  Works on every dtype, metric and filter kind."""
+        q = self._vecs(queries)
+        nq = q.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        mask = self._device_mask(mask, n_rows)
+        check(self.lib.rc_index_search_deep(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(mask), ptr(scores), ptr(rows),
+                                            stream_ptr(stream)))
+        return scores, rows
+
+    def search_pages_deep(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None):
+        """``search_deep`` over positions [0, n_pos) of a slot (rc_index_search_pages_deep)."""
+        q = self._vecs(queries)
+        nq = q.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        mask = self._device_mask(mask, n_pos)
+        check(self.lib.rc_index_search_pages_deep(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), ptr(mask), ptr(scores),
+                                                  ptr(rows), stream_ptr(stream)))
+        return scores, rows
+
+    def scores(self, query: torch.Tensor, n_rows: int, slot: int | None = None, stream=None) -> torch.Tensor:
+        """A diagnostic (rc_index_scores): the deep search's score pass alone, f32 [n_rows] = the
+        score of one raw query against every local row — the bits every search path gives that
+        row.  ``slot``: the positions [0, n_rows) of that slot instead (rc_index_scores_pages)."""
+        q = self._vecs(query)
+        if q.shape[0] != 1:
+            raise ValueError("scores takes one query")
+        out = torch.empty((int(n_rows),), dtype=torch.float32, device=self.device)
+        if slot is None:
+            check(self.lib.rc_index_scores(self.handle, ptr(q), int(n_rows), ptr(out), stream_ptr(stream)))
+        else:
+            check(self.lib.rc_index_scores_pages(self.handle, ptr(q), int(slot), int(n_rows), ptr(out), stream_ptr(stream)))
+        return out
+
     def export_rows(self, row0: int, n: int, stream=None):
         """Raw stored rows [row0, row0+n) (storage dtype bits, ld-padded) and norms, on the device."""
         el = _lib.dtype_bytes(self.dtype)
@@ -811,6 +858,37 @@ class ShardSet:
                                                   _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
+    def search_deep(self, queries: torch.Tensor, k: int, n_rows: int, stream=None, mask=None):
+        """``search`` for ``k`` up to 10000 (rc_sharded_search_deep; ``DeviceIndex.search_deep``):
+        every shard selects its own ``k``, the leader selects among the shards' lists — the
+        result of a single-shard index holding the same rows.  ``mask``: an optional HOST uint32
+        bitmap over the global rows."""
+        if queries.dim() == 1:
+            queries = queries[None]
+        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        nq = q.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        m = None if mask is None else self._host_mask(mask, n_rows)
+        check(self.lib.rc_sharded_search_deep(self.handle, ptr(q), nq, int(n_rows), int(k), None if m is None else m.ctypes.data,
+                                              ptr(scores), ptr(rows), stream_ptr(stream)))
+        return scores, rows
+
+    def search_pages_deep(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None):
+        """``search_deep`` over the positions [0, n_pos) of a slot (rc_sharded_search_pages_deep):
+        (scores, positions).  ``mask``: an optional HOST uint32 bitmap over the positions."""
+        if queries.dim() == 1:
+            queries = queries[None]
+        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        nq = q.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        m = None if mask is None else self._host_mask(mask, n_pos)
+        check(self.lib.rc_sharded_search_pages_deep(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k),
+                                                    None if m is None else m.ctypes.data, ptr(scores), ptr(rows),
+                                                    stream_ptr(stream)))
+        return scores, rows
+
     def query_host_pages(self, q: np.ndarray, k: int, slot: int, n_pos: int, with_values: bool, mask=None):
         """``query_host`` over the positions [0, n_pos) of a slot (rc_sharded_query_host_pages):
         host (scores, positions, values or None), new arrays."""
@@ -992,12 +1070,26 @@ class Index:
     before.  ``metadata_index_stats()`` reports which path ran.  Anything but a dict with exactly
     the key ``"indexed"`` and a list of distinct non-empty names not starting with ``$`` raises
     ``ValueError``.
+
+    ``max_top_k`` (default 256; anything outside [256, 10000] raises ``ValueError``) opts the
+    index into deep top-k: ``query`` and ``query_batch`` then accept ``top_k <= max_top_k``.
+    A ``top_k`` up to 256 takes the paths above, untouched; a larger one goes through the deep
+    search (``ShardSet.search_deep`` / ``search_pages_deep``: one pass over the rows that keeps
+    every score, then ``ceil(top_k / 256)`` selection rounds over the scores), in the default
+    namespace and in named ones, with or without a metadata filter, under every dtype, metric
+    and filter kind.  Its matches are those an exact scan able to hold ``top_k`` results would
+    give: the first 256 are the ``top_k=256`` answer, scores and tie order included.  ``mode``
+    is validated and otherwise ignored there.  With the default every message and exception
+    is what it was.  (``sharded.ShardedIndex``, one process per GPU, has no deep search.)
     """
 
     def __init__(self, name: str, dimension: int = 768, metric: str = "cosine", dtype: str = "float32",
                  capacity: int = 1 << 20, device=None, shards: int | None = None, devices=None,
-                 filter: str = "native", paged_search: str = "scan", metadata_config: dict | None = None):
+                 filter: str = "native", paged_search: str = "scan", metadata_config: dict | None = None,
+                 max_top_k: int = _lib.RC_TOPK_MAX):
         indexed = metacolumns.validate_config(metadata_config)
+        if isinstance(max_top_k, bool) or not isinstance(max_top_k, int) or not _lib.RC_TOPK_MAX <= max_top_k <= _lib.RC_DEEP_TOPK_MAX:
+            raise ValueError(f"max_top_k must be an integer in [{_lib.RC_TOPK_MAX}, {_lib.RC_DEEP_TOPK_MAX}] (got {max_top_k!r})")
         if paged_search not in ("scan", "mfma"):
             raise ValueError(f"unknown paged_search {paged_search!r} (expected 'scan' or 'mfma')")
         if paged_search == "mfma" and (_lib.is_f8(dtype) or dtype in ("float32", "f32") or filter in ("i8", "f8")):
@@ -1021,6 +1113,7 @@ class Index:
         self.dimension = int(dimension)
         self.metric = metric
         self.paged_search = paged_search
+        self.max_top_k = max_top_k
         n = len(devices)
         self._set = ShardSet(self.dimension, dtype=dtype, capacity_per_shard=max(1, -(-int(capacity) // n)),
                              devices=devices, metric=metric)
@@ -1536,8 +1629,9 @@ class Index:
         if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 1:
             raise ValueError("top_k must be a positive integer")
         top_k = int(top_k)
-        if top_k > _lib.RC_TOPK_MAX:
-            raise ValueError(f"top_k must be <= {_lib.RC_TOPK_MAX}")
+        if top_k > self.max_top_k:
+            raise ValueError(f"top_k must be <= {self.max_top_k}")
+        deep = top_k > _lib.RC_TOPK_MAX  # only with max_top_k: the deep search, through _query_locked
         namespace = _namespace_name(namespace)
         if namespace:
             with self._mu:
@@ -1551,7 +1645,10 @@ class Index:
                     vector = self._pool.fetch_rows(self._ns_rows(ns, [p]))[0]
                 q = _as_vector_np(vector, self.dimension)
                 bm = self._bitmap_locked(filter, ns)
-                res = self._query_host_locked(q, top_k, include_values, include_metadata, bm, ns)[0]
+                if deep:
+                    res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm, ns)[0]
+                else:
+                    res = self._query_host_locked(q, top_k, include_values, include_metadata, bm, ns)[0]
             return {"matches": res, "namespace": namespace}
         with self._mu:
             if vector is None:
@@ -1561,7 +1658,10 @@ class Index:
                 vector = self._set.fetch_rows([r])[0]
             q = _as_vector_np(vector, self.dimension)
             bm = self._bitmap_locked(filter)
-            res = self._query_host_locked(q, top_k, include_values, include_metadata, bm)[0]
+            if deep:
+                res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm)[0]
+            else:
+                res = self._query_host_locked(q, top_k, include_values, include_metadata, bm)[0]
         return {"matches": res, "namespace": namespace}
 
     def query_batch(self, vectors, top_k: int = 10, include_values: bool = False,
@@ -1577,8 +1677,8 @@ class Index:
         ``paged_search="mfma"``: then all four modes go down to the batched MFMA search over the
         namespace's pages ("auto" scans under a metadata filter, and otherwise follows the
         library's rule)."""
-        if top_k < 1 or top_k > _lib.RC_TOPK_MAX:
-            raise ValueError(f"top_k must be in [1, {_lib.RC_TOPK_MAX}]")
+        if top_k < 1 or top_k > self.max_top_k:
+            raise ValueError(f"top_k must be in [1, {self.max_top_k}]")
         if isinstance(vectors, torch.Tensor):
             q = vectors.to(torch.float32)
             if q.dim() != 2 or q.shape[1] != self.dimension:
@@ -1665,7 +1765,15 @@ class Index:
             return [[] for _ in range(q.shape[0])]
         if bitmap is not None and bitmap[1] == 0:  # nothing is eligible: no device work
             return [[] for _ in range(q.shape[0])]
-        if ns is not None:
+        if k > _lib.RC_TOPK_MAX:  # deep top-k (max_top_k): one path whatever the mode, the filter kind or the mask's share
+            if mode not in _lib.SEARCH_MODES:
+                raise ValueError(f"unknown search mode {mode!r}")
+            mask = None if bitmap is None else bitmap[0]
+            if ns is not None:
+                scores, rows = self._pool.search_pages_deep(q, k, ns.slot, n, mask=mask)
+            else:
+                scores, rows = self._set.search_deep(q, k, n, mask=mask)
+        elif ns is not None:
             # (under a metadata filter the library's "auto" scans: the masked paged forms are unmeasured)
             scores, rows = self._pool.search_pages(q, k, ns.slot, n, mask=None if bitmap is None else bitmap[0], mode=mode)
         elif bitmap is None:
@@ -1827,9 +1935,10 @@ class Index:
     @classmethod
     def load(cls, path: str, capacity: int | None = None, device=None, shards: int | None = None,
              devices=None, filter: str | None = None, paged_search: str = "scan",
-             metadata_config: dict | None = None) -> "Index":
+             metadata_config: dict | None = None, max_top_k: int = _lib.RC_TOPK_MAX) -> "Index":
         """``metadata_config=None`` means the snapshot's own (none, if it was saved without one);
-        the columns and string dictionaries are rebuilt from the loaded metadata."""
+        the columns and string dictionaries are rebuilt from the loaded metadata.  ``max_top_k``
+        is the loaded object's (the constructor's; a snapshot does not record it)."""
         import numpy as np
 
         with open(os.path.join(path, "manifest.json")) as f:
@@ -1840,7 +1949,8 @@ class Index:
         idx = cls(man["name"], dimension=man["dimension"], metric=man["metric"], dtype=man["dtype"],
                   capacity=max(int(capacity or man.get("capacity", 0)), n, 1), device=device, shards=shards,
                   devices=devices, filter=filter or man.get("filter", "native"), paged_search=paged_search,
-                  metadata_config=metadata_config if metadata_config is not None else man.get("metadata_config"))
+                  metadata_config=metadata_config if metadata_config is not None else man.get("metadata_config"),
+                  max_top_k=max_top_k)
         if idx._set.ld != man["ld"]:
             raise ValueError("snapshot row layout does not match this build")
         rows = np.load(os.path.join(path, "rows.npy"), allow_pickle=False)

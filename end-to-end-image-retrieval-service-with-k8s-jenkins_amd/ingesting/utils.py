@@ -54,7 +54,8 @@ def get_index(index_name: str, dimension: int | None = None, dtype: str | None =
             idx = Index(index_name, dimension=dimension or Config.INPUT_RESOLUTION, metric=Config.INDEX_METRIC,
                         dtype=dtype or Config.INDEX_DTYPE, capacity=capacity or Config.INDEX_CAPACITY,
                         devices=devices if devices is not None else index_devices(), filter=Config.INDEX_FILTER,
-                        metadata_config={"indexed": list(Config.INDEX_METADATA_FIELDS)} if Config.INDEX_METADATA_FIELDS else None)
+                        metadata_config={"indexed": list(Config.INDEX_METADATA_FIELDS)} if Config.INDEX_METADATA_FIELDS else None,
+                        max_top_k=Config.INDEX_MAX_TOP_K)
             _indexes[index_name] = idx
             logger.info("Created in-HBM index: %s", index_name)
         return idx

@@ -419,6 +419,52 @@ int rc_sharded_query_host_pages(rc_sharded *h, const float *queries, int nq, int
                                 float *values);
 
 /* ------------------------------------------------------------------------
+ * Deep top-k: exact results past RC_TOPK_MAX per query, up to RC_DEEP_TOPK_MAX
+ * ("Deep top-k").  The calls above keep refusing k > RC_TOPK_MAX; these
+ * take 1 <= k <= RC_DEEP_TOPK_MAX and a mask that may be NULL, on every dtype, metric
+ * and filter kind (they never run the filter GEMM).
+ *
+ * One pass over the stored rows writes every row's f32 score (the scan's own bits)
+ * to a workspace; ceil(k / RC_TOPK_MAX) selection rounds over those 4 bytes per row
+ * follow, round j taking the RC_TOPK_MAX smallest keys at or above a bound that round
+ * j - 1 left in device memory (its last key + 1), so all rounds are enqueued at once
+ * and nothing waits for the host.  The key is the searches' total order (score
+ * descending, then row ascending), so for every k the result is what an exact scan
+ * able to hold k keys would give: the first min(k, RC_TOPK_MAX) slots are
+ * bit-identical to rc_*_search_masked(..., RC_SEARCH_SCAN) with the same arguments,
+ * and slots past the eligible rows are (-inf, -1).  Several shards each select their
+ * own k and the leader runs the same rounds over the S x k gathered keys: the result
+ * of one index holding the same rows.
+ *
+ * Masks, rows and positions follow the twins: rc_index_search_deep takes a DEVICE
+ * bitmap over the local rows and rc_index_search_pages_deep one over the positions
+ * (as rc_index_search_masked / rc_index_search_pages); the rc_sharded_* calls take a
+ * HOST bitmap over the global rows / positions.  Queries are processed in chunks of at
+ * most RC_DEEP_CHUNK_QUERIES whose scores fit RC_DEEP_WS_BYTES (at least one query);
+ * the workspace (4 x local rows bytes per query in flight, the blocks' partial lists
+ * and k keys per query of a chunk) is allocated by the first deep call of a size and
+ * reused: a repeated call leaves rc_alloc_count() unchanged.  Every argument is
+ * checked before any device call (RC_ERR_INVALID).
+ *
+ * rc_index_scores / rc_index_scores_pages are diagnostics in the style of
+ * rc_index_filter_scores: the score pass alone, out_scores (device f32 [n_rows] /
+ * [n_pos]) = the score of one raw query against every local row / position. */
+#define RC_DEEP_TOPK_MAX 10000
+#define RC_DEEP_SELECT_ROWS 2048            /* a selection block owns at least this many stream entries */
+#define RC_DEEP_CHUNK_QUERIES 64            /* queries in flight, at most */
+#define RC_DEEP_WS_BYTES (256ll << 20)      /* ... and their score arrays, at most (one query always runs) */
+int rc_index_search_deep(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                         float *scores, int64_t *out_rows, void *stream);
+int rc_index_search_pages_deep(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                               const uint32_t *mask, float *scores, int64_t *out_rows, void *stream);
+int rc_sharded_search_deep(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                           float *scores, int64_t *out_rows, void *stream);
+int rc_sharded_search_pages_deep(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                                 const uint32_t *mask, float *scores, int64_t *out_rows, void *stream);
+int rc_index_scores(rc_index *h, const float *query, int64_t n_rows, float *out_scores, void *stream);
+int rc_index_scores_pages(rc_index *h, const float *query, int slot, int64_t n_pos, float *out_scores, void *stream);
+
+/* ------------------------------------------------------------------------
  * Metadata columns: the indexed metadata fields of an index's rows as typed
  * columns in device memory, and the kernel that turns a metadata filter
  * (index.query(filter=...)) into the row-eligibility bitmap the masked searches
