@@ -29,6 +29,7 @@ RC_F32, RC_F16, RC_BF16, RC_F8 = 0, 1, 2, 3
 RC_TOPK_MAX = 256
 RC_DEEP_TOPK_MAX = 10000  # largest k of the deep calls (rc_*_search_deep); the others keep RC_TOPK_MAX
 RC_DEEP_SELECT_ROWS = 2048  # stream entries a deep selection block owns at least (retrieval_core.h)
+RC_SPARSE_MAX_NNZ = 1024  # widest sparse store and longest sparse query (retrieval_core.h)
 RC_PAGE_ROWS = 256  # local rows per shard in one page of a paged row pool (retrieval_core.h)
 RC_SEARCH_AUTO, RC_SEARCH_SCAN, RC_SEARCH_MFMA, RC_SEARCH_MFMA_MASKED = 0, 1, 2, 3
 SEARCH_MODES = {"auto": RC_SEARCH_AUTO, "scan": RC_SEARCH_SCAN, "mfma": RC_SEARCH_MFMA, "mfma_masked": RC_SEARCH_MFMA_MASKED}
@@ -161,6 +162,16 @@ SIGNATURES = {
     "rc_sharded_search_pages_deep": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
     "rc_index_scores": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "rc_index_scores_pages": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp]),
+    "rc_index_sparse_enable": (C.c_int, [_vp, _i32, _vp]),
+    "rc_index_sparse_width": (C.c_int, [_vp, _pi32]),
+    "rc_index_sparse_write": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "rc_sharded_sparse_enable": (C.c_int, [_vp, _i32]),
+    "rc_sharded_sparse_write": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64]),
+    "rc_index_search_hybrid": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rc_index_search_pages_hybrid": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rc_sharded_search_hybrid": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rc_sharded_search_pages_hybrid": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rc_index_scores_hybrid": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "rc_meta_write": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _vp]),
     "rc_meta_move": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _vp]),
     "rc_meta_eval": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),

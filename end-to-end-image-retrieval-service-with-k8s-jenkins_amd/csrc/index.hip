@@ -17,11 +17,13 @@
 // (scan_metric.h): each row's key carries q · v_r or −‖q − v_r‖² instead of the cosine, formed
 // from the cosine and norms[r] before the top-k; nothing after the push differs.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "deep.h"
+#include "sparse.h"
 #include "paged.h"
 
 namespace rc {
@@ -397,12 +399,17 @@ struct rc_index {
     float *dscores = nullptr;  // [dscores_cap]
     int64_t dscores_cap = 0;
     DeepSel dsel;
+    // sparse-dense hybrid (rc_index_sparse_enable): the store, [width][capacity] slot-major, and the staging of
+    // sparse queries and store writes
+    SparseStore sparse;
+    SparseWs sws;
 };
 
 namespace {
 
 constexpr int kNchSet[] = {1, 2, 3, 4, 6, 8, 12, 16};
 constexpr int kMaxBlocks = 2048;
+constexpr int64_t kSparseWriteSlots = int64_t(1) << 20;  // slots one round of rc_index_sparse_write stages (8 MB)
 constexpr int kBatchMinQueries = 8;      // below this the HBM-bound scan wins (1-4 queries per pass)
 constexpr int64_t kBatchMinRows = 65536;  // tiny shards: the staged path's fixed cost dominates
 // The float8 filter (RC_FILTER_F8) has a corner of its own: the scan it competes with reads half the
@@ -684,8 +691,9 @@ void deep_score_pass(rc_index *h, const float *queries, int nq, int64_t n, const
 // (pages: positions) [0, n) per query, in chunks of deep_chunk_queries() queries: the chunk's
 // score pass, then every selection round over its scores.  out_keys (sharded.hip: [nq][k] keys
 // carrying global rows) or, when it is null, scores / out_rows through the emit kernel.
+// after (the hybrid searches; null for the deep ones): a step between a chunk's score pass and its selection.
 void deep_search_locked(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, const int32_t *pages,
-                        uint64_t *out_keys, float *scores, int64_t *out_rows, hipStream_t s) {
+                        uint64_t *out_keys, float *scores, int64_t *out_rows, hipStream_t s, const DeepAfterScores *after = nullptr) {
     if (n == 0) {  // an empty shard: every slot is empty
         if (out_keys != nullptr) RC_HIP(hipMemsetAsync(out_keys, 0xff, (size_t)nq * k * sizeof(uint64_t), s));
         else empty_search(nq, k, scores, out_rows, s);
@@ -703,6 +711,7 @@ void deep_search_locked(rc_index *h, const float *queries, int nq, int64_t n, in
     for (int q0 = 0; q0 < nq; q0 += qc) {
         const int m = std::min(qc, nq - q0);
         deep_score_pass(h, queries + (int64_t)q0 * h->dim, m, n, pages, h->dscores, s);
+        if (after != nullptr) (*after)(q0, m, h->dscores, s);
         DeepStream st;
         st.scores = h->dscores;
         st.n = n;
@@ -713,6 +722,26 @@ void deep_search_locked(rc_index *h, const float *queries, int nq, int64_t n, in
         deep_select_rounds(st, h->dsel, m, k, ko, s);
         if (out_keys == nullptr) deep_emit(ko, (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, s);
     }
+}
+
+// The hybrid searches' step after the score pass (caller holds h->mu, the device is current): checks
+// done, the sparse queries of the whole call are staged on `s` and the step adds a chunk's terms
+// over rows (pages: positions) [0, n).  No query holds an entry: no step (null), the deep search as it is.
+DeepAfterScores sparse_step(rc_index *h, const SparseQueries &sq, int nq, int64_t n, const int32_t *pages, hipStream_t s) {
+    if (sq.off[nq] == 0 || n == 0) return nullptr;
+    h->sws.stage_queries(sq, nq, s);
+    return [h, n, pages](int q0, int m, float *scores, hipStream_t st) {
+        const SparseAddArgs a{h->sparse.idx, h->sparse.val, h->sparse.width, h->capacity, h->sws.off_d, h->sws.idx_d, h->sws.val_d,
+                              q0,            m,             n,               pages,       scores,       st};
+        launch_sparse_add(a);
+    };
+}
+
+// What every hybrid call checks of its sparse queries before any device call (caller holds h->mu).
+void check_hybrid(const rc_index *h, const SparseQueries &sq, int nq) {
+    RC_REQUIRE(h->sparse.width > 0, RC_ERR_INVALID, "this index has no sparse store (rc_index_sparse_enable)");
+    RC_REQUIRE(h->metric == RC_METRIC_DOT, RC_ERR_INVALID, "sparse-dense hybrid scores need the dotproduct metric");
+    sparse_check_queries(sq, nq);
 }
 
 }  // namespace
@@ -834,8 +863,9 @@ void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos,
 // carry global rows (slot >= 0: global positions of that slot over [0, n) local positions),
 // KEY_EMPTY past the eligible rows, on stream `s`.  mask: device bitmap over the local rows /
 // positions, or null.  The caller has checked nq, k and the buffers.
+// sq (rc_sharded_search_hybrid): the call's sparse queries, already checked; null: the deep search.
 void index_search_deep_keys(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, int slot,
-                            uint64_t *out_keys, hipStream_t s) {
+                            uint64_t *out_keys, hipStream_t s, const SparseQueries *sq) {
     std::lock_guard<std::mutex> lk(h->mu);
     const int32_t *pages = nullptr;
     if (slot >= 0) {
@@ -845,8 +875,10 @@ void index_search_deep_keys(rc_index *h, const float *queries, int nq, int64_t n
     } else {
         RC_REQUIRE(n >= 0 && n <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
     }
+    if (sq != nullptr) RC_REQUIRE(h->sparse.width > 0, RC_ERR_INVALID, "this index has no sparse store (rc_index_sparse_enable)");
     DeviceScope ds(h->device);
-    deep_search_locked(h, queries, nq, n, k, mask, pages, out_keys, nullptr, nullptr, s);
+    const DeepAfterScores step = sq != nullptr ? sparse_step(h, *sq, nq, n, pages, s) : nullptr;
+    deep_search_locked(h, queries, nq, n, k, mask, pages, out_keys, nullptr, nullptr, s, step ? &step : nullptr);
 }
 }  // namespace rc
 
@@ -914,6 +946,9 @@ int rc_index_destroy(rc_index *h) {
         dfree(h->pg_rows);
         dfree(h->dscores);
         h->dsel.release();
+        dfree(h->sparse.idx);
+        dfree(h->sparse.val);
+        h->sws.release();
         delete h;
     });
 }
@@ -965,6 +1000,8 @@ int rc_index_grow(rc_index *h, int64_t new_capacity, void *stream) {
         float *norms = nullptr;
         int8_t *rows8 = nullptr;
         float *rsx = nullptr, *rex = nullptr;
+        uint32_t *sp_idx = nullptr;
+        float *sp_val = nullptr;
         try {
             norms = (float *)dmalloc((size_t)new_capacity * sizeof(float));
             RC_HIP(hipMemcpyAsync(rows, h->rows, (size_t)old_pad * rb, hipMemcpyDeviceToDevice, s));
@@ -983,8 +1020,15 @@ int rc_index_grow(rc_index *h, int64_t new_capacity, void *stream) {
                 RC_HIP(hipMemcpyAsync(rex, h->rex, (size_t)old_pad * sizeof(float), hipMemcpyDeviceToDevice, s));
                 RC_HIP(hipMemsetAsync(rex + old_pad, 0, (size_t)(new_pad - old_pad) * sizeof(float), s));
             }
+            if (h->sparse.width > 0) {  // the sparse store keeps its rows; the new ones are padding
+                sp_idx = (uint32_t *)dmalloc((size_t)h->sparse.width * new_capacity * sizeof(uint32_t));
+                sp_val = (float *)dmalloc((size_t)h->sparse.width * new_capacity * sizeof(float));
+                launch_sparse_regrow(h->sparse, h->capacity, sp_idx, sp_val, new_capacity, s);
+            }
             RC_HIP(hipStreamSynchronize(s));  // work queued earlier on other streams is the caller's to order
         } catch (...) {
+            dfree(sp_idx);
+            dfree(sp_val);
             dfree(rows);
             dfree(norms);
             dfree(rows8);
@@ -1004,6 +1048,12 @@ int rc_index_grow(rc_index *h, int64_t new_capacity, void *stream) {
             h->rows8 = rows8;
             h->rsx = rsx;
             h->rex = rex;
+        }
+        if (h->sparse.width > 0) {
+            dfree(h->sparse.idx);
+            dfree(h->sparse.val);
+            h->sparse.idx = sp_idx;
+            h->sparse.val = sp_val;
         }
         h->capacity = new_capacity;
     });
@@ -1390,6 +1440,158 @@ int rc_index_scores_pages(rc_index *h, const float *query, int slot, int64_t n_p
         if (n_pos == 0) return;
         DeviceScope ds(h->device);
         deep_score_pass(h, query, 1, n_pos, t.dev, out_scores, (hipStream_t)stream);
+    });
+}
+
+int rc_index_sparse_enable(rc_index *h, int width, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(width >= 1 && width <= RC_SPARSE_MAX_NNZ, RC_ERR_INVALID, "sparse width must be in [1, 1024]");
+        std::lock_guard<std::mutex> lk(h->mu);
+        RC_REQUIRE(h->sparse.width == 0 || h->sparse.width == width, RC_ERR_INVALID, "the sparse store has another width already");
+        if (h->sparse.width == width) return;
+        DeviceScope ds(h->device);
+        hipStream_t s = (hipStream_t)stream;
+        const size_t slots = (size_t)width * h->capacity;
+        uint32_t *idx = (uint32_t *)dmalloc(slots * sizeof(uint32_t));
+        float *val = nullptr;
+        try {
+            val = (float *)dmalloc(slots * sizeof(float));
+            RC_HIP(hipMemsetAsync(idx, 0xff, slots * sizeof(uint32_t), s));  // SPARSE_PAD everywhere
+            RC_HIP(hipMemsetAsync(val, 0, slots * sizeof(float), s));
+            RC_HIP(hipStreamSynchronize(s));
+        } catch (...) {
+            dfree(idx);
+            dfree(val);
+            throw;
+        }
+        h->sparse.idx = idx;
+        h->sparse.val = val;
+        h->sparse.width = width;
+    });
+}
+
+int rc_index_sparse_width(const rc_index *h, int *width) {
+    return guard([&] {
+        RC_REQUIRE(h && width, RC_ERR_INVALID, "null argument");
+        *width = h->sparse.width;
+    });
+}
+
+int rc_index_sparse_write(rc_index *h, const int64_t *rows, const int64_t *off, const uint32_t *idx, const float *val, int64_t n,
+                          void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(n >= 0, RC_ERR_INVALID, "negative count");
+        if (n == 0) return;
+        RC_REQUIRE(rows && off, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const int width = h->sparse.width;
+        RC_REQUIRE(width > 0, RC_ERR_INVALID, "this index has no sparse store (rc_index_sparse_enable)");
+        RC_REQUIRE(off[0] == 0, RC_ERR_INVALID, "sparse offsets must start at 0");
+        for (int64_t i = 0; i < n; ++i) {
+            RC_REQUIRE(rows[i] >= 0 && rows[i] < h->capacity, RC_ERR_INVALID, "row out of capacity");
+            const int64_t b = off[i], e = off[i + 1];
+            RC_REQUIRE(e >= b && e - b <= width, RC_ERR_INVALID, "a row holds at most the store's width of sparse entries");
+            RC_REQUIRE(e == b || (idx && val), RC_ERR_INVALID, "null buffer");
+            for (int64_t j = b; j < e; ++j) {
+                RC_REQUIRE(idx[j] != SPARSE_PAD, RC_ERR_INVALID, "sparse index 2^32 - 1 is reserved (the store's padding)");
+                RC_REQUIRE(j == b || idx[j] > idx[j - 1], RC_ERR_INVALID, "a row's sparse indices must be strictly ascending");
+                RC_REQUIRE(std::isfinite(val[j]), RC_ERR_INVALID, "sparse values must be finite");
+            }
+        }
+        DeviceScope ds(h->device);
+        hipStream_t s = (hipStream_t)stream;
+        // rounds of at most kSparseWriteSlots slots: the staging is sized by the round, not by the call
+        const int64_t round = std::max<int64_t>(1, std::min<int64_t>(n, kSparseWriteSlots / width));
+        h->sws.ensure_write(round, width);
+        SparseWs &w = h->sws;
+        for (int64_t r0 = 0; r0 < n; r0 += round) {
+            const int64_t m = std::min(round, n - r0);
+            w.wait();
+            for (int64_t i = 0; i < m; ++i) {
+                w.wrow_h[i] = rows[r0 + i];
+                const int64_t b = off[r0 + i], cnt = off[r0 + i + 1] - b;
+                for (int64_t j = 0; j < width; ++j) {
+                    w.widx_h[i * width + j] = j < cnt ? idx[b + j] : SPARSE_PAD;
+                    w.wval_h[i * width + j] = j < cnt ? val[b + j] : 0.0f;
+                }
+            }
+            RC_HIP(hipMemcpyAsync(w.wrow_d, w.wrow_h, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            RC_HIP(hipMemcpyAsync(w.widx_d, w.widx_h, (size_t)m * width * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            RC_HIP(hipMemcpyAsync(w.wval_d, w.wval_h, (size_t)m * width * sizeof(float), hipMemcpyHostToDevice, s));
+            RC_HIP(hipEventRecord(w.ev, s));
+            w.pending = true;
+            launch_sparse_scatter(h->sparse, h->capacity, w.wrow_d, w.widx_d, w.wval_d, m, s);
+        }
+        RC_HIP(hipStreamSynchronize(s));  // synchronous, as the sharded write: the caller's lists are free and the store is written
+        w.pending = false;
+    });
+}
+
+int rc_index_search_hybrid(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                           const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores, int64_t *out_rows,
+                           void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
+        RC_REQUIRE(n_rows >= 0 && n_rows <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
+        if (nq == 0) return;
+        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const SparseQueries sq{sq_off, sq_idx, sq_val};
+        check_hybrid(h, sq, nq);
+        DeviceScope ds(h->device);
+        hipStream_t s = (hipStream_t)stream;
+        const DeepAfterScores step = sparse_step(h, sq, nq, n_rows, nullptr, s);
+        deep_search_locked(h, queries, nq, n_rows, k, mask, nullptr, nullptr, scores, out_rows, s, step ? &step : nullptr);
+    });
+}
+
+int rc_index_search_pages_hybrid(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
+                                 const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores,
+                                 int64_t *out_rows, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
+        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const rc_index::PageTable &t = page_table(h, slot);
+        RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+        if (nq == 0) return;
+        const SparseQueries sq{sq_off, sq_idx, sq_val};
+        check_hybrid(h, sq, nq);
+        DeviceScope ds(h->device);
+        hipStream_t s = (hipStream_t)stream;
+        const DeepAfterScores step = sparse_step(h, sq, nq, n_pos, t.dev, s);
+        deep_search_locked(h, queries, nq, n_pos, k, mask, t.dev, nullptr, scores, out_rows, s, step ? &step : nullptr);
+    });
+}
+
+int rc_index_scores_hybrid(rc_index *h, const float *query, int slot, int64_t n, const int32_t *sq_off, const uint32_t *sq_idx,
+                           const float *sq_val, float *out_scores, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(n == 0 || (query && out_scores), RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const int32_t *pages = nullptr;
+        if (slot >= 0) {
+            const rc_index::PageTable &t = page_table(h, slot);
+            RC_REQUIRE(n >= 0 && n <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+            pages = t.dev;
+        } else {
+            RC_REQUIRE(n >= 0 && n <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
+        }
+        const SparseQueries sq{sq_off, sq_idx, sq_val};
+        check_hybrid(h, sq, 1);
+        if (n == 0) return;
+        DeviceScope ds(h->device);
+        hipStream_t s = (hipStream_t)stream;
+        const DeepAfterScores step = sparse_step(h, sq, 1, n, pages, s);
+        deep_score_pass(h, query, 1, n, pages, out_scores, s);
+        if (step) step(0, 1, out_scores, s);
     });
 }
 

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "deep.h"
+#include "sparse.h"
 #include "index_common.h"
 
 namespace rc {
@@ -36,7 +37,7 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
                   unsigned *seq = nullptr);
 void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos, int64_t n, float *out, hipStream_t s);
 void index_search_deep_keys(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, int slot,
-                            uint64_t *out_keys, hipStream_t s);
+                            uint64_t *out_keys, hipStream_t s, const SparseQueries *sq = nullptr);
 
 // Wait for query1's completion word instead of the stream: the word is stored after the results
 // (system-scope release), so the host can read them the moment it changes, without the
@@ -918,15 +919,23 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
 // staged per shard.  Each shard selects its own k keys (global rows) with no traffic per round;
 // the leader gathers the n lists and runs the same rounds over those n x k keys.  A key's order
 // does not depend on the shard that held the row, so the result is that of one index.
+// sq (rc_sharded_search_hybrid, checked by the caller): the sparse queries, which every shard stages on
+// its own device and adds to its scores before it selects; null: the deep search.
 void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
-                        void *stream, const uint32_t *mask, int slot) {
+                        void *stream, const uint32_t *mask, int slot, const SparseQueries *sq = nullptr) {
     hipStream_t ls = (hipStream_t)stream;
     const bool masked = mask != nullptr;
     if (masked) stage_mask(h, mask, n_rows, ls);
     if (h->n == 1) {
         const uint32_t *m = masked ? h->mk_d[0] : nullptr;
-        check_status(slot >= 0 ? rc_index_search_pages_deep(h->shard[0], queries, nq, slot, n_rows, k, m, scores, out_rows, stream)
-                               : rc_index_search_deep(h->shard[0], queries, nq, n_rows, k, m, scores, out_rows, stream));
+        if (sq != nullptr)
+            check_status(slot >= 0 ? rc_index_search_pages_hybrid(h->shard[0], queries, nq, slot, n_rows, k, m, sq->off, sq->idx, sq->val,
+                                                                  scores, out_rows, stream)
+                                   : rc_index_search_hybrid(h->shard[0], queries, nq, n_rows, k, m, sq->off, sq->idx, sq->val, scores,
+                                                            out_rows, stream));
+        else
+            check_status(slot >= 0 ? rc_index_search_pages_deep(h->shard[0], queries, nq, slot, n_rows, k, m, scores, out_rows, stream)
+                                   : rc_index_search_deep(h->shard[0], queries, nq, n_rows, k, m, scores, out_rows, stream));
         if (masked) {
             fence_mask_single(h, ls);
             wait_mask(h);
@@ -949,7 +958,8 @@ void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_r
             q = h->dq[s];
         }
         uint64_t *ko = local ? h->dg_keys + s * slice : h->dk_loc[s];
-        index_search_deep_keys(h->shard[s], q, nq, shard_rows(h, s, n_rows), k, masked ? h->mk_d[s] : nullptr, slot, ko, h->st[s]);
+        index_search_deep_keys(h->shard[s], q, nq, shard_rows(h, s, n_rows), k, masked ? h->mk_d[s] : nullptr, slot, ko, h->st[s],
+                               sq);
         if (!local)
             RC_HIP(hipMemcpyPeerAsync(h->dg_keys + s * slice, h->dev[0], ko, h->dev[s], (size_t)slice * sizeof(uint64_t), h->st[s]));
         RC_HIP(hipEventRecord(h->ev_done[s], h->st[s]));
@@ -972,9 +982,78 @@ void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_r
     if (masked) wait_mask(h);
 }
 
+// What the sharded hybrid calls check of the store and the sparse queries before any device call
+// (caller holds h->mu; the shards are enabled and given their metric together: shard 0 speaks for all).
+void check_hybrid(const rc_sharded *h, const SparseQueries &sq, int nq) {
+    int width = 0, metric = RC_METRIC_COSINE;
+    check_status(rc_index_sparse_width(h->shard[0], &width));
+    check_status(rc_index_get_metric(h->shard[0], &metric));
+    RC_REQUIRE(width > 0, RC_ERR_INVALID, "this index has no sparse store (rc_sharded_sparse_enable)");
+    RC_REQUIRE(metric == RC_METRIC_DOT, RC_ERR_INVALID, "sparse-dense hybrid scores need the dotproduct metric");
+    sparse_check_queries(sq, nq);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rc_sharded_sparse_enable(rc_sharded *h, int width) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(width >= 1 && width <= RC_SPARSE_MAX_NNZ, RC_ERR_INVALID, "sparse width must be in [1, 1024]");
+        std::lock_guard<std::mutex> lk(h->mu);
+        for (int s = 0; s < h->n; ++s) check_status(rc_index_sparse_enable(h->shard[s], width, h->st[s]));
+    });
+}
+
+int rc_sharded_sparse_write(rc_sharded *h, const int64_t *rows, const int64_t *off, const uint32_t *idx, const float *val, int64_t n) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(n >= 0, RC_ERR_INVALID, "negative count");
+        if (n == 0) return;
+        RC_REQUIRE(rows && off, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        RC_REQUIRE(off[0] == 0, RC_ERR_INVALID, "sparse offsets must start at 0");
+        for (int64_t i = 0; i < n; ++i) {
+            RC_REQUIRE(rows[i] >= 0 && rows[i] < h->cap * h->n, RC_ERR_INVALID, "row out of capacity");
+            RC_REQUIRE(off[i + 1] >= off[i], RC_ERR_INVALID, "sparse offsets must not descend");
+            RC_REQUIRE(off[i + 1] == off[i] || (idx && val), RC_ERR_INVALID, "null buffer");
+        }
+        // global row g = local row g / n of shard g % n: one CSR per shard, which the shard checks and writes
+        for (int s = 0; s < h->n; ++s) {
+            std::vector<int64_t> lrows, loff{0};
+            std::vector<uint32_t> lidx;
+            std::vector<float> lval;
+            for (int64_t i = 0; i < n; ++i) {
+                if (rows[i] % h->n != s) continue;
+                lrows.push_back(rows[i] / h->n);
+                lidx.insert(lidx.end(), idx + off[i], idx + off[i + 1]);
+                lval.insert(lval.end(), val + off[i], val + off[i + 1]);
+                loff.push_back((int64_t)lidx.size());
+            }
+            if (lrows.empty()) continue;
+            check_status(rc_index_sparse_write(h->shard[s], lrows.data(), loff.data(), lidx.data(), lval.data(), (int64_t)lrows.size(),
+                                               h->st[s]));
+        }
+    });
+}
+
+int rc_sharded_search_hybrid(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                             const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores, int64_t *out_rows,
+                             void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
+        RC_REQUIRE(n_rows >= 0 && n_rows <= h->cap * h->n, RC_ERR_INVALID, "n_rows out of range");
+        if (nq == 0) return;
+        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const SparseQueries sq{sq_off, sq_idx, sq_val};
+        check_hybrid(h, sq, nq);
+        search_deep_locked(h, queries, nq, n_rows, k, scores, out_rows, stream, mask, -1, &sq);
+    });
+}
 
 int rc_sharded_search_deep(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask, float *scores,
                            int64_t *out_rows, void *stream) {
@@ -1181,6 +1260,23 @@ int rc_sharded_search_pages_deep(rc_sharded *h, const float *queries, int nq, in
         (void)page_list(h, slot, n_pos);
         if (nq == 0) return;
         search_deep_locked(h, queries, nq, n_pos, k, scores, out_rows, stream, mask, slot);
+    });
+}
+
+int rc_sharded_search_pages_hybrid(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
+                                   const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores,
+                                   int64_t *out_rows, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
+        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        (void)page_list(h, slot, n_pos);
+        if (nq == 0) return;
+        const SparseQueries sq{sq_off, sq_idx, sq_val};
+        check_hybrid(h, sq, nq);
+        search_deep_locked(h, queries, nq, n_pos, k, scores, out_rows, stream, mask, slot, &sq);
     });
 }
 

@@ -23,7 +23,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 import torch
 
-from . import _lib, compaction, metacolumns, metafilter, pages
+from . import _lib, compaction, metacolumns, metafilter, pages, sparsevalues
 from ._lib import check, ptr, stream_ptr
 
 # query_batch(filter=..., mode="auto") takes the batched MFMA path when the unmasked conditions
@@ -334,6 +334,76 @@ class DeviceIndex:
             check(self.lib.rc_index_scores(self.handle, ptr(q), int(n_rows), ptr(out), stream_ptr(stream)))
         else:
             check(self.lib.rc_index_scores_pages(self.handle, ptr(q), int(slot), int(n_rows), ptr(out), stream_ptr(stream)))
+        return out
+
+    # ------------------------------------------------------------ sparse-dense hybrid --
+    def sparse_enable(self, width: int, stream=None) -> None:
+        """Give this shard its sparse store (rc_index_sparse_enable): ``width`` slots of (index,
+        value) per local row, 8 * width * capacity bytes; it grows with ``grow``."""
+        check(self.lib.rc_index_sparse_enable(self.handle, int(width), stream_ptr(stream)))
+
+    @property
+    def sparse_width(self) -> int:
+        w = _lib.C.c_int()
+        check(self.lib.rc_index_sparse_width(self.handle, _lib.C.byref(w)))
+        return w.value
+
+    def sparse_write(self, rows, sparse, stream=None) -> None:
+        """The sparse values of local rows (rc_index_sparse_write; synchronous): ``sparse[i]`` (a
+        ``{"indices", "values"}`` dict, its normal form, or ``None`` for none) replaces every slot
+        of row ``rows[i]``."""
+        rows = np.ascontiguousarray(torch.as_tensor(rows, dtype=torch.int64).cpu().numpy().reshape(-1))
+        if rows.shape[0] != len(sparse):
+            raise ValueError("rows and sparse values differ in length")
+        off, idx, val = sparsevalues.csr([sparsevalues.normalize(sp, sparsevalues.MAX_NNZ) for sp in sparse])
+        check(self.lib.rc_index_sparse_write(self.handle, rows.ctypes.data, off.ctypes.data, idx.ctypes.data, val.ctypes.data,
+                                             rows.shape[0], stream_ptr(stream)))
+
+    @staticmethod
+    def _sparse_queries(sparse, nq: int):
+        """The sparse parts of ``nq`` queries as the host CSR the hybrid calls take."""
+        if len(sparse) != nq:
+            raise ValueError("queries and sparse vectors differ in length")
+        return sparsevalues.csr([sparsevalues.normalize(sp, sparsevalues.MAX_NNZ, "sparse_vector") for sp in sparse], np.int32)
+
+    def search_hybrid(self, queries: torch.Tensor, k: int, n_rows: int, sparse, stream=None, mask=None):
+        """``search_deep`` on ``dense . dense + sparse . sparse`` (rc_index_search_hybrid; a
+        dotproduct index with a sparse store): ``sparse[q]`` is query q's sparse part (``None`` =
+        none).  The score is ``fadd(d, t)``: ``d`` what ``scores`` gives the row, ``t`` the
+        row's sparse term (``sparsevalues.model_term``); for any ``k`` up to 10000."""
+        q = self._vecs(queries)
+        nq = q.shape[0]
+        off, idx, val = self._sparse_queries(sparse, nq)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        mask = self._device_mask(mask, n_rows)
+        check(self.lib.rc_index_search_hybrid(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(mask), off.ctypes.data,
+                                              idx.ctypes.data, val.ctypes.data, ptr(scores), ptr(rows), stream_ptr(stream)))
+        return scores, rows
+
+    def search_pages_hybrid(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, sparse, stream=None, mask=None):
+        """``search_hybrid`` over positions [0, n_pos) of a slot (rc_index_search_pages_hybrid)."""
+        q = self._vecs(queries)
+        nq = q.shape[0]
+        off, idx, val = self._sparse_queries(sparse, nq)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        mask = self._device_mask(mask, n_pos)
+        check(self.lib.rc_index_search_pages_hybrid(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), ptr(mask),
+                                                    off.ctypes.data, idx.ctypes.data, val.ctypes.data, ptr(scores), ptr(rows),
+                                                    stream_ptr(stream)))
+        return scores, rows
+
+    def scores_hybrid(self, query: torch.Tensor, n_rows: int, sparse, slot: int | None = None, stream=None) -> torch.Tensor:
+        """A diagnostic (rc_index_scores_hybrid): ``scores`` plus the sparse add kernel for one
+        query — the hybrid score of every local row (``slot``: position) before any selection."""
+        q = self._vecs(query)
+        if q.shape[0] != 1:
+            raise ValueError("scores_hybrid takes one query")
+        off, idx, val = self._sparse_queries([sparse], 1)
+        out = torch.empty((int(n_rows),), dtype=torch.float32, device=self.device)
+        check(self.lib.rc_index_scores_hybrid(self.handle, ptr(q), -1 if slot is None else int(slot), int(n_rows), off.ctypes.data,
+                                              idx.ctypes.data, val.ctypes.data, ptr(out), stream_ptr(stream)))
         return out
 
     def export_rows(self, row0: int, n: int, stream=None):
@@ -889,6 +959,75 @@ class ShardSet:
                                                     stream_ptr(stream)))
         return scores, rows
 
+    # ------------------------------------------------------------ sparse-dense hybrid --
+    def sparse_enable(self, width: int) -> None:
+        """``DeviceIndex.sparse_enable`` on every shard (rc_sharded_sparse_enable)."""
+        check(self.lib.rc_sharded_sparse_enable(self.handle, int(width)))
+
+    @property
+    def sparse_width(self) -> int:
+        return self._shards[0].sparse_width
+
+    def sparse_write(self, rows, sparse) -> None:
+        """``DeviceIndex.sparse_write`` by GLOBAL row (rc_sharded_sparse_write; host lists,
+        synchronous): row g is local row g // n of shard g % n."""
+        rows = np.ascontiguousarray(torch.as_tensor(rows, dtype=torch.int64).cpu().numpy().reshape(-1))
+        if rows.shape[0] != len(sparse):
+            raise ValueError("rows and sparse values differ in length")
+        if rows.shape[0] == 0:
+            return
+        off, idx, val = sparsevalues.csr([sparsevalues.normalize(sp, sparsevalues.MAX_NNZ) for sp in sparse])
+        check(self.lib.rc_sharded_sparse_write(self.handle, rows.ctypes.data, off.ctypes.data, idx.ctypes.data, val.ctypes.data,
+                                               rows.shape[0]))
+
+    def search_hybrid(self, queries: torch.Tensor, k: int, n_rows: int, sparse, stream=None, mask=None):
+        """``search_deep`` on ``dense . dense + sparse . sparse`` (rc_sharded_search_hybrid;
+        ``DeviceIndex.search_hybrid``): every shard adds its rows' sparse terms to its own scores
+        before it selects — the result of a single-shard index holding the same records.
+        ``mask``: an optional HOST uint32 bitmap over the global rows."""
+        if queries.dim() == 1:
+            queries = queries[None]
+        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        nq = q.shape[0]
+        off, idx, val = DeviceIndex._sparse_queries(sparse, nq)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        m = None if mask is None else self._host_mask(mask, n_rows)
+        check(self.lib.rc_sharded_search_hybrid(self.handle, ptr(q), nq, int(n_rows), int(k), None if m is None else m.ctypes.data,
+                                                off.ctypes.data, idx.ctypes.data, val.ctypes.data, ptr(scores), ptr(rows),
+                                                stream_ptr(stream)))
+        return scores, rows
+
+    def search_pages_hybrid(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, sparse, stream=None, mask=None):
+        """``search_hybrid`` over the positions [0, n_pos) of a slot (rc_sharded_search_pages_hybrid):
+        (scores, positions).  ``mask``: an optional HOST uint32 bitmap over the positions."""
+        if queries.dim() == 1:
+            queries = queries[None]
+        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        nq = q.shape[0]
+        off, idx, val = DeviceIndex._sparse_queries(sparse, nq)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        m = None if mask is None else self._host_mask(mask, n_pos)
+        check(self.lib.rc_sharded_search_pages_hybrid(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k),
+                                                      None if m is None else m.ctypes.data, off.ctypes.data, idx.ctypes.data,
+                                                      val.ctypes.data, ptr(scores), ptr(rows), stream_ptr(stream)))
+        return scores, rows
+
+    def scores_hybrid(self, query: torch.Tensor, n_rows: int, sparse, slot: int | None = None) -> torch.Tensor:
+        """``DeviceIndex.scores_hybrid`` of every shard, interleaved into global row (``slot``:
+        position) order on the leader: f32 [n_rows].  A diagnostic; it waits for each shard."""
+        out = torch.empty((int(n_rows),), dtype=torch.float32, device=self.device)
+        for s, sh in enumerate(self._shards):
+            m = self.shard_rows(s, int(n_rows))
+            if m == 0:
+                continue
+            with torch.cuda.device(sh.device):
+                part = sh.scores_hybrid(query.to(sh.device), m, sparse, slot=slot)
+                torch.cuda.synchronize(sh.device)
+            out[s::self.n] = part.to(self.device)
+        return out
+
     def query_host_pages(self, q: np.ndarray, k: int, slot: int, n_pos: int, with_values: bool, mask=None):
         """``query_host`` over the positions [0, n_pos) of a slot (rc_sharded_query_host_pages):
         host (scores, positions, values or None), new arrays."""
@@ -977,7 +1116,7 @@ class _Namespace:
     the ordered page list and the slot of its device-resident page table.  An id's position is
     its index in ``_ids``; ``pages.position_to_row`` gives the pool row."""
 
-    __slots__ = ("name", "slot", "pages", "_ids", "_rows", "_meta", "_gen", "_recent", "_bitmaps")
+    __slots__ = ("name", "slot", "pages", "_ids", "_rows", "_meta", "_gen", "_recent", "_bitmaps", "_sparse")
 
     def __init__(self, name: str, slot: int):
         self.name = name
@@ -989,6 +1128,7 @@ class _Namespace:
         self._gen = 0
         self._recent: tuple[int, dict[str, np.ndarray]] = (-1, {})
         self._bitmaps: dict[tuple[str, int], tuple[np.ndarray, int]] = {}
+        self._sparse: dict[str, tuple[np.ndarray, np.ndarray]] = {}  # id -> sparse values (sparsevalues' normal form)
 
 
 class Index:
@@ -1081,13 +1221,33 @@ class Index:
     give: the first 256 are the ``top_k=256`` answer, scores and tie order included.  ``mode``
     is validated and otherwise ignored there.  With the default every message and exception
     is what it was.  (``sharded.ShardedIndex``, one process per GPU, has no deep search.)
+
+    ``sparse_max_nnz=W`` (default 0 = off; an integer in [1, 1024]; ``metric="dotproduct"`` only,
+    ``ValueError`` otherwise, as in Pinecone) makes the index sparse-dense: a record may carry
+    ``sparse_values={"indices": [...], "values": [...]}`` (at most ``W`` distinct indices in
+    [0, 2**32 - 2], finite values) beside its mandatory dense vector — in ``upsert``'s dict items
+    and ``upsert_tensor(sparse_values=...)``; an upsert without them clears the id's entries —
+    and ``query(..., sparse_vector=...)`` / ``query_batch(..., sparse_vectors=[...])`` (up to 1024
+    entries each, whatever ``W``) score ``dense . dense + sparse . sparse``.  Such a query goes through the hybrid search
+    (``ShardSet.search_hybrid`` / ``search_pages_hybrid``: the deep search with the sparse add
+    kernel between its score pass and its selection) for every ``top_k``, with metadata filters,
+    in named namespaces and over several shards; ``mode`` is validated and otherwise ignored.  A
+    query without a sparse part (``None`` or an empty pair) takes the paths above, untouched.
+    ``query(id=...)`` uses the id's stored dense and sparse parts.  ``fetch`` returns
+    ``"sparse_values"`` for records that have them, and so do matches under
+    ``include_values=True``; ``save`` / ``load`` keep them.  The store costs ``8 * W`` bytes per
+    row slot of capacity on each shard.  With the default every path, message and snapshot byte
+    is what it was.  (``sharded.ShardedIndex`` has no sparse values.)
     """
 
     def __init__(self, name: str, dimension: int = 768, metric: str = "cosine", dtype: str = "float32",
                  capacity: int = 1 << 20, device=None, shards: int | None = None, devices=None,
                  filter: str = "native", paged_search: str = "scan", metadata_config: dict | None = None,
-                 max_top_k: int = _lib.RC_TOPK_MAX):
+                 max_top_k: int = _lib.RC_TOPK_MAX, sparse_max_nnz: int = 0):
         indexed = metacolumns.validate_config(metadata_config)
+        sparse_max_nnz = sparsevalues.validate_width(sparse_max_nnz)
+        if sparse_max_nnz and metric != "dotproduct":
+            raise ValueError(f"sparse values need metric='dotproduct' (metric={metric!r}, sparse_max_nnz={sparse_max_nnz})")
         if isinstance(max_top_k, bool) or not isinstance(max_top_k, int) or not _lib.RC_TOPK_MAX <= max_top_k <= _lib.RC_DEEP_TOPK_MAX:
             raise ValueError(f"max_top_k must be an integer in [{_lib.RC_TOPK_MAX}, {_lib.RC_DEEP_TOPK_MAX}] (got {max_top_k!r})")
         if paged_search not in ("scan", "mfma"):
@@ -1114,11 +1274,15 @@ class Index:
         self.metric = metric
         self.paged_search = paged_search
         self.max_top_k = max_top_k
+        self.sparse_max_nnz = sparse_max_nnz
         n = len(devices)
         self._set = ShardSet(self.dimension, dtype=dtype, capacity_per_shard=max(1, -(-int(capacity) // n)),
                              devices=devices, metric=metric)
         if filter != "native":
             self._set.set_filter(filter)
+        if sparse_max_nnz:
+            self._set.sparse_enable(sparse_max_nnz)
+        self._sparse: dict[str, tuple[np.ndarray, np.ndarray]] = {}  # id -> sparse values (default namespace)
         self._rows: dict[str, int] = {}
         self._ids: list[str] = []
         self._meta: dict[str, dict] = {}
@@ -1144,6 +1308,11 @@ class Index:
         self._fields = None if indexed is None else metacolumns.FieldIndex(indexed)
         self._cols = metacolumns.Columns(len(indexed), self._set.capacity, self._set.device) if indexed else None
         self._pool_cols: "metacolumns.Columns | None" = None
+
+    @property
+    def _sparse_query_nnz(self) -> int:
+        """Entries a query's sparse part may hold: the library's limit, whatever the records' ``sparse_max_nnz``; 0 when off."""
+        return sparsevalues.MAX_NNZ if self.sparse_max_nnz else 0
 
     @property
     def shard_set(self) -> ShardSet:
@@ -1175,11 +1344,17 @@ class Index:
         if self._pool is not None:
             self._pool.close()
 
-    def _normalize_items(self, vectors: Iterable) -> list[tuple[str, list[float], dict]]:
+    def _normalize_items(self, vectors: Iterable, sparse_out: dict | None = None) -> list[tuple[str, list[float], dict]]:
+        """``sparse_out`` (a sparse-dense index): receives id -> the item's validated sparse values
+        (``None`` for none); an item with ``"sparse_values"`` on any other index raises."""
         items: dict[str, tuple[str, list[float], dict]] = {}
         for v in vectors:
             if isinstance(v, dict):
                 vid, vals, md = v["id"], v["values"], v.get("metadata") or {}
+                if v.get("sparse_values") is not None or sparse_out is not None:
+                    sp = sparsevalues.normalize(v.get("sparse_values"), self.sparse_max_nnz)
+                    if sparse_out is not None and isinstance(vid, str):
+                        sparse_out[vid] = sp
             else:
                 v = tuple(v)
                 if len(v) == 2:
@@ -1194,6 +1369,8 @@ class Index:
             # one row per id: a repeated id in one call keeps its LAST values (two
             # writes of one row slot in the same launch would interleave)
             items[vid] = (vid, _as_vector(vals, self.dimension), dict(md))
+            if sparse_out is not None and not isinstance(v, dict):
+                sparse_out[vid] = None  # (the last occurrence of an id wins, its sparse values included)
         return list(items.values())
 
     def _ensure_capacity(self, n_total: int) -> None:
@@ -1207,27 +1384,43 @@ class Index:
 
     def upsert(self, vectors: Sequence, namespace: str = "") -> dict:
         namespace = _namespace_name(namespace)
-        items = self._normalize_items(vectors)
+        by_id: dict | None = {} if self.sparse_max_nnz else None
+        items = self._normalize_items(vectors, by_id)
         if not items:
             return {"upserted_count": 0}
+        sp = None if by_id is None else [by_id[it[0]] for it in items]
         vecs = torch.tensor([it[1] for it in items], dtype=torch.float32)
         with self._mu:
             if namespace:
-                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_rows(vecs, rows))
+                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_rows(vecs, rows), sp)
             else:
-                self._upsert_locked(items, vecs)
+                self._upsert_locked(items, vecs, sp)
         return {"upserted_count": len(items)}
 
-    def upsert_tensor(self, ids: Sequence[str], vecs, metadata: Sequence[dict] | None = None, namespace: str = "") -> dict:
+    def _sparse_arg(self, sparse_values, n: int):
+        """``upsert_tensor``'s ``sparse_values``: one entry (dict or ``None``) per id, validated; ``None``
+        on an index without sparse values (where passing any raises)."""
+        if sparse_values is None:
+            return [None] * n if self.sparse_max_nnz else None
+        sparse_values = list(sparse_values)
+        if len(sparse_values) != n:
+            raise ValueError("sparse_values and ids differ in length")
+        sp = [sparsevalues.normalize(x, self.sparse_max_nnz) for x in sparse_values]
+        return sp if self.sparse_max_nnz else None
+
+    def upsert_tensor(self, ids: Sequence[str], vecs, metadata: Sequence[dict] | None = None, namespace: str = "",
+                      sparse_values: Sequence | None = None) -> dict:
         """Batched upsert of device-resident vectors (the ingest path: embeddings never leave HBM).
 
         ``vecs``: f32 [len(ids), dimension] on a GPU, or a list of parts ``(positions,
         tensor)`` — the vectors of ``ids[positions]`` on whatever GPU produced them (an
         ``EmbedderPool`` batch): each goes straight to its shard's GPU.  Same semantics as
-        ``upsert`` (overwrite by id, last occurrence wins)."""
+        ``upsert`` (overwrite by id, last occurrence wins).  ``sparse_values`` (a sparse-dense
+        index): one ``{"indices", "values"}`` dict or ``None`` per id."""
         namespace = _namespace_name(namespace)
+        sp_all = self._sparse_arg(sparse_values, len(ids))
         if isinstance(vecs, (list, tuple)):
-            return self._upsert_parts(ids, vecs, metadata, namespace)
+            return self._upsert_parts(ids, vecs, metadata, namespace, sp_all)
         if vecs.dim() != 2 or vecs.shape[0] != len(ids) or vecs.shape[1] != self.dimension:
             raise ValueError("vecs must be [len(ids), dimension]")
         metadata = list(metadata) if metadata is not None else [{}] * len(ids)
@@ -1243,16 +1436,17 @@ class Index:
             vecs = vecs[torch.tensor(keep, dtype=torch.int64, device=vecs.device)]
         nonzero = (vecs != 0).any(dim=1).all()  # queued behind the producer of vecs; read below
         items = [(ids[i], None, dict(metadata[i] or {})) for i in keep]
+        sp = None if sp_all is None else [sp_all[i] for i in keep]
         if not bool(nonzero):
             raise ValueError("Dense vectors must contain at least one non-zero value for the cosine metric")
         with self._mu:
             if namespace:
-                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_rows(vecs, rows))
+                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_rows(vecs, rows), sp)
             else:
-                self._upsert_locked(items, vecs)
+                self._upsert_locked(items, vecs, sp)
         return {"upserted_count": len(items)}
 
-    def _upsert_parts(self, ids, parts, metadata, namespace: str = "") -> dict:
+    def _upsert_parts(self, ids, parts, metadata, namespace: str = "", sp_all=None) -> dict:
         metadata = list(metadata) if metadata is not None else [{}] * len(ids)
         if len(metadata) != len(ids):
             raise ValueError("metadata and ids differ in length")
@@ -1275,6 +1469,7 @@ class Index:
             if t.shape[0] and not bool((t != 0).any(dim=1).all()):
                 raise ValueError("Dense vectors must contain at least one non-zero value for the cosine metric")
         items = [(ids[i], None, dict(metadata[i] or {})) for i in keep]
+        sp = None if sp_all is None else [sp_all[i] for i in keep]
         def split(rows):  # the parts as ShardSet.upsert_parts takes them: (global rows, vectors)
             sel = [[] for _ in parts]  # per part: (offset, global row) of the kept positions
             for i, r in zip(keep, rows):
@@ -1291,12 +1486,13 @@ class Index:
 
         with self._mu:
             if namespace:
-                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_parts(split(rows)))
+                self._ns_upsert_locked(namespace, items, lambda pool, rows: pool.upsert_parts(split(rows)), sp)
             else:
                 rows = self._plan_rows(items)
                 self._device_write(self._set.upsert_parts, split(rows))
                 self._device_write(self._columns_write, self._cols, self._set, rows, items)
-                self._commit_rows(items, rows)
+                self._device_write(self._sparse_write, self._set, rows, sp)
+                self._commit_rows(items, rows, sp)
         return {"upserted_count": len(items)}
 
     # ------------------------------------------------------------ named namespaces --
@@ -1307,6 +1503,8 @@ class Index:
                                   devices=list(self._set.devices), metric=self.metric)
             if self.paged_search == "mfma" and self._set.filter == "metric":  # else the pool stays native
                 self._pool.set_filter("metric")
+            if self.sparse_max_nnz:  # the pool's own store, by pool row; it grows with the pool
+                self._pool.sparse_enable(self.sparse_max_nnz)
             self._alloc.set_capacity(per // pages.PAGE_ROWS)
             if self._cols is not None:  # the pool's metadata columns, by pool row; they grow with it
                 self._pool_cols = metacolumns.Columns(self._cols.n_fields, self._pool.capacity, self._pool.device)
@@ -1327,7 +1525,7 @@ class Index:
         pl = ns.pages if page_list is None else page_list
         return [pl[p // sp] * sp + p % sp for p in positions]
 
-    def _ns_upsert_locked(self, name: str, items, write) -> None:
+    def _ns_upsert_locked(self, name: str, items, write, sp=None) -> None:
         """``_upsert_locked`` in a named namespace: positions for the items (an existing id keeps
         its position), the pages the new length needs, the device write ``write(pool, pool
         rows)``, the page table if it gained a page, then the host maps.  If the write raises
@@ -1349,6 +1547,7 @@ class Index:
             rows = self._ns_rows(ns, pos, page_list)
             write(self._pool, rows)
             self._columns_write(self._pool_cols, self._pool, rows, items)
+            self._sparse_write(self._pool, rows, sp)
             if gained:
                 self._pool.set_pages(ns.slot, page_list)
         except BaseException:
@@ -1369,6 +1568,7 @@ class Index:
                 ns._rows[vid] = p
                 ns._ids.append(vid)
             ns._meta[vid] = md
+        self._sparse_commit(ns, items, sp)
         ns._gen += 1
 
     def _ns_drop_locked(self, ns: _Namespace) -> None:
@@ -1390,6 +1590,7 @@ class Index:
             try:
                 self._pool.move_rows(self._ns_rows(ns, src), self._ns_rows(ns, dst))
                 self._columns_move(self._pool_cols, self._ns_rows(ns, src), self._ns_rows(ns, dst))
+                self._sparse_move(self._pool, ns, src, self._ns_rows(ns, dst))
             except BaseException:
                 ns._gen += 1
                 raise
@@ -1398,6 +1599,7 @@ class Index:
             vid = ids[p]
             del ns._rows[vid]
             ns._meta.pop(vid, None)
+            ns._sparse.pop(vid, None)
         for s, d in zip(src, dst):
             vid = ids[s]
             ids[d] = vid
@@ -1425,13 +1627,38 @@ class Index:
         self._ensure_capacity(nxt)
         return rows
 
-    def _commit_rows(self, items, rows) -> None:
+    def _commit_rows(self, items, rows, sp=None) -> None:
         for (vid, _, md), r in zip(items, rows):
             if vid not in self._rows:
                 self._rows[vid] = r
                 self._ids.append(vid)
             self._meta[vid] = md
+        self._sparse_commit(self, items, sp)
         self._gen += 1
+
+    # sparse values (sparse_max_nnz): the host keeps each id's, as it keeps metadata; the device store
+    # is written where the metadata columns are and re-written where they move
+    def _sparse_write(self, owner: ShardSet, rows, sp) -> None:
+        """The store slots of the rows an upsert just wrote: ALL slots of every row (padding where
+        an item has no sparse values), so a reused row shows nothing of its former owner."""
+        if self.sparse_max_nnz:
+            owner.sparse_write(rows, sp if sp is not None else [None] * len(rows))
+
+    def _sparse_commit(self, st, items, sp) -> None:
+        if not self.sparse_max_nnz:
+            return
+        for i, (vid, _, _) in enumerate(items):
+            x = None if sp is None else sp[i]
+            if x is None:
+                st._sparse.pop(vid, None)  # an upsert without sparse values clears the id's entries
+            else:
+                st._sparse[vid] = x
+
+    def _sparse_move(self, owner: ShardSet, st, src, dst_rows) -> None:
+        """After a compaction's row moves (before the host maps change): the destination rows get
+        the sparse values of the ids that moved there.  ``src``: rows / positions of ``st``."""
+        if self.sparse_max_nnz and src:
+            owner.sparse_write(dst_rows, [st._sparse.get(st._ids[r]) for r in src])
 
     def _device_write(self, fn, *args) -> None:
         """A shard write under the lock.  If it raises part-way (an earlier shard already
@@ -1481,12 +1708,13 @@ class Index:
                 return {"indexed": [], "device": [], "demoted": {}, "valid": False, "device_evals": 0, "host_evals": 0}
             return self._fields.stats()
 
-    def _upsert_locked(self, items, vecs: torch.Tensor) -> None:
+    def _upsert_locked(self, items, vecs: torch.Tensor, sp=None) -> None:
         # device write first: if it raises, no id is registered (no zero rows behind live ids)
         rows = self._plan_rows(items)
         self._device_write(self._set.upsert_rows, vecs, rows)
         self._device_write(self._columns_write, self._cols, self._set, rows, items)
-        self._commit_rows(items, rows)
+        self._device_write(self._sparse_write, self._set, rows, sp)
+        self._commit_rows(items, rows, sp)
 
     def delete(self, ids: Sequence[str] | None = None, delete_all: bool = False, namespace: str = "",
                filter: dict | None = None) -> dict:
@@ -1540,6 +1768,7 @@ class Index:
             if delete_all:
                 n = len(self._ids)
                 self._ids, self._rows, self._meta = [], {}, {}  # the stored rows are simply never searched again
+                self._sparse = {}
                 self._gen += 1
                 return n
             if ids is not None:
@@ -1561,11 +1790,13 @@ class Index:
         if src:
             self._device_write(self._set.move_rows, src, dst)
             self._device_write(self._columns_move, self._cols, src, dst)
+            self._device_write(self._sparse_move, self._set, self, src, dst)
         ids = self._ids
         for r in rows:
             vid = ids[r]
             del self._rows[vid]
             self._meta.pop(vid, None)
+            self._sparse.pop(vid, None)
         for s, d in zip(src, dst):
             vid = ids[s]
             ids[d] = vid
@@ -1621,11 +1852,16 @@ class Index:
         return metafilter.build_bitmap(pred, st._ids, st._meta)
 
     def query(self, vector=None, top_k: int = 10, include_values: bool = False, include_metadata: bool = False,
-              id: str | None = None, namespace: str = "", filter: dict | None = None, **_: Any) -> dict:
+              id: str | None = None, namespace: str = "", filter: dict | None = None, sparse_vector: dict | None = None,
+              **_: Any) -> dict:
         """``filter``: a Pinecone-style metadata filter (``metafilter``); ``None`` / ``{}`` = no
-        filter.  Not the constructor's ``filter`` (the filter-GEMM kind)."""
+        filter.  Not the constructor's ``filter`` (the filter-GEMM kind).  ``sparse_vector`` (a
+        sparse-dense index): the query's sparse part; the score is then ``dense . dense + sparse .
+        sparse`` (the hybrid search, for every ``top_k``).  ``id=``: the id's stored dense and
+        sparse parts."""
         if vector is None and id is None:
             raise ValueError("query needs a vector or an id")
+        sp = sparsevalues.normalize(sparse_vector, self._sparse_query_nnz, "sparse_vector")
         if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 1:
             raise ValueError("top_k must be a positive integer")
         top_k = int(top_k)
@@ -1643,9 +1879,12 @@ class Index:
                     if p is None:
                         return {"matches": [], "namespace": namespace}
                     vector = self._pool.fetch_rows(self._ns_rows(ns, [p]))[0]
+                    sp = ns._sparse.get(id)
                 q = _as_vector_np(vector, self.dimension)
                 bm = self._bitmap_locked(filter, ns)
-                if deep:
+                if sp is not None:
+                    res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm, ns, [sp])[0]
+                elif deep:
                     res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm, ns)[0]
                 else:
                     res = self._query_host_locked(q, top_k, include_values, include_metadata, bm, ns)[0]
@@ -1656,9 +1895,12 @@ class Index:
                 if r is None:
                     return {"matches": [], "namespace": namespace}
                 vector = self._set.fetch_rows([r])[0]
+                sp = self._sparse.get(id)
             q = _as_vector_np(vector, self.dimension)
             bm = self._bitmap_locked(filter)
-            if deep:
+            if sp is not None:
+                res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm, None, [sp])[0]
+            elif deep:
                 res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm)[0]
             else:
                 res = self._query_host_locked(q, top_k, include_values, include_metadata, bm)[0]
@@ -1666,7 +1908,7 @@ class Index:
 
     def query_batch(self, vectors, top_k: int = 10, include_values: bool = False,
                     include_metadata: bool = False, mode: str = "auto", filter: dict | None = None,
-                    namespace: str = "") -> list[dict]:
+                    namespace: str = "", sparse_vectors: Sequence | None = None) -> list[dict]:
         """Batched form of ``query`` (f16/bf16 shards run the MFMA path for >= 8 queries).
         ``filter``: one metadata filter for the whole batch (see ``query``); with ``mode="auto"``
         a filtered batch takes the MFMA path at an eligible share of at least
@@ -1676,15 +1918,24 @@ class Index:
         "scan" there; "mfma" / "mfma_masked" raise ``ValueError``), unless the index has
         ``paged_search="mfma"``: then all four modes go down to the batched MFMA search over the
         namespace's pages ("auto" scans under a metadata filter, and otherwise follows the
-        library's rule)."""
+        library's rule).  ``sparse_vectors`` (a sparse-dense index): one sparse part (or ``None``)
+        per query; if any query has one, the whole batch takes the hybrid search (``mode`` is
+        validated and otherwise ignored)."""
         if top_k < 1 or top_k > self.max_top_k:
             raise ValueError(f"top_k must be in [1, {self.max_top_k}]")
+        sp = None
+        if sparse_vectors is not None:
+            sp = [sparsevalues.normalize(x, self._sparse_query_nnz, "sparse_vector") for x in sparse_vectors]
+            if all(x is None for x in sp):
+                sp = None
         if isinstance(vectors, torch.Tensor):
             q = vectors.to(torch.float32)
             if q.dim() != 2 or q.shape[1] != self.dimension:
                 raise ValueError("queries must be [n, dimension]")
         else:
             q = torch.tensor([_as_vector(v, self.dimension) for v in vectors], dtype=torch.float32)
+        if sp is not None and len(sp) != q.shape[0]:
+            raise ValueError("sparse_vectors and vectors differ in length")
         namespace = _namespace_name(namespace)
         if namespace:
             if mode not in _lib.SEARCH_MODES:
@@ -1699,10 +1950,10 @@ class Index:
                 if ns is None:
                     res = [[] for _ in range(q.shape[0])]
                 else:
-                    res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter, ns), ns)
+                    res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter, ns), ns, sp)
             return [{"matches": m, "namespace": namespace} for m in res]
         with self._mu:
-            res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter))
+            res = self._query_locked(q, top_k, include_values, include_metadata, mode, self._bitmap_locked(filter), None, sp)
         return [{"matches": m, "namespace": ""} for m in res]
 
     def _masked_mode(self, mode: str, nq: int, n: int, eligible: int, k: int = 10) -> str:
@@ -1755,17 +2006,27 @@ class Index:
         return "scan"
 
     def _query_locked(self, q: torch.Tensor, k: int, include_values: bool, include_metadata: bool,
-                      mode: str = "auto", bitmap=None, ns: _Namespace | None = None) -> list[list[dict]]:
+                      mode: str = "auto", bitmap=None, ns: _Namespace | None = None, sparse=None) -> list[list[dict]]:
         """``ns``: a named namespace's state — the paged search over its pages (``mode`` as
         ``query_batch`` resolved it: "scan" unless the index has ``paged_search="mfma"``); the rows
-        that come back are its positions, mapped to pool rows where values are fetched."""
+        that come back are its positions, mapped to pool rows where values are fetched.
+        ``sparse``: the queries' sparse parts (a sparse-dense index) — the hybrid search, one path
+        for every ``k``, whatever the mode, the filter kind or the mask's share."""
         st = self if ns is None else ns
         n = len(st._ids)
         if n == 0 or q.shape[0] == 0:
             return [[] for _ in range(q.shape[0])]
         if bitmap is not None and bitmap[1] == 0:  # nothing is eligible: no device work
             return [[] for _ in range(q.shape[0])]
-        if k > _lib.RC_TOPK_MAX:  # deep top-k (max_top_k): one path whatever the mode, the filter kind or the mask's share
+        if sparse is not None:
+            if mode not in _lib.SEARCH_MODES:
+                raise ValueError(f"unknown search mode {mode!r}")
+            mask = None if bitmap is None else bitmap[0]
+            if ns is not None:
+                scores, rows = self._pool.search_pages_hybrid(q, k, ns.slot, n, sparse, mask=mask)
+            else:
+                scores, rows = self._set.search_hybrid(q, k, n, sparse, mask=mask)
+        elif k > _lib.RC_TOPK_MAX:  # deep top-k (max_top_k): one path whatever the mode, the filter kind or the mask's share
             if mode not in _lib.SEARCH_MODES:
                 raise ValueError(f"unknown search mode {mode!r}")
             mask = None if bitmap is None else bitmap[0]
@@ -1804,6 +2065,8 @@ class Index:
             for j, (s, r) in enumerate(sel):
                 vid = st._ids[r]
                 m = Record(vals[j], id=vid, score=float(s)) if include_values else {"id": vid, "score": float(s)}
+                if include_values and vid in st._sparse:
+                    dict.__setitem__(m, "sparse_values", sparsevalues.to_dict(st._sparse[vid]))
                 if include_metadata:
                     dict.__setitem__(m, "metadata", dict(st._meta.get(vid, {})))
                 matches.append(m)
@@ -1846,6 +2109,8 @@ class Index:
                 for j in range(live):
                     vid = ids[rows[j]]
                     m = Record(vals[j], id=vid, score=scores[j])
+                    if vid in st._sparse:
+                        dict.__setitem__(m, "sparse_values", sparsevalues.to_dict(st._sparse[vid]))
                     recent[vid] = vals[j]
                     if include_metadata:
                         dict.__setitem__(m, "metadata", dict(meta.get(vid, {})))
@@ -1880,6 +2145,8 @@ class Index:
             if found:
                 for (vid, _), v in zip(found, vals):
                     rec = Record(v, id=vid)  # "values" becomes a list when read (retriever/main.py reads metadata)
+                    if vid in st._sparse:
+                        dict.__setitem__(rec, "sparse_values", sparsevalues.to_dict(st._sparse[vid]))
                     dict.__setitem__(rec, "metadata", dict(st._meta.get(vid, {})))
                     vectors[vid] = rec
         return {"vectors": vectors, "namespace": namespace}
@@ -1906,6 +2173,7 @@ class Index:
             rows, norms = self._set.export_rows(n)
             np.save(os.path.join(path, "rows.npy"), rows)
             np.save(os.path.join(path, "norms.npy"), norms)
+            self._save_sparse(path, "", self)
             spaces = []
             for i, ns in enumerate(self._ns.values()):
                 cnt = len(ns._ids)
@@ -1916,6 +2184,7 @@ class Index:
                     nrows[pos0:pos0 + m], nnorms[pos0:pos0 + m] = self._pool.export_run(row0, m)
                 np.save(os.path.join(path, f"ns{i}_rows.npy"), nrows)
                 np.save(os.path.join(path, f"ns{i}_norms.npy"), nnorms)
+                self._save_sparse(path, f"ns{i}_", ns)
                 spaces.append({"name": ns.name, "count": cnt, "ids": list(ns._ids),
                                "metadata": {v: ns._meta.get(v, {}) for v in ns._ids}})
             manifest = {"format": self.SNAPSHOT_FORMAT_NAMESPACES if spaces else self.SNAPSHOT_FORMAT,
@@ -1927,10 +2196,36 @@ class Index:
                 manifest["namespaces"] = spaces
             if self.metadata_config is not None:  # only then: every other manifest stays byte for byte what it was
                 manifest["metadata_config"] = {"indexed": list(self.metadata_config["indexed"])}
+            if self.sparse_max_nnz:  # likewise only then
+                manifest["sparse_max_nnz"] = self.sparse_max_nnz
             tmp = os.path.join(path, "manifest.json.tmp")
             with open(tmp, "w") as f:
                 json.dump(manifest, f)
             os.replace(tmp, os.path.join(path, "manifest.json"))  # the manifest lands last
+
+    def _save_sparse(self, path: str, prefix: str, st) -> None:
+        """A sparse-dense index only: the sparse values of ``st``'s ids in row (position) order as CSR,
+        ``<prefix>sparse_off.npy`` int64 [count + 1], ``_idx.npy`` uint32, ``_val.npy`` float32."""
+        if not self.sparse_max_nnz:
+            return
+        off, idx, val = sparsevalues.csr([st._sparse.get(vid) for vid in st._ids])
+        total = int(off[-1])
+        np.save(os.path.join(path, prefix + "sparse_off.npy"), off)
+        np.save(os.path.join(path, prefix + "sparse_idx.npy"), idx[:total])
+        np.save(os.path.join(path, prefix + "sparse_val.npy"), val[:total])
+
+    @staticmethod
+    def _load_sparse(path: str, prefix: str, count: int, width: int) -> list:
+        off = np.load(os.path.join(path, prefix + "sparse_off.npy"), allow_pickle=False)
+        idx = np.load(os.path.join(path, prefix + "sparse_idx.npy"), allow_pickle=False)
+        val = np.load(os.path.join(path, prefix + "sparse_val.npy"), allow_pickle=False)
+        if off.shape != (count + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or idx.shape != (int(off[-1]),) or val.shape != idx.shape:
+            raise ValueError("snapshot files disagree on the sparse values")
+        out = []
+        for i in range(count):
+            a, b = int(off[i]), int(off[i + 1])
+            out.append(sparsevalues.normalize({"indices": idx[a:b].tolist(), "values": val[a:b].tolist()}, width))
+        return out
 
     @classmethod
     def load(cls, path: str, capacity: int | None = None, device=None, shards: int | None = None,
@@ -1950,7 +2245,8 @@ class Index:
                   capacity=max(int(capacity or man.get("capacity", 0)), n, 1), device=device, shards=shards,
                   devices=devices, filter=filter or man.get("filter", "native"), paged_search=paged_search,
                   metadata_config=metadata_config if metadata_config is not None else man.get("metadata_config"),
-                  max_top_k=max_top_k)
+                  max_top_k=max_top_k, **({"sparse_max_nnz": int(man["sparse_max_nnz"])} if "sparse_max_nnz" in man else {}))
+        width = idx.sparse_max_nnz
         if idx._set.ld != man["ld"]:
             raise ValueError("snapshot row layout does not match this build")
         rows = np.load(os.path.join(path, "rows.npy"), allow_pickle=False)
@@ -1965,6 +2261,11 @@ class Index:
         if n:
             with idx._mu:
                 idx._columns_write(idx._cols, idx._set, list(range(n)), [(vid, None, idx._meta[vid]) for vid in idx._ids])
+        if n and width:
+            sp = cls._load_sparse(path, "", n, width)
+            with idx._mu:
+                idx._sparse_write(idx._set, list(range(n)), sp)
+                idx._sparse_commit(idx, [(vid, None, None) for vid in idx._ids], sp)
         for i, sp in enumerate(man.get("namespaces", [])):
             cnt = int(sp["count"])
             nrows = np.load(os.path.join(path, f"ns{i}_rows.npy"), allow_pickle=False)
@@ -1983,7 +2284,7 @@ class Index:
                     r0 = r1
 
             with idx._mu:
-                idx._ns_upsert_locked(sp["name"], items, write)
+                idx._ns_upsert_locked(sp["name"], items, write, cls._load_sparse(path, f"ns{i}_", cnt, width) if width else None)
         return idx
 
     def describe_index_stats(self) -> dict:

@@ -465,6 +465,66 @@ int rc_index_scores(rc_index *h, const float *query, int64_t n_rows, float *out_
 int rc_index_scores_pages(rc_index *h, const float *query, int slot, int64_t n_pos, float *out_scores, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Sparse-dense hybrid scores on a dotproduct index ("Sparse-dense
+ * hybrid"): a record may carry sparse values beside its dense vector, a query a
+ * sparse vector, and the score is  dense . dense + sparse . sparse.
+ *
+ * The store, one per rc_index (per shard), is made by rc_index_sparse_enable(h,
+ * width), 1 <= width <= RC_SPARSE_MAX_NNZ: width slots of (uint32 index, f32 value)
+ * per local row, slot-major ([width][capacity]: 8 x width x capacity bytes), a row's
+ * slots ascending by index, unused ones padded with index 0xFFFFFFFF, which no record
+ * or query may carry.  It grows with rc_index_grow and is freed with the index.
+ * rc_index_sparse_write takes n local rows as HOST CSR (row rows[i] holds entries
+ * [off[i], off[i + 1]) of idx / val: strictly ascending indices, finite values, at
+ * most width of them), stages it itself and overwrites ALL width slots of every
+ * named row, so a reused row keeps nothing of its former owner; it returns when the
+ * store is written.  rc_sharded_sparse_enable / rc_sharded_sparse_write do the same
+ * for global rows (shard row % S, local row row / S).  There is no move call: the
+ * host layer keeps each id's sparse values and re-writes the rows a compaction moved.
+ *
+ * The rc_*_search_hybrid calls are their rc_*_search_deep twins plus the sparse
+ * queries as HOST CSR: sq_off int32 [nq + 1] from 0, query q holding entries
+ * [sq_off[q], sq_off[q + 1]) of sq_idx / sq_val, strictly ascending, at most
+ * RC_SPARSE_MAX_NNZ.  They run the deep search with one kernel between its score pass
+ * and its selection.  With d the f32 the score pass gives a row (rc_index_scores' bits),
+ *   t = +0.0f;  for the row's stored entries (i, v) in ascending i with (i, w) in the
+ *   query:  t = fadd(t, fmul(v, w))   (round to nearest, unfused);   score = fadd(d, t).
+ * A row without stored entries, and every row under a query without entries, keeps
+ * d's bits: with no sparse entries at all the call is rc_*_search_deep bit for bit.
+ * The result is the first k keys of the searches' total order (score descending, row
+ * ascending) over the eligible rows, for 1 <= k <= RC_DEEP_TOPK_MAX.  Masks, rows,
+ * positions, chunking and workspace follow the deep calls (a repeated call leaves
+ * rc_alloc_count() unchanged).  Every argument is checked before any device call
+ * (RC_ERR_INVALID): a store that is not enabled, a metric other than
+ * RC_METRIC_DOT, unsorted or repeated query indices, more than RC_SPARSE_MAX_NNZ
+ * entries, the padding value as an index, k outside [1, RC_DEEP_TOPK_MAX].
+ *
+ * rc_index_scores_hybrid is a diagnostic: rc_index_scores (slot < 0) or
+ * rc_index_scores_pages (slot >= 0) plus the add, for one query (sq_off [2]). */
+#define RC_SPARSE_MAX_NNZ 1024
+int rc_index_sparse_enable(rc_index *h, int width, void *stream);
+int rc_index_sparse_width(const rc_index *h, int *width); /* 0: not enabled */
+int rc_index_sparse_write(rc_index *h, const int64_t *rows, const int64_t *off, const uint32_t *idx, const float *val,
+                          int64_t n, void *stream);
+int rc_sharded_sparse_enable(rc_sharded *h, int width);
+int rc_sharded_sparse_write(rc_sharded *h, const int64_t *rows, const int64_t *off, const uint32_t *idx, const float *val,
+                            int64_t n);
+int rc_index_search_hybrid(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                           const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores,
+                           int64_t *out_rows, void *stream);
+int rc_index_search_pages_hybrid(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                                 const uint32_t *mask, const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val,
+                                 float *scores, int64_t *out_rows, void *stream);
+int rc_sharded_search_hybrid(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
+                             const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores,
+                             int64_t *out_rows, void *stream);
+int rc_sharded_search_pages_hybrid(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k,
+                                   const uint32_t *mask, const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val,
+                                   float *scores, int64_t *out_rows, void *stream);
+int rc_index_scores_hybrid(rc_index *h, const float *query, int slot, int64_t n, const int32_t *sq_off,
+                           const uint32_t *sq_idx, const float *sq_val, float *out_scores, void *stream);
+
+/* ------------------------------------------------------------------------
  * Metadata columns: the indexed metadata fields of an index's rows as typed
  * columns in device memory, and the kernel that turns a metadata filter
  * (index.query(filter=...)) into the row-eligibility bitmap the masked searches
