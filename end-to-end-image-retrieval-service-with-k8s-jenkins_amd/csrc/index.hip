@@ -744,6 +744,118 @@ void check_hybrid(const rc_index *h, const SparseQueries &sq, int nq) {
     sparse_check_queries(sq, nq);
 }
 
+// One search request, as every rc_index_search* entry point (and sharded.hip's deep search) fills it.
+struct SearchArgs {
+    const float *queries;
+    int nq;
+    int64_t n;  // rows [0, n), or positions [0, n) of `slot`
+    int k;
+    const uint32_t *mask;
+    int slot;  // -1: the rows
+    float *scores;
+    int64_t *out_rows;
+    hipStream_t stream;
+    uint64_t *out_keys = nullptr;  // the deep searches only: keys instead of scores / out_rows
+};
+
+// The range [0, n) of a request (caller holds h->mu): the device page list of `slot`, or null for
+// the rows (slot < 0).  Nothing reads h->capacity or h->tables for a search outside this.
+const int32_t *resolve_range(const rc_index *h, int slot, int64_t n) {
+    if (slot < 0) {
+        RC_REQUIRE(n >= 0 && n <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
+        return nullptr;
+    }
+    RC_REQUIRE(slot < (int)h->tables.size() && h->tables[slot].n_pages > 0, RC_ERR_INVALID,
+               "unknown slot (no page table was set for it)");
+    const rc_index::PageTable &t = h->tables[slot];
+    RC_REQUIRE(n >= 0 && n <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+    return t.dev;
+}
+
+// rc_index_search_masked / rc_index_search_pages_ex: the top-k searches' mode resolution.  Over a
+// slot the batched path has predicates of its own, and one refusal more.
+void topk_search(rc_index *h, const SearchArgs &a, int mode) {
+    check_search_args(h, a.nq, a.k, RC_TOPK_MAX, a.queries && a.scores && a.out_rows, mode);
+    // RC_SEARCH_MFMA_MASKED is RC_SEARCH_MFMA (refused where it is, with its errors; the same path
+    // without a mask) whose filter kernels read the mask too
+    const bool mask_filter = mode == RC_SEARCH_MFMA_MASKED;
+    if (mask_filter) mode = RC_SEARCH_MFMA;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int32_t *pages = resolve_range(h, a.slot, a.n);
+    if (a.nq == 0) return;
+    DeviceScope ds(h->device);
+    // without RC_FILTER_METRIC the batched path's candidate threshold is a bound in cosine space:
+    // a non-cosine index scans (AUTO) and refuses MFMA, whatever it holds.  With it the filter
+    // bounds the metric's own score (search_mfma.hip) on the f16 / bf16 rows it was set on.
+    const bool metric_ok = h->metric == RC_METRIC_COSINE || h->filter == RC_FILTER_METRIC;
+    RC_REQUIRE(mode != RC_SEARCH_MFMA || metric_ok, RC_ERR_UNSUPPORTED,
+               "batched MFMA search is cosine-only without RC_FILTER_METRIC (this index scores by dotproduct or euclidean)");
+    // an empty shard (a shard with none of the slot's positions) answers (-inf, -1) in every mode:
+    // over the rows before the refusals below, over a slot after them
+    if (a.n == 0 && pages == nullptr) return empty_search(a.nq, a.k, a.scores, a.out_rows, a.stream);
+    // (a float8 index scans unless its own filter is switched on: RC_FILTER_F8); the paged kernels are
+    // the native f16 / bf16 ones, cosine or RC_FILTER_METRIC: the int8 and float8 filters have no paged form
+    const bool mfma_ok =
+        metric_ok && (pages != nullptr ? (h->dtype == RC_F16 || h->dtype == RC_BF16) && h->rows8 == nullptr &&
+                                             (h->filter == RC_FILTER_NATIVE || h->filter == RC_FILTER_METRIC)
+                                       : (h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr || h->filter == RC_FILTER_F8);
+    RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
+               pages != nullptr ? "batched MFMA search over pages needs an f16/bf16 index with the native or the metric filter"
+                                : "batched MFMA search needs an f16/bf16 index, the int8 filter copy, or a float8 index with RC_FILTER_F8");
+    RC_REQUIRE(mode != RC_SEARCH_MFMA || pages == nullptr ||
+                   paged_filter_supported(h->ld, h->metric != RC_METRIC_COSINE, mask_filter && a.mask != nullptr),
+               RC_ERR_UNSUPPORTED,
+               "RC_SEARCH_MFMA_MASKED over pages is not available under a non-cosine metric at row width 512 (use RC_SEARCH_MFMA)");
+    if (a.n == 0) return empty_search(a.nq, a.k, a.scores, a.out_rows, a.stream);
+    // with a mask AUTO scans: only the caller knows the eligible share, and a selective mask
+    // makes the scan cheaper while the filter GEMM still reads every row (MFMA on request; the
+    // masked paged forms are unmeasured)
+    bool auto_mfma = a.nq >= kBatchMinQueries && a.n >= kBatchMinRows;
+    if (pages != nullptr) {  // its own corner (see kPagedBatchMinQueries)
+        auto_mfma = (a.nq >= kPagedBatchMinQueries && a.n >= kPagedBatchMinPositions) ||
+                    (a.nq >= kPagedBatchMinQueriesLarge && a.n >= kPagedBatchMinPositionsLarge);
+    } else if (h->filter == RC_FILTER_F8) {  // its own corner (see kF8BatchMinPasses)
+        const int qb = scan_max_qb(h->nch, a.k);
+        const int passes = (a.nq + qb - 1) / qb;
+        auto_mfma = (passes >= kF8BatchMinPasses && a.n >= kF8BatchMinRows) ||
+                    (passes >= kF8BatchMinPassesLarge && a.n * h->ld >= kF8BatchMinBytesLarge);
+    } else if (h->filter == RC_FILTER_METRIC && h->metric != RC_METRIC_COSINE) {  // its own corner (see kMetricBatchMinQueries); f16 / bf16 rows
+        auto_mfma = (a.nq >= kMetricBatchMinQueries && a.n >= kBatchMinRows) ||
+                    (a.nq >= kMetricBatchMinQueriesLarge && a.n * h->ld * 2 >= kMetricBatchMinBytesLarge);
+    }
+    const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && a.mask == nullptr && mfma_ok && auto_mfma);
+    if (use_mfma) batched_search_exact(h, a.queries, a.nq, a.n, a.k, a.mask, mask_filter, a.scores, a.out_rows, a.stream, pages);
+    else scan_search(h, a.queries, a.nq, a.n, a.k, a.mask, a.scores, a.out_rows, a.stream, pages);
+}
+
+// The deep and the hybrid (sq != null) searches, rc_index_search_deep to rc_index_search_pages_hybrid
+// and index_search_deep (sharded.hip): into a.scores / a.out_rows, or into a.out_keys when that is given.
+void deep_search(rc_index *h, const SearchArgs &a, const SparseQueries *sq) {
+    check_search_args(h, a.nq, a.k, RC_DEEP_TOPK_MAX, a.queries && (a.out_keys || (a.scores && a.out_rows)));
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int32_t *pages = resolve_range(h, a.slot, a.n);
+    if (a.nq == 0) return;
+    if (sq != nullptr) check_hybrid(h, *sq, a.nq);
+    DeviceScope ds(h->device);
+    const DeepAfterScores step = sq != nullptr ? sparse_step(h, *sq, a.nq, a.n, pages, a.stream) : nullptr;
+    deep_search_locked(h, a.queries, a.nq, a.n, a.k, a.mask, pages, a.out_keys, a.scores, a.out_rows, a.stream, step ? &step : nullptr);
+}
+
+// rc_index_scores, rc_index_scores_pages and rc_index_scores_hybrid (sq != null): the score pass of
+// one query over the range, then its sparse terms.
+void scores_pass(rc_index *h, const float *query, int slot, int64_t n, const SparseQueries *sq, float *out, hipStream_t s) {
+    RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+    RC_REQUIRE(n == 0 || (query && out), RC_ERR_INVALID, "null buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int32_t *pages = resolve_range(h, slot, n);
+    if (sq != nullptr) check_hybrid(h, *sq, 1);
+    if (n == 0) return;
+    DeviceScope ds(h->device);
+    const DeepAfterScores step = sq != nullptr ? sparse_step(h, *sq, 1, n, pages, s) : nullptr;
+    deep_score_pass(h, query, 1, n, pages, out, s);
+    if (step) step(0, 1, out, s);
+}
+
 }  // namespace
 
 namespace rc {
@@ -831,20 +943,12 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
     return true;
 }
 
-// The table of a slot, or an error (caller holds h->mu).
-static const rc_index::PageTable &page_table(const rc_index *h, int slot) {
-    RC_REQUIRE(slot >= 0 && slot < (int)h->tables.size() && h->tables[slot].n_pages > 0, RC_ERR_INVALID,
-               "unknown slot (no page table was set for it)");
-    return h->tables[slot];
-}
-
 // Internal (sharded.hip, rc_sharded_query_host_pages): the values of the positions pos[0..n)
 // (device; < 0 = empty: NaN) of a slot, as rc_index_fetch gives them, on stream `s`.
 void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos, int64_t n, float *out, hipStream_t s) {
     if (n == 0) return;
     std::lock_guard<std::mutex> lk(h->mu);
-    const rc_index::PageTable &t = page_table(h, slot);
-    RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+    const int32_t *pages = resolve_range(h, paged_slot(slot), n_pos);
     DeviceScope ds(h->device);
     if (n > h->pg_rows_cap) {
         RC_HIP(hipDeviceSynchronize());  // no gather may still read the old list
@@ -854,31 +958,19 @@ void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos,
         h->pg_rows = (int64_t *)dmalloc((size_t)n * sizeof(int64_t));
         h->pg_rows_cap = n;
     }
-    hipLaunchKernelGGL(pages_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pos, n, t.dev, n_pos, h->pg_rows);
+    hipLaunchKernelGGL(pages_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pos, n, pages, n_pos, h->pg_rows);
     RC_LAUNCH_CHECK();
     dispatch_dtype(h->dtype, [&](auto tt) { launch_fetch<decltype(tt)>(h, h->pg_rows, n, out, false, s); });
 }
 
-// Internal (sharded.hip, rc_sharded_search_deep): a shard's own deep top-k as keys [nq][k] that
-// carry global rows (slot >= 0: global positions of that slot over [0, n) local positions),
-// KEY_EMPTY past the eligible rows, on stream `s`.  mask: device bitmap over the local rows /
-// positions, or null.  The caller has checked nq, k and the buffers.
-// sq (rc_sharded_search_hybrid): the call's sparse queries, already checked; null: the deep search.
-void index_search_deep_keys(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, int slot,
-                            uint64_t *out_keys, hipStream_t s, const SparseQueries *sq) {
-    std::lock_guard<std::mutex> lk(h->mu);
-    const int32_t *pages = nullptr;
-    if (slot >= 0) {
-        const rc_index::PageTable &t = page_table(h, slot);
-        RC_REQUIRE(n >= 0 && n <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
-        pages = t.dev;
-    } else {
-        RC_REQUIRE(n >= 0 && n <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
-    }
-    if (sq != nullptr) RC_REQUIRE(h->sparse.width > 0, RC_ERR_INVALID, "this index has no sparse store (rc_index_sparse_enable)");
-    DeviceScope ds(h->device);
-    const DeepAfterScores step = sq != nullptr ? sparse_step(h, *sq, nq, n, pages, s) : nullptr;
-    deep_search_locked(h, queries, nq, n, k, mask, pages, out_keys, nullptr, nullptr, s, step ? &step : nullptr);
+// Internal (sharded.hip, rc_sharded_search_deep / _hybrid): a shard's own deep top-k on stream `s`,
+// slot >= 0: over [0, n) local positions of that slot.  out_keys: keys [nq][k] that carry global
+// rows, KEY_EMPTY past the eligible rows; null: scores / out_rows, as rc_index_search_deep gives
+// them.  mask: device bitmap over the local rows / positions, or null.
+// sq: the call's sparse queries (the hybrid searches); null: the deep search.
+void index_search_deep(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, int slot,
+                       uint64_t *out_keys, float *scores, int64_t *out_rows, hipStream_t s, const SparseQueries *sq) {
+    deep_search(h, SearchArgs{queries, nq, n, k, mask, slot, scores, out_rows, s, out_keys}, sq);
 }
 }  // namespace rc
 
@@ -1250,56 +1342,7 @@ int rc_index_search_ex(rc_index *h, const float *queries, int nq, int64_t n_rows
 
 int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
                            float *scores, int64_t *out_rows, int mode, void *stream) {
-    return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
-        RC_REQUIRE(n_rows >= 0 && n_rows <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
-        RC_REQUIRE(mode == RC_SEARCH_AUTO || mode == RC_SEARCH_SCAN || mode == RC_SEARCH_MFMA || mode == RC_SEARCH_MFMA_MASKED,
-                   RC_ERR_INVALID, "unknown search mode");
-        // RC_SEARCH_MFMA_MASKED is RC_SEARCH_MFMA (refused where it is, with its errors; the same path
-        // without a mask) whose filter kernels read the mask too
-        const bool mask_filter = mode == RC_SEARCH_MFMA_MASKED;
-        if (mask_filter) mode = RC_SEARCH_MFMA;
-        if (nq == 0) return;
-        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        DeviceScope ds(h->device);
-        hipStream_t s = (hipStream_t)stream;
-        // without RC_FILTER_METRIC the batched path's candidate threshold is a bound in cosine space:
-        // a non-cosine index scans (AUTO) and refuses MFMA, whatever it holds.  With it the filter
-        // bounds the metric's own score (search_mfma.hip) on the f16 / bf16 rows it was set on.
-        const bool metric_ok = h->metric == RC_METRIC_COSINE || h->filter == RC_FILTER_METRIC;
-        RC_REQUIRE(mode != RC_SEARCH_MFMA || metric_ok, RC_ERR_UNSUPPORTED,
-                   "batched MFMA search is cosine-only without RC_FILTER_METRIC (this index scores by dotproduct or euclidean)");
-        if (n_rows == 0) {  // an empty shard answers (-inf, -1) in every mode
-            empty_search(nq, k, scores, out_rows, s);
-            return;
-        }
-        // (a float8 index scans unless its own filter is switched on: RC_FILTER_F8)
-        const bool mfma_ok = metric_ok && ((h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr ||
-                                           h->filter == RC_FILTER_F8);
-        RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
-                   "batched MFMA search needs an f16/bf16 index, the int8 filter copy, or a float8 index with RC_FILTER_F8");
-        // with a mask AUTO scans: only the caller knows the eligible share, and a selective mask
-        // makes the scan cheaper while the filter GEMM still reads every row (MFMA on request)
-        bool auto_mfma = nq >= kBatchMinQueries && n_rows >= kBatchMinRows;
-        if (h->filter == RC_FILTER_F8) {  // its own corner (see kF8BatchMinPasses)
-            const int qb = scan_max_qb(h->nch, k);
-            const int passes = (nq + qb - 1) / qb;
-            auto_mfma = (passes >= kF8BatchMinPasses && n_rows >= kF8BatchMinRows) ||
-                        (passes >= kF8BatchMinPassesLarge && n_rows * h->ld >= kF8BatchMinBytesLarge);
-        }
-        if (h->filter == RC_FILTER_METRIC && h->metric != RC_METRIC_COSINE)  // its own corner (see kMetricBatchMinQueries); f16 / bf16 rows
-            auto_mfma = (nq >= kMetricBatchMinQueries && n_rows >= kBatchMinRows) ||
-                        (nq >= kMetricBatchMinQueriesLarge && n_rows * h->ld * 2 >= kMetricBatchMinBytesLarge);
-        const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && mask == nullptr && mfma_ok && auto_mfma);
-        if (!use_mfma) {
-            scan_search(h, queries, nq, n_rows, k, mask, scores, out_rows, s);
-            return;
-        }
-        batched_search_exact(h, queries, nq, n_rows, k, mask, mask_filter, scores, out_rows, s);
-    });
+    return guard([&] { topk_search(h, SearchArgs{queries, nq, n_rows, k, mask, -1, scores, out_rows, (hipStream_t)stream}, mode); });
 }
 
 int rc_index_pages_set(rc_index *h, int slot, const int32_t *pages_host, int n_pages, void *stream) {
@@ -1345,102 +1388,28 @@ int rc_index_search_pages(rc_index *h, const float *queries, int nq, int slot, i
 int rc_index_search_pages_ex(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
                              float *scores, int64_t *out_rows, int mode, void *stream) {
     return guard([&] {
-        RC_REQUIRE(mode == RC_SEARCH_AUTO || mode == RC_SEARCH_SCAN || mode == RC_SEARCH_MFMA || mode == RC_SEARCH_MFMA_MASKED,
-                   RC_ERR_INVALID, "unknown search mode");
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
-        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
-        const bool mask_filter = mode == RC_SEARCH_MFMA_MASKED;  // without a mask it is RC_SEARCH_MFMA
-        if (mask_filter) mode = RC_SEARCH_MFMA;
-        std::lock_guard<std::mutex> lk(h->mu);
-        const rc_index::PageTable &t = page_table(h, slot);
-        RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
-        if (nq == 0) return;
-        // refused where rc_index_search_ex refuses the mode, and on the int8 and float8 filters, which
-        // have no paged form: the paged kernels are the native f16 / bf16 ones, cosine or RC_FILTER_METRIC
-        const bool metric_ok = h->metric == RC_METRIC_COSINE || h->filter == RC_FILTER_METRIC;
-        RC_REQUIRE(mode != RC_SEARCH_MFMA || metric_ok, RC_ERR_UNSUPPORTED,
-                   "batched MFMA search is cosine-only without RC_FILTER_METRIC (this index scores by dotproduct or euclidean)");
-        const bool mfma_ok = metric_ok && (h->dtype == RC_F16 || h->dtype == RC_BF16) && h->rows8 == nullptr &&
-                             (h->filter == RC_FILTER_NATIVE || h->filter == RC_FILTER_METRIC);
-        RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
-                   "batched MFMA search over pages needs an f16/bf16 index with the native or the metric filter");
-        RC_REQUIRE(mode != RC_SEARCH_MFMA || paged_filter_supported(h->ld, h->metric != RC_METRIC_COSINE, mask_filter && mask != nullptr),
-                   RC_ERR_UNSUPPORTED,
-                   "RC_SEARCH_MFMA_MASKED over pages is not available under a non-cosine metric at row width 512 (use RC_SEARCH_MFMA)");
-        DeviceScope ds(h->device);
-        hipStream_t s = (hipStream_t)stream;
-        if (n_pos == 0) {  // this shard holds none of the slot's positions
-            empty_search(nq, k, scores, out_rows, s);
-            return;
-        }
-        // with a mask AUTO scans (as rc_index_search_masked, and the masked paged forms are unmeasured)
-        const bool auto_mfma = (nq >= kPagedBatchMinQueries && n_pos >= kPagedBatchMinPositions) ||
-                               (nq >= kPagedBatchMinQueriesLarge && n_pos >= kPagedBatchMinPositionsLarge);
-        const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && mask == nullptr && mfma_ok && auto_mfma);
-        if (!use_mfma) {
-            scan_search(h, queries, nq, n_pos, k, mask, scores, out_rows, s, t.dev);
-            return;
-        }
-        batched_search_exact(h, queries, nq, n_pos, k, mask, mask_filter, scores, out_rows, s, t.dev);
+        topk_search(h, SearchArgs{queries, nq, n_pos, k, mask, paged_slot(slot), scores, out_rows, (hipStream_t)stream}, mode);
     });
 }
 
 int rc_index_search_deep(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask, float *scores,
                          int64_t *out_rows, void *stream) {
-    return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
-        RC_REQUIRE(n_rows >= 0 && n_rows <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
-        if (nq == 0) return;
-        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        DeviceScope ds(h->device);
-        deep_search_locked(h, queries, nq, n_rows, k, mask, nullptr, nullptr, scores, out_rows, (hipStream_t)stream);
-    });
+    return guard([&] { deep_search(h, SearchArgs{queries, nq, n_rows, k, mask, -1, scores, out_rows, (hipStream_t)stream}, nullptr); });
 }
 
 int rc_index_search_pages_deep(rc_index *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
                                float *scores, int64_t *out_rows, void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
-        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        const rc_index::PageTable &t = page_table(h, slot);
-        RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
-        if (nq == 0) return;
-        DeviceScope ds(h->device);
-        deep_search_locked(h, queries, nq, n_pos, k, mask, t.dev, nullptr, scores, out_rows, (hipStream_t)stream);
+        deep_search(h, SearchArgs{queries, nq, n_pos, k, mask, paged_slot(slot), scores, out_rows, (hipStream_t)stream}, nullptr);
     });
 }
 
 int rc_index_scores(rc_index *h, const float *query, int64_t n_rows, float *out_scores, void *stream) {
-    return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(n_rows >= 0 && n_rows <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
-        if (n_rows == 0) return;
-        RC_REQUIRE(query && out_scores, RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        DeviceScope ds(h->device);
-        deep_score_pass(h, query, 1, n_rows, nullptr, out_scores, (hipStream_t)stream);
-    });
+    return guard([&] { scores_pass(h, query, -1, n_rows, nullptr, out_scores, (hipStream_t)stream); });
 }
 
 int rc_index_scores_pages(rc_index *h, const float *query, int slot, int64_t n_pos, float *out_scores, void *stream) {
-    return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(n_pos == 0 || (query && out_scores), RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        const rc_index::PageTable &t = page_table(h, slot);
-        RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
-        if (n_pos == 0) return;
-        DeviceScope ds(h->device);
-        deep_score_pass(h, query, 1, n_pos, t.dev, out_scores, (hipStream_t)stream);
-    });
+    return guard([&] { scores_pass(h, query, paged_slot(slot), n_pos, nullptr, out_scores, (hipStream_t)stream); });
 }
 
 int rc_index_sparse_enable(rc_index *h, int width, void *stream) {
@@ -1533,19 +1502,8 @@ int rc_index_search_hybrid(rc_index *h, const float *queries, int nq, int64_t n_
                            const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores, int64_t *out_rows,
                            void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
-        RC_REQUIRE(n_rows >= 0 && n_rows <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
-        if (nq == 0) return;
-        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
         const SparseQueries sq{sq_off, sq_idx, sq_val};
-        check_hybrid(h, sq, nq);
-        DeviceScope ds(h->device);
-        hipStream_t s = (hipStream_t)stream;
-        const DeepAfterScores step = sparse_step(h, sq, nq, n_rows, nullptr, s);
-        deep_search_locked(h, queries, nq, n_rows, k, mask, nullptr, nullptr, scores, out_rows, s, step ? &step : nullptr);
+        deep_search(h, SearchArgs{queries, nq, n_rows, k, mask, -1, scores, out_rows, (hipStream_t)stream}, &sq);
     });
 }
 
@@ -1553,45 +1511,16 @@ int rc_index_search_pages_hybrid(rc_index *h, const float *queries, int nq, int 
                                  const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores,
                                  int64_t *out_rows, void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
-        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        const rc_index::PageTable &t = page_table(h, slot);
-        RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
-        if (nq == 0) return;
         const SparseQueries sq{sq_off, sq_idx, sq_val};
-        check_hybrid(h, sq, nq);
-        DeviceScope ds(h->device);
-        hipStream_t s = (hipStream_t)stream;
-        const DeepAfterScores step = sparse_step(h, sq, nq, n_pos, t.dev, s);
-        deep_search_locked(h, queries, nq, n_pos, k, mask, t.dev, nullptr, scores, out_rows, s, step ? &step : nullptr);
+        deep_search(h, SearchArgs{queries, nq, n_pos, k, mask, paged_slot(slot), scores, out_rows, (hipStream_t)stream}, &sq);
     });
 }
 
 int rc_index_scores_hybrid(rc_index *h, const float *query, int slot, int64_t n, const int32_t *sq_off, const uint32_t *sq_idx,
                            const float *sq_val, float *out_scores, void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(n == 0 || (query && out_scores), RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        const int32_t *pages = nullptr;
-        if (slot >= 0) {
-            const rc_index::PageTable &t = page_table(h, slot);
-            RC_REQUIRE(n >= 0 && n <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
-            pages = t.dev;
-        } else {
-            RC_REQUIRE(n >= 0 && n <= h->capacity, RC_ERR_INVALID, "n_rows out of range");
-        }
         const SparseQueries sq{sq_off, sq_idx, sq_val};
-        check_hybrid(h, sq, 1);
-        if (n == 0) return;
-        DeviceScope ds(h->device);
-        hipStream_t s = (hipStream_t)stream;
-        const DeepAfterScores step = sparse_step(h, sq, 1, n, pages, s);
-        deep_score_pass(h, query, 1, n, pages, out_scores, s);
-        if (step) step(0, 1, out_scores, s);
+        scores_pass(h, query, slot, n, &sq, out_scores, (hipStream_t)stream);
     });
 }
 

@@ -47,6 +47,23 @@ template <typename T> constexpr float query_unscale() { return sizeof(T) == 1 ? 
 
 inline size_t dtype_size(int dtype) { return dtype == RC_F32 ? 4 : dtype == RC_F8 ? 1 : 2; }
 
+// The argument check of every search entry point (index.hip, sharded.hip), in the one order they
+// all keep: nothing here reads *h, so a bad mode, count, k or buffer is refused whatever the handle
+// points to.  k_max: RC_TOPK_MAX or RC_DEEP_TOPK_MAX; buffers: the call's buffers are all there
+// (asked only of a call with queries).
+inline void check_search_args(const void *h, int nq, int k, int k_max, bool buffers, int mode = RC_SEARCH_AUTO) {
+    RC_REQUIRE(mode == RC_SEARCH_AUTO || mode == RC_SEARCH_SCAN || mode == RC_SEARCH_MFMA || mode == RC_SEARCH_MFMA_MASKED,
+               RC_ERR_INVALID, "unknown search mode");
+    RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+    RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
+    RC_REQUIRE(k >= 1 && k <= k_max, RC_ERR_INVALID, k_max == RC_TOPK_MAX ? "top_k must be in [1, 256]" : "top_k must be in [1, 10000]");
+    RC_REQUIRE(nq == 0 || buffers, RC_ERR_INVALID, "null buffer");
+}
+
+// The slot of an entry point that takes one: a negative slot is an unknown slot there, never the
+// rows (which -1 stands for inside index.hip and sharded.hip).  No table is ever set for this one.
+inline int paged_slot(int slot) { return slot < 0 ? RC_PAGE_SLOTS_MAX : slot; }
+
 // A staging block of stored rows outside any index (row moves between shards, sharded.hip):
 // cap rows of ld elements in the storage dtype, and their f32 norms.
 struct RowBlock {

@@ -36,8 +36,8 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
                   int64_t *out_rows, float *out_values, hipStream_t s, volatile unsigned **done = nullptr,
                   unsigned *seq = nullptr);
 void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos, int64_t n, float *out, hipStream_t s);
-void index_search_deep_keys(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, int slot,
-                            uint64_t *out_keys, hipStream_t s, const SparseQueries *sq = nullptr);
+void index_search_deep(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, int slot,
+                       uint64_t *out_keys, float *scores, int64_t *out_rows, hipStream_t s, const SparseQueries *sq);
 
 // Wait for query1's completion word instead of the stream: the word is stored after the results
 // (system-scope release), so the host can read them the moment it changes, without the
@@ -860,90 +860,39 @@ void fetch_locked(rc_sharded *h, const int64_t *rows, int64_t n, float *out, int
         }
 }
 
-// rc_sharded_search's body (caller holds h->mu; device buffers on the leader, stream = leader stream)
-// mask (optional): HOST bitmap over the global rows; staged per shard first, and the call then
-// returns only once the staged words were copied (the next call may overwrite them).
-// slot >= 0 (rc_sharded_search_pages): n_rows, the mask and the returned rows are positions of
-// that slot; position i is on shard i % n as its position i / n, exactly as global rows are, so
-// the split of the mask, the shards' row maps and the merge are the ones of the dense search.
-void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
-                   int mode, void *stream, const uint32_t *mask = nullptr, int slot = -1) {
-        hipStream_t ls = (hipStream_t)stream;
-        const bool masked = mask != nullptr;
-        if (masked) stage_mask(h, mask, n_rows, ls);
-        auto shard_search = [&](int s, const float *q, int64_t n_local, float *so, int64_t *ro, void *st) {
-            const uint32_t *m = masked ? h->mk_d[s] : nullptr;
-            return slot >= 0 ? rc_index_search_pages_ex(h->shard[s], q, nq, slot, n_local, k, m, so, ro, mode, st)
-                             : rc_index_search_masked(h->shard[s], q, nq, n_local, k, m, so, ro, mode, st);
-        };
-        if (h->n == 1) {
-            check_status(shard_search(0, queries, n_rows, scores, out_rows, stream));
-            if (masked) {
-                fence_mask_single(h, ls);
-                wait_mask(h);
-            }
-            return;
-        }
-        ensure_search(h, nq, k);
-        const int64_t slice = (int64_t)nq * k;
-        {
-            DeviceScope dl(h->dev[0]);
-            for (int s = 0; s < h->n; ++s) RC_HIP(hipEventRecord(h->ev_start[s], ls));
-        }
-        for (int s = 0; s < h->n; ++s) {
-            DeviceScope ds(h->dev[s]);
-            RC_HIP(hipStreamWaitEvent(h->st[s], h->ev_start[s], 0));
-            const bool local = !h->remote[s];
-            const float *q = queries;
-            if (!local) {
-                RC_HIP(hipMemcpyPeerAsync(h->q[s], h->dev[s], queries, h->dev[0], (size_t)nq * h->dim * sizeof(float), h->st[s]));
-                q = h->q[s];
-            }
-            float *so = local ? h->g_s + s * slice : h->s_loc[s];
-            int64_t *ro = local ? h->g_r + s * slice : h->r_loc[s];
-            check_status(shard_search(s, q, shard_rows(h, s, n_rows), so, ro, h->st[s]));
-            if (!local) {
-                RC_HIP(hipMemcpyPeerAsync(h->g_s + s * slice, h->dev[0], so, h->dev[s], slice * sizeof(float), h->st[s]));
-                RC_HIP(hipMemcpyPeerAsync(h->g_r + s * slice, h->dev[0], ro, h->dev[s], slice * sizeof(int64_t), h->st[s]));
-            }
-            RC_HIP(hipEventRecord(h->ev_done[s], h->st[s]));
-        }
-        DeviceScope dl(h->dev[0]);
-        for (int s = 0; s < h->n; ++s) RC_HIP(hipStreamWaitEvent(ls, h->ev_done[s], 0));
-        check_status(rc_topk_merge(h->g_s, h->g_r, h->n, nq, k, k, scores, out_rows, stream));
-        if (masked) wait_mask(h);
-}
+// One result array of a fan-out, `bytes` per shard (nq x k entries): a single shard writes to `single`
+// (the caller's own buffer), a shard on the leader's device to its slice of `gather` (leader,
+// [n] slices), any other to loc[s] on its device, which is then peer-copied to that slice.
+struct FanBuf {
+    size_t bytes;
+    void *single;
+    void *gather;
+    void *const *loc;
+};
 
-// rc_sharded_search_deep's body (caller holds h->mu; device buffers on the leader, stream = leader
-// stream), as search_locked: the mask is a HOST bitmap over the global rows (slot >= 0: positions)
-// staged per shard.  Each shard selects its own k keys (global rows) with no traffic per round;
-// the leader gathers the n lists and runs the same rounds over those n x k keys.  A key's order
-// does not depend on the shard that held the row, so the result is that of one index.
-// sq (rc_sharded_search_hybrid, checked by the caller): the sparse queries, which every shard stages on
-// its own device and adds to its scores before it selects; null: the deep search.
-void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
-                        void *stream, const uint32_t *mask, int slot, const SparseQueries *sq = nullptr) {
-    hipStream_t ls = (hipStream_t)stream;
+// The fan-out of a search over the shards (caller holds h->mu; `queries` on the leader, ls = the
+// leader stream): the HOST mask over the global rows (optional) is staged per shard first, then
+// every shard waits for the leader stream, takes the queries (a peer copy into qcopy[s] when it
+// is remote), runs call(s, queries, its row count, its device mask, its nbuf outputs, its stream)
+// and hands its results to the leader, whose stream waits for all of them.  Returns false when
+// the one shard there is answered the caller directly, on ls (nothing is left to merge and the
+// mask's words are free again), true with every buf's gather filled in stream order: the caller
+// merges, then wait_mask()s if it gave a mask (the next call may overwrite the staged words).
+template <typename Call>
+bool fan_out(rc_sharded *h, const float *queries, int nq, int64_t n_rows, const uint32_t *mask, hipStream_t ls,
+             const std::vector<float *> &qcopy, const FanBuf *buf, int nbuf, Call call) {
     const bool masked = mask != nullptr;
     if (masked) stage_mask(h, mask, n_rows, ls);
+    void *out[2] = {nullptr, nullptr};
     if (h->n == 1) {
-        const uint32_t *m = masked ? h->mk_d[0] : nullptr;
-        if (sq != nullptr)
-            check_status(slot >= 0 ? rc_index_search_pages_hybrid(h->shard[0], queries, nq, slot, n_rows, k, m, sq->off, sq->idx, sq->val,
-                                                                  scores, out_rows, stream)
-                                   : rc_index_search_hybrid(h->shard[0], queries, nq, n_rows, k, m, sq->off, sq->idx, sq->val, scores,
-                                                            out_rows, stream));
-        else
-            check_status(slot >= 0 ? rc_index_search_pages_deep(h->shard[0], queries, nq, slot, n_rows, k, m, scores, out_rows, stream)
-                                   : rc_index_search_deep(h->shard[0], queries, nq, n_rows, k, m, scores, out_rows, stream));
+        for (int b = 0; b < nbuf; ++b) out[b] = buf[b].single;
+        call(0, queries, n_rows, masked ? h->mk_d[0] : nullptr, out, ls);
         if (masked) {
             fence_mask_single(h, ls);
             wait_mask(h);
         }
-        return;
+        return false;
     }
-    ensure_deep(h, nq, k);
-    const int64_t slice = (int64_t)nq * k;
     {
         DeviceScope dl(h->dev[0]);
         for (int s = 0; s < h->n; ++s) RC_HIP(hipEventRecord(h->ev_start[s], ls));
@@ -954,18 +903,61 @@ void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_r
         const bool local = !h->remote[s];
         const float *q = queries;
         if (!local) {
-            RC_HIP(hipMemcpyPeerAsync(h->dq[s], h->dev[s], queries, h->dev[0], (size_t)nq * h->dim * sizeof(float), h->st[s]));
-            q = h->dq[s];
+            RC_HIP(hipMemcpyPeerAsync(qcopy[s], h->dev[s], queries, h->dev[0], (size_t)nq * h->dim * sizeof(float), h->st[s]));
+            q = qcopy[s];
         }
-        uint64_t *ko = local ? h->dg_keys + s * slice : h->dk_loc[s];
-        index_search_deep_keys(h->shard[s], q, nq, shard_rows(h, s, n_rows), k, masked ? h->mk_d[s] : nullptr, slot, ko, h->st[s],
-                               sq);
-        if (!local)
-            RC_HIP(hipMemcpyPeerAsync(h->dg_keys + s * slice, h->dev[0], ko, h->dev[s], (size_t)slice * sizeof(uint64_t), h->st[s]));
+        for (int b = 0; b < nbuf; ++b) out[b] = local ? (uint8_t *)buf[b].gather + s * buf[b].bytes : buf[b].loc[s];
+        call(s, q, shard_rows(h, s, n_rows), masked ? h->mk_d[s] : nullptr, out, h->st[s]);
+        for (int b = 0; b < nbuf && !local; ++b)
+            RC_HIP(hipMemcpyPeerAsync((uint8_t *)buf[b].gather + s * buf[b].bytes, h->dev[0], out[b], h->dev[s], buf[b].bytes, h->st[s]));
         RC_HIP(hipEventRecord(h->ev_done[s], h->st[s]));
     }
     DeviceScope dl(h->dev[0]);
     for (int s = 0; s < h->n; ++s) RC_HIP(hipStreamWaitEvent(ls, h->ev_done[s], 0));
+    return true;
+}
+
+// rc_sharded_search's body (caller holds h->mu; device buffers on the leader, stream = leader stream)
+// mask (optional): HOST bitmap over the global rows (fan_out).
+// slot >= 0 (rc_sharded_search_pages): n_rows, the mask and the returned rows are positions of
+// that slot; position i is on shard i % n as its position i / n, exactly as global rows are, so
+// the split of the mask, the shards' row maps and the merge are the ones of the dense search.
+void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
+                   int mode, void *stream, const uint32_t *mask = nullptr, int slot = -1) {
+    if (h->n > 1) ensure_search(h, nq, k);
+    const size_t slice = (size_t)nq * k;
+    const FanBuf out[2] = {{slice * sizeof(float), scores, h->g_s, (void *const *)h->s_loc.data()},
+                           {slice * sizeof(int64_t), out_rows, h->g_r, (void *const *)h->r_loc.data()}};
+    const bool gathered = fan_out(h, queries, nq, n_rows, mask, (hipStream_t)stream, h->q, out, 2,
+                                  [&](int s, const float *q, int64_t n_local, const uint32_t *m, void *const *o, hipStream_t st) {
+        check_status(slot >= 0 ? rc_index_search_pages_ex(h->shard[s], q, nq, slot, n_local, k, m, (float *)o[0], (int64_t *)o[1], mode, st)
+                               : rc_index_search_masked(h->shard[s], q, nq, n_local, k, m, (float *)o[0], (int64_t *)o[1], mode, st));
+    });
+    if (!gathered) return;
+    DeviceScope dl(h->dev[0]);
+    check_status(rc_topk_merge(h->g_s, h->g_r, h->n, nq, k, k, scores, out_rows, stream));
+    if (mask != nullptr) wait_mask(h);
+}
+
+// rc_sharded_search_deep's body (caller holds h->mu; device buffers on the leader, stream = leader
+// stream), as search_locked: the mask is a HOST bitmap over the global rows (slot >= 0: positions).
+// Each shard selects its own k keys (global rows) with no traffic per round;
+// the leader gathers the n lists and runs the same rounds over those n x k keys.  A key's order
+// does not depend on the shard that held the row, so the result is that of one index.  A single
+// shard has no keys to gather: it writes scores / out_rows itself.
+// sq (rc_sharded_search_hybrid, checked by the caller): the sparse queries, which every shard stages on
+// its own device and adds to its scores before it selects; null: the deep search.
+void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, float *scores, int64_t *out_rows,
+                        void *stream, const uint32_t *mask, int slot, const SparseQueries *sq = nullptr) {
+    hipStream_t ls = (hipStream_t)stream;
+    if (h->n > 1) ensure_deep(h, nq, k);
+    const FanBuf out{(size_t)nq * k * sizeof(uint64_t), nullptr, h->dg_keys, (void *const *)h->dk_loc.data()};
+    const bool gathered = fan_out(h, queries, nq, n_rows, mask, ls, h->dq, &out, 1,
+                                  [&](int s, const float *q, int64_t n_local, const uint32_t *m, void *const *o, hipStream_t st) {
+        index_search_deep(h->shard[s], q, nq, n_local, k, m, slot, (uint64_t *)o[0], scores, out_rows, st, sq);
+    });
+    if (!gathered) return;
+    DeviceScope dl(h->dev[0]);
     const int qc = deep_chunk_queries(nq, (int64_t)h->n * k);
     h->dsel.ensure(qc, (int64_t)qc * k);
     for (int q0 = 0; q0 < nq; q0 += qc) {
@@ -979,7 +971,7 @@ void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_r
         deep_select_rounds(st, h->dsel, m, k, h->dsel.keys, ls);
         deep_emit(h->dsel.keys, (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, ls);
     }
-    if (masked) wait_mask(h);
+    if (mask != nullptr) wait_mask(h);
 }
 
 // What the sharded hybrid calls check of the store and the sparse queries before any device call
@@ -991,6 +983,27 @@ void check_hybrid(const rc_sharded *h, const SparseQueries &sq, int nq) {
     RC_REQUIRE(width > 0, RC_ERR_INVALID, "this index has no sparse store (rc_sharded_sparse_enable)");
     RC_REQUIRE(metric == RC_METRIC_DOT, RC_ERR_INVALID, "sparse-dense hybrid scores need the dotproduct metric");
     sparse_check_queries(sq, nq);
+}
+
+// The table of a slot and the range of n_pos it covers, or an error (caller holds h->mu).
+const std::vector<int32_t> &page_list(const rc_sharded *h, int slot, int64_t n_pos) {
+    RC_REQUIRE(slot >= 0 && slot < (int)h->tables.size() && !h->tables[slot].empty(), RC_ERR_INVALID,
+               "unknown slot (no page table was set for it)");
+    const std::vector<int32_t> &L = h->tables[slot];
+    RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)L.size() * RC_PAGE_ROWS * h->n, RC_ERR_INVALID, "n_pos beyond the slot's pages");
+    return L;
+}
+
+// What every sharded search entry point checks, and the lock its body runs under: the arguments
+// (check_search_args: nothing reads *h before they passed), then under h->mu the range, global
+// rows [0, n) or (slot >= 0) positions [0, n) of that slot.  A call without queries ends after this.
+std::unique_lock<std::mutex> checked_lock(rc_sharded *h, int nq, int k, int k_max, bool buffers, int slot, int64_t n,
+                                          int mode = RC_SEARCH_AUTO) {
+    check_search_args(h, nq, k, k_max, buffers, mode);
+    std::unique_lock<std::mutex> lk(h->mu);
+    if (slot >= 0) (void)page_list(h, slot, n);
+    else RC_REQUIRE(n >= 0 && n <= h->cap * h->n, RC_ERR_INVALID, "n_rows out of range");
+    return lk;
 }
 
 }  // namespace
@@ -1042,13 +1055,8 @@ int rc_sharded_search_hybrid(rc_sharded *h, const float *queries, int nq, int64_
                              const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores, int64_t *out_rows,
                              void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
-        RC_REQUIRE(n_rows >= 0 && n_rows <= h->cap * h->n, RC_ERR_INVALID, "n_rows out of range");
+        const auto lk = checked_lock(h, nq, k, RC_DEEP_TOPK_MAX, queries && scores && out_rows, -1, n_rows);
         if (nq == 0) return;
-        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
         const SparseQueries sq{sq_off, sq_idx, sq_val};
         check_hybrid(h, sq, nq);
         search_deep_locked(h, queries, nq, n_rows, k, scores, out_rows, stream, mask, -1, &sq);
@@ -1058,14 +1066,8 @@ int rc_sharded_search_hybrid(rc_sharded *h, const float *queries, int nq, int64_
 int rc_sharded_search_deep(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask, float *scores,
                            int64_t *out_rows, void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
-        RC_REQUIRE(n_rows >= 0 && n_rows <= h->cap * h->n, RC_ERR_INVALID, "n_rows out of range");
-        if (nq == 0) return;
-        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        search_deep_locked(h, queries, nq, n_rows, k, scores, out_rows, stream, mask, -1);
+        const auto lk = checked_lock(h, nq, k, RC_DEEP_TOPK_MAX, queries && scores && out_rows, -1, n_rows);
+        if (nq != 0) search_deep_locked(h, queries, nq, n_rows, k, scores, out_rows, stream, mask, -1);
     });
 }
 
@@ -1088,14 +1090,8 @@ int rc_sharded_search(rc_sharded *h, const float *queries, int nq, int64_t n_row
 int rc_sharded_search_masked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
                              float *scores, int64_t *out_rows, int mode, void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
-        RC_REQUIRE(n_rows >= 0 && n_rows <= h->cap * h->n, RC_ERR_INVALID, "n_rows out of range");
-        if (nq == 0) return;
-        RC_REQUIRE(queries && scores && out_rows, RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        search_locked(h, queries, nq, n_rows, k, scores, out_rows, mode, stream, mask);
+        const auto lk = checked_lock(h, nq, k, RC_TOPK_MAX, queries && scores && out_rows, -1, n_rows);
+        if (nq != 0) search_locked(h, queries, nq, n_rows, k, scores, out_rows, mode, stream, mask);
     });
 }
 
@@ -1107,12 +1103,9 @@ int rc_sharded_query_host(rc_sharded *h, const float *queries, int nq, int64_t n
 int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, int k, int with_values,
                                  const uint32_t *mask, float *scores, int64_t *out_rows, float *values) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
-        RC_REQUIRE(n_rows >= 0 && n_rows <= h->cap * h->n, RC_ERR_INVALID, "n_rows out of range");
+        // (the lock is given back at once: query_host_checked takes it after its own early return)
+        checked_lock(h, nq, k, RC_TOPK_MAX, queries && scores && out_rows && (!with_values || values), -1, n_rows);
         if (nq == 0) return;
-        RC_REQUIRE(queries && scores && out_rows && (!with_values || values), RC_ERR_INVALID, "null buffer");
         query_host_checked(h, queries, nq, n_rows, k, with_values, mask, scores, out_rows, values, -1);
     });
 }
@@ -1120,15 +1113,6 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
 }  // extern "C"
 
 namespace {
-
-// The table of a slot and the range of n_pos it covers, or an error (caller holds h->mu).
-const std::vector<int32_t> &page_list(const rc_sharded *h, int slot, int64_t n_pos) {
-    RC_REQUIRE(slot >= 0 && slot < (int)h->tables.size() && !h->tables[slot].empty(), RC_ERR_INVALID,
-               "unknown slot (no page table was set for it)");
-    const std::vector<int32_t> &L = h->tables[slot];
-    RC_REQUIRE(n_pos >= 0 && n_pos <= (int64_t)L.size() * RC_PAGE_ROWS * h->n, RC_ERR_INVALID, "n_pos beyond the slot's pages");
-    return L;
-}
 
 // rc_sharded_query_host_masked's body after its argument checks; slot >= 0:
 // rc_sharded_query_host_pages (n_rows and out_rows are positions of that slot).
@@ -1236,30 +1220,16 @@ int rc_sharded_search_pages(rc_sharded *h, const float *queries, int nq, int slo
 int rc_sharded_search_pages_ex(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
                                float *scores, int64_t *out_rows, int mode, void *stream) {
     return guard([&] {
-        RC_REQUIRE(mode == RC_SEARCH_AUTO || mode == RC_SEARCH_SCAN || mode == RC_SEARCH_MFMA || mode == RC_SEARCH_MFMA_MASKED,
-                   RC_ERR_INVALID, "unknown search mode");
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
-        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        (void)page_list(h, slot, n_pos);
-        if (nq == 0) return;
-        search_locked(h, queries, nq, n_pos, k, scores, out_rows, mode, stream, mask, slot);  // every shard takes the mode
+        const auto lk = checked_lock(h, nq, k, RC_TOPK_MAX, queries && scores && out_rows, paged_slot(slot), n_pos, mode);
+        if (nq != 0) search_locked(h, queries, nq, n_pos, k, scores, out_rows, mode, stream, mask, slot);  // every shard takes the mode
     });
 }
 
 int rc_sharded_search_pages_deep(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, const uint32_t *mask,
                                  float *scores, int64_t *out_rows, void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
-        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        (void)page_list(h, slot, n_pos);
-        if (nq == 0) return;
-        search_deep_locked(h, queries, nq, n_pos, k, scores, out_rows, stream, mask, slot);
+        const auto lk = checked_lock(h, nq, k, RC_DEEP_TOPK_MAX, queries && scores && out_rows, paged_slot(slot), n_pos);
+        if (nq != 0) search_deep_locked(h, queries, nq, n_pos, k, scores, out_rows, stream, mask, slot);
     });
 }
 
@@ -1267,12 +1237,7 @@ int rc_sharded_search_pages_hybrid(rc_sharded *h, const float *queries, int nq, 
                                    const int32_t *sq_off, const uint32_t *sq_idx, const float *sq_val, float *scores,
                                    int64_t *out_rows, void *stream) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_DEEP_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 10000]");
-        RC_REQUIRE(nq == 0 || (queries && scores && out_rows), RC_ERR_INVALID, "null buffer");
-        std::lock_guard<std::mutex> lk(h->mu);
-        (void)page_list(h, slot, n_pos);
+        const auto lk = checked_lock(h, nq, k, RC_DEEP_TOPK_MAX, queries && scores && out_rows, paged_slot(slot), n_pos);
         if (nq == 0) return;
         const SparseQueries sq{sq_off, sq_idx, sq_val};
         check_hybrid(h, sq, nq);
@@ -1283,10 +1248,7 @@ int rc_sharded_search_pages_hybrid(rc_sharded *h, const float *queries, int nq, 
 int rc_sharded_query_host_pages(rc_sharded *h, const float *queries, int nq, int slot, int64_t n_pos, int k, int with_values,
                                 const uint32_t *mask, float *scores, int64_t *out_rows, float *values) {
     return guard([&] {
-        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(nq >= 0, RC_ERR_INVALID, "negative query count");
-        RC_REQUIRE(k >= 1 && k <= RC_TOPK_MAX, RC_ERR_INVALID, "top_k must be in [1, 256]");
-        RC_REQUIRE(nq == 0 || (queries && scores && out_rows && (!with_values || values)), RC_ERR_INVALID, "null buffer");
+        check_search_args(h, nq, k, RC_TOPK_MAX, queries && scores && out_rows && (!with_values || values));
         RC_REQUIRE(slot >= 0 && slot < RC_PAGE_SLOTS_MAX && n_pos >= 0, RC_ERR_INVALID, "slot or n_pos out of range");
         if (nq == 0 || n_pos == 0) {
             std::lock_guard<std::mutex> lk(h->mu);

@@ -67,6 +67,11 @@ MASK_FILTER_LARGE_MIN_SHARE = 0.1
 BITMAP_CACHE_ENTRIES = 8
 
 
+def _addr(a):
+    """The address of a host array, or None (a null pointer) for None."""
+    return None if a is None else a.ctypes.data
+
+
 def _device_index(device) -> int:
     if device is None:
         return torch.cuda.current_device()
@@ -242,20 +247,8 @@ class DeviceIndex:
         where "mfma" is, and without a mask it is "mfma"."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
-        q = self._vecs(queries)
-        nq = q.shape[0]
-        if out is None:
-            scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        else:
-            scores, rows = out
-        if mask is None:
-            check(self.lib.rc_index_search_ex(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(scores), ptr(rows),
-                                              _lib.SEARCH_MODES[mode], stream_ptr(stream)))
-            return scores, rows
-        if mask.dtype not in (torch.int32, torch.uint32) or mask.numel() < (int(n_rows) + 31) // 32:
-            raise ValueError("mask must hold ceil(n_rows / 32) 32-bit words")
-        mask = mask.to(device=self.device).contiguous()
+        q, nq, scores, rows = self._search_io(queries, k, out)
+        mask = self._device_mask(mask, n_rows)
         check(self.lib.rc_index_search_masked(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(mask), ptr(scores),
                                               ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
@@ -277,14 +270,8 @@ class DeviceIndex:
         from 64 queries over 65536 positions or 16 queries over 262144)."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
-        q = self._vecs(queries)
-        nq = q.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        if mask is not None:
-            if mask.dtype not in (torch.int32, torch.uint32) or mask.numel() < (int(n_pos) + 31) // 32:
-                raise ValueError("mask must hold ceil(n_pos / 32) 32-bit words")
-            mask = mask.to(device=self.device).contiguous()
+        q, nq, scores, rows = self._search_io(queries, k)
+        mask = self._device_mask(mask, n_pos)
         check(self.lib.rc_index_search_pages_ex(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), ptr(mask), ptr(scores),
                                                 ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
@@ -296,16 +283,23 @@ class DeviceIndex:
             raise ValueError("mask must hold ceil(n / 32) 32-bit words")
         return mask.to(device=self.device).contiguous()
 
+    def _search_io(self, queries: torch.Tensor, k: int, out=None):
+        """What every search starts from, ``(q, nq, scores, rows)``: the queries as f32 [nq, dim] on
+        this device and the result tensors f32 / i64 [nq, k] (``out``: a pair to use instead)."""
+        q = self._vecs(queries)
+        nq = q.shape[0]
+        if out is None:
+            out = (torch.empty((nq, k), dtype=torch.float32, device=self.device),
+                   torch.empty((nq, k), dtype=torch.int64, device=self.device))
+        return q, nq, out[0], out[1]
+
     def search_deep(self, queries: torch.Tensor, k: int, n_rows: int, stream=None, mask=None):
         """Exact top-k for ``k`` up to 10000 (rc_index_search_deep): one pass over the rows that
         keeps every row's score, then ``ceil(k / 256)`` selection rounds over the scores.  The
         scores, rows and tie order of ``search(mode="scan")`` continued past 256; slots past the
         eligible rows are ``(-inf, -1)``.  ``mask``: as ``search`` (a device bitmap over the
         local rows).  Works on every dtype, metric and filter kind."""
-        q = self._vecs(queries)
-        nq = q.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        q, nq, scores, rows = self._search_io(queries, k)
         mask = self._device_mask(mask, n_rows)
         check(self.lib.rc_index_search_deep(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(mask), ptr(scores), ptr(rows),
                                             stream_ptr(stream)))
@@ -313,10 +307,7 @@ class DeviceIndex:
 
     def search_pages_deep(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None):
         """``search_deep`` over positions [0, n_pos) of a slot (rc_index_search_pages_deep)."""
-        q = self._vecs(queries)
-        nq = q.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        q, nq, scores, rows = self._search_io(queries, k)
         mask = self._device_mask(mask, n_pos)
         check(self.lib.rc_index_search_pages_deep(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), ptr(mask), ptr(scores),
                                                   ptr(rows), stream_ptr(stream)))
@@ -371,11 +362,8 @@ class DeviceIndex:
         dotproduct index with a sparse store): ``sparse[q]`` is query q's sparse part (``None`` =
         none).  The score is ``fadd(d, t)``: ``d`` what ``scores`` gives the row, ``t`` the
         row's sparse term (``sparsevalues.model_term``); for any ``k`` up to 10000."""
-        q = self._vecs(queries)
-        nq = q.shape[0]
+        q, nq, scores, rows = self._search_io(queries, k)
         off, idx, val = self._sparse_queries(sparse, nq)
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         mask = self._device_mask(mask, n_rows)
         check(self.lib.rc_index_search_hybrid(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(mask), off.ctypes.data,
                                               idx.ctypes.data, val.ctypes.data, ptr(scores), ptr(rows), stream_ptr(stream)))
@@ -383,11 +371,8 @@ class DeviceIndex:
 
     def search_pages_hybrid(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, sparse, stream=None, mask=None):
         """``search_hybrid`` over positions [0, n_pos) of a slot (rc_index_search_pages_hybrid)."""
-        q = self._vecs(queries)
-        nq = q.shape[0]
+        q, nq, scores, rows = self._search_io(queries, k)
         off, idx, val = self._sparse_queries(sparse, nq)
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         mask = self._device_mask(mask, n_pos)
         check(self.lib.rc_index_search_pages_hybrid(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), ptr(mask),
                                                     off.ctypes.data, idx.ctypes.data, val.ctypes.data, ptr(scores), ptr(rows),
@@ -837,6 +822,18 @@ class ShardSet:
             raise ValueError("mask must hold ceil(n_rows / 32) uint32 words")
         return m
 
+    def _leader_io(self, queries: torch.Tensor, k: int, mask, n: int):
+        """What every leader-side search starts from, ``(q, nq, scores, rows, mask)``: the queries as
+        f32 [nq, dim] on the leader, the result tensors f32 / i64 [nq, k] there, and the HOST bitmap
+        over [0, n) as ``_host_mask`` gives it (None without one; ``_addr`` is what the library takes)."""
+        if queries.dim() == 1:
+            queries = queries[None]
+        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        nq = q.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        return q, nq, scores, rows, None if mask is None else self._host_mask(mask, n)
+
     def query_host(self, q: np.ndarray, k: int, n_rows: int, with_values: bool, mask=None):
         """Host f32 [nq, dim] → host (scores [nq, k], global rows [nq, k], values [nq, k, dim] or
         None): rc_sharded_query_host — one H2D copy, the search and the matched rows' gather, one
@@ -883,19 +880,9 @@ class ShardSet:
         (``DeviceIndex.search``)."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
-        if queries.dim() == 1:
-            queries = queries[None]
-        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
-        nq = q.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        if mask is None:
-            check(self.lib.rc_sharded_search(self.handle, ptr(q), nq, int(n_rows), int(k), ptr(scores), ptr(rows),
-                                             _lib.SEARCH_MODES[mode], stream_ptr(stream)))
-        else:
-            m = self._host_mask(mask, n_rows)
-            check(self.lib.rc_sharded_search_masked(self.handle, ptr(q), nq, int(n_rows), int(k), m.ctypes.data,
-                                                    ptr(scores), ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
+        q, nq, scores, rows, m = self._leader_io(queries, k, mask, n_rows)
+        check(self.lib.rc_sharded_search_masked(self.handle, ptr(q), nq, int(n_rows), int(k), _addr(m), ptr(scores), ptr(rows),
+                                                _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
     # ------------------------------------------------------------------ page tables --
@@ -916,16 +903,9 @@ class ShardSet:
         ``DeviceIndex.search_pages``; every shard takes it (rc_sharded_search_pages_ex)."""
         if mode not in _lib.SEARCH_MODES:
             raise ValueError(f"unknown search mode {mode!r}")
-        if queries.dim() == 1:
-            queries = queries[None]
-        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
-        nq = q.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        m = None if mask is None else self._host_mask(mask, n_pos)
-        check(self.lib.rc_sharded_search_pages_ex(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k),
-                                                  None if m is None else m.ctypes.data, ptr(scores), ptr(rows),
-                                                  _lib.SEARCH_MODES[mode], stream_ptr(stream)))
+        q, nq, scores, rows, m = self._leader_io(queries, k, mask, n_pos)
+        check(self.lib.rc_sharded_search_pages_ex(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), _addr(m), ptr(scores),
+                                                  ptr(rows), _lib.SEARCH_MODES[mode], stream_ptr(stream)))
         return scores, rows
 
     def search_deep(self, queries: torch.Tensor, k: int, n_rows: int, stream=None, mask=None):
@@ -933,30 +913,17 @@ class ShardSet:
         every shard selects its own ``k``, the leader selects among the shards' lists — the
         result of a single-shard index holding the same rows.  ``mask``: an optional HOST uint32
         bitmap over the global rows."""
-        if queries.dim() == 1:
-            queries = queries[None]
-        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
-        nq = q.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        m = None if mask is None else self._host_mask(mask, n_rows)
-        check(self.lib.rc_sharded_search_deep(self.handle, ptr(q), nq, int(n_rows), int(k), None if m is None else m.ctypes.data,
-                                              ptr(scores), ptr(rows), stream_ptr(stream)))
+        q, nq, scores, rows, m = self._leader_io(queries, k, mask, n_rows)
+        check(self.lib.rc_sharded_search_deep(self.handle, ptr(q), nq, int(n_rows), int(k), _addr(m), ptr(scores), ptr(rows),
+                                              stream_ptr(stream)))
         return scores, rows
 
     def search_pages_deep(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, stream=None, mask=None):
         """``search_deep`` over the positions [0, n_pos) of a slot (rc_sharded_search_pages_deep):
         (scores, positions).  ``mask``: an optional HOST uint32 bitmap over the positions."""
-        if queries.dim() == 1:
-            queries = queries[None]
-        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
-        nq = q.shape[0]
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        m = None if mask is None else self._host_mask(mask, n_pos)
-        check(self.lib.rc_sharded_search_pages_deep(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k),
-                                                    None if m is None else m.ctypes.data, ptr(scores), ptr(rows),
-                                                    stream_ptr(stream)))
+        q, nq, scores, rows, m = self._leader_io(queries, k, mask, n_pos)
+        check(self.lib.rc_sharded_search_pages_deep(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), _addr(m), ptr(scores),
+                                                    ptr(rows), stream_ptr(stream)))
         return scores, rows
 
     # ------------------------------------------------------------ sparse-dense hybrid --
@@ -985,33 +952,20 @@ class ShardSet:
         ``DeviceIndex.search_hybrid``): every shard adds its rows' sparse terms to its own scores
         before it selects — the result of a single-shard index holding the same records.
         ``mask``: an optional HOST uint32 bitmap over the global rows."""
-        if queries.dim() == 1:
-            queries = queries[None]
-        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
-        nq = q.shape[0]
+        q, nq, scores, rows, m = self._leader_io(queries, k, mask, n_rows)
         off, idx, val = DeviceIndex._sparse_queries(sparse, nq)
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        m = None if mask is None else self._host_mask(mask, n_rows)
-        check(self.lib.rc_sharded_search_hybrid(self.handle, ptr(q), nq, int(n_rows), int(k), None if m is None else m.ctypes.data,
-                                                off.ctypes.data, idx.ctypes.data, val.ctypes.data, ptr(scores), ptr(rows),
-                                                stream_ptr(stream)))
+        check(self.lib.rc_sharded_search_hybrid(self.handle, ptr(q), nq, int(n_rows), int(k), _addr(m), off.ctypes.data,
+                                                idx.ctypes.data, val.ctypes.data, ptr(scores), ptr(rows), stream_ptr(stream)))
         return scores, rows
 
     def search_pages_hybrid(self, queries: torch.Tensor, k: int, slot: int, n_pos: int, sparse, stream=None, mask=None):
         """``search_hybrid`` over the positions [0, n_pos) of a slot (rc_sharded_search_pages_hybrid):
         (scores, positions).  ``mask``: an optional HOST uint32 bitmap over the positions."""
-        if queries.dim() == 1:
-            queries = queries[None]
-        q = queries.to(device=self.device, dtype=torch.float32).contiguous()
-        nq = q.shape[0]
+        q, nq, scores, rows, m = self._leader_io(queries, k, mask, n_pos)
         off, idx, val = DeviceIndex._sparse_queries(sparse, nq)
-        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        rows = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        m = None if mask is None else self._host_mask(mask, n_pos)
-        check(self.lib.rc_sharded_search_pages_hybrid(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k),
-                                                      None if m is None else m.ctypes.data, off.ctypes.data, idx.ctypes.data,
-                                                      val.ctypes.data, ptr(scores), ptr(rows), stream_ptr(stream)))
+        check(self.lib.rc_sharded_search_pages_hybrid(self.handle, ptr(q), nq, int(slot), int(n_pos), int(k), _addr(m),
+                                                      off.ctypes.data, idx.ctypes.data, val.ctypes.data, ptr(scores), ptr(rows),
+                                                      stream_ptr(stream)))
         return scores, rows
 
     def scores_hybrid(self, query: torch.Tensor, n_rows: int, sparse, slot: int | None = None) -> torch.Tensor:
@@ -1037,8 +991,7 @@ class ShardSet:
         val = np.empty((nq, k, self.dim), np.float32) if with_values else None
         m = None if mask is None else self._host_mask(mask, n_pos)
         check(self.lib.rc_sharded_query_host_pages(self.handle, q.ctypes.data, nq, int(slot), int(n_pos), int(k),
-                                                   1 if with_values else 0, None if m is None else m.ctypes.data,
-                                                   sc.ctypes.data, rw.ctypes.data, None if val is None else val.ctypes.data))
+                                                   1 if with_values else 0, _addr(m), sc.ctypes.data, rw.ctypes.data, _addr(val)))
         return sc, rw, val
 
     def export_run(self, row0: int, n: int):
@@ -1072,29 +1025,10 @@ class ShardSet:
 
     # raw stored rows in GLOBAL row order (the snapshot layout, independent of the shard count)
     def export_rows(self, n_rows: int):
-        import numpy as np
-
-        el = _lib.dtype_bytes(self.dtype)
-        rows = np.zeros((n_rows, self.ld * el), dtype=np.uint8)
-        norms = np.zeros((n_rows,), dtype=np.float32)
-        for s in range(self.n):
-            m = self.shard_rows(s, n_rows)
-            if m == 0:
-                continue
-            r, nr = self._shards[s].export_rows(0, m)
-            torch.cuda.synchronize(self._shards[s].device)
-            rows[s::self.n] = r.cpu().numpy()
-            norms[s::self.n] = nr.cpu().numpy()
-        return rows, norms
+        return self.export_run(0, n_rows)
 
     def import_rows(self, rows, norms) -> None:
-        n_rows = len(norms)
-        for s in range(self.n):
-            if self.shard_rows(s, n_rows) == 0:
-                continue
-            self._shards[s].import_rows(0, torch.from_numpy(rows[s::self.n].copy()),
-                                        torch.from_numpy(norms[s::self.n].copy()))
-            torch.cuda.synchronize(self._shards[s].device)
+        self.import_run(0, rows, norms)
 
 
 def _namespace_name(namespace) -> str:
@@ -1869,41 +1803,25 @@ class Index:
             raise ValueError(f"top_k must be <= {self.max_top_k}")
         deep = top_k > _lib.RC_TOPK_MAX  # only with max_top_k: the deep search, through _query_locked
         namespace = _namespace_name(namespace)
-        if namespace:
-            with self._mu:
-                ns = self._ns.get(namespace)
-                if ns is None:  # no such namespace: no device work
-                    return {"matches": [], "namespace": namespace}
-                if vector is None:
-                    p = ns._rows.get(id)
-                    if p is None:
-                        return {"matches": [], "namespace": namespace}
-                    vector = self._pool.fetch_rows(self._ns_rows(ns, [p]))[0]
-                    sp = ns._sparse.get(id)
-                q = _as_vector_np(vector, self.dimension)
-                bm = self._bitmap_locked(filter, ns)
-                if sp is not None:
-                    res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm, ns, [sp])[0]
-                elif deep:
-                    res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm, ns)[0]
-                else:
-                    res = self._query_host_locked(q, top_k, include_values, include_metadata, bm, ns)[0]
-            return {"matches": res, "namespace": namespace}
         with self._mu:
+            ns = self._ns.get(namespace) if namespace else None
+            if namespace and ns is None:  # no such namespace: no device work
+                return {"matches": [], "namespace": namespace}
+            st = self if ns is None else ns
+            owner = self._set if ns is None else self._pool
             if vector is None:
-                r = self._rows.get(id)
+                r = st._rows.get(id)  # a namespace's rows are positions
                 if r is None:
                     return {"matches": [], "namespace": namespace}
-                vector = self._set.fetch_rows([r])[0]
-                sp = self._sparse.get(id)
+                vector = owner.fetch_rows([r] if ns is None else self._ns_rows(ns, [r]))[0]
+                sp = st._sparse.get(id)
             q = _as_vector_np(vector, self.dimension)
-            bm = self._bitmap_locked(filter)
-            if sp is not None:
-                res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm, None, [sp])[0]
-            elif deep:
-                res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm)[0]
+            bm = self._bitmap_locked(filter, ns)
+            if sp is not None or deep:
+                res = self._query_locked(torch.from_numpy(q), top_k, include_values, include_metadata, "scan", bm, ns,
+                                         None if sp is None else [sp])[0]
             else:
-                res = self._query_host_locked(q, top_k, include_values, include_metadata, bm)[0]
+                res = self._query_host_locked(q, top_k, include_values, include_metadata, bm, ns)[0]
         return {"matches": res, "namespace": namespace}
 
     def query_batch(self, vectors, top_k: int = 10, include_values: bool = False,
@@ -2018,32 +1936,22 @@ class Index:
             return [[] for _ in range(q.shape[0])]
         if bitmap is not None and bitmap[1] == 0:  # nothing is eligible: no device work
             return [[] for _ in range(q.shape[0])]
+        if mode not in _lib.SEARCH_MODES:
+            raise ValueError(f"unknown search mode {mode!r}")
+        mask = None if bitmap is None else bitmap[0]
         if sparse is not None:
-            if mode not in _lib.SEARCH_MODES:
-                raise ValueError(f"unknown search mode {mode!r}")
-            mask = None if bitmap is None else bitmap[0]
-            if ns is not None:
-                scores, rows = self._pool.search_pages_hybrid(q, k, ns.slot, n, sparse, mask=mask)
-            else:
-                scores, rows = self._set.search_hybrid(q, k, n, sparse, mask=mask)
+            scores, rows = (self._set.search_hybrid(q, k, n, sparse, mask=mask) if ns is None else
+                            self._pool.search_pages_hybrid(q, k, ns.slot, n, sparse, mask=mask))
         elif k > _lib.RC_TOPK_MAX:  # deep top-k (max_top_k): one path whatever the mode, the filter kind or the mask's share
-            if mode not in _lib.SEARCH_MODES:
-                raise ValueError(f"unknown search mode {mode!r}")
-            mask = None if bitmap is None else bitmap[0]
-            if ns is not None:
-                scores, rows = self._pool.search_pages_deep(q, k, ns.slot, n, mask=mask)
-            else:
-                scores, rows = self._set.search_deep(q, k, n, mask=mask)
+            scores, rows = (self._set.search_deep(q, k, n, mask=mask) if ns is None else
+                            self._pool.search_pages_deep(q, k, ns.slot, n, mask=mask))
         elif ns is not None:
             # (under a metadata filter the library's "auto" scans: the masked paged forms are unmeasured)
-            scores, rows = self._pool.search_pages(q, k, ns.slot, n, mask=None if bitmap is None else bitmap[0], mode=mode)
-        elif bitmap is None:
-            scores, rows = self._set.search(q, k, n, mode=mode)
+            scores, rows = self._pool.search_pages(q, k, ns.slot, n, mask=mask, mode=mode)
         else:
-            if mode not in _lib.SEARCH_MODES:
-                raise ValueError(f"unknown search mode {mode!r}")
-            scores, rows = self._set.search(q, k, n, mode=self._masked_mode(mode, q.shape[0], n, bitmap[1], k),
-                                            mask=bitmap[0])
+            if bitmap is not None:
+                mode = self._masked_mode(mode, q.shape[0], n, bitmap[1], k)
+            scores, rows = self._set.search(q, k, n, mode=mode, mask=mask)
         scores = scores.cpu().numpy()
         if self.metric == "euclidean":  # the library's -||q - v||^2 (descending) as Pinecone's squared distance
             scores = np.maximum(np.float32(0.0), -scores)
