@@ -31,6 +31,12 @@ CFLAGS = [
     "-munsafe-fp-atomics",
 ]
 
+# Units compiled without the packed-f32 VALU forms (v_pk_{add,mul,fma}_f32): the float32 filter's
+# bound arithmetic and the rescoring of f32 rows are meant as the scalar f32 operations they are
+# written as.  Per unit, so that every other unit's code object stays what it was.
+NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+UNIT_FLAGS = {"search_mfma_f32.hip": NO_PACKED_F32, "rescore_metric_f32.hip": NO_PACKED_F32}
+
 
 def _sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
@@ -64,6 +70,7 @@ def _deps(src: str) -> list[str]:
 def _compile(src: str, extra: list[str]) -> str:
     obj = os.path.join(OBJDIR, os.path.basename(src) + ".o")
     stamp = obj + ".flags"
+    extra = extra + UNIT_FLAGS.get(os.path.basename(src), [])
     flags = " ".join(CFLAGS + extra)
     newest_dep = max(os.path.getmtime(p) for p in [__file__] + _deps(src))
     same_flags = os.path.exists(stamp) and open(stamp).read() == flags

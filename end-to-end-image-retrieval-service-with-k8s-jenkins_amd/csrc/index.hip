@@ -443,6 +443,27 @@ constexpr int64_t kF8BatchMinBytesLarge = int64_t(1) << 28;  // this many bytes 
 constexpr int kMetricBatchMinQueries = 16;
 constexpr int kMetricBatchMinQueriesLarge = 8;                    // ... with at least
 constexpr int64_t kMetricBatchMinBytesLarge = int64_t(1) << 28;  // this many bytes of rows
+// The float32 filter (RC_FILTER_F32) competes with the f32 scan, and as for the float8 filter what
+// decides is the scan's passes P = ceil(nq / queries per pass) (scan_max_qb under cosine: 2 at ld 512,
+// 1 at ld 768 for k <= 64; 1 under a metric).  Top-10, wall ms per call, scan / batched, median of 5
+// interleaved rounds (tools/f32_filter_micro.py --part crossover, profiles/f32_filter/
+// f32_filter_crossover.jsonl, which has [min, max]):
+//   rows x width     cosine 8 q       cosine 16 q      dotproduct 8 q   dotproduct 16 q
+//    65 536 x 512   0.186 / 0.333    0.361 / 0.408    0.292 / 0.331    0.573 / 0.403
+//   131 072 x 512   0.233 / 0.365    0.457 / 0.460    0.391 / 0.371    0.773 / 0.460
+//   262 144 x 512   0.416 / 0.440    0.816 / 0.551    0.746 / 0.474    1.472 / 0.558
+//    65 536 x 768   0.384 / 0.427    0.755 / 0.491    0.380 / 0.401    0.747 / 0.463
+//   131 072 x 768   0.565 / 0.510    1.122 / 0.586    0.568 / 0.490    1.120 / 0.554
+//   262 144 x 768   1.046 / 0.687    2.073 / 0.759    1.042 / 0.657    2.065 / 0.747
+// P = 16 is ahead in every cell from 16 384 rows (1.36-2.8x); P = 8 is behind at 65 536 rows
+// (0.88-0.95x) and at parity or ahead from 131 072 (0.99-1.16x; 262 144: 1.48-1.59x); P = 4 (8
+// cosine queries at ld 512) is behind up to 262 144 rows (0.94x) and ahead at 1M x 512, top-100
+// (1.47x, f32_filter_throughput.jsonl); between those it was not measured and scans.
+constexpr int kF32BatchMinPasses = 16;            // from kBatchMinRows
+constexpr int kF32BatchMinPassesMid = 8;          // ... or with at least
+constexpr int64_t kF32BatchMinRowsMid = 131072;   // this many rows
+constexpr int kF32BatchMinPassesLarge = 4;        // ... or with at least
+constexpr int64_t kF32BatchMinRowsLarge = 1000000;  // this many
 // The batched search over pages (rc_index_search_pages_ex) competes with the paged scan of the same
 // slot (f16 x 512 on a shuffled page list in a 4M-row pool, wall ms per call, median of 5 interleaved
 // rounds, paged MFMA / paged scan, tools/paged_batched_micro.py, profiles/paged_batched/; DESIGN.md,
@@ -638,6 +659,7 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
     h->bws.ensure(nq, k, h->ld, batch_query_bytes(h));
     BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, n_rows, h->row_base, h->row_stride, queries, nq, k, scores, out_rows};
     p.f8_filter = h->filter == RC_FILTER_F8;
+    p.f32_filter = h->filter == RC_FILTER_F32;
     p.rows8 = h->rows8;
     p.rsx = h->rsx;
     p.rex = h->rex;
@@ -786,10 +808,12 @@ void topk_search(rc_index *h, const SearchArgs &a, int mode) {
     DeviceScope ds(h->device);
     // without RC_FILTER_METRIC the batched path's candidate threshold is a bound in cosine space:
     // a non-cosine index scans (AUTO) and refuses MFMA, whatever it holds.  With it the filter
-    // bounds the metric's own score (search_mfma.hip) on the f16 / bf16 rows it was set on.
-    const bool metric_ok = h->metric == RC_METRIC_COSINE || h->filter == RC_FILTER_METRIC;
+    // bounds the metric's own score (search_mfma.hip) on the f16 / bf16 rows it was set on; the
+    // float32 filter does the same on f32 rows (search_mfma_f32.hip), but not over pages.
+    const bool metric_ok = h->metric == RC_METRIC_COSINE || h->filter == RC_FILTER_METRIC || (h->filter == RC_FILTER_F32 && pages == nullptr);
     RC_REQUIRE(mode != RC_SEARCH_MFMA || metric_ok, RC_ERR_UNSUPPORTED,
-               "batched MFMA search is cosine-only without RC_FILTER_METRIC (this index scores by dotproduct or euclidean)");
+               "batched MFMA search is cosine-only without RC_FILTER_METRIC or RC_FILTER_F32 (this index scores by dotproduct or euclidean; "
+               "over pages only RC_FILTER_METRIC serves them)");
     // an empty shard (a shard with none of the slot's positions) answers (-inf, -1) in every mode:
     // over the rows before the refusals below, over a slot after them
     if (a.n == 0 && pages == nullptr) return empty_search(a.nq, a.k, a.scores, a.out_rows, a.stream);
@@ -798,10 +822,13 @@ void topk_search(rc_index *h, const SearchArgs &a, int mode) {
     const bool mfma_ok =
         metric_ok && (pages != nullptr ? (h->dtype == RC_F16 || h->dtype == RC_BF16) && h->rows8 == nullptr &&
                                              (h->filter == RC_FILTER_NATIVE || h->filter == RC_FILTER_METRIC)
-                                       : (h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr || h->filter == RC_FILTER_F8);
+                                       : (h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr || h->filter == RC_FILTER_F8 ||
+                                             h->filter == RC_FILTER_F32);
     RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
-               pages != nullptr ? "batched MFMA search over pages needs an f16/bf16 index with the native or the metric filter"
-                                : "batched MFMA search needs an f16/bf16 index, the int8 filter copy, or a float8 index with RC_FILTER_F8");
+               pages != nullptr ? "batched MFMA search over pages needs an f16/bf16 index with the native or the metric filter "
+                                  "(the int8, float8 and float32 filters have no paged form)"
+                                : "batched MFMA search needs an f16/bf16 index, the int8 filter copy, a float8 index with RC_FILTER_F8, "
+                                  "or a float32 index with RC_FILTER_F32");
     RC_REQUIRE(mode != RC_SEARCH_MFMA || pages == nullptr ||
                    paged_filter_supported(h->ld, h->metric != RC_METRIC_COSINE, mask_filter && a.mask != nullptr),
                RC_ERR_UNSUPPORTED,
@@ -822,6 +849,12 @@ void topk_search(rc_index *h, const SearchArgs &a, int mode) {
     } else if (h->filter == RC_FILTER_METRIC && h->metric != RC_METRIC_COSINE) {  // its own corner (see kMetricBatchMinQueries); f16 / bf16 rows
         auto_mfma = (a.nq >= kMetricBatchMinQueries && a.n >= kBatchMinRows) ||
                     (a.nq >= kMetricBatchMinQueriesLarge && a.n * h->ld * 2 >= kMetricBatchMinBytesLarge);
+    } else if (h->filter == RC_FILTER_F32) {  // its own corner (see kF32BatchMinPasses); a width it does not serve scans
+        const int qb = h->metric == RC_METRIC_COSINE ? scan_max_qb(h->nch, a.k) : 1;
+        const int passes = (a.nq + qb - 1) / qb;
+        auto_mfma = f32_filter_supported(h->ld) && ((passes >= kF32BatchMinPasses && a.n >= kBatchMinRows) ||
+                                                    (passes >= kF32BatchMinPassesMid && a.n >= kF32BatchMinRowsMid) ||
+                                                    (passes >= kF32BatchMinPassesLarge && a.n >= kF32BatchMinRowsLarge));
     }
     const bool use_mfma = mode == RC_SEARCH_MFMA || (mode == RC_SEARCH_AUTO && a.mask == nullptr && mfma_ok && auto_mfma);
     if (use_mfma) batched_search_exact(h, a.queries, a.nq, a.n, a.k, a.mask, mask_filter, a.scores, a.out_rows, a.stream, pages);
@@ -1164,8 +1197,9 @@ int rc_index_reserve(rc_index *h, int max_nq, int max_k) {
 int rc_index_set_filter(rc_index *h, int kind, void *stream) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_I8 || kind == RC_FILTER_F8 || kind == RC_FILTER_METRIC,
-                   RC_ERR_INVALID, "filter must be RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8 or RC_FILTER_METRIC");
+        RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_I8 || kind == RC_FILTER_F8 || kind == RC_FILTER_METRIC ||
+                       kind == RC_FILTER_F32,
+                   RC_ERR_INVALID, "filter must be RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8, RC_FILTER_METRIC or RC_FILTER_F32");
         std::lock_guard<std::mutex> lk(h->mu);
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
@@ -1181,6 +1215,13 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
             RC_HIP(hipDeviceSynchronize());
             free_filter(h);  // an int8 copy goes, as on a switch to RC_FILTER_NATIVE
             h->filter = RC_FILTER_METRIC;
+            return;
+        }
+        if (kind == RC_FILTER_F32) {  // allocates nothing: the filter GEMM reads the stored f32 rows, under every metric
+            RC_REQUIRE(h->dtype == RC_F32, RC_ERR_UNSUPPORTED, "the float32 filter reads stored float32 rows: it needs a float32 index");
+            RC_HIP(hipDeviceSynchronize());
+            free_filter(h);  // an int8 copy goes, as on a switch to RC_FILTER_NATIVE
+            h->filter = RC_FILTER_F32;  // (a row width it does not serve: RC_SEARCH_MFMA says so, RC_SEARCH_AUTO scans)
             return;
         }
         if (kind == RC_FILTER_F8) {  // allocates nothing: the filter GEMM reads the stored rows
@@ -1230,7 +1271,9 @@ int rc_index_set_metric(rc_index *h, int metric) {
         RC_REQUIRE(metric == RC_METRIC_COSINE || metric == RC_METRIC_DOT || metric == RC_METRIC_EUCLIDEAN, RC_ERR_INVALID,
                    "metric must be RC_METRIC_COSINE, RC_METRIC_DOT or RC_METRIC_EUCLIDEAN");
         std::lock_guard<std::mutex> lk(h->mu);
-        RC_REQUIRE(metric == RC_METRIC_COSINE || h->filter == RC_FILTER_NATIVE || h->filter == RC_FILTER_METRIC, RC_ERR_UNSUPPORTED,
+        RC_REQUIRE(metric == RC_METRIC_COSINE || h->filter == RC_FILTER_NATIVE || h->filter == RC_FILTER_METRIC ||
+                       h->filter == RC_FILTER_F32,
+                   RC_ERR_UNSUPPORTED,
                    "a non-cosine metric on an index with the int8 filter copy or the float8 filter (those filters are cosine-only)");
         h->metric = metric;  // no device call: searches already enqueued took the metric they were launched with
     });
@@ -1534,10 +1577,15 @@ int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t ro
         if (nq == 0 || n == 0) return;
         RC_REQUIRE(queries && out_scores && out_eps, RC_ERR_INVALID, "null buffer");
         std::lock_guard<std::mutex> lk(h->mu);
-        RC_REQUIRE(h->filter == RC_FILTER_F8, RC_ERR_UNSUPPORTED, "filter scores are the float8 filter's (RC_FILTER_F8)");
+        RC_REQUIRE(h->filter == RC_FILTER_F8 || h->filter == RC_FILTER_F32, RC_ERR_UNSUPPORTED,
+                   "filter scores are the float8 filter's (RC_FILTER_F8) and the float32 filter's (RC_FILTER_F32)");
         DeviceScope ds(h->device);
         h->bws.ensure(nq, 16, h->ld, batch_query_bytes(h));
         BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, row0 + n, h->row_base, h->row_stride, queries, nq, 16, nullptr, nullptr};
+        if (h->filter == RC_FILTER_F32) {  // s' and eps in cosine space, whatever the metric (p.metric stays cosine)
+            p.f32_filter = true;
+            return filter_scores_f32(p, h->bws, row0, n, out_scores, out_eps, (hipStream_t)stream);
+        }
         p.f8_filter = true;
         filter_scores_f8(p, h->bws, row0, n, out_scores, out_eps, (hipStream_t)stream);
     });

@@ -426,6 +426,9 @@ struct BatchPlan {
     bool mask_filter = false;
     // float8 index with rc_index_set_filter(RC_FILTER_F8): the filter GEMM reads the stored e4m3 rows
     bool f8_filter = false;
+    // float32 index with rc_index_set_filter(RC_FILTER_F32): the filter GEMM reads the stored f32 rows and
+    // narrows them to f16 in registers (search_mfma_f32.hip), under every metric (norms as below)
+    bool f32_filter = false;
     // RC_FILTER_METRIC under a non-cosine metric: the native filter kernels' metric forms, which
     // bound each row's metric score and read norms [n_rows]; the keys carry metric scores
     int metric = RC_METRIC_COSINE;
@@ -444,6 +447,7 @@ __host__ __device__ __forceinline__ int64_t i8_slot(int64_t row) {
 }
 bool i8_filter_supported(int64_t ld);  // row widths filter_i8_kernel is instantiated for
 bool f8_filter_supported(int64_t ld);  // ... and filter_f8_kernel
+bool f32_filter_supported(int64_t ld);  // ... and filter_f32_kernel (search_mfma_f32.hip)
 // the paged native filter kernels (search_mfma_paged.hip): every form but ld 512 with METRIC and MASKED
 bool paged_filter_supported(int64_t ld, bool metric, bool mask_filter);
 
@@ -454,5 +458,13 @@ int batch_stage_ratio(int k, int cap, int inflation = 1);
 // of 128), f32 [nq][n], and its eps [nq], enqueued on `s` (rc_index_filter_scores).
 void filter_scores_f8(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, float *out_scores, float *out_eps,
                       hipStream_t s);
+// The float32 filter (search_mfma_f32.hip): its query preparation for nq_pad slots (the METRIC form
+// under p.metric), one filter dispatch over local rows [c0, c1) in nchunk row chunks (dump != null:
+// the DUMP form, s' into dump), and rc_index_filter_scores' body as filter_scores_f8.
+void prepare_queries_f32(const BatchPlan &p, const BatchWs &ws, int nq_pad, hipStream_t s);
+void launch_filter_f32(const BatchPlan &p, const BatchWs &ws, int nq_pad, int64_t c0, int64_t c1, int64_t nchunk, float *dump,
+                       hipStream_t s);
+void filter_scores_f32(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, float *out_scores, float *out_eps,
+                       hipStream_t s);
 
 }  // namespace rc

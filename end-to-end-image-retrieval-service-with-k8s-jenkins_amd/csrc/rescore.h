@@ -67,11 +67,12 @@ __global__ __launch_bounds__(256) void rescore_metric_kernel(const T *__restrict
 #include "rescore_body.inc"
 }
 
-// The metric form's launch, for the f16 / bf16 rows the metric filter serves.  search_mfma.hip
-// calls it through an extern template declaration; rescore_metric_{f16,bf16}.hip instantiate it.
+// The metric form's launch, for the f16 / bf16 rows the metric filter serves and the f32 rows the
+// float32 filter serves.  search_mfma.hip calls it through an extern template declaration;
+// rescore_metric_{f16,bf16,f32}.hip instantiate it.
 template <typename T>
 void launch_rescore_metric(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
-    static_assert(sizeof(T) == 2, "the metric filter serves f16 / bf16 rows");
+    static_assert(sizeof(T) == 2 || sizeof(T) == 4, "the metric filter serves f16 / bf16 rows, the float32 filter f32 rows");
     const bool ok = with_nch<16, T>(p.nch, [&](auto nch) {
         with_topk_cap(topk_cap(p.k), [&](auto cap) {
             auto launch = [&](auto masked) {

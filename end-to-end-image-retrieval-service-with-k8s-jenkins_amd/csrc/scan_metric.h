@@ -22,8 +22,8 @@ __global__ __launch_bounds__(256, (scan_min_waves<T, NCH, 1, CAP>())) void scan_
                                             mask, norms, metric);
 }
 
-// The exact fallback of the metric batched search (RC_FILTER_METRIC; f16 / bf16 rows, the dtypes
-// that search serves): as scan_topk_kernel's fallback branch, block (b, y) scans its row range for
+// The exact fallback of the metric batched search (RC_FILTER_METRIC on f16 / bf16 rows, RC_FILTER_F32
+// on f32 rows: the dtypes that search serves): as scan_topk_kernel's fallback branch, block (b, y) scans its row range for
 // the queries y, y + gridDim.y, ... whose candidate list overflowed (flags), each normalised from
 // the raw queries as every metric scan does; partial is [nblk][nq_total][k].  A kernel of its own:
 // scan_topk_metric_kernel keeps its arguments and its code.
@@ -44,14 +44,14 @@ template <typename T>
 void launch_scan_metric(const ScanArgs &a) {
     if (a.qraw == nullptr || a.norms == nullptr || a.qb != 1)
         throw Error(RC_ERR_INVALID, "internal: a metric scan takes raw queries, one per pass, and the norms");
-    if (a.flags != nullptr && (sizeof(T) != 2 || a.nq_real != a.nq_total))
-        throw Error(RC_ERR_INVALID, "internal: the metric fallback scan serves f16 / bf16 rows and unpadded queries");
+    if (a.flags != nullptr && (sizeof(T) == 1 || a.nq_real != a.nq_total))
+        throw Error(RC_ERR_INVALID, "internal: the metric fallback scan serves f16 / bf16 / f32 rows and unpadded queries");
     const dim3 grid(a.nblk, a.flags != nullptr ? a.grid_y : 1);
     const bool ok = with_nch<16, T>(a.nch, [&](auto nch) {
         with_topk_cap(topk_cap(a.k), [&](auto cap) {
             constexpr int NCH = decltype(nch)::value, CAP = decltype(cap)::value;
             auto launch = [&](auto masked) {
-                if constexpr (sizeof(T) == 2) {
+                if constexpr (sizeof(T) != 1) {  // (f32 rows: the float32 filter's fallback under a metric)
                     if (a.flags != nullptr) {
                         hipLaunchKernelGGL((scan_topk_metric_fallback_kernel<T, NCH, CAP, decltype(masked)::value>), grid, dim3(256),
                                            0, a.stream, (const T *)a.rows, a.norms, a.ld, a.n_rows, a.rows_per_block, a.nq_total,

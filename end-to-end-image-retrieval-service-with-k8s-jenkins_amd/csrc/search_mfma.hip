@@ -870,6 +870,7 @@ __global__ __launch_bounds__(512, 1) void filter_f8_kernel(std::conditional_t<MA
 // rescore_metric_{f16,bf16}.hip, not here.
 extern template void launch_rescore_metric<f16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
 extern template void launch_rescore_metric<bf16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
+extern template void launch_rescore_metric<float>(const BatchPlan &, const BatchWs &, int, hipStream_t);  // rescore_metric_f32.hip
 // ... and the page-table form of both (BatchPlan::pages) in rescore_paged_{f16,bf16}.hip
 extern template void launch_rescore_paged<f16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
 extern template void launch_rescore_paged<bf16_t>(const BatchPlan &, const BatchWs &, int, hipStream_t);
@@ -879,6 +880,9 @@ template <typename T>
 void launch_rescore(const BatchPlan &p, const BatchWs &ws, int final_pass, hipStream_t s) {
     if constexpr (sizeof(T) == 2) {  // the metric filter's dtypes: f16 / bf16
         if (p.pages != nullptr) return launch_rescore_paged<T>(p, ws, final_pass, s);  // candidates are positions
+        if (p.metric != RC_METRIC_COSINE) return launch_rescore_metric<T>(p, ws, final_pass, s);
+    }
+    if constexpr (sizeof(T) == 4) {  // the float32 filter under a metric (the int8 filter on f32 rows is cosine-only)
         if (p.metric != RC_METRIC_COSINE) return launch_rescore_metric<T>(p, ws, final_pass, s);
     }
     // (float8 rows: the even widths up to 768, what the float8 filter serves)
@@ -1097,6 +1101,18 @@ void run_batched_f8(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
     run_stages<f8_t>(p, ws, s, timer, batch_stage_ratio(p.k, ws.cap), p.ld, filter);
 }
 
+// The float32 filter (search_mfma_f32.hip: filter_f32_kernel on the stored f32 rows, one f16 term per
+// operand), under every metric.  No stage inflation: its eps is a few times the native filter's, which
+// lengthens the lists by an estimated 5 % (that file's header).
+void run_batched_f32(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
+    const int nq_pad = (p.nq + SB_TILE - 1) / SB_TILE * SB_TILE;
+    prepare_queries_f32(p, ws, nq_pad, s);
+    auto filter = [&](int64_t c0, int64_t c1, int64_t nchunk, int) {
+        launch_filter_f32(p, ws, nq_pad, c0, c1, nchunk, nullptr, s);
+    };
+    run_stages<float>(p, ws, s, timer, batch_stage_ratio(p.k, ws.cap), p.ld * (int64_t)sizeof(float), filter);
+}
+
 bool i8_filter_supported(int64_t ld) { return ld == 256 || ld == 512 || ld == 768; }
 bool f8_filter_supported(int64_t ld) { return ld == 256 || ld == 512 || ld == 768; }
 
@@ -1114,12 +1130,21 @@ void filter_scores_f8(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, 
 void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
     RC_REQUIRE(p.ld % 64 == 0, RC_ERR_UNSUPPORTED, "batched search needs ld % 64 == 0");
     RC_REQUIRE(p.n_rows > 0, RC_ERR_INVALID, "batched search over an empty range");
-    if (p.pages != nullptr)  // the int8 and float8 filters have no paged form
-        RC_REQUIRE((p.dtype == RC_F16 || p.dtype == RC_BF16) && !p.f8_filter && p.rows8 == nullptr, RC_ERR_UNSUPPORTED,
-                   "batched MFMA search over pages needs an f16 or bf16 index with the native or the metric filter");
-    if (p.metric != RC_METRIC_COSINE)  // the native kernels' METRIC forms only: the int8 and float8 filters are cosine-only
-        RC_REQUIRE((p.dtype == RC_F16 || p.dtype == RC_BF16) && !p.f8_filter && p.rows8 == nullptr && p.norms != nullptr,
-                   RC_ERR_UNSUPPORTED, "batched MFMA search under a non-cosine metric needs an f16 or bf16 index with RC_FILTER_METRIC");
+    if (p.pages != nullptr)  // the int8, float8 and float32 filters have no paged form
+        RC_REQUIRE((p.dtype == RC_F16 || p.dtype == RC_BF16) && !p.f8_filter && !p.f32_filter && p.rows8 == nullptr, RC_ERR_UNSUPPORTED,
+                   "batched MFMA search over pages needs an f16 or bf16 index with the native or the metric filter "
+                   "(the int8, float8 and float32 filters have no paged form)");
+    if (p.metric != RC_METRIC_COSINE)  // the native kernels' METRIC forms and the float32 filter's: the int8 and float8 filters are cosine-only
+        RC_REQUIRE(((p.dtype == RC_F16 || p.dtype == RC_BF16 || p.f32_filter) && !p.f8_filter && p.rows8 == nullptr && p.norms != nullptr),
+                   RC_ERR_UNSUPPORTED,
+                   "batched MFMA search under a non-cosine metric needs an f16 or bf16 index with RC_FILTER_METRIC, or a float32 index with "
+                   "RC_FILTER_F32");
+    if (p.f32_filter) {
+        RC_REQUIRE(p.dtype == RC_F32 && p.rows8 == nullptr, RC_ERR_UNSUPPORTED, "the float32 filter needs a float32 index");
+        RC_REQUIRE(f32_filter_supported(p.ld), RC_ERR_UNSUPPORTED,
+                   "the float32 filter serves row widths (dim rounded up to 128) 128, 256, 512 and 768, not " + std::to_string(p.ld));
+        return run_batched_f32(p, ws, s, timer);
+    }
     if (p.f8_filter) {
         RC_REQUIRE(p.dtype == RC_F8 && f8_filter_supported(p.ld), RC_ERR_UNSUPPORTED,
                    "float8 filter needs a float8 index of ld 256, 512 or 768");

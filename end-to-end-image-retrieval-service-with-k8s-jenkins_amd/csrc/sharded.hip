@@ -612,7 +612,8 @@ int rc_sharded_set_filter(rc_sharded *h, int kind) {
         // from RC_FILTER_I8 / RC_FILTER_F8 a failure ends at RC_FILTER_NATIVE, as before.
         int prev = RC_FILTER_NATIVE;
         if (h->n > 0) check_status(rc_index_get_filter(h->shard[0], &prev));
-        const int back = prev == RC_FILTER_METRIC ? RC_FILTER_METRIC : RC_FILTER_NATIVE;
+        // (RC_FILTER_F32 likewise: it too allocates nothing and carries a non-cosine index's batched search)
+        const int back = prev == RC_FILTER_METRIC || prev == RC_FILTER_F32 ? prev : RC_FILTER_NATIVE;
         try {
             for (int s = 0; s < h->n; ++s) check_status(rc_index_set_filter(h->shard[s], kind, h->st[s]));
         } catch (...) {  // all or nothing: a failed shard (e.g. no room for the int8 copy) rolls every shard back
@@ -632,7 +633,7 @@ int rc_sharded_set_metric(rc_sharded *h, int metric) {
         for (int s = 0; s < h->n && metric != RC_METRIC_COSINE; ++s) {
             int kind = RC_FILTER_NATIVE;
             check_status(rc_index_get_filter(h->shard[s], &kind));
-            RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_METRIC, RC_ERR_UNSUPPORTED,
+            RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_METRIC || kind == RC_FILTER_F32, RC_ERR_UNSUPPORTED,
                        "a non-cosine metric on an index with the int8 filter copy or the float8 filter (those filters are cosine-only)");
         }
         for (int s = 0; s < h->n; ++s) check_status(rc_index_set_metric(h->shard[s], metric));

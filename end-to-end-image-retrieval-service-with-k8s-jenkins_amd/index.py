@@ -162,8 +162,11 @@ class DeviceIndex:
         copy; it is what gives a float8 index ``mode="mfma"``) or "metric" (an f16/bf16 index
         only: "native" under cosine, and under dotproduct / euclidean the same filter GEMM with
         a bound on the metric's own score, which is what gives a non-cosine index
-        ``mode="mfma"``; no copy).  "i8" and "f8" are cosine-only.  Results never change —
-        candidates are rescored exactly on the stored rows."""
+        ``mode="mfma"``; no copy) or "f32" (a float32 index only: the filter GEMM reads the stored
+        f32 rows and rounds them to f16 in registers, its bound carrying the rounding; no copy,
+        every metric; it is what gives a float32 index ``mode="mfma"`` on its own rows).  "i8" and
+        "f8" are cosine-only.  Results never change — candidates are rescored exactly on the
+        stored rows."""
         if kind not in _lib.FILTERS:
             raise ValueError(f"unknown filter {kind!r} (expected one of {sorted(_lib.FILTERS)})")
         check(self.lib.rc_index_set_filter(self.handle, _lib.FILTERS[kind], stream_ptr(stream)))
@@ -175,10 +178,10 @@ class DeviceIndex:
         return {v: n for n, v in _lib.FILTERS.items()}[k.value]
 
     def filter_scores(self, queries: torch.Tensor, row0: int, n: int, stream=None):
-        """What the "f8" filter computes (rc_index_filter_scores): its scores ``s'`` of the
-        queries against local rows [row0, row0 + n) (``row0`` a multiple of 128), f32 [nq, n],
-        and each query's bound ``eps`` on ``|s' - exact score|``, f32 [nq].  Raises unless the
-        filter kind is "f8"."""
+        """What the "f8" or the "f32" filter computes (rc_index_filter_scores): its scores ``s'``
+        of the queries against local rows [row0, row0 + n) (``row0`` a multiple of 128), f32
+        [nq, n], and each query's bound ``eps`` on ``|s' - exact score|`` (the cosine, whatever
+        the metric), f32 [nq].  Raises unless the filter kind is "f8" or "f32"."""
         q = self._vecs(queries)
         out = torch.empty((q.shape[0], int(n)), dtype=torch.float32, device=self.device)
         eps = torch.empty((q.shape[0],), dtype=torch.float32, device=self.device)
@@ -237,7 +240,8 @@ class DeviceIndex:
         ``mode``: "scan" (HBM-bound streaming scan), "mfma" (batched filter GEMM +
         exact rescoring, f16/bf16 index; under dotproduct / euclidean only with the "metric"
         filter) or "auto" (MFMA for >= 8 queries; a float8 index scans and refuses "mfma" unless
-        its filter is "f8", a non-cosine index unless its filter is "metric").
+        its filter is "f8", a float32 index unless its filter is "f32" or "i8", a non-cosine
+        index unless its filter is "metric" or "f32").
         ``mask``: optional row-eligibility bitmap over the LOCAL rows (rc_index_search_masked):
         an int32 / uint32 tensor of ceil(n_rows / 32) words on this device, bit r & 31 of word
         r >> 5 = row r may be returned; "auto" then scans.  "mfma" with a mask keeps the filter
@@ -1081,15 +1085,21 @@ class Index:
     keep it.  By default the batched MFMA search is cosine-only: a non-cosine index scans,
     ``mode="mfma"`` and ``filter="i8"`` raise ``ValueError`` on it.  ``filter="metric"`` (an
     f16/bf16 index) gives it the batched search — ``mode="mfma"``, and ``"auto"`` under the
-    usual conditions — with the scan's ids and score bits.  All-zero vectors and queries are
-    rejected under every metric.
+    usual conditions — with the scan's ids and score bits, and ``filter="f32"`` does the same
+    for a float32 index.  All-zero vectors and queries are rejected under every metric.
 
     ``dtype`` is the storage of the normalised rows: ``"float32"``, ``"float16"``, ``"bfloat16"``
     or ``"float8_e4m3fn"`` (alias ``"f8"``: one byte per element, each element of the direction
     rounded to 3 mantissa bits).  A float8 index scans by default (``mode="mfma"`` raises
     ``ValueError``, ``"auto"`` scans); ``filter="f8"`` gives it the batched search on the
     block-scaled fp8 MFMA (cosine, dimensions up to 768), with unchanged results.
-    ``filter="i8"`` raises on it, ``filter="f8"`` on every other dtype.
+    ``filter="i8"`` raises on it, ``filter="f8"`` on every other dtype.  A float32 index (the
+    default) has no batched search of its own rows either (``mode="mfma"`` raises, ``"auto"``
+    scans) until ``filter="f32"``: the filter GEMM then streams the stored float32 rows and rounds
+    them to f16 on their way to the matrix cores, with the rounding inside its error bound — no
+    copy of the rows (``filter="i8"`` keeps one, and is cosine-only), every metric, dimensions up
+    to 128, 256, 512 or 768 after rounding up to 128, unchanged results.  ``filter="f32"`` raises
+    on every other dtype, and with ``paged_search="mfma"``.
 
     ``upsert(vectors)`` accepts ``(id, values)``, ``(id, values, metadata)``
     tuples or ``{"id", "values", "metadata"}`` dicts and overwrites existing
@@ -1106,7 +1116,7 @@ class Index:
     same vectors.  Capacity grows on demand (doubling), as a Pinecone index
     has no fixed size.
 
-    Two things are called "filter" here.  The constructor's ``filter="native" | "i8" | "f8" | "metric"`` is
+    Two things are called "filter" here.  The constructor's ``filter="native" | "i8" | "f8" | "metric" | "f32"`` is
     the kind of filter GEMM the batched search runs (``DeviceIndex.set_filter``); it never
     changes a result.  ``query(..., filter={...})`` / ``query_batch(..., filter={...})`` is
     Pinecone's metadata filter (``metafilter``): only vectors whose metadata satisfies it can
@@ -1186,21 +1196,24 @@ class Index:
             raise ValueError(f"max_top_k must be an integer in [{_lib.RC_TOPK_MAX}, {_lib.RC_DEEP_TOPK_MAX}] (got {max_top_k!r})")
         if paged_search not in ("scan", "mfma"):
             raise ValueError(f"unknown paged_search {paged_search!r} (expected 'scan' or 'mfma')")
-        if paged_search == "mfma" and (_lib.is_f8(dtype) or dtype in ("float32", "f32") or filter in ("i8", "f8")):
+        if paged_search == "mfma" and (_lib.is_f8(dtype) or dtype in ("float32", "f32") or filter in ("i8", "f8", "f32")):
             raise ValueError("paged_search='mfma' runs the native f16 / bf16 kernels over pages: it needs dtype float16 or "
                              f"bfloat16 and filter 'native' or 'metric' (dtype={dtype!r}, filter={filter!r})")
         if metric not in _lib.METRICS:
             raise ValueError(f"unknown metric {metric!r} (expected one of {sorted(_lib.METRICS)})")
         if filter not in _lib.FILTERS:
             raise ValueError(f"unknown filter {filter!r} (expected one of {sorted(_lib.FILTERS)})")
-        if metric != "cosine" and filter not in ("native", "metric"):
-            raise ValueError(f"filter={filter!r} is cosine-only (metric={metric!r}); filter='metric' serves the other metrics")
+        if metric != "cosine" and filter not in ("native", "metric", "f32"):
+            raise ValueError(f"filter={filter!r} is cosine-only (metric={metric!r}); filter='metric' serves the other metrics "
+                             "(filter='f32' on a float32 index)")
         if filter == "metric" and (_lib.is_f8(dtype) or dtype in ("float32", "f32")):
             raise ValueError(f"filter='metric' reads stored f16 / bf16 rows: it needs dtype float16 or bfloat16 (dtype={dtype!r})")
         if _lib.is_f8(dtype) and filter == "i8":
             raise ValueError("filter='i8' is not available on a float8 index (its batched search is filter='f8')")
         if filter == "f8" and not _lib.is_f8(dtype):
             raise ValueError(f"filter='f8' reads stored float8 rows: it needs dtype='f8' (dtype={dtype!r})")
+        if filter == "f32" and dtype not in ("float32", "f32"):
+            raise ValueError(f"filter='f32' reads stored float32 rows: it needs dtype='float32' (dtype={dtype!r})")
         if devices is None:
             devices = [device] * int(shards or 1)
         self.name = name
@@ -1908,6 +1921,8 @@ class Index:
         else:
             mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter == "i8"
             size_ok = mfma_ok and nq >= 8 and per_shard >= 65536
+            if self._set.filter == "f32":  # the widths it serves, and where every measured unmasked cell is ahead of the scan
+                size_ok = self._set.ld in (128, 256, 512, 768) and nq >= 16 and per_shard >= 262144
         if size_ok and eligible >= MASKED_MFMA_MIN_SHARE * n:
             return "mfma"
         # below that share: the mask inside the filter GEMM, where it was measured 2x ahead of the

@@ -216,19 +216,35 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
  *                      RC_SEARCH_AUTO takes the batched path under its usual
  *                      conditions.  It allocates nothing (switching to it from
  *                      RC_FILTER_I8 frees the int8 copy); all three metrics may be set
- *                      on it, in any order. */
+ *                      on it, in any order.
+ *   RC_FILTER_F32    — an RC_F32 index only (RC_ERR_UNSUPPORTED on any other): the batched
+ *                      search on the stored float32 rows, under every metric, with no
+ *                      copy of them.  The filter GEMM streams the f32 rows, rounds each
+ *                      fragment to f16 (to nearest even) in registers on its way to the
+ *                      f16 MFMA, and its error bound carries that rounding (2⁻¹¹ relative,
+ *                      2⁻²⁵ absolute per element below f16's normal range) beside the
+ *                      query's; candidates are rescored exactly on the stored rows, so
+ *                      RC_SEARCH_MFMA and RC_SEARCH_MFMA_MASKED return the scan's rows and
+ *                      score bits.  Row widths (dim rounded up to 128) 128, 256, 512 and
+ *                      768: on another width RC_SEARCH_MFMA is RC_ERR_UNSUPPORTED (the
+ *                      message names the width) and RC_SEARCH_AUTO scans.  It allocates
+ *                      nothing; RC_FILTER_NATIVE switches it off, RC_FILTER_I8 replaces it
+ *                      (cosine only).  All three metrics may be set on it.  No paged form. */
 #define RC_FILTER_NATIVE 0
 #define RC_FILTER_I8 1
 #define RC_FILTER_F8 2
 #define RC_FILTER_METRIC 3
+#define RC_FILTER_F32 4
 int rc_index_set_filter(rc_index *h, int kind, void *stream);
 int rc_index_get_filter(const rc_index *h, int *kind);
-/* What the RC_FILTER_F8 filter computes (a diagnostic: no reference counterpart).  Runs the
+/* What the RC_FILTER_F8 or the RC_FILTER_F32 filter computes (a diagnostic: no reference counterpart).  Runs the
  * filter's query preparation and its kernel's own K loop over the local rows
  * [row0, row0 + n) (row0 a multiple of 128) and writes the filter scores s' — the two-term
- * e4m3 query against the stored rows, before any threshold — to out_scores (device f32
+ * e4m3 query against the stored rows, or the f16 query against the f16-rounded f32 rows (in
+ * cosine space, whatever the index's metric), before any threshold — to out_scores (device f32
  * [nq][n]) and each query's bound on |s' − exact score| to out_eps (device f32 [nq]).
- * queries: device f32 [nq][dim].  RC_ERR_UNSUPPORTED unless the filter kind is RC_FILTER_F8. */
+ * queries: device f32 [nq][dim].  RC_ERR_UNSUPPORTED unless the filter kind is RC_FILTER_F8 or
+ * RC_FILTER_F32. */
 int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t row0, int64_t n, float *out_scores,
                            float *out_eps, void *stream);
 
@@ -253,7 +269,7 @@ int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t ro
  * function of the row and the query alone: every search path and a sharded index give
  * the same bits.  All-zero vectors and queries stay rejected by the host layer.
  * The batched MFMA path serves a non-cosine metric only through RC_FILTER_METRIC (an
- * f16 / bf16 index), whose filter bounds the metric's own score per row.  With any other
+ * f16 / bf16 index) or RC_FILTER_F32 (an f32 index), whose filters bound the metric's own score per row.  With any other
  * filter kind its candidate threshold is a bound in cosine space: on a non-cosine index
  * with RC_FILTER_NATIVE RC_SEARCH_AUTO scans and RC_SEARCH_MFMA is RC_ERR_UNSUPPORTED;
  * rc_index_set_filter(RC_FILTER_I8 / RC_FILTER_F8) on a non-cosine index is
@@ -351,10 +367,10 @@ int rc_sharded_query_host_masked(rc_sharded *h, const float *queries, int nq, in
                                  int with_values, const uint32_t *mask, float *scores, int64_t *out_rows,
                                  float *values);
 /* rc_index_set_filter on every shard; all or nothing (a failure restores
- * RC_FILTER_NATIVE on every shard, or RC_FILTER_METRIC if that was the kind before). */
+ * RC_FILTER_NATIVE on every shard, or RC_FILTER_METRIC / RC_FILTER_F32 if that was the kind before). */
 int rc_sharded_set_filter(rc_sharded *h, int kind);
 /* rc_index_set_metric on every shard; the metric is validated against every shard
- * before any is set (an unknown metric, or a shard whose filter is neither RC_FILTER_NATIVE nor RC_FILTER_METRIC under a non-cosine metric, changes none). */
+ * before any is set (an unknown metric, or a shard whose filter is none of RC_FILTER_NATIVE, RC_FILTER_METRIC and RC_FILTER_F32 under a non-cosine metric, changes none). */
 int rc_sharded_set_metric(rc_sharded *h, int metric);
 
 /* ------------------------------------------------------------------------
@@ -384,7 +400,7 @@ int rc_sharded_set_metric(rc_sharded *h, int metric);
  * f16 / bf16 filter, rescore and fallback kernels; cosine, or dotproduct / euclidean with
  * RC_FILTER_METRIC): the same bits as RC_SEARCH_SCAN, ties included.  They return
  * RC_ERR_UNSUPPORTED where rc_index_search_ex refuses them and on an index whose filter
- * is RC_FILTER_I8 or RC_FILTER_F8, which have no paged form.  RC_SEARCH_MFMA_MASKED
+ * is RC_FILTER_I8, RC_FILTER_F8 or RC_FILTER_F32, which have no paged form.  RC_SEARCH_MFMA_MASKED
  * without a mask is RC_SEARCH_MFMA; with one it is refused (RC_ERR_UNSUPPORTED) under a
  * non-cosine metric at row width 512, the one form that is not built.  RC_SEARCH_AUTO scans with a mask, and without one
  * takes the batched search where it is available and measured ahead of the paged scan:
