@@ -97,6 +97,21 @@ class JpegInfo(C.Structure):
     ]
 
 
+class PngImage(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("depth", C.c_int32),
+        ("color", C.c_int32),
+        ("palette_entries", C.c_int32),
+        ("reserved", C.c_int32),
+        ("scanlines", C.c_char_p),
+        ("scan_bytes", C.c_int64),
+        ("palette", C.c_char_p),
+        ("out_offset", C.c_int64),
+    ]
+
+
 _vp = C.c_void_p
 _i64 = C.c_int64
 _i32 = C.c_int
@@ -200,6 +215,7 @@ SIGNATURES = {
     "rc_jpeg_decoder_destroy": (C.c_int, [_vp]),
     "rc_jpeg_decode": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), _pi64, _vp, _pi64, _vp]),
     "rc_jpeg_decode_resized": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), _pi64, _i32, _i32, _vp, _vp]),
+    "rc_png_reconstruct": (C.c_int, [_i32, _i32, C.POINTER(PngImage), _vp, _i64, _vp]),
 }
 
 # diagnostic builds only (tools/build_diag.sh, loaded with RC_LIB_PATH): bound when present,

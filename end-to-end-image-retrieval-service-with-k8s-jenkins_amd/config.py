@@ -54,6 +54,8 @@ class Config:
     MODEL_PATH = os.getenv("RC_MODEL_PATH", "")  # local checkpoint dir (config.json + weights)
     WEIGHT_SEED = int(os.getenv("RC_WEIGHT_SEED", "1907"))
     GPU_JPEG = os.getenv("RC_GPU_JPEG", "1") != "0"  # decode baseline JPEGs on the GPU (bit-exact with PIL)
+    # reconstruct PNGs on the GPU (host inflate + HIP un-filter, bit-exact with PIL); DESIGN.md "PNG decode"
+    GPU_PNG = os.getenv("RC_GPU_PNG", "1") != "0"
     # ingest / retrieve services: embed in process on the GPU (1) or POST to EMBEDDING_SERVICE_URL (0)
     EMBED_IN_PROCESS = os.getenv("RC_EMBED_IN_PROCESS", "1") != "0"
 

@@ -8,8 +8,10 @@ Contract kept from the reference (``embedding/main.py:78-124``):
                  422 when ``file`` is missing; other decode errors propagate (500)
 
 Compute: baseline JPEGs are decoded on the GPU (host Huffman + HIP IDCT /
-upsampling / colour, bit-exact with the reference's PIL decode at ``:97``); any
-other image goes through PIL on the host as in the reference.  Then one
+upsampling / colour, bit-exact with the reference's PIL decode at ``:97``).  PNGs
+that are not interlaced and hold 8 bits or less per sample are inflated on the host and
+un-filtered on the GPU (``png.py``, bit-exact with the same PIL decode).  Any other image
+goes through PIL on the host as in the reference.  Then one
 ``rc_embed`` call on the GPU (resize → normalize → ViT-MSN → final LN of the CLS
 row) instead of ``extractor`` + ``model`` (``:107-113``).  ``POST /embed_batch`` (field ``files``,
 repeated) returns one vector per image — the batched form of the same contract.
@@ -106,20 +108,37 @@ def _gpu_jpeg(data: bytes) -> bool:
     return is_gpu_decodable(data)
 
 
+def _gpu_png(data: bytes) -> bool:
+    if not Config.GPU_PNG:
+        return False
+    from ..png import is_gpu_decodable
+
+    return is_gpu_decodable(data)
+
+
 def decode_many(blobs: List[bytes]) -> list:
     """Image bytes → the embedder's u8 HWC RGB inputs, validated as the reference validates
     them: baseline JPEGs decoded AND resized to the model's input size on the GPU in one pass
-    (device tensors, bit-exact with PIL decode + the processor's resize), anything else — and
-    any stream the GPU decoder rejects — through PIL on the host at its own size
-    (``UnidentifiedImageError`` → 400), resized later inside rc_embed."""
+    (device tensors, bit-exact with PIL decode + the processor's resize), non-interlaced PNGs of
+    8 bits or less inflated on the host and reconstructed on the GPU at their own size (device
+    tensors, bit-exact with the PIL decode), anything else — and any stream a GPU decoder
+    rejects — through PIL on the host at its own size (``UnidentifiedImageError`` → 400); images
+    at their own size are resized later inside rc_embed."""
     import numpy as np
     import torch
 
     out: list = [None] * len(blobs)
     gpu = [i for i, b in enumerate(blobs) if _gpu_jpeg(b)]
-    gset = set(gpu)
+    png, staged = [i for i, b in enumerate(blobs) if _gpu_png(b)], []
+    if png:  # the host half first: a PNG that fails it is one more host image, on its own
+        from ..png import stage
+
+        results = stage([blobs[i] for i in png], tolerant=True)
+        keep = [k for k, r in enumerate(results) if not isinstance(r, ValueError)]
+        png, staged = [png[k] for k in keep], [results[k] for k in keep]
+    gset = set(gpu) | set(png)
     host = [i for i in range(len(blobs)) if i not in gset]
-    for i in host:  # validate before touching the model (400 needs no GPU)
+    for i in host:  # validate before touching the model (400 needs no GPU), in upload order
         out[i] = np.asarray(decode_image(blobs[i]), dtype=np.uint8)
     if gpu:
         try:
@@ -128,6 +147,13 @@ def decode_many(blobs: List[bytes]) -> list:
                 out[i] = im
         except ValueError:  # a damaged stream: the reference's host decode decides (image or 400)
             for i in gpu:
+                out[i] = np.asarray(decode_image(blobs[i]), dtype=np.uint8)
+    if png:
+        try:
+            for i, im in zip(png, get_embedder().reconstruct_png(staged)):  # per member GPU on a pool
+                out[i] = im
+        except ValueError:  # the library refused the launch (its staging cap): valid images, host decode
+            for i in png:
                 out[i] = np.asarray(decode_image(blobs[i]), dtype=np.uint8)
     return out
 

@@ -172,6 +172,7 @@ class VitMsnEmbedder:
         self.max_batch = int(max_batch)
         self.hidden = cfg["hidden_size"]
         self._jpeg = None  # GPU JPEG decoder, created on first embed_jpeg
+        self._png = None  # GPU PNG decoder, created on first decode_png
         c = _lib.VitConfig(cfg["image_size"], cfg["patch_size"], cfg["hidden_size"], cfg["num_hidden_layers"],
                            cfg["num_attention_heads"], cfg["intermediate_size"], float(cfg["layer_norm_eps"]),
                            self.max_batch)
@@ -302,6 +303,22 @@ class VitMsnEmbedder:
         decode + Image.resize); rc_embed then runs no resize."""
         S = self.config["image_size"]
         return self._decoder().decode_resized(datas, S, int(self.preprocess_params["resample"]))
+
+    def decode_png(self, datas: Sequence[bytes]) -> list[torch.Tensor]:
+        """PNG byte strings → device HWC RGB u8 images at their own size (host inflate +
+        rc_png_reconstruct, bit-exact with the reference's PIL decode); rc_embed resizes them as it
+        resizes host arrays.  Raises png.PngUnsupported / ValueError."""
+        from .png import stage
+
+        return self.reconstruct_png(stage(datas))
+
+    def reconstruct_png(self, staged: Sequence) -> list[torch.Tensor]:
+        """The device half of ``decode_png``: ``png.stage`` results → device images."""
+        from .png import PngDecoder
+
+        if self._png is None:
+            self._png = PngDecoder(self.device, max_images=max(self.max_batch, 64))
+        return self._png.reconstruct(staged)
 
     def embed_jpeg(self, datas: Sequence[bytes]) -> list[list[float]]:
         """Baseline-JPEG byte strings → raw CLS vectors, decoded (and resized) on the GPU and
@@ -545,6 +562,21 @@ class EmbedderPool:
         between concurrent calls), queued on the caller's current stream of that GPU.  An image
         stays on the GPU that decoded it and ``embed_parts`` embeds it there: only its 768-float
         vector ever crosses GPUs, not the 150 KB image."""
+        return self._decode_per_member(datas, assign, lambda m, part: m.decode_jpeg_for_embed(part).unbind(0))
+
+    def decode_png(self, datas: Sequence[bytes], assign: Sequence[int] | None = None) -> list[torch.Tensor]:
+        """Per-image device u8 [H, W, 3] images at their own size (input order), each member
+        decoding its share on its own GPU as in ``decode_jpeg_for_embed``."""
+        return self._decode_per_member(datas, assign, lambda m, part: m.decode_png(part))
+
+    def reconstruct_png(self, staged: Sequence, assign: Sequence[int] | None = None) -> list[torch.Tensor]:
+        """``png.stage`` results → device images, every member reconstructing its share."""
+        return self._decode_per_member(staged, assign, lambda m, part: m.reconstruct_png(part))
+
+    def _decode_per_member(self, datas: Sequence[bytes], assign, decode) -> list[torch.Tensor]:
+        """``decode(member, its byte strings)`` -> images, run for every member that got a share
+        (``assign``, default round-robin) concurrently, each on the caller's current stream of the
+        member's GPU; the images come back in input order."""
         n = len(datas)
         assign = list(assign) if assign is not None else self.assign(n)
         if len(assign) != n:
@@ -558,7 +590,7 @@ class EmbedderPool:
             mi, pos = item
             m = self.members[mi]
             with torch.cuda.device(m.device), torch.cuda.stream(streams[m.device.index]):
-                return pos, m.decode_jpeg_for_embed([datas[j] for j in pos])
+                return pos, decode(m, [datas[j] for j in pos])
 
         items = list(groups.items())
         if len(items) == 1:
@@ -569,8 +601,8 @@ class EmbedderPool:
             with cf.ThreadPoolExecutor(len(items)) as ex:
                 results = list(ex.map(work, items))
         out: list = [None] * n
-        for pos, x in results:
-            for j, im in zip(pos, x.unbind(0)):
+        for pos, ims in results:
+            for j, im in zip(pos, ims):
                 out[j] = im
         return out
 

@@ -790,6 +790,34 @@ int rc_jpeg_decode(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const 
 int rc_jpeg_decode_resized(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const int64_t *lens, int out_size,
                            int resample, uint8_t *out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * PNG reconstruction.  The host parses the chunks and inflates IDAT (png.py);
+ * this call un-filters the scanlines (None / Sub / Up / Average / Paeth) and
+ * expands them to HWC RGB u8 on the GPU, bit-exact with Pillow's
+ * Image.open(...).convert("RGB"): gray replicated (depths 1, 2, 4 scaled by
+ * 255, 85, 17), palette looked up (entries past PLTE are black), alpha dropped.
+ * Non-interlaced only; colour type 0 or 3 at depth 1/2/4/8, 2, 4 or 6 at depth 8.
+ * ---------------------------------------------------------------------- */
+typedef struct rc_png_image {
+    int32_t width, height, depth, color; /* IHDR */
+    int32_t palette_entries, reserved;   /* PLTE entries (colour type 3), else 0 */
+    const uint8_t *scanlines;            /* host: the inflated IDAT, height * (1 + stride) bytes */
+    int64_t scan_bytes;
+    const uint8_t *palette;              /* host: palette_entries * 3 bytes (colour type 3), else NULL */
+    int64_t out_offset;                  /* bytes from rgb: height x width x 3 are written there */
+} rc_png_image;
+
+/* Reconstruct n images in one launch on `stream` of `device`; rgb is device memory of rgb_bytes.
+ * The scanlines are copied into a pinned staging block of the library's (per device; it grows
+ * with the largest batch seen and is reused: a repeated call leaves rc_alloc_count() unchanged),
+ * so the host buffers may be reused once the call returns.  Checked before any device call,
+ * RC_ERR_INVALID: sizes, scan_bytes != height * (1 + stride), a filter byte above 4, a missing
+ * palette, an output range outside rgb.  RC_ERR_UNSUPPORTED: 16-bit samples; a row of more
+ * than 3072 filter units (pixels at depth 8, bytes below): the last row of a 64-row band is
+ * kept in LDS for the band under it; an image of more than 2^24 pixels; a call whose scanlines
+ * exceed 512 MiB, which is as far as the staging grows. */
+int rc_png_reconstruct(int device, int n, const rc_png_image *images, uint8_t *rgb, int64_t rgb_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,126 @@
+"""PNG uploads through the embedding service's core, GPU reconstruction against the host decode.
+
+The yardstick is what the service did before the GPU path: ``Image.open(...).convert("RGB")`` per
+image on the host, then the same embed (``RC_GPU_PNG=0``).  Both run in this one process on the
+same model, alternating round by round (host, gpu, host, gpu, ...) after a warm-up of each; every
+figure is a median over --rounds with its [min, max].  RGB at depth 8, smooth synthetic pictures
+(sinusoids plus a little noise, so that the deflate stream is not a stored one) saved by Pillow at
+its default compression, at 300x168 and 1024x768:
+
+  batch64_ms   a batch of 64 PNGs through decode_many + the embed, to a device synchronise
+  single_ms    one PNG through embed_bytes (the /embed core)
+and, for the GPU path alone, where the time of a batch of 64 goes:
+  inflate_ms   PngDecoder.host_stage: chunk parsing, CRCs and zlib inflate in the thread pool
+  reconstruct_ms  PngDecoder.reconstruct between two events on the stream: the copy of the scanlines
+               into the pinned staging (the device waits for it), the upload and png_reconstruct_kernel
+The kernel alone: ``--kernel-only WxH`` stages a batch of 64 once and runs the device stage 20
+times, timing nothing itself; run it under ``rocprofv3 --kernel-trace --stats`` (a run of its own)
+and read png_reconstruct_kernel's row of the kernel statistics.
+
+Every line printed is one JSON record; --out appends them to a file.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+from io import BytesIO
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+PKG = "end-to-end-image-retrieval-service-with-k8s-jenkins_amd"
+SIZES = ((300, 168), (1024, 768))
+BATCH = 64
+
+
+def picture(w, h, seed):
+    import numpy as np
+    from PIL import Image
+
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:h, 0:w].astype(np.float32)
+    chans = [127 + 90 * np.sin(x / rng.uniform(9, 60) + rng.uniform(0, 6)) * np.cos(y / rng.uniform(9, 60)) for _ in range(3)]
+    a = np.stack(chans, -1) + rng.normal(0, 2, (h, w, 3))
+    b = BytesIO()
+    Image.fromarray(a.clip(0, 255).astype(np.uint8)).save(b, format="PNG")
+    return b.getvalue()
+
+
+def stats(v):
+    s = sorted(v)
+    return {"median": s[len(s) // 2], "minmax": [s[0], s[-1]]}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=None, help="append the JSON records to this file")
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--kernel-only", metavar="WxH", default=None, help="the profiler's target: 20 device stages of one batch")
+    args = ap.parse_args()
+    import torch
+
+    assert torch.cuda.is_available(), "png_micro needs a GPU"
+    if args.kernel_only:
+        w, h = map(int, args.kernel_only.split("x"))
+        dec = importlib.import_module(f"{PKG}.png").PngDecoder(0)
+        staged = dec.host_stage([picture(w, h, 1000 + i) for i in range(BATCH)])
+        for _ in range(20):
+            dec.reconstruct(staged)
+        torch.cuda.synchronize()
+        return
+    main_mod = importlib.import_module(f"{PKG}.embedding.main")
+    png = importlib.import_module(f"{PKG}.png")
+    emb = main_mod.get_embedder()
+    dec = png.PngDecoder(emb.device)
+
+    def batch(blobs):
+        t = time.perf_counter()
+        main_mod.embed_many_device(blobs)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
+    def single(blob):
+        t = time.perf_counter()
+        main_mod.embed_bytes(blob)  # ends in a stream synchronise
+        return (time.perf_counter() - t) * 1e3
+
+    for w, h in SIZES:
+        blobs = [picture(w, h, 1000 + i) for i in range(BATCH)]
+        t = {(m, k): [] for m in ("host", "gpu") for k in ("batch64_ms", "single_ms")}
+        split = {"inflate_ms": [], "reconstruct_ms": []}
+        for rnd in range(-1, args.rounds):  # round -1 warms every shape of both paths
+            for mode in ("host", "gpu"):
+                main_mod.Config.GPU_PNG = mode == "gpu"
+                b, s = batch(blobs), single(blobs[rnd % BATCH])
+                if rnd >= 0:
+                    t[mode, "batch64_ms"].append(b)
+                    t[mode, "single_ms"].append(s)
+            t0 = time.perf_counter()
+            staged = dec.host_stage(blobs)
+            t1 = time.perf_counter()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dec.reconstruct(staged)
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd >= 0:
+                split["inflate_ms"].append((t1 - t0) * 1e3)
+                split["reconstruct_ms"].append(e0.elapsed_time(e1))
+        rec = {"width": w, "height": h, "batch": BATCH, "rounds": args.rounds,
+               "png_bytes_mean": sum(map(len, blobs)) // BATCH}
+        for (mode, k), v in t.items():
+            rec[f"{mode}_{k}"] = stats(v)
+        for k, v in split.items():
+            rec[f"gpu_{k}"] = stats(v)
+        rec["batch64_images_per_s"] = {m: BATCH / rec[f"{m}_batch64_ms"]["median"] * 1e3 for m in ("host", "gpu")}
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+    main_mod.reset_embedder()
+
+
+if __name__ == "__main__":
+    main()
