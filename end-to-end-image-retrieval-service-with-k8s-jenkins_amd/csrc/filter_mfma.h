@@ -1,9 +1,8 @@
-// filter_mfma.h — what the batched search's native (f16 / bf16) filter kernels share between their
-// two translation units: search_mfma.hip (the contiguous kernels and every host function) and
-// search_mfma_paged.hip (the page-table forms of the same bodies).  The MFMA wrappers, the filter
-// arguments, the block mapping, the candidate append, and the MASKED and METRIC epilogues' helpers
-// with the arguments that make them exact.  The kernel bodies themselves are filter_gemm_body.inc
-// and filter_qs_body.inc.
+// filter_mfma.h — what the batched search's filter kernels share: the MFMA wrappers, the filter
+// arguments, the block mapping, the chunk split, the candidate append, and the MASKED, METRIC and
+// PAGED forms' helpers with the arguments that make them exact.  The native (f16 / bf16) kernels
+// are filter_native.h's; the int8 and float8 kernels are in search_mfma.hip, the float32 kernel in
+// search_mfma_f32.hip.
 #pragma once
 
 #include "index_common.h"
@@ -63,6 +62,12 @@ struct FilterBlock {
         rt1 = min(rt_total, rt0 + a.tiles_per_chunk);
     }
 };
+
+// Row tiles per chunk: the rows [c0, c1) of one dispatch, in tiles of rt rows, split into nchunk chunks
+// (FilterArgs::tiles_per_chunk).
+inline int64_t tiles_per_chunk(int64_t c0, int64_t c1, int rt, int64_t nchunk) {
+    return ((c1 - c0 + rt - 1) / rt + nchunk - 1) / nchunk;
+}
 
 // Row `row` passed query q's filter: append it to q's candidate list (the count keeps running
 // past cap: rescore_kernel reads an overflow from it).
@@ -176,11 +181,11 @@ __device__ __forceinline__ float metric_upper(const f32x4_t &k4, float sp, float
     return metric_score(MetricCoef{k4[1], k4[2], k4[3]}, sp + k4[0], n);
 }
 
-// filter_qs_kernel's shape (search_mfma.hip): queries/16 per wave, rows per tile, LDS ring steps
+// filter_qs_kernel's shape (filter_native.h): queries/16 per wave, rows per tile, LDS ring steps
 constexpr int QS_QT = 2, QS_RT = 128, QS_NS = 8;
 
-// ------------------------------------------------ PAGED forms (search_mfma_paged.hip) --
-// Both bodies have a PAGED form (`constexpr bool PAGED`, `const int32_t *pages`): the rows are a
+// ------------------------------------------------------------ PAGED forms --
+// Both native kernels have a PAGED form (FilterNativeArgs::pages): the rows are a
 // namespace's positions [r_begin, r_end) of a page table (scan_paged.h), and everything but two
 // addresses stays in position space.  A row tile is SB_TILE or QS_RT positions from a multiple of
 // its own size, and every stage and sub-launch boundary of run_stages is a multiple of SB_TILE, so a
@@ -194,13 +199,5 @@ __device__ __forceinline__ int32_t load_page(const int32_t *__restrict__ pages, 
     typedef const __attribute__((address_space(4))) int32_t *const_pages;
     return ((const_pages)pages)[pos / RC_PAGE_ROWS];
 }
-// One filter dispatch over a page table (search_mfma_paged.hip, instantiated for f16 / bf16): fa as
-// run_batched fills it, in positions.
-template <typename T>
-void launch_filter_paged(const BatchPlan &p, const BatchWs &ws, FilterArgs fa, int64_t nchunk, int nqb, hipStream_t s);
-// what a contiguous kernel declares ahead of the body in place of the paged form's argument
-#define RC_FILTER_NOT_PAGED         \
-    constexpr bool PAGED = false; \
-    [[maybe_unused]] const int32_t *const pages = nullptr;
 
 }  // namespace rc

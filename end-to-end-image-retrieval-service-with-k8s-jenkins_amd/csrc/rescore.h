@@ -35,7 +35,7 @@ namespace rc {
 // constants (mcoef: eps, alpha, beta, gamma) — the scan's rule on the scan's operands (qn is the
 // RC_UNIT_ELEM product the metric scan forms), so the scan's bits — and thr[q] is the k-th best
 // metric score itself: the filter's u is an upper bound of the exact score with no slack left to
-// subtract (the metric epilogue's comment in search_mfma.hip).  The masked argument carries over
+// subtract (the metric epilogue's comment in filter_mfma.h).  The masked argument carries over
 // unchanged: the list holds eligible rows only, so thr[q] is a lower bound of the final masked
 // k-th best.
 // The body is rescore_body.inc, included in both kernels: one copy of the text, and the cosine

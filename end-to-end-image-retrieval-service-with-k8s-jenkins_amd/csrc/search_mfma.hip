@@ -28,10 +28,15 @@
 //
 // HBM layout: rows [cap256][ld] T (capacity rounded up to 256 rows so whole
 // row tiles are readable), queries q̂ [nqb*256][ld] T (zero rows past nq).
+//
+// In this file: the query preparation, the int8 and float8 filter kernels, and every host function
+// (run_stages, the five filters' run_batched_*).  The native f16 / bf16 filter kernels and their
+// dispatch are filter_native.h's (their PAGED forms compile in search_mfma_paged.hip), the float32
+// filter is search_mfma_f32.hip's, the rescoring rescore.h's.
 #include <algorithm>
 #include <vector>
 
-#include "filter_mfma.h"
+#include "filter_native.h"
 #include "index_common.h"
 #include "rescore.h"
 
@@ -103,104 +108,6 @@ __global__ __launch_bounds__(64) void prepare_queries_metric_kernel(const float 
         mcoef[4 * qi + 2] = mc.beta;
         mcoef[4 * qi + 3] = mc.gamma;
     }
-}
-
-// The int8 and float8 kernels take MASKED as a template parameter; their MASKED forms get the bitmap
-// beside the arguments, and the unmasked forms keep the kernel arguments they had.
-struct FilterArgsMasked {
-    FilterArgs a;
-    const uint32_t *mask;  // [ceil(r_end / 32)], over the local rows (BatchPlan::mask)
-};
-__device__ __forceinline__ const FilterArgs &filter_args(const FilterArgs &a) { return a; }
-__device__ __forceinline__ const FilterArgs &filter_args(const FilterArgsMasked &m) { return m.a; }
-
-// 256x256x64 tile, 512 threads = 8 waves in two groups (G0 = waves 0-3 own
-// query rows 0-127, G1 = waves 4-7 rows 128-255; wave w and w+4 share a SIMD).
-// Each wave owns 128 queries x 64 index rows as 4 quadrants of 64x32.  The
-// (row tile, K-tile) steps of the block's chunk are one flattened sequence, so
-// the next row tile's first K-tile streams in under the current tile's last
-// MFMAs.  A K-tile is 4 phases; each phase is an M segment (ds_read the
-// quadrant's fragments, issue this wave's LDS-DMA share of the next step,
-// lgkmcnt(0)) and a C segment (16 MFMAs), each closed by a block barrier; G1
-// runs one segment behind G0 so one wave per SIMD is in MFMAs while its partner
-// reads LDS.  MFMA roles: A operand = index rows, B operand = queries, so a
-// lane's accumulator holds 4 consecutive ROWS of one query: the epilogue tests
-// one per-lane threshold against 16 values at a time.
-// The body is filter_gemm_body.inc, included in the cosine kernel and in its METRIC form: one copy
-// of the text, and the cosine kernel keeps the instructions it had.
-template <typename T>
-__global__ __launch_bounds__(512, 1) void filter_gemm_kernel(FilterArgs a) {
-    constexpr bool METRIC = false, MASKED = false;
-    [[maybe_unused]] const FilterMetric fm{};
-    [[maybe_unused]] const uint32_t *const mask = nullptr;
-    RC_FILTER_NOT_PAGED
-#include "filter_gemm_body.inc"
-}
-template <typename T>
-__global__ __launch_bounds__(512, 1) void filter_gemm_metric_kernel(FilterArgs a, FilterMetric fm) {
-    constexpr bool METRIC = true, MASKED = false;
-    [[maybe_unused]] const uint32_t *const mask = nullptr;
-    RC_FILTER_NOT_PAGED
-#include "filter_gemm_body.inc"
-}
-// the MASKED form of both (new kernels, so a template parameter costs no existing symbol; cosine: fm unused)
-template <typename T, bool METRIC>
-__global__ __launch_bounds__(512, 1) void filter_gemm_masked_kernel(FilterArgs a, FilterMetric fm, const uint32_t *mask) {
-    constexpr bool MASKED = true;
-    RC_FILTER_NOT_PAGED
-#include "filter_gemm_body.inc"
-}
-
-// Query-stationary filter GEMM (ld = 64·NKT <= 512).  The filter GEMM above
-// streams BOTH operands through LDS (256 queries x 256 rows per 64 KB K-step:
-// 128 flop/B), which the L2->LDS fill rate caps near 45 % of MFMA peak.  Here a
-// block's 256 queries live in REGISTERS for the whole launch and only index rows
-// stream: one wave per SIMD (4 waves, up to 512 VGPRs each), wave w holds
-// queries [64w, 64w+64) of the block's query group as 4 x 2·NKT B-fragments
-// (256 VGPRs at ld 512) plus a 64 x 128 f32 accumulator (128 VGPRs).  Rows come
-// in 128-row tiles, one 16 KB K-step (128 rows x 64) per stage of an 8-deep LDS
-// ring (7 steps ≈ 112 KB in flight: enough to hide the HBM latency of a row
-// tile's first touch): 2·256·128·64 flop per 16 KB = 256 flop/B, half the fill
-// bytes of filter_gemm_kernel.  DMA through a per-step buffer descriptor (uniform
-// base, 32-bit lane offsets) keeps addresses out of the VGPR budget.
-// MFMA roles as above (A = index rows, B = queries): lane (li, g) of acc[rf][qt]
-// holds rows 16·rf + 4g + j of query 16·qt + li.  Same thresholds, candidate
-// appends and exactness argument as filter_gemm_kernel.
-// Each wave holds 32 queries (2 x 16, QS_QT) for 128-row tiles: 8 waves, 2 per SIMD,
-// every row-fragment read feeds two MFMAs and the SIMD partner wave's MFMAs cover
-// its latency.  (A 4-wave form with 64 queries per wave pinned in AGPRs and
-// inline-asm MFMAs was measured against it in round 2 — within 1 %, behind after
-// the 2-GB sub-launches — and removed.)
-// (QS_QT, QS_RT, QS_NS: filter_mfma.h)
-
-// ABL (A/B diagnostics, diagnostic builds only; 0 in production): bit0 no DMA in the
-// loop, bit1 no MFMA, bit2 no fragment reads (MFMAs on the query registers), bit3 no
-// epilogue.
-// The body is filter_qs_body.inc (as filter_gemm_body.inc); the METRIC form's epilogue loads the
-// tile's norms itself.
-template <typename T, int NKT, int ABL = 0>  // 256 queries per block
-__global__ __launch_bounds__(512, 1) void filter_qs_kernel(FilterArgs a) {
-    constexpr bool METRIC = false, MASKED = false;
-    [[maybe_unused]] const FilterMetric fm{};
-    [[maybe_unused]] const uint32_t *const mask = nullptr;
-    RC_FILTER_NOT_PAGED
-#include "filter_qs_body.inc"
-}
-template <typename T, int NKT>
-__global__ __launch_bounds__(512, 1) void filter_qs_metric_kernel(FilterArgs a, FilterMetric fm) {
-    constexpr bool METRIC = true, MASKED = false;
-    constexpr int ABL = 0;
-    [[maybe_unused]] const uint32_t *const mask = nullptr;
-    RC_FILTER_NOT_PAGED
-#include "filter_qs_body.inc"
-}
-// the MASKED form of both (as filter_gemm_masked_kernel)
-template <typename T, int NKT, bool METRIC>
-__global__ __launch_bounds__(512, 1) void filter_qs_masked_kernel(FilterArgs a, FilterMetric fm, const uint32_t *mask) {
-    constexpr bool MASKED = true;
-    constexpr int ABL = 0;
-    RC_FILTER_NOT_PAGED
-#include "filter_qs_body.inc"
 }
 
 // ------------------------------------------------ int8 filter (optional) --
@@ -282,16 +189,19 @@ __device__ __forceinline__ void lds_write_u32(uint32_t *p, uint32_t v) {
 }
 
 // AUX: cache-policy bits of the row DMA (0; 2 = nontemporal: diagnostic builds' A/B)
-// MASKED (the MASKED epilogues' comment above): here a lane holds ONE row per accumulator, row
+// MASKED (the MASKED epilogues' comment in filter_mfma.h): here a lane holds ONE row per accumulator, row
 // 16·rf + li of the tile, so its eligibility is one bit per rf (em).  The accumulators are integers:
 // an ineligible row's become INT_MIN ahead of the gate's maximum, and since a huge negative value
 // still passes v >= thr while thr is -inf, the append tests the row's bit as well.
+struct FilterI8Args {
+    FilterArgs a;
+    const uint32_t *mask;  // MASKED: [ceil(r_end / 32)], over the local rows (BatchPlan::mask)
+};
 template <int NKT, int RT, int AUX = 0, bool MASKED = false>
-__global__ __launch_bounds__(512, 1) void filter_i8_kernel(std::conditional_t<MASKED, FilterArgsMasked, FilterArgs> am) {
+__global__ __launch_bounds__(512, 1) void filter_i8_kernel(FilterI8Args fa) {
     typedef int i32x4_t __attribute__((ext_vector_type(4)));
-    const FilterArgs &a = filter_args(am);
-    [[maybe_unused]] const uint32_t *mask = nullptr;
-    if constexpr (MASKED) mask = am.mask;
+    const FilterArgs &a = fa.a;
+    [[maybe_unused]] const uint32_t *const mask = fa.mask;
     constexpr int QT = QS_QT, WAVES = 16 / QS_QT, RF = RT / 16, RH = RF / 4;
     constexpr int STEP_BYTES = RT * 128;
     constexpr int SPS = 2, SXL = 2 * RH;
@@ -622,13 +532,8 @@ struct FilterF8Args {
     const uint8_t *qlo;   // the q_lo plane (TERMS 2)
     float *dump;          // DUMP: s' of queries [0, dump_nq) x rows [r_begin, r_end), [dump_nq][r_end - r_begin]
     int dump_nq;
+    const uint32_t *mask;  // MASKED: [ceil(r_end / 32)], over the local rows
 };
-struct FilterF8ArgsMasked {  // the MASKED form's (as FilterArgsMasked)
-    FilterF8Args f;
-    const uint32_t *mask;
-};
-__device__ __forceinline__ const FilterF8Args &filter_args(const FilterF8Args &f) { return f; }
-__device__ __forceinline__ const FilterF8Args &filter_args(const FilterF8ArgsMasked &m) { return m.f; }
 
 // Query-stationary, as filter_qs_kernel / filter_i8_kernel: same FilterBlock mapping, 8 waves, the
 // same LDS ring of RT rows x 128 B per step filled by buffer-descriptor DMA, every ring step issued
@@ -666,14 +571,12 @@ __device__ __forceinline__ f32x4_t mfma_f8_scaled(i32x8_t row, i32x8_t query, f3
                                                             qscale * 0x01010101);
 }
 
-// MASKED (the MASKED epilogues' comment above): rows and accumulators as filter_qs_kernel's, so the
+// MASKED (the MASKED epilogues' comment in filter_mfma.h): rows and accumulators as filter_qs_kernel's, so the
 // same 4-bit fields.  No MASKED DUMP form.
 template <int NKT, int RT, int TERMS, int QT, bool DUMP = false, bool MASKED = false>
-__global__ __launch_bounds__(512, 1) void filter_f8_kernel(std::conditional_t<MASKED, FilterF8ArgsMasked, FilterF8Args> fam) {
+__global__ __launch_bounds__(512, 1) void filter_f8_kernel(FilterF8Args fa) {
     static_assert(!(DUMP && MASKED), "the DUMP form has no mask");
-    const FilterF8Args &fa = filter_args(fam);
-    [[maybe_unused]] const uint32_t *mask = nullptr;
-    if constexpr (MASKED) mask = fam.mask;
+    [[maybe_unused]] const uint32_t *const mask = fa.mask;
     constexpr int WAVES = 8, QPB = WAVES * 16 * QT, RF = RT / 16, RH = RF / 4;
     constexpr int STEP_BYTES = RT * 128;
     constexpr int NS = QS_NS * 128 / RT;  // ring steps: 128 KB of rows either way
@@ -965,52 +868,8 @@ void run_batched(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *ti
                            (T *)ws.qh, ws.eps, ws.thr);
     RC_LAUNCH_CHECK();
     auto filter = [&](int64_t c0, int64_t c1, int64_t nchunk, int nqb) {
-        const int64_t rt_total = (c1 - c0 + SB_TILE - 1) / SB_TILE;
-        const int64_t tpc = (rt_total + nchunk - 1) / nchunk;
-        FilterArgs fa{p.rows, ws.qh, p.ld, (int)(p.ld / 64), c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap};
-        const int nkt = (int)(p.ld / 64);
-        if (p.pages != nullptr) return launch_filter_paged<T>(p, ws, fa, nchunk, nqb, s);  // the PAGED forms (search_mfma_paged.hip)
-        if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED: the MASKED forms (cosine: fm is not read)
-            const FilterMetric fm{p.norms, ws.mcoef};
-            auto launch = [&](auto m) {
-                constexpr bool M = decltype(m)::value;
-                if (nkt == 2 || nkt == 4 || nkt == 8) {
-                    fa.tiles_per_chunk = ((c1 - c0 + QS_RT - 1) / QS_RT + nchunk - 1) / nchunk;
-                    const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
-                    if (nkt == 8) hipLaunchKernelGGL((filter_qs_masked_kernel<T, 8, M>), gr, bl, 0, s, fa, fm, p.mask);
-                    else if (nkt == 4) hipLaunchKernelGGL((filter_qs_masked_kernel<T, 4, M>), gr, bl, 0, s, fa, fm, p.mask);
-                    else hipLaunchKernelGGL((filter_qs_masked_kernel<T, 2, M>), gr, bl, 0, s, fa, fm, p.mask);
-                } else {
-                    hipLaunchKernelGGL((filter_gemm_masked_kernel<T, M>), dim3((unsigned)(nchunk * nqb)), dim3(512), 0, s, fa, fm,
-                                       p.mask);
-                }
-            };
-            if (metric) launch(std::true_type{});
-            else launch(std::false_type{});
-            return;
-        }
-        if (metric) {
-            const FilterMetric fm{p.norms, ws.mcoef};
-            if (nkt == 2 || nkt == 4 || nkt == 8) {
-                fa.tiles_per_chunk = ((c1 - c0 + QS_RT - 1) / QS_RT + nchunk - 1) / nchunk;
-                const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
-                if (nkt == 8) hipLaunchKernelGGL((filter_qs_metric_kernel<T, 8>), gr, bl, 0, s, fa, fm);
-                else if (nkt == 4) hipLaunchKernelGGL((filter_qs_metric_kernel<T, 4>), gr, bl, 0, s, fa, fm);
-                else hipLaunchKernelGGL((filter_qs_metric_kernel<T, 2>), gr, bl, 0, s, fa, fm);
-            } else {
-                hipLaunchKernelGGL(filter_gemm_metric_kernel<T>, dim3((unsigned)(nchunk * nqb)), dim3(512), 0, s, fa, fm);
-            }
-            return;
-        }
-        if (nkt == 2 || nkt == 4 || nkt == 8) {
-            fa.tiles_per_chunk = ((c1 - c0 + QS_RT - 1) / QS_RT + nchunk - 1) / nchunk;
-            const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
-            if (nkt == 8) hipLaunchKernelGGL((filter_qs_kernel<T, 8>), gr, bl, 0, s, fa);
-            else if (nkt == 4) hipLaunchKernelGGL((filter_qs_kernel<T, 4>), gr, bl, 0, s, fa);
-            else hipLaunchKernelGGL((filter_qs_kernel<T, 2>), gr, bl, 0, s, fa);
-        } else {
-            hipLaunchKernelGGL(filter_gemm_kernel<T>, dim3((unsigned)(nchunk * nqb)), dim3(512), 0, s, fa);
-        }
+        if (p.pages != nullptr) launch_filter_native<T, true>(p, ws, c0, c1, nchunk, nqb, s);  // search_mfma_paged.hip
+        else launch_filter_native<T, false>(p, ws, c0, c1, nchunk, nqb, s);
     };
     run_stages<T>(p, ws, s, timer, batch_stage_ratio(p.k, ws.cap), p.ld * (int64_t)sizeof(T), filter);
 }
@@ -1029,18 +888,17 @@ void run_batched_i8(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
     auto filter = [&](int64_t c0, int64_t c1, int64_t nchunk, int nqb) {
         const int rt = nkt == 6 ? 64 : 128;
         RC_REQUIRE(c0 % rt == 0, RC_ERR_INVALID, "internal: int8 filter range not tile-aligned");
-        const int64_t tpc = ((c1 - c0 + rt - 1) / rt + nchunk - 1) / nchunk;
-        FilterArgs fa{p.rows8, ws.qh, p.ld, nkt, c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap};
-        fa.rsx = p.rsx;
-        fa.rex = p.rex;
-        fa.sq = ws.sq;
-        fa.aq = ws.aq;
+        FilterI8Args fa{FilterArgs{p.rows8, ws.qh, p.ld, nkt, c0, c1, tiles_per_chunk(c0, c1, rt, nchunk), nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
+                        p.mask};
+        fa.a.rsx = p.rsx;
+        fa.a.rex = p.rex;
+        fa.a.sq = ws.sq;
+        fa.a.aq = ws.aq;
         const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
         if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED
-            const FilterArgsMasked fm{fa, p.mask};
-            if (nkt == 4) hipLaunchKernelGGL((filter_i8_kernel<4, 128, 0, true>), gr, bl, 0, s, fm);
-            else if (nkt == 6) hipLaunchKernelGGL((filter_i8_kernel<6, 64, 0, true>), gr, bl, 0, s, fm);
-            else hipLaunchKernelGGL((filter_i8_kernel<2, 128, 0, true>), gr, bl, 0, s, fm);
+            if (nkt == 4) hipLaunchKernelGGL((filter_i8_kernel<4, 128, 0, true>), gr, bl, 0, s, fa);
+            else if (nkt == 6) hipLaunchKernelGGL((filter_i8_kernel<6, 64, 0, true>), gr, bl, 0, s, fa);
+            else hipLaunchKernelGGL((filter_i8_kernel<2, 128, 0, true>), gr, bl, 0, s, fa);
             return;
         }
 #if defined(RC_GEMM_ABLATION)
@@ -1068,16 +926,14 @@ void launch_filter_f8(const BatchPlan &p, const BatchWs &ws, int nq_pad, int64_t
     const int rt = nkt >= 4 ? 64 : 128, qt = nkt == 6 ? 1 : QS_QT;
     const int nqb = nq_pad / (128 * qt);
     RC_REQUIRE(c0 % rt == 0, RC_ERR_INVALID, "internal: float8 filter range not tile-aligned");
-    const int64_t tpc = ((c1 - c0 + rt - 1) / rt + nchunk - 1) / nchunk;
-    FilterF8Args fa{FilterArgs{p.rows, ws.qh, p.ld, nkt, c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
-                    (const uint8_t *)ws.qh + (int64_t)nq_pad * p.ld, dump, p.nq};
+    const FilterF8Args fa{FilterArgs{p.rows, ws.qh, p.ld, nkt, c0, c1, tiles_per_chunk(c0, c1, rt, nchunk), nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
+                          (const uint8_t *)ws.qh + (int64_t)nq_pad * p.ld, dump, p.nq, p.mask};
     const dim3 gr((unsigned)(nchunk * nqb)), bl(512);
     if constexpr (!DUMP) {
         if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED
-            const FilterF8ArgsMasked fm{fa, p.mask};
-            if (nkt == 4) hipLaunchKernelGGL((filter_f8_kernel<4, 64, F8_TERMS, QS_QT, false, true>), gr, bl, 0, s, fm);
-            else if (nkt == 6) hipLaunchKernelGGL((filter_f8_kernel<6, 64, F8_TERMS, 1, false, true>), gr, bl, 0, s, fm);
-            else hipLaunchKernelGGL((filter_f8_kernel<2, 128, F8_TERMS, QS_QT, false, true>), gr, bl, 0, s, fm);
+            if (nkt == 4) hipLaunchKernelGGL((filter_f8_kernel<4, 64, F8_TERMS, QS_QT, false, true>), gr, bl, 0, s, fa);
+            else if (nkt == 6) hipLaunchKernelGGL((filter_f8_kernel<6, 64, F8_TERMS, 1, false, true>), gr, bl, 0, s, fa);
+            else hipLaunchKernelGGL((filter_f8_kernel<2, 128, F8_TERMS, QS_QT, false, true>), gr, bl, 0, s, fa);
             return;
         }
     }

@@ -376,9 +376,8 @@ void launch_filter_f32_shape(const BatchPlan &p, const BatchWs &ws, int nq_pad, 
                              hipStream_t s) {
     const int nqb = nq_pad / (128 * QT);
     RC_REQUIRE(c0 % RT == 0, RC_ERR_INVALID, "internal: float32 filter range not tile-aligned");
-    const int64_t tpc = ((c1 - c0 + RT - 1) / RT + nchunk - 1) / nchunk;
     const bool metric = p.metric != RC_METRIC_COSINE, masked = p.mask_filter;
-    const FilterF32Args fa{FilterArgs{p.rows, ws.qh, p.ld, NKS, c0, c1, tpc, nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
+    const FilterF32Args fa{FilterArgs{p.rows, ws.qh, p.ld, NKS, c0, c1, tiles_per_chunk(c0, c1, RT, nchunk), nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
                            FilterMetric{p.norms, ws.mcoef}, p.mask, dump, p.nq};
     const dim3 gr((unsigned)(nchunk * nqb)), bl(512);
     if (dump != nullptr) hipLaunchKernelGGL((filter_f32_kernel<NKS, RT, QT, false, false, true>), gr, bl, 0, s, fa);

@@ -18,13 +18,13 @@ pytestmark = pytest.mark.gpu
 
 METRICS = ["dotproduct", "euclidean"]
 DTYPES = ["float16", "bfloat16"]
-# 128 and 512: filter_qs_metric_kernel at NKT 2 and 8; 768: filter_gemm_metric_kernel (the embedder's
+# 128 and 512: filter_qs_kernel's METRIC form at NKT 2 and 8; 768: filter_gemm_kernel's (the embedder's
 # width); 100: a padded row (ld 128: the NKT 2 kernel again, over zero columns)
 DIMS = [128, 512, 768, 100]
 # (n, k, nq): a ragged last tile and one padded query block; three stages, the last shorter than a
 # chunk; two query blocks and the largest list
 SHAPES = [(20_011, 10, 9), (70_000, 100, 20), (70_000, 256, 300)]
-# ... and the remaining instantiation, filter_qs_metric_kernel at NKT 4, on the smallest shape
+# ... and the remaining instantiation, filter_qs_kernel's METRIC form at NKT 4, on the smallest shape
 EXTRA = [(256,) + SHAPES[0]]
 NQ_MAX = 300
 FIRST_STAGE = 4096

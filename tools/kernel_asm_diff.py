@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Compare the device code of two source trees, kernel by kernel.  CPU only.
+r"""Compare the device code of two source trees, kernel by kernel.  CPU only.
 
     tools/kernel_asm_diff.py A B [-D MACRO ...] [-o report.txt] [--show N] [--allow-removed NAME ...]
+                             [--rename REGEX=REPLACEMENT ...]
 
 A and B are each a source tree (a directory holding the package with build.py and csrc/) or
 a git revision of this repository, which is exported to a temporary directory.  Every
-csrc/*.hip of both is compiled to gfx950 assembly with the tree's own build.py CFLAGS
-(hipcc --cuda-device-only -S), the assembly is split per kernel symbol, and each kernel is
+csrc/*.hip of both is compiled to gfx950 assembly with the tree's own build.py CFLAGS and the
+unit's UNIT_FLAGS (hipcc --cuda-device-only -S), the assembly is split per kernel symbol, and each kernel is
 reported as identical (same instruction stream and same .amdhsa_* block), differing, only in
 A or only in B.  Exit status 0 only if every kernel of every source is identical; a kernel
 deleted on purpose is named with --allow-removed (its demangled name without template and
@@ -14,8 +15,15 @@ function arguments, e.g. rc::some_kernel: every instantiation), and then may be 
 
 The comparison is a plain text diff after dropping comments and renumbering the
 compiler's local labels (.LBB<function>_<block> and the long-branch .Lpost_getpc<n>: the
-function number and n depend on the order in which kernels are emitted, not on their code).  Refactors that must not change device
-code (moving kernels between headers, merging duplicated device helpers) are checked with
+function number and n depend on the order in which kernels are emitted, not on their code), with
+the kernel's own symbol replaced by a placeholder on both sides.
+
+Kernels pair by demangled name.  A refactor that renames a kernel or changes its signature says so
+with --rename REGEX=REPLACEMENT (repeatable; re.sub on side A's demangled names before pairing), e.g.
+    --rename 'some_metric_kernel<(\S+), (\d+)>\(.*\)=some_kernel<\1, \2, true>(rc::SomeArgs)'
+For a pair matched through a rule, .amdhsa_kernarg_size is reported and not counted as a difference
+(the signature changed on purpose); every other .amdhsa_* line still counts.  Refactors that must
+not change device code (moving kernels between headers, merging duplicated device helpers) are checked with
     tools/kernel_asm_diff.py <parent revision> .
 """
 from __future__ import annotations
@@ -54,7 +62,8 @@ def load_build(tree: str):
 
 
 def compile_asm(build, src: str, extra: list[str], out: str) -> str:
-    cmd = [build.HIPCC, *build.CFLAGS, *extra, "--cuda-device-only", "-S", src, "-o", out]
+    unit = getattr(build, "UNIT_FLAGS", {}).get(os.path.basename(src), [])  # the shipped code's flags
+    cmd = [build.HIPCC, *build.CFLAGS, *extra, *unit, "--cuda-device-only", "-S", src, "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
@@ -112,6 +121,57 @@ def demangle(names: list[str]) -> dict[str, str]:
     return dict(zip(names, out)) if r.returncode == 0 and len(out) == len(names) else {n: n for n in names}
 
 
+def parse_renames(specs: list[str]) -> list[tuple[re.Pattern, str]]:
+    rules = []
+    for spec in specs:
+        regex, sep, repl = spec.partition("=")
+        if not sep:
+            sys.exit(f"--rename {spec}: expected REGEX=REPLACEMENT")
+        rules.append((re.compile(regex), repl))
+    return rules
+
+
+KERNARG = re.compile(r"\s*\.amdhsa_kernarg_size\s+(\d+)")
+
+
+def compare_kernels(ka: dict, kb: dict, pretty_a: dict[str, str], pretty_b: dict[str, str],
+                    rules: list[tuple[re.Pattern, str]]) -> list[dict]:
+    """Pair the kernels of one source (split_kernels' dictionaries) by demangled name, side A's
+    after the rename rules, and compare each pair.  One record per name, sorted: name, status
+    (identical / differing / only in A / only in B), renamed, a, b (the two sides' (instructions,
+    .amdhsa) with the kernel's own symbol replaced; None where missing) and kernarg (sizes A, B)."""
+    def own(sym: str, k: tuple[list[str], list[str]]):
+        return tuple([ln.replace(sym, "<kernel>") for ln in part] for part in k)
+
+    side_a = {}
+    for sym in ka:
+        name, n = pretty_a[sym], 0
+        for regex, repl in rules:
+            name, m = regex.subn(repl, name)
+            n += m
+        side_a[name] = (sym, n > 0)
+    side_b = {pretty_b[sym]: sym for sym in kb}
+    out = []
+    for name in sorted(set(side_a) | set(side_b)):
+        rec = {"name": name, "renamed": False, "a": None, "b": None, "kernarg": None}
+        if name in side_a:
+            rec["a"] = own(side_a[name][0], ka[side_a[name][0]])
+            rec["renamed"] = side_a[name][1]
+            if rec["renamed"]:
+                rec["name"] = f"{name}  (A: {pretty_a[side_a[name][0]]})"
+        if name in side_b:
+            rec["b"] = own(side_b[name], kb[side_b[name]])
+        if rec["a"] is None or rec["b"] is None:
+            rec["status"] = "only in B" if rec["a"] is None else "only in A"
+        else:
+            rec["kernarg"] = tuple(next((m.group(1) for m in map(KERNARG.match, k[1]) if m), "?") for k in (rec["a"], rec["b"]))
+            if rec["renamed"]:  # (the directive can sit in either part: the stream runs to the function's end label)
+                rec["a"], rec["b"] = (tuple([ln for ln in part if not KERNARG.match(ln)] for part in k) for k in (rec["a"], rec["b"]))
+            rec["status"] = "identical" if rec["a"] == rec["b"] else "differing"
+        out.append(rec)
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("a", help="tree or git revision A")
@@ -123,8 +183,11 @@ def main() -> int:
     ap.add_argument("--keep", metavar="DIR", help="keep the assembly files (A_<source>.s, B_<source>.s) in DIR")
     ap.add_argument("--allow-removed", action="append", default=[], metavar="NAME",
                     help="a kernel that may be only in A (demangled name without template / function arguments)")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPLACEMENT",
+                    help="re.sub applied to side A's demangled kernel names before pairing (a renamed kernel, a changed signature)")
     ap.add_argument("-j", dest="jobs", type=int, default=min(8, os.cpu_count() or 4))
     args = ap.parse_args()
+    rules = parse_renames(args.rename)
     extra = ["-D" + d for d in args.defines]
 
     report: list[str] = []
@@ -159,25 +222,28 @@ def main() -> int:
                 shutil.copy(f, args.keep)
 
     say(f"kernel_asm_diff  A = {args.a}  B = {args.b}  flags: {' '.join(extra) or '(product build)'}")
+    for spec in args.rename:
+        say(f"  --rename {spec}")
     total = {"identical": 0, "differing": 0, "only in A": 0, "only in B": 0}
     removed = 0  # kernels only in A that --allow-removed names
     for name in sorted(set(srcs["A"]) | set(srcs["B"])):
         ka, kb = asm.get(("A", name), {}), asm.get(("B", name), {})
-        status = {}
-        for k in sorted(set(ka) | set(kb)):
-            status[k] = "only in B" if k not in ka else "only in A" if k not in kb else "identical" if ka[k] == kb[k] else "differing"
-        count = {s: sum(1 for v in status.values() if v == s) for s in total}
+        recs = compare_kernels(ka, kb, demangle(list(ka)), demangle(list(kb)), rules)
+        count = {s: sum(1 for r in recs if r["status"] == s) for s in total}
         for s in total:
             total[s] += count[s]
         say()
-        say(f"{name}: {len(status)} kernels: " + ", ".join(f"{count[s]} {s}" for s in total))
-        pretty = demangle(list(status))
-        for k, s in status.items():
-            allowed = s == "only in A" and re.split(r"[<(]", pretty[k])[0].split()[-1] in args.allow_removed
+        say(f"{name}: {len(recs)} kernels: " + ", ".join(f"{count[s]} {s}" for s in total))
+        for r in recs:
+            s = r["status"]
+            allowed = s == "only in A" and re.split(r"[<(]", r["name"])[0].split()[-1] in args.allow_removed
             removed += allowed
-            say(f"  {s:10s} {pretty[k]}" + ("  (allowed: --allow-removed)" if allowed else ""))
+            note = "  (allowed: --allow-removed)" if allowed else ""
+            if r["renamed"] and r["kernarg"] and r["kernarg"][0] != r["kernarg"][1]:
+                note += f"  [kernarg_size {r['kernarg'][0]} -> {r['kernarg'][1]}, not counted]"
+            say(f"  {s:10s} {r['name']}{note}")
             if s == "differing":
-                for part, x, y in (("instructions", ka[k][0], kb[k][0]), (".amdhsa", ka[k][1], kb[k][1])):
+                for part, x, y in (("instructions", r["a"][0], r["b"][0]), (".amdhsa", r["a"][1], r["b"][1])):
                     d = list(difflib.unified_diff(x, y, "A", "B", lineterm="", n=1))
                     for ln in d[:args.show]:
                         say(f"      {part}: {ln}")

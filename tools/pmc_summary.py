@@ -81,7 +81,7 @@ def main():
                 "oproj": ("gemm_w2_kernel<6, 0>", "gemm_pp_kernel<6, 0, 12>"), "fc2": ("gemm_pp_kernel<6, 0, 48>",),
                 "attention": ("attention_v2_kernel<197>",), "patch": ("patch_gemm_kernel<16, 7>",),
                 "scan_f16": ("scan_topk_kernel<f16_t, 4, 1, 128>",),
-                "filter_f16": ("filter_qs_kernel<f16_t, 8, 0>",), "filter_i8": ("filter_i8_kernel<4, 128>",)}
+                "filter_f16": ("filter_qs_kernel<f16_t, 8, 0, false, false, false>",), "filter_i8": ("filter_i8_kernel<4, 128>",)}
         latest = {}
         if "--merge" in sys.argv:  # keep the entries of kernels this run did not launch
             try:
