@@ -29,6 +29,8 @@ RC_F32, RC_F16, RC_BF16, RC_F8 = 0, 1, 2, 3
 RC_TOPK_MAX = 256
 RC_DEEP_TOPK_MAX = 10000  # largest k of the deep calls (rc_*_search_deep); the others keep RC_TOPK_MAX
 RC_DEEP_SELECT_ROWS = 2048  # stream entries a deep selection block owns at least (retrieval_core.h)
+RC_DEEP_SELECT_ROUNDS, RC_DEEP_SELECT_RADIX = 0, 1  # the deep calls' selection (rc_*_set_deep_select)
+DEEP_SELECTS = {"rounds": RC_DEEP_SELECT_ROUNDS, "radix": RC_DEEP_SELECT_RADIX}
 RC_SPARSE_MAX_NNZ = 1024  # widest sparse store and longest sparse query (retrieval_core.h)
 RC_PAGE_ROWS = 256  # local rows per shard in one page of a paged row pool (retrieval_core.h)
 RC_SEARCH_AUTO, RC_SEARCH_SCAN, RC_SEARCH_MFMA, RC_SEARCH_MFMA_MASKED = 0, 1, 2, 3
@@ -175,6 +177,8 @@ SIGNATURES = {
     "rc_index_search_pages_deep": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
     "rc_sharded_search_deep": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
     "rc_sharded_search_pages_deep": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "rc_index_set_deep_select": (C.c_int, [_vp, _i32]),
+    "rc_sharded_set_deep_select": (C.c_int, [_vp, _i32]),
     "rc_index_scores": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "rc_index_scores_pages": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp]),
     "rc_index_sparse_enable": (C.c_int, [_vp, _i32, _vp]),

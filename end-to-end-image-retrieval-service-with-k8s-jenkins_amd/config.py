@@ -43,6 +43,9 @@ class Config:
     # largest top_k a query may ask for (Index(max_top_k=...)): 256 (the default) to 10000; above
     # 256 a query runs the deep top-k search
     INDEX_MAX_TOP_K = int(os.getenv("RC_INDEX_MAX_TOP_K", "256"))
+    # the deep search's selection (Index(deep_select=...)): "rounds" (the default) or "radix" (one-shot
+    # radix select: its launches do not grow with top_k; the same results)
+    INDEX_DEEP_SELECT = os.getenv("RC_INDEX_DEEP_SELECT", "rounds")
     # index shards: RC_INDEX_DEVICES = "all" (one shard per visible GPU) or a comma list
     # of device ordinals ("0,1,2,3"); otherwise RC_INDEX_SHARDS shards on the current GPU
     INDEX_DEVICES = os.getenv("RC_INDEX_DEVICES", "")

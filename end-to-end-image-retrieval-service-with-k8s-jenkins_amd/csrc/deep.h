@@ -1,7 +1,8 @@
 // deep.h — deep top-k (rc_*_search_deep: exact results past RC_TOPK_MAX per query): what the host
 // side (index.hip, sharded.hip) and the deep translation units share.  The score pass is in
 // deep_scores.h (deep_scores_{f32,f16,bf16,f8}.hip), the bounded selection, its round chaining and
-// the emit kernel in deep_select.hip.  DESIGN.md, "Deep top-k", has the argument for exactness.
+// the emit kernel in deep_select.hip, the one-shot radix selection in deep_radix.hip.  DESIGN.md,
+// "Deep top-k", has the argument for exactness.
 #pragma once
 
 #include <algorithm>
@@ -49,17 +50,25 @@ struct DeepStream {
 };
 
 // The selection's workspace for up to nq queries in flight: the blocks' partial lists, the
-// rounds' lower bounds and (ensure's with_keys) k keys per query.  Grows, never shrinks.
+// rounds' lower bounds and (ensure's with_keys) k keys per query; for the radix selection (made by
+// its first call, ensure_radix) one histogram per query and pass, the per-query states and the
+// candidate counts — its candidate lists are the caller's k output slots.  Grows, never shrinks.
 struct DeepSel {
     int nq_cap = 0;
     int64_t keys_cap = 0;
     uint64_t *partial = nullptr;  // [DEEP_SELECT_BLOCKS][nq_cap][RC_TOPK_MAX]
     uint64_t *lower = nullptr;    // [nq_cap]
     uint64_t *keys = nullptr;     // [keys_cap]
+    int radix_cap = 0;
+    uint32_t *radix = nullptr;  // deep_radix.hip's RadixWs for radix_cap queries
     void ensure(int nq, int64_t nkeys);
+    void ensure_radix(int nq);
     void release();
 };
 constexpr int DEEP_SELECT_BLOCKS = 256;  // partial lists per query, at most
+constexpr int DEEP_RADIX_BINS = 4096;    // a digit is at most 12 bits: a block's histogram is 16 KB of LDS
+constexpr int DEEP_RADIX_PASSES = 6;     // three digits over the score word, at most three over the row
+constexpr int DEEP_RADIX_SORT_MAX = 16384;  // keys one block sorts in LDS (128 KB): RC_DEEP_TOPK_MAX padded to a power of two
 
 // queries in flight for score arrays of n entries each (the documented workspace bound)
 inline int deep_chunk_queries(int nq, int64_t n) {
@@ -70,6 +79,14 @@ inline int deep_chunk_queries(int nq, int64_t n) {
 // Enqueue every round of the selection of the k smallest keys of nq streams (nq <= ws.nq_cap) on
 // `s`: out_keys[q * k + j] = the j-th key, KEY_EMPTY past the eligible entries.  No host wait.
 void deep_select_rounds(const DeepStream &st, DeepSel &ws, int nq, int k, uint64_t *out_keys, hipStream_t s);
+// The same contract and the same keys by a radix select (deep_radix.hip): digit passes that find
+// the k-th key, one compaction into out_keys, one sort per query; the launches do not grow with k.
+void deep_select_radix(const DeepStream &st, DeepSel &ws, int nq, int k, uint64_t *out_keys, hipStream_t s);
+// The selection an index was given (rc_*_set_deep_select): RC_DEEP_SELECT_ROUNDS or RC_DEEP_SELECT_RADIX.
+inline void deep_select(int kind, const DeepStream &st, DeepSel &ws, int nq, int k, uint64_t *out_keys, hipStream_t s) {
+    if (kind == RC_DEEP_SELECT_RADIX) deep_select_radix(st, ws, nq, k, out_keys, s);
+    else deep_select_rounds(st, ws, nq, k, out_keys, s);
+}
 // keys -> (score, row) by RC_EMIT_KEY with base 0 and stride 1 (the keys carry global rows)
 void deep_emit(const uint64_t *keys, int64_t n, float *scores, int64_t *rows, hipStream_t s);
 

@@ -125,9 +125,12 @@ void DeepSel::release() {
     dfree(partial);
     dfree(lower);
     dfree(keys);
+    dfree(radix);
     partial = lower = keys = nullptr;
+    radix = nullptr;
     nq_cap = 0;
     keys_cap = 0;
+    radix_cap = 0;
 }
 
 void deep_select_rounds(const DeepStream &st, DeepSel &ws, int nq, int k, uint64_t *out_keys, hipStream_t s) {

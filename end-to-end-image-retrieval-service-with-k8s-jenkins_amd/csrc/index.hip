@@ -399,6 +399,7 @@ struct rc_index {
     float *dscores = nullptr;  // [dscores_cap]
     int64_t dscores_cap = 0;
     DeepSel dsel;
+    int deep_select = RC_DEEP_SELECT_ROUNDS;  // the selection of the deep and hybrid calls (rc_index_set_deep_select)
     // sparse-dense hybrid (rc_index_sparse_enable): the store, [width][capacity] slot-major, and the staging of
     // sparse queries and store writes
     SparseStore sparse;
@@ -711,7 +712,7 @@ void deep_score_pass(rc_index *h, const float *queries, int nq, int64_t n, const
 
 // rc_index_search_deep's body (caller holds h->mu, the device is current): the k best of rows
 // (pages: positions) [0, n) per query, in chunks of deep_chunk_queries() queries: the chunk's
-// score pass, then every selection round over its scores.  out_keys (sharded.hip: [nq][k] keys
+// score pass, then the index's selection (deep.h: the rounds or the radix select) over its scores.  out_keys (sharded.hip: [nq][k] keys
 // carrying global rows) or, when it is null, scores / out_rows through the emit kernel.
 // after (the hybrid searches; null for the deep ones): a step between a chunk's score pass and its selection.
 void deep_search_locked(rc_index *h, const float *queries, int nq, int64_t n, int k, const uint32_t *mask, const int32_t *pages,
@@ -741,7 +742,7 @@ void deep_search_locked(rc_index *h, const float *queries, int nq, int64_t n, in
         st.row_stride = h->row_stride;
         st.mask = mask;
         uint64_t *ko = out_keys != nullptr ? out_keys + (int64_t)q0 * k : h->dsel.keys;
-        deep_select_rounds(st, h->dsel, m, k, ko, s);
+        deep_select(h->deep_select, st, h->dsel, m, k, ko, s);
         if (out_keys == nullptr) deep_emit(ko, (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, s);
     }
 }
@@ -1276,6 +1277,16 @@ int rc_index_set_metric(rc_index *h, int metric) {
                    RC_ERR_UNSUPPORTED,
                    "a non-cosine metric on an index with the int8 filter copy or the float8 filter (those filters are cosine-only)");
         h->metric = metric;  // no device call: searches already enqueued took the metric they were launched with
+    });
+}
+
+int rc_index_set_deep_select(rc_index *h, int kind) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(kind == RC_DEEP_SELECT_ROUNDS || kind == RC_DEEP_SELECT_RADIX, RC_ERR_INVALID,
+                   "deep selection must be RC_DEEP_SELECT_ROUNDS or RC_DEEP_SELECT_RADIX");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->deep_select = kind;  // no device call: searches already enqueued ran the selection they were launched with
     });
 }
 

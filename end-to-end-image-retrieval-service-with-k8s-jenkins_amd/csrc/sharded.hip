@@ -138,6 +138,7 @@ struct rc_sharded {
     std::vector<uint64_t *> dk_loc;     // [dkeys_cap]
     uint64_t *dg_keys = nullptr;        // leader [n][dkeys_cap]
     DeepSel dsel;
+    int deep_select = RC_DEEP_SELECT_ROUNDS;  // the selection of the leader's merge (rc_sharded_set_deep_select)
 };
 
 namespace {
@@ -623,6 +624,17 @@ int rc_sharded_set_filter(rc_sharded *h, int kind) {
     });
 }
 
+int rc_sharded_set_deep_select(rc_sharded *h, int kind) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null index");
+        RC_REQUIRE(kind == RC_DEEP_SELECT_ROUNDS || kind == RC_DEEP_SELECT_RADIX, RC_ERR_INVALID,
+                   "deep selection must be RC_DEEP_SELECT_ROUNDS or RC_DEEP_SELECT_RADIX");
+        std::lock_guard<std::mutex> lk(h->mu);
+        for (int s = 0; s < h->n; ++s) check_status(rc_index_set_deep_select(h->shard[s], kind));  // cannot fail: the kind is valid
+        h->deep_select = kind;
+    });
+}
+
 int rc_sharded_set_metric(rc_sharded *h, int metric) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
@@ -943,7 +955,7 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
 // rc_sharded_search_deep's body (caller holds h->mu; device buffers on the leader, stream = leader
 // stream), as search_locked: the mask is a HOST bitmap over the global rows (slot >= 0: positions).
 // Each shard selects its own k keys (global rows) with no traffic per round;
-// the leader gathers the n lists and runs the same rounds over those n x k keys.  A key's order
+// the leader gathers the n lists and runs the same selection over those n x k keys.  A key's order
 // does not depend on the shard that held the row, so the result is that of one index.  A single
 // shard has no keys to gather: it writes scores / out_rows itself.
 // sq (rc_sharded_search_hybrid, checked by the caller): the sparse queries, which every shard stages on
@@ -969,7 +981,7 @@ void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_r
         st.klist = k;
         st.nq_total = nq;
         st.q0 = q0;
-        deep_select_rounds(st, h->dsel, m, k, h->dsel.keys, ls);
+        deep_select(h->deep_select, st, h->dsel, m, k, h->dsel.keys, ls);
         deep_emit(h->dsel.keys, (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, ls);
     }
     if (mask != nullptr) wait_mask(h);

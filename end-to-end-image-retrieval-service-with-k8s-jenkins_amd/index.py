@@ -72,6 +72,12 @@ def _addr(a):
     return None if a is None else a.ctypes.data
 
 
+def _deep_select_kind(kind) -> int:
+    if not isinstance(kind, str) or kind not in _lib.DEEP_SELECTS:
+        raise ValueError(f"unknown deep_select {kind!r} (expected 'rounds' or 'radix')")
+    return _lib.DEEP_SELECTS[kind]
+
+
 def _device_index(device) -> int:
     if device is None:
         return torch.cuda.current_device()
@@ -170,6 +176,13 @@ class DeviceIndex:
         if kind not in _lib.FILTERS:
             raise ValueError(f"unknown filter {kind!r} (expected one of {sorted(_lib.FILTERS)})")
         check(self.lib.rc_index_set_filter(self.handle, _lib.FILTERS[kind], stream_ptr(stream)))
+
+    def set_deep_select(self, kind: str) -> None:
+        """Selection of the deep and hybrid searches (rc_index_set_deep_select): "rounds" (the
+        default: ``ceil(k / 256)`` chained top-256 rounds) or "radix" (digit histograms over the
+        64-bit keys find the k-th key, one pass compacts, one block sorts: the launches do not
+        grow with ``k``).  Results never change: both return the same rows and score bits."""
+        check(self.lib.rc_index_set_deep_select(self.handle, _deep_select_kind(kind)))
 
     @property
     def filter(self) -> str:
@@ -752,6 +765,10 @@ class ShardSet:
             raise ValueError(f"unknown filter {kind!r} (expected one of {sorted(_lib.FILTERS)})")
         check(self.lib.rc_sharded_set_filter(self.handle, _lib.FILTERS[kind]))
 
+    def set_deep_select(self, kind: str) -> None:
+        """``DeviceIndex.set_deep_select`` on every shard and on the leader's merge."""
+        check(self.lib.rc_sharded_set_deep_select(self.handle, _deep_select_kind(kind)))
+
     @property
     def filter(self) -> str:
         return self._shards[0].filter
@@ -1165,6 +1182,9 @@ class Index:
     give: the first 256 are the ``top_k=256`` answer, scores and tie order included.  ``mode``
     is validated and otherwise ignored there.  With the default every message and exception
     is what it was.  (``sharded.ShardedIndex``, one process per GPU, has no deep search.)
+    ``deep_select`` ("rounds", the default, or "radix"; anything else raises ``ValueError``) names
+    the selection behind the deep and the hybrid searches (``DeviceIndex.set_deep_select``); it
+    never changes a result and is not saved.
 
     ``sparse_max_nnz=W`` (default 0 = off; an integer in [1, 1024]; ``metric="dotproduct"`` only,
     ``ValueError`` otherwise, as in Pinecone) makes the index sparse-dense: a record may carry
@@ -1187,13 +1207,14 @@ class Index:
     def __init__(self, name: str, dimension: int = 768, metric: str = "cosine", dtype: str = "float32",
                  capacity: int = 1 << 20, device=None, shards: int | None = None, devices=None,
                  filter: str = "native", paged_search: str = "scan", metadata_config: dict | None = None,
-                 max_top_k: int = _lib.RC_TOPK_MAX, sparse_max_nnz: int = 0):
+                 max_top_k: int = _lib.RC_TOPK_MAX, sparse_max_nnz: int = 0, deep_select: str = "rounds"):
         indexed = metacolumns.validate_config(metadata_config)
         sparse_max_nnz = sparsevalues.validate_width(sparse_max_nnz)
         if sparse_max_nnz and metric != "dotproduct":
             raise ValueError(f"sparse values need metric='dotproduct' (metric={metric!r}, sparse_max_nnz={sparse_max_nnz})")
         if isinstance(max_top_k, bool) or not isinstance(max_top_k, int) or not _lib.RC_TOPK_MAX <= max_top_k <= _lib.RC_DEEP_TOPK_MAX:
             raise ValueError(f"max_top_k must be an integer in [{_lib.RC_TOPK_MAX}, {_lib.RC_DEEP_TOPK_MAX}] (got {max_top_k!r})")
+        _deep_select_kind(deep_select)
         if paged_search not in ("scan", "mfma"):
             raise ValueError(f"unknown paged_search {paged_search!r} (expected 'scan' or 'mfma')")
         if paged_search == "mfma" and (_lib.is_f8(dtype) or dtype in ("float32", "f32") or filter in ("i8", "f8", "f32")):
@@ -1221,12 +1242,15 @@ class Index:
         self.metric = metric
         self.paged_search = paged_search
         self.max_top_k = max_top_k
+        self.deep_select = deep_select
         self.sparse_max_nnz = sparse_max_nnz
         n = len(devices)
         self._set = ShardSet(self.dimension, dtype=dtype, capacity_per_shard=max(1, -(-int(capacity) // n)),
                              devices=devices, metric=metric)
         if filter != "native":
             self._set.set_filter(filter)
+        if deep_select != "rounds":
+            self._set.set_deep_select(deep_select)
         if sparse_max_nnz:
             self._set.sparse_enable(sparse_max_nnz)
         self._sparse: dict[str, tuple[np.ndarray, np.ndarray]] = {}  # id -> sparse values (default namespace)
@@ -1450,6 +1474,8 @@ class Index:
                                   devices=list(self._set.devices), metric=self.metric)
             if self.paged_search == "mfma" and self._set.filter == "metric":  # else the pool stays native
                 self._pool.set_filter("metric")
+            if self.deep_select != "rounds":
+                self._pool.set_deep_select(self.deep_select)
             if self.sparse_max_nnz:  # the pool's own store, by pool row; it grows with the pool
                 self._pool.sparse_enable(self.sparse_max_nnz)
             self._alloc.set_capacity(per // pages.PAGE_ROWS)
@@ -2153,10 +2179,10 @@ class Index:
     @classmethod
     def load(cls, path: str, capacity: int | None = None, device=None, shards: int | None = None,
              devices=None, filter: str | None = None, paged_search: str = "scan",
-             metadata_config: dict | None = None, max_top_k: int = _lib.RC_TOPK_MAX) -> "Index":
+             metadata_config: dict | None = None, max_top_k: int = _lib.RC_TOPK_MAX, deep_select: str = "rounds") -> "Index":
         """``metadata_config=None`` means the snapshot's own (none, if it was saved without one);
         the columns and string dictionaries are rebuilt from the loaded metadata.  ``max_top_k``
-        is the loaded object's (the constructor's; a snapshot does not record it)."""
+        is the loaded object's (the constructor's; a snapshot does not record it), and so is ``deep_select``."""
         import numpy as np
 
         with open(os.path.join(path, "manifest.json")) as f:
@@ -2168,7 +2194,7 @@ class Index:
                   capacity=max(int(capacity or man.get("capacity", 0)), n, 1), device=device, shards=shards,
                   devices=devices, filter=filter or man.get("filter", "native"), paged_search=paged_search,
                   metadata_config=metadata_config if metadata_config is not None else man.get("metadata_config"),
-                  max_top_k=max_top_k, **({"sparse_max_nnz": int(man["sparse_max_nnz"])} if "sparse_max_nnz" in man else {}))
+                  max_top_k=max_top_k, deep_select=deep_select, **({"sparse_max_nnz": int(man["sparse_max_nnz"])} if "sparse_max_nnz" in man else {}))
         width = idx.sparse_max_nnz
         if idx._set.ld != man["ld"]:
             raise ValueError("snapshot row layout does not match this build")

@@ -480,6 +480,18 @@ int rc_sharded_search_pages_deep(rc_sharded *h, const float *queries, int nq, in
 int rc_index_scores(rc_index *h, const float *query, int64_t n_rows, float *out_scores, void *stream);
 int rc_index_scores_pages(rc_index *h, const float *query, int slot, int64_t n_pos, float *out_scores, void *stream);
 
+/* The selection behind every deep and hybrid call of an index (the leader's merge of a sharded
+ * one included): the rounds above (RC_DEEP_SELECT_ROUNDS, the default) or a radix select over
+ * the 64-bit keys (RC_DEEP_SELECT_RADIX: digit histograms find the k-th key, one pass compacts
+ * the keys up to it, one block per query sorts them; the number of launches does not grow with
+ * k).  Both give the same bits.  The radix selection's workspace (96 KB of histograms per query in
+ * flight) is allocated by its first call and reused.  Any other kind: RC_ERR_INVALID.
+ * rc_sharded_set_deep_select sets every shard and the leader. */
+#define RC_DEEP_SELECT_ROUNDS 0
+#define RC_DEEP_SELECT_RADIX 1
+int rc_index_set_deep_select(rc_index *h, int kind);
+int rc_sharded_set_deep_select(rc_sharded *h, int kind);
+
 /* ------------------------------------------------------------------------
  * Sparse-dense hybrid scores on a dotproduct index ("Sparse-dense
  * hybrid"): a record may carry sparse values beside its dense vector, a query a

@@ -12,6 +12,11 @@ the rounds, with [min, max].  deep and chain must return the same bits ("same_re
 printed is one JSON record; --out appends them to a file as well (default
 profiles/deep_topk/deep_topk_micro.jsonl).  One child process per (dtype, rows), each under its own
 time limit.
+
+--select compare times the two selections instead (DeviceIndex.set_deep_select): per cell, interleaved
+rounds of "rounds" and "radix" (two indexes over the same rows, one per selection) and the floor, for
+one query at k in {300, 1000, 10000} and for 16 queries at k = 1000; the two must return the same
+bits.  Its records go to profiles/deep_radix/deep_radix_micro.jsonl unless --out says otherwise.
 """
 import argparse
 import importlib
@@ -30,6 +35,8 @@ SIZES = (65536, 1048576)
 TOPK = (1000, 10000)
 LIMIT = 200  # seconds per (dtype, rows)
 DEFAULT_OUT = os.path.join(REPO, "profiles", "deep_topk", "deep_topk_micro.jsonl")
+SELECT_OUT = os.path.join(REPO, "profiles", "deep_radix", "deep_radix_micro.jsonl")
+SELECT_CELLS = ((1, 300), (1, 1000), (1, 10000), (16, 1000))  # (queries, top_k)
 
 
 def emit(rec, out):
@@ -105,21 +112,55 @@ def run_cell(dtype, n, args):
     dev.close()
 
 
+def run_cell_select(dtype, n, args):
+    import torch
+
+    M = importlib.import_module(f"{PKG}.index")
+    devs = {}
+    for kind in ("rounds", "radix"):
+        devs[kind] = M.DeviceIndex(DIM, dtype=dtype, capacity=n)
+        devs[kind].fill_random(2, 0, n)
+        devs[kind].set_deep_select(kind)
+    for nq, k in SELECT_CELLS:
+        q = torch.randn(nq, DIM, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
+        fns = {"rounds": lambda: devs["rounds"].search_deep(q, k, n), "radix": lambda: devs["radix"].search_deep(q, k, n),
+               "floor": lambda: devs["rounds"].search(q, 256, n, mode="scan")}
+        (rs, rr), (xs, xr) = fns["rounds"](), fns["radix"]()
+        torch.cuda.synchronize()
+        same = torch.equal(rs.view(torch.int32), xs.view(torch.int32)) and torch.equal(rr, xr)
+        reps = {name: args.reps for name in fns}
+        res = interleaved(fns, reps, args.rounds)
+        rec = {"part": "deep_radix", "dtype": dtype, "dim": DIM, "rows": n, "queries": nq, "top_k": k, "same_results": bool(same),
+               "rounds": args.rounds, "reps": args.reps}
+        for name, (ms, mm) in res.items():
+            rec[name + "_wall_ms"] = ms
+            rec[name + "_wall_ms_minmax"] = mm
+        rec["rounds_over_radix"] = res["rounds"][0] / res["radix"][0]
+        rec["radix_over_floor"] = res["radix"][0] / res["floor"][0]
+        rec["radix_ahead"] = res["radix"][1][1] < res["rounds"][1][0]  # its [min, max] wholly below the rounds'
+        emit(rec, args.out)
+    for dev in devs.values():
+        dev.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--out")
+    ap.add_argument("--select", choices=("rounds", "compare"), default="rounds",
+                    help="rounds: the deep search as it is against the floor and the chain; compare: rounds against radix")
     ap.add_argument("--cell", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    args.out = args.out or (SELECT_OUT if args.select == "compare" else DEFAULT_OUT)
     if args.cell:
         dtype, n = args.cell.split(":")
-        run_cell(dtype, int(n), args)
+        (run_cell_select if args.select == "compare" else run_cell)(dtype, int(n), args)
         return
     for dtype in DTYPES:
         for n in SIZES:
             cmd = [sys.executable, os.path.abspath(__file__), "--cell", f"{dtype}:{n}", "--reps", str(args.reps), "--rounds",
-                   str(args.rounds), "--out", args.out]
+                   str(args.rounds), "--out", args.out, "--select", args.select]
             subprocess.run(cmd, check=True, timeout=LIMIT)
 
 
