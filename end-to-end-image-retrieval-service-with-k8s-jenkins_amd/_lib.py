@@ -33,6 +33,12 @@ RC_DEEP_SELECT_ROUNDS, RC_DEEP_SELECT_RADIX = 0, 1  # the deep calls' selection 
 DEEP_SELECTS = {"rounds": RC_DEEP_SELECT_ROUNDS, "radix": RC_DEEP_SELECT_RADIX}
 RC_SPARSE_MAX_NNZ = 1024  # widest sparse store and longest sparse query (retrieval_core.h)
 RC_PAGE_ROWS = 256  # local rows per shard in one page of a paged row pool (retrieval_core.h)
+# where a JPEG decoder's entropy stage runs, and the device stage's split of a scan: bits per
+# subsequence (one lane), subsequences per workgroup (retrieval_core.h)
+RC_JPEG_ENTROPY_HOST = 0
+RC_JPEG_ENTROPY_DEVICE = 1
+RC_JPEG_ENTROPY_SUBSEQ_BITS = 1024
+RC_JPEG_ENTROPY_GROUP_LANES = 256
 RC_SEARCH_AUTO, RC_SEARCH_SCAN, RC_SEARCH_MFMA, RC_SEARCH_MFMA_MASKED = 0, 1, 2, 3
 SEARCH_MODES = {"auto": RC_SEARCH_AUTO, "scan": RC_SEARCH_SCAN, "mfma": RC_SEARCH_MFMA, "mfma_masked": RC_SEARCH_MFMA_MASKED}
 DTYPES = {"float32": RC_F32, "f32": RC_F32, "float16": RC_F16, "f16": RC_F16, "bfloat16": RC_BF16, "bf16": RC_BF16,
@@ -219,6 +225,11 @@ SIGNATURES = {
     "rc_jpeg_decoder_destroy": (C.c_int, [_vp]),
     "rc_jpeg_decode": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), _pi64, _vp, _pi64, _vp]),
     "rc_jpeg_decode_resized": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), _pi64, _i32, _i32, _vp, _vp]),
+    "rc_jpeg_decoder_set_entropy": (C.c_int, [_vp, _i32]),
+    "rc_jpeg_decoder_get_entropy": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "rc_jpeg_decoder_entropy_stats": (C.c_int, [_vp, _pi64, _pi64]),
+    "rc_jpeg_decoder_coefficients": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), _pi64, _vp, _vp]),
+    "rc_jpeg_decoder_upload_bytes": (C.c_int, [_vp, _pi64]),
     "rc_png_reconstruct": (C.c_int, [_i32, _i32, C.POINTER(PngImage), _vp, _i64, _vp]),
 }
 

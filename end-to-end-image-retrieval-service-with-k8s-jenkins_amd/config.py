@@ -57,6 +57,8 @@ class Config:
     MODEL_PATH = os.getenv("RC_MODEL_PATH", "")  # local checkpoint dir (config.json + weights)
     WEIGHT_SEED = int(os.getenv("RC_WEIGHT_SEED", "1907"))
     GPU_JPEG = os.getenv("RC_GPU_JPEG", "1") != "0"  # decode baseline JPEGs on the GPU (bit-exact with PIL)
+    # Huffman-decode those JPEGs on the GPU too (the embedder's decoder; DESIGN.md "JPEG entropy decode on the device")
+    GPU_HUFFMAN = os.getenv("RC_GPU_HUFFMAN", "0") != "0"
     # reconstruct PNGs on the GPU (host inflate + HIP un-filter, bit-exact with PIL); DESIGN.md "PNG decode"
     GPU_PNG = os.getenv("RC_GPU_PNG", "1") != "0"
     # ingest / retrieve services: embed in process on the GPU (1) or POST to EMBEDDING_SERVICE_URL (0)

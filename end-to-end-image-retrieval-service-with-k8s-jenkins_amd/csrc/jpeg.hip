@@ -36,6 +36,7 @@
 #include <tuple>
 #include <type_traits>
 
+#include "jpeg_host.h"
 #include "rc_common.h"
 #include "resample.h"
 
@@ -47,37 +48,7 @@ static const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 
                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
                                     58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-struct Huff {
-    bool present = false;
-    // canonical decoding: maxcode[l] (codes of length l are < maxcode[l]),
-    // valptr[l] - mincode[l] indexes vals; a 9-bit lookahead table for speed
-    int32_t maxcode[18];
-    int32_t delta[17];
-    uint8_t vals[256];
-    uint16_t look[512];  // (length << 8) | value, length 0 = not in table
-};
-
-struct Comp {
-    int id = 0, h = 1, v = 1, tq = 0, td = 0, ta = 0;
-    int bw = 0, bh = 0;  // blocks per plane (MCU padded)
-    int64_t blk0 = 0;    // first block of the plane within the image
-};
-
-struct Header {
-    int width = 0, height = 0, ncomp = 0, hmax = 1, vmax = 1, restart = 0, mcux = 0, mcuy = 0;
-    Comp c[3];
-    uint16_t qt[4][64];
-    bool qt_present[4] = {false, false, false, false};
-    Huff dc[4], ac[4];
-    const uint8_t *scan = nullptr;
-    const uint8_t *end = nullptr;
-    int scan_ncomp = 0, scan_comp[3] = {0, 0, 0};
-    bool jfif = false, adobe = false;
-    int adobe_transform = -1;
-    int64_t blocks = 0;
-    bool supported = false;
-    std::string why;
-};
+// Huff / Comp / Header: jpeg_host.h (shared with the device entropy stage)
 
 static void build_huff(Huff &t, const uint8_t *counts, const uint8_t *vals, int nvals) {
     t.present = true;
@@ -1199,6 +1170,12 @@ struct JpegDecoder {
         std::vector<int> hbounds;  // host copy of bounds (the band planner reads it)
     };
     std::map<std::tuple<int, int, int, int>, Coeffs> coeffs;
+    // entropy stage: RC_JPEG_ENTROPY_HOST (one host thread per image) or _DEVICE (jpeg_entropy.hip,
+    // its workspace made on first use); images decoded by the device stage / handed back to the host
+    int entropy = RC_JPEG_ENTROPY_HOST;
+    jpeg::EntropyWork *ent = nullptr;
+    std::atomic<int64_t> device_images{0}, host_fallbacks{0};
+    std::atomic<int64_t> upload_bytes{0};  // host-to-device bytes of the decode calls, either kind
 };
 
 }  // namespace rc
@@ -1283,6 +1260,7 @@ extern "C" int rc_jpeg_decoder_destroy(rc_jpeg_decoder *h) {
         dfree(h->d_stage);
         dfree(h->d_planes);
         dfree(h->d_tmp);
+        jpeg::entropy_destroy(h->ent);
         for (auto &kv : h->coeffs) {
             dfree(kv.second.bounds);
             dfree(kv.second.coef);
@@ -1326,11 +1304,18 @@ void stage_host(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const int
     // the pinned staging is reused: wait for the previous call's upload
     RC_HIP(hipEventSynchronize(h->staged));
     stage_layout(h, n, base[n]);
-    // Huffman decode, one image per worker
+    const bool on_device = h->entropy == RC_JPEG_ENTROPY_DEVICE;
+    if (on_device) {
+        if (!h->ent) h->ent = jpeg::entropy_create(h->max_images, h->max_blocks);
+        jpeg::entropy_begin(h->ent, n, hd.data());
+    }
+    // Huffman decode, one image per worker (device entropy: the image's scan, unstuffed and cut at
+    // its restart markers, into the same slice of the staging; upload_idct runs the kernels)
     std::vector<std::string> errs(n);
     auto work = [&](int i) {
         try {
-            jpeg::decode_coefficients(hd[i], h->h_coef + base[i] * 64);
+            if (on_device) jpeg::entropy_prepare(h->ent, i, hd[i], base[i], reinterpret_cast<uint8_t *>(h->h_coef));
+            else jpeg::decode_coefficients(hd[i], h->h_coef + base[i] * 64);
         } catch (const std::exception &e) {
             errs[i] = e.what();
         }
@@ -1383,8 +1368,42 @@ void stage_host(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const int
 
 // One H2D copy of the call's staging (descriptors, plans, tables, coefficients), the event the
 // next call waits on before it rewrites the staging, and the IDCT into h->d_planes.
-void upload_idct(rc_jpeg_decoder *h, int64_t nb, hipStream_t s) {
-    RC_HIP(hipMemcpyAsync(h->d_stage, h->h_stage, h->stage_used, hipMemcpyHostToDevice, s));
+//
+// Device entropy: the copy stops before the coefficients; the entropy kernels fill d_coef from
+// the uploaded scans and report one flag per image (this waits for the stream once).  A flagged
+// image is decoded by jpeg::decode_coefficients as it always was: that call either produces the
+// coefficients, uploaded into the image's range of d_coef, or raises the host decoder's error
+// with its message, before the IDCT and before anything reaches the caller's buffer.
+void upload_idct(rc_jpeg_decoder *h, const std::vector<jpeg::Header> &hd, int64_t nb, hipStream_t s) {
+    if (h->entropy == RC_JPEG_ENTROPY_DEVICE) {
+        const int n = (int)hd.size();
+        const size_t head = reinterpret_cast<uint8_t *>(h->h_coef) - h->h_stage;
+        RC_HIP(hipMemcpyAsync(h->d_stage, h->h_stage, head, hipMemcpyHostToDevice, s));
+        std::vector<int32_t> flags(n, 0);
+        const size_t sent = jpeg::entropy_decode(h->ent, n, nb, reinterpret_cast<const uint8_t *>(h->h_coef), h->d_coef, s,
+                                                 flags.data());
+        h->upload_bytes.fetch_add((int64_t)(head + sent));
+        int64_t base = 0;
+        for (int i = 0; i < n; base += hd[i].blocks, ++i) {
+            if (!flags[i]) {
+                h->device_images.fetch_add(1);
+                continue;
+            }
+            h->host_fallbacks.fetch_add(1);
+            try {
+                jpeg::decode_coefficients(hd[i], h->h_coef + base * 64);
+            } catch (const std::exception &e) {
+                RC_HIP(hipEventRecord(h->staged, s));
+                throw Error(RC_ERR_INVALID, "JPEG " + std::to_string(i) + ": " + e.what());
+            }
+            RC_HIP(hipMemcpyAsync(h->d_coef + base * 64, h->h_coef + base * 64, (size_t)hd[i].blocks * 128,
+                                  hipMemcpyHostToDevice, s));
+            h->upload_bytes.fetch_add(hd[i].blocks * 128);
+        }
+    } else {
+        RC_HIP(hipMemcpyAsync(h->d_stage, h->h_stage, h->stage_used, hipMemcpyHostToDevice, s));
+        h->upload_bytes.fetch_add((int64_t)h->stage_used);
+    }
     RC_HIP(hipEventRecord(h->staged, s));
     hipLaunchKernelGGL(jpeg::jpeg_idct_kernel, dim3((unsigned)((nb + 7) / 8)), dim3(64), 0, s, h->d_coef, h->d_qsel,
                        h->d_qtab, nb, h->d_planes);
@@ -1433,7 +1452,7 @@ extern "C" int rc_jpeg_decode(rc_jpeg_decoder *h, int n, const uint8_t *const *j
         int maxpix = 0;
         int64_t nb = 0;
         stage_host(h, n, jpgs, lens, rgb_offsets, hd, maxpix, nb);
-        upload_idct(h, nb, s);
+        upload_idct(h, hd, nb, s);
         hipLaunchKernelGGL(jpeg::jpeg_color_kernel, dim3((unsigned)((maxpix + 255) / 256), (unsigned)n), dim3(256), 0, s,
                            h->d_planes, h->d_desc, rgb);
         RC_LAUNCH_CHECK();
@@ -1525,7 +1544,7 @@ extern "C" int rc_jpeg_decode_resized(rc_jpeg_decoder *h, int n, const uint8_t *
                 band_lds = std::max(band_lds, need);
             }
         }
-        upload_idct(h, nb, s);  // with the plans
+        upload_idct(h, hd, nb, s);  // with the plans
         if (band_ok) {
             const dim3 gr((unsigned)maxbands, (unsigned)n);
             // horizontal taps in registers: 5 (any bicubic upscale, e.g. the fixture's 168 -> 224), 7
@@ -1557,6 +1576,59 @@ extern "C" int rc_jpeg_decode_resized(rc_jpeg_decoder *h, int n, const uint8_t *
         hipLaunchKernelGGL(jpeg::jpeg_resize_v_kernel, dim3((unsigned)((S * S + 255) / 256), (unsigned)n), dim3(256), 0, s,
                            h->d_rdesc, h->d_tmp, out);
         RC_LAUNCH_CHECK();
+    });
+}
+
+extern "C" int rc_jpeg_decoder_set_entropy(rc_jpeg_decoder *h, int kind) {
+    return guard([&] {
+        RC_REQUIRE(h, RC_ERR_INVALID, "null decoder");
+        RC_REQUIRE(kind == RC_JPEG_ENTROPY_HOST || kind == RC_JPEG_ENTROPY_DEVICE, RC_ERR_INVALID,
+                   "entropy kind must be RC_JPEG_ENTROPY_HOST (0) or RC_JPEG_ENTROPY_DEVICE (1)");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->entropy = kind;
+    });
+}
+
+extern "C" int rc_jpeg_decoder_get_entropy(rc_jpeg_decoder *h, int *kind) {
+    return guard([&] {
+        RC_REQUIRE(h && kind, RC_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        *kind = h->entropy;
+    });
+}
+
+extern "C" int rc_jpeg_decoder_entropy_stats(rc_jpeg_decoder *h, int64_t *device_images, int64_t *host_fallbacks) {
+    return guard([&] {
+        RC_REQUIRE(h && device_images && host_fallbacks, RC_ERR_INVALID, "null argument");
+        *device_images = h->device_images.load();
+        *host_fallbacks = h->host_fallbacks.load();
+    });
+}
+
+extern "C" int rc_jpeg_decoder_upload_bytes(rc_jpeg_decoder *h, int64_t *bytes) {
+    return guard([&] {
+        RC_REQUIRE(h && bytes, RC_ERR_INVALID, "null argument");
+        *bytes = h->upload_bytes.load();
+    });
+}
+
+extern "C" int rc_jpeg_decoder_coefficients(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const int64_t *lens,
+                                            int16_t *coef_out, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(h && jpgs && lens && coef_out, RC_ERR_INVALID, "null argument");
+        RC_REQUIRE(n >= 0 && n <= h->max_images, RC_ERR_INVALID, "batch exceeds the decoder's max_images");
+        if (n == 0) return;
+        std::lock_guard<std::mutex> lk(h->mu);
+        DeviceScope ds(h->device);
+        hipStream_t s = (hipStream_t)stream;
+        std::vector<jpeg::Header> hd;
+        int maxpix = 0;
+        int64_t nb = 0;
+        stage_host(h, n, jpgs, lens, nullptr, hd, maxpix, nb);
+        std::memset(h->h_rdesc, 0, (size_t)n * sizeof(jpeg::RDesc));
+        upload_idct(h, hd, nb, s);
+        RC_HIP(hipMemcpyAsync(coef_out, h->d_coef, (size_t)nb * 128, hipMemcpyDeviceToHost, s));
+        RC_HIP(hipStreamSynchronize(s));
     });
 }
 

@@ -55,7 +55,15 @@ def decode_coefficients(data: bytes):
 class JpegDecoder:
     """Batched GPU JPEG decoder with a fixed workspace (max_images, max_pixels)."""
 
-    def __init__(self, device=None, max_images: int = 256, max_pixels: int = 1 << 22):
+    ENTROPY = {"host": 0, "device": 1}  # RC_JPEG_ENTROPY_HOST / _DEVICE
+
+    def __init__(self, device=None, max_images: int = 256, max_pixels: int = 1 << 22, entropy: str = "host"):
+        """``entropy``: where the Huffman stage runs, ``"host"`` (one thread per image, the
+        coefficients uploaded) or ``"device"`` (the scan uploaded and decoded by the entropy
+        kernels; a stream they do not accept is decoded on the host within the call)."""
+        if entropy not in self.ENTROPY:
+            raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+        self.entropy = entropy
         self.lib = load()
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else
                                    (device.index if isinstance(device, torch.device) else int(device)))
@@ -66,6 +74,43 @@ class JpegDecoder:
         h = C.c_void_p()
         check(self.lib.rc_jpeg_decoder_create(self.device.index, self.max_images, self.max_blocks, C.byref(h)))
         self._h = h
+        if entropy != "host":
+            check(self.lib.rc_jpeg_decoder_set_entropy(self._h, self.ENTROPY[entropy]))
+
+    def entropy_stats(self) -> dict:
+        """Images the device entropy stage decoded / handed to the host stage, since creation."""
+        dev, host = C.c_int64(), C.c_int64()
+        check(self.lib.rc_jpeg_decoder_entropy_stats(self._h, C.byref(dev), C.byref(host)))
+        return {"device_images": dev.value, "host_fallbacks": host.value}
+
+    def upload_bytes(self) -> int:
+        """Bytes the decoder's calls copied host to device since creation (either entropy kind)."""
+        b = C.c_int64()
+        check(self.lib.rc_jpeg_decoder_upload_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def coefficients(self, datas: Sequence[bytes], stream=None) -> list:
+        """Test hook: the quantised coefficients the decoder's entropy stage leaves on the device,
+        one int16 [blocks, 64] array per image (what ``decode_coefficients`` gives on the host)."""
+        import numpy as np
+
+        infos = [probe(d) for d in datas]
+        for i, inf in enumerate(infos):
+            if not inf.supported:
+                raise JpegUnsupported(f"image {i}: JPEG stream outside the GPU decoder's scope")
+        outs = []
+        for s in range(0, len(datas), self.max_images):
+            chunk, cinf = datas[s:s + self.max_images], infos[s:s + self.max_images]
+            n = len(chunk)
+            coef = np.zeros((sum(inf.blocks for inf in cinf), 64), dtype=np.int16)
+            ptrs = (C.c_char_p * n)(*chunk)
+            lens = (C.c_int64 * n)(*[len(d) for d in chunk])
+            check(self.lib.rc_jpeg_decoder_coefficients(self._h, n, ptrs, lens, coef.ctypes.data, stream_ptr(stream)))
+            b = 0
+            for inf in cinf:
+                outs.append(coef[b:b + inf.blocks])
+                b += inf.blocks
+        return outs
 
     def close(self) -> None:
         if getattr(self, "_h", None):

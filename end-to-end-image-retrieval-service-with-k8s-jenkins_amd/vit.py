@@ -286,10 +286,12 @@ class VitMsnEmbedder:
         return raw.cpu().tolist()
 
     def _decoder(self):
+        from .config import Config
         from .jpeg import JpegDecoder
 
         if self._jpeg is None:
-            self._jpeg = JpegDecoder(self.device, max_images=max(self.max_batch, 32), max_pixels=1 << 24)
+            self._jpeg = JpegDecoder(self.device, max_images=max(self.max_batch, 32), max_pixels=1 << 24,
+                                     entropy="device" if Config.GPU_HUFFMAN else "host")
         return self._jpeg
 
     def decode_jpeg(self, datas: Sequence[bytes]) -> list[torch.Tensor]:

@@ -802,6 +802,34 @@ int rc_jpeg_decode(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const 
 int rc_jpeg_decode_resized(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const int64_t *lens, int out_size,
                            int resample, uint8_t *out, void *stream);
 
+/* Where a decoder's entropy (Huffman) stage runs.  HOST, the default of a new decoder: one
+ * host thread per image, the coefficients uploaded.  DEVICE: the scan itself is uploaded and
+ * decoded by self-synchronising subsequence decoders (DESIGN.md "JPEG entropy decode on the
+ * device"): a scan is cut into subsequences of RC_JPEG_ENTROPY_SUBSEQ_BITS bits, one GPU lane
+ * each, RC_JPEG_ENTROPY_GROUP_LANES of them to a workgroup.  The coefficients are the host
+ * stage's bit for bit; a stream the device stage does not take or does not accept (anything
+ * the host decoder would refuse, among others) is decoded by the host stage within the same
+ * call, with that stage's result or error. */
+#define RC_JPEG_ENTROPY_HOST 0
+#define RC_JPEG_ENTROPY_DEVICE 1
+#define RC_JPEG_ENTROPY_SUBSEQ_BITS 1024
+#define RC_JPEG_ENTROPY_GROUP_LANES 256
+/* RC_ERR_INVALID for a null handle or an unknown kind, before any device call. */
+int rc_jpeg_decoder_set_entropy(rc_jpeg_decoder *h, int kind);
+int rc_jpeg_decoder_get_entropy(rc_jpeg_decoder *h, int *kind);
+/* Counters since creation, of calls with the DEVICE kind: images whose coefficients the
+ * device stage produced, and images handed to the host stage instead. */
+int rc_jpeg_decoder_entropy_stats(rc_jpeg_decoder *h, int64_t *device_images, int64_t *host_fallbacks);
+/* Bytes the decoder's calls copied host to device since creation, either kind: descriptors,
+ * plans and tables, and the coefficients (HOST) or the scans (DEVICE, with the coefficients of
+ * the images that fell back). */
+int rc_jpeg_decoder_upload_bytes(rc_jpeg_decoder *h, int64_t *bytes);
+/* Test hook: the decoder's staging with its current entropy kind, and the quantised
+ * coefficients it leaves on the device copied to the host buffer coef_out ([blocks][64] int16,
+ * the images back to back, each as rc_jpeg_decode_coefficients gives it). */
+int rc_jpeg_decoder_coefficients(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const int64_t *lens,
+                                 int16_t *coef_out, void *stream);
+
 /* ------------------------------------------------------------------------
  * PNG reconstruction.  The host parses the chunks and inflates IDAT (png.py);
  * this call un-filters the scanlines (None / Sub / Up / Average / Paeth) and
