@@ -39,6 +39,11 @@ RC_JPEG_ENTROPY_HOST = 0
 RC_JPEG_ENTROPY_DEVICE = 1
 RC_JPEG_ENTROPY_SUBSEQ_BITS = 1024
 RC_JPEG_ENTROPY_GROUP_LANES = 256
+# the device inflate's split of a deflate block (bits per lane, lanes per workgroup) and the longest
+# zlib stream it takes (retrieval_core.h)
+RC_PNG_INFLATE_ROW_BITS = 128
+RC_PNG_INFLATE_LANES = 256
+RC_PNG_INFLATE_MAX_BYTES = 1 << 26
 RC_SEARCH_AUTO, RC_SEARCH_SCAN, RC_SEARCH_MFMA, RC_SEARCH_MFMA_MASKED = 0, 1, 2, 3
 SEARCH_MODES = {"auto": RC_SEARCH_AUTO, "scan": RC_SEARCH_SCAN, "mfma": RC_SEARCH_MFMA, "mfma_masked": RC_SEARCH_MFMA_MASKED}
 DTYPES = {"float32": RC_F32, "f32": RC_F32, "float16": RC_F16, "f16": RC_F16, "bfloat16": RC_BF16, "bf16": RC_BF16,
@@ -115,6 +120,21 @@ class PngImage(C.Structure):
         ("reserved", C.c_int32),
         ("scanlines", C.c_char_p),
         ("scan_bytes", C.c_int64),
+        ("palette", C.c_char_p),
+        ("out_offset", C.c_int64),
+    ]
+
+
+class PngStream(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("depth", C.c_int32),
+        ("color", C.c_int32),
+        ("palette_entries", C.c_int32),
+        ("reserved", C.c_int32),
+        ("idat", C.c_char_p),
+        ("idat_bytes", C.c_int64),
         ("palette", C.c_char_p),
         ("out_offset", C.c_int64),
     ]
@@ -231,6 +251,9 @@ SIGNATURES = {
     "rc_jpeg_decoder_coefficients": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), _pi64, _vp, _vp]),
     "rc_jpeg_decoder_upload_bytes": (C.c_int, [_vp, _pi64]),
     "rc_png_reconstruct": (C.c_int, [_i32, _i32, C.POINTER(PngImage), _vp, _i64, _vp]),
+    "rc_png_decode": (C.c_int, [_i32, _i32, C.POINTER(PngStream), _vp, _i64, C.POINTER(C.c_int32), _vp]),
+    "rc_png_decode_stats": (C.c_int, [_i32, _pi64, _pi64]),
+    "rc_png_decode_timing": (C.c_int, [_i32, _i32, _pd, _pi64]),
 }
 
 # diagnostic builds only (tools/build_diag.sh, loaded with RC_LIB_PATH): bound when present,

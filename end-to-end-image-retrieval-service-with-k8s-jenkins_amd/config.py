@@ -61,6 +61,8 @@ class Config:
     GPU_HUFFMAN = os.getenv("RC_GPU_HUFFMAN", "0") != "0"
     # reconstruct PNGs on the GPU (host inflate + HIP un-filter, bit-exact with PIL); DESIGN.md "PNG decode"
     GPU_PNG = os.getenv("RC_GPU_PNG", "1") != "0"
+    # inflate those PNGs on the GPU too (the embedder's decoder; DESIGN.md "PNG inflate on the device")
+    GPU_INFLATE = os.getenv("RC_GPU_INFLATE", "0") != "0"
     # ingest / retrieve services: embed in process on the GPU (1) or POST to EMBEDDING_SERVICE_URL (0)
     EMBED_IN_PROCESS = os.getenv("RC_EMBED_IN_PROCESS", "1") != "0"
 

@@ -46,7 +46,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "rc_common.h"
+#include "png_host.h"
 
 namespace rc {
 namespace png {
@@ -55,21 +55,6 @@ constexpr int kNW = 2;            // waves (bands in flight) per block
 constexpr int kT = 64;            // steps per phase = units per tile row
 constexpr int kPitch = kT + 1;    // tile row pitch in dwords (odd: conflict-free transposed access)
 constexpr int kLag = 2;           // phases wave w runs behind wave w-1 (kLag * kT >= kT + 63)
-constexpr int kMaxUnits = 3072;   // widest row in filter units (carry row in LDS)
-constexpr int64_t kMaxPixels = 1 << 24;          // largest image (png.py MAX_PIXELS)
-constexpr size_t kMaxStageBytes = 512u << 20;    // the staging of one call, so how far it grows
-
-struct Desc {
-    int64_t in_off;   // filtered scanlines in the staging block
-    int64_t out_off;  // HWC RGB output, bytes from the output base
-    int32_t width, height;
-    int32_t stride;  // data bytes per scanline (without the filter byte)
-    int32_t bpp;     // filter unit, bytes
-    int32_t depth;   // bits per sample
-    int32_t color;   // PNG colour type 0, 2, 3, 4, 6
-    int32_t pal_off; // palette (256 packed 0x00BBGGRR entries) in the palette table, or -1
-    int32_t pad;
-};
 
 typedef short short2_t __attribute__((ext_vector_type(2)));
 
@@ -230,8 +215,6 @@ static Workspace &workspace(int device) {
     return ws[device];
 }
 
-static int channels_of(int color) { return color == 2 ? 3 : color == 4 ? 2 : color == 6 ? 4 : 1; }
-
 // Everything the kernel's bounds rest on, checked on the host before any device call.
 static void validate(int n, const rc_png_image *im, const uint8_t *rgb, int64_t rgb_bytes) {
     RC_REQUIRE(n >= 1 && n <= 65535, RC_ERR_INVALID, "image count must be 1..65535");
@@ -239,27 +222,19 @@ static void validate(int n, const rc_png_image *im, const uint8_t *rgb, int64_t 
     for (int i = 0; i < n; ++i) {
         const rc_png_image &p = im[i];
         const std::string id = "image " + std::to_string(i) + ": ";
-        RC_REQUIRE(p.width >= 1 && p.height >= 1 && p.width <= kMaxPixels && p.height <= kMaxPixels, RC_ERR_INVALID,
-                   id + "bad size");
-        RC_REQUIRE((int64_t)p.width * p.height <= kMaxPixels, RC_ERR_UNSUPPORTED, id + "more than 2^24 pixels");
-        const bool sub8 = p.depth == 1 || p.depth == 2 || p.depth == 4;
-        const bool ok = (p.color == 0 || p.color == 3) ? (sub8 || p.depth == 8)
-                                                       : ((p.color == 2 || p.color == 4 || p.color == 6) && p.depth == 8);
-        RC_REQUIRE(ok, p.depth == 16 ? RC_ERR_UNSUPPORTED : RC_ERR_INVALID, id + "colour type / bit depth not handled");
-        const int64_t bits = (int64_t)p.depth * channels_of(p.color);
-        const int64_t stride = ((int64_t)p.width * bits + 7) / 8;
-        const int bpp = (int)std::max<int64_t>(1, bits / 8);
-        RC_REQUIRE(stride / bpp <= kMaxUnits, RC_ERR_UNSUPPORTED, id + "row wider than the carry row in LDS");
+        const int64_t stride = check_header(p, id);
         RC_REQUIRE(p.scanlines && p.scan_bytes == (int64_t)p.height * (1 + stride), RC_ERR_INVALID,
                    id + "scanline bytes are not height * (1 + stride)");
         for (int64_t r = 0; r < p.height; ++r)
             RC_REQUIRE(p.scanlines[r * (1 + stride)] <= 4, RC_ERR_INVALID, id + "filter byte above 4");
-        if (p.color == 3)
-            RC_REQUIRE(p.palette && p.palette_entries >= 1 && p.palette_entries <= 256, RC_ERR_INVALID,
-                       id + "indexed image without a palette of 1..256 entries");
-        RC_REQUIRE(p.out_offset >= 0 && p.out_offset + (int64_t)p.width * p.height * 3 <= rgb_bytes, RC_ERR_INVALID,
-                   id + "output range outside the buffer");
+        check_palette_and_output(p, id, rgb_bytes);
     }
+}
+
+void launch_reconstruct(const uint8_t *stage, const Desc *descs, const uint32_t *palettes, uint8_t *out, int n,
+                        hipStream_t s) {
+    png_reconstruct_kernel<<<n, 64 * kNW, 0, s>>>(stage, descs, palettes, out);
+    RC_LAUNCH_CHECK();
 }
 
 }  // namespace png
@@ -305,24 +280,7 @@ extern "C" int rc_png_reconstruct(int device, int n, const rc_png_image *images,
         int ipal = 0;
         for (int i = 0; i < n; ++i) {
             const rc_png_image &p = images[i];
-            const int64_t bits = (int64_t)p.depth * png::channels_of(p.color);
-            png::Desc &d = desc[i];
-            d.in_off = (int64_t)at;
-            d.out_off = p.out_offset;
-            d.width = p.width, d.height = p.height;
-            d.stride = (int32_t)(((int64_t)p.width * bits + 7) / 8);
-            d.bpp = (int32_t)std::max<int64_t>(1, bits / 8);
-            d.depth = p.depth, d.color = p.color;
-            d.pal_off = -1, d.pad = 0;
-            if (p.color == 3) {  // entries past PLTE are black, as Pillow's palette has them
-                d.pal_off = ipal * 256;
-                uint32_t *q = pal + d.pal_off;
-                for (int e = 0; e < 256; ++e)
-                    q[e] = e < p.palette_entries ? (uint32_t)p.palette[3 * e] | (uint32_t)p.palette[3 * e + 1] << 8 |
-                                                       (uint32_t)p.palette[3 * e + 2] << 16
-                                                 : 0u;
-                ++ipal;
-            }
+            png::fill_desc(desc[i], p, (int64_t)at, pal, ipal);
             std::memcpy(ws.h_stage + at, p.scanlines, (size_t)p.scan_bytes);
             at += al((size_t)p.scan_bytes);
         }
@@ -330,9 +288,8 @@ extern "C" int rc_png_reconstruct(int device, int n, const rc_png_image *images,
         RC_HIP(hipStreamWaitEvent(s, ws.done, 0));
         RC_HIP(hipMemcpyAsync(ws.d_stage, ws.h_stage, total, hipMemcpyHostToDevice, s));
         RC_HIP(hipEventRecord(ws.staged, s));
-        png::png_reconstruct_kernel<<<n, 64 * png::kNW, 0, s>>>(ws.d_stage, reinterpret_cast<png::Desc *>(ws.d_stage),
-                                                               reinterpret_cast<uint32_t *>(ws.d_stage + o_pal), rgb);
-        RC_LAUNCH_CHECK();
+        png::launch_reconstruct(ws.d_stage, reinterpret_cast<png::Desc *>(ws.d_stage),
+                                reinterpret_cast<uint32_t *>(ws.d_stage + o_pal), rgb, n, s);
         RC_HIP(hipEventRecord(ws.done, s));
     });
 }

@@ -133,7 +133,8 @@ def decode_many(blobs: List[bytes]) -> list:
     if png:  # the host half first: a PNG that fails it is one more host image, on its own
         from ..png import stage
 
-        results = stage([blobs[i] for i in png], tolerant=True)
+        # RC_GPU_INFLATE: the compressed streams are handed over and inflated by the device
+        results = stage([blobs[i] for i in png], tolerant=True, inflate="device" if Config.GPU_INFLATE else "host")
         keep = [k for k, r in enumerate(results) if not isinstance(r, ValueError)]
         png, staged = [png[k] for k in keep], [results[k] for k in keep]
     gset = set(gpu) | set(png)
@@ -150,8 +151,9 @@ def decode_many(blobs: List[bytes]) -> list:
                 out[i] = np.asarray(decode_image(blobs[i]), dtype=np.uint8)
     if png:
         try:
-            for i, im in zip(png, get_embedder().reconstruct_png(staged)):  # per member GPU on a pool
-                out[i] = im
+            for i, im in zip(png, get_embedder().reconstruct_png(staged, tolerant=True)):  # per member GPU on a pool
+                # a stream the device and then the host inflate refused: one more host image
+                out[i] = np.asarray(decode_image(blobs[i]), dtype=np.uint8) if isinstance(im, ValueError) else im
         except ValueError:  # the library refused the launch (its staging cap): valid images, host decode
             for i in png:
                 out[i] = np.asarray(decode_image(blobs[i]), dtype=np.uint8)

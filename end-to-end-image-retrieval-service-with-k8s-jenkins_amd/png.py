@@ -5,6 +5,9 @@
 path handles it); ``PngDecoder.decode(list_of_bytes)`` parses the chunks and inflates
 IDAT on the host (``zlib`` in a small thread pool: it releases the GIL) and un-filters
 and expands to HWC RGB u8 on the GPU (``rc_png_reconstruct``, one launch per batch),
+or, with ``inflate="device"``, hands the compressed bytes to ``rc_png_decode``, whose
+kernels inflate them into device memory (an image they refuse is inflated on the host,
+with the host kind's result or error); either way
 bit-exact with ``Image.open(...).convert("RGB")``: ``tRNS``, ``gAMA`` and ``iCCP`` are
 ignored and alpha is dropped, as ``convert("RGB")`` does.  Streams the GPU path does not
 handle (Adam7, 16-bit samples, APNG, rows wider than the kernel's carry row) are reported
@@ -29,6 +32,10 @@ MAX_UNITS = 3072  # widest row in filter units (csrc/png.hip: the carry row in L
 # bounds what one image may inflate to (4 bytes a pixel) and the library's staging.
 MAX_PIXELS = 1 << 24
 INFLATE_THREADS = 16
+# Longest zlib stream the device inflate takes (RC_PNG_INFLATE_MAX_BYTES: its bit positions are
+# int32); a longer one is inflated on the host.  No image of MAX_PIXELS pixels comes near it.
+INFLATE_MAX_BYTES = 1 << 26
+INFLATES = ("host", "device")
 
 
 class PngUnsupported(ValueError):
@@ -106,9 +113,19 @@ def is_gpu_decodable(data: bytes) -> bool:
         return False
 
 
-def parse(data: bytes):
+class PngStream(NamedTuple):
+    """An image whose IDAT is still compressed: what ``parse(data, inflate="device")`` returns."""
+    info: PngInfo
+    idat: bytes
+    palette: "bytes | None"
+
+
+def parse(data: bytes, inflate: str = "host"):
     """Full host stage of one image: (info, filtered scanlines, palette bytes or None).
-    Every check the kernel's bounds rest on happens here; anything wrong is a ValueError."""
+    Every check the kernel's bounds rest on happens here; anything wrong is a ValueError.
+    ``inflate="device"``: everything but the inflate (chunk walk, every CRC, the IHDR / PLTE
+    rules, the two zlib header bytes) and a ``PngStream`` (info, joined IDAT bytes, palette); a
+    stream above INFLATE_MAX_BYTES is inflated here as for "host"."""
     info, palette, idat, seen_idat, closed = None, None, [], False, False
     for kind, body in _chunks(data, verify=True):
         if info is None:
@@ -136,10 +153,22 @@ def parse(data: bytes):
         raise PngUnsupported("PNG stream outside the GPU decoder's scope (interlaced, 16-bit, too wide or too large)")
     if info.color == 3 and palette is None:
         raise ValueError("indexed PNG without PLTE")
+    palette = palette if info.color == 3 else None
+    idat = idat[0] if len(idat) == 1 else b"".join(idat)
+    if inflate == "device" and len(idat) <= INFLATE_MAX_BYTES:
+        # CM = 8 (deflate), CINFO <= 7 (32 KiB window), FCHECK, FDICT = 0: what zlib checks first
+        if len(idat) < 6 or idat[0] & 15 != 8 or idat[0] >> 4 > 7 or (idat[0] << 8 | idat[1]) % 31 or idat[1] & 32:
+            raise ValueError("PNG IDAT does not inflate: bad zlib header")
+        return PngStream(info, idat, palette)
+    return info, inflate_idat(info, idat), palette
+
+
+def inflate_idat(info: PngInfo, idat: bytes) -> bytes:
+    """The host inflate of one image's joined IDAT bytes, with its checks: the filtered scanlines."""
     want = info.height * (1 + stride_of(info.width, info.depth, info.color))
     z = zlib.decompressobj()
     try:
-        raw = z.decompress(b"".join(idat), want + 1)  # one byte over: an over-long stream is seen, not inflated
+        raw = z.decompress(idat, want + 1)  # one byte over: an over-long stream is seen, not inflated
     except zlib.error as e:
         raise ValueError(f"PNG IDAT does not inflate: {e}") from None
     if len(raw) != want or not z.eof:
@@ -148,7 +177,7 @@ def parse(data: bytes):
     if worst > 4:
         raise ValueError(f"PNG filter byte {worst} (0..4 exist)")
     # an index past PLTE is not an error for Pillow (it reads black), so it is none here either
-    return info, raw, palette if info.color == 3 else None
+    return raw
 
 
 _pool = None
@@ -163,12 +192,12 @@ def _inflate_pool() -> cf.ThreadPoolExecutor:
         return _pool
 
 
-def stage(datas: Sequence[bytes], tolerant: bool = False) -> list:
+def stage(datas: Sequence[bytes], tolerant: bool = False, inflate: str = "host") -> list:
     """parse() of every image, inflating in the thread pool (one image: in the caller).  No device
     work.  ``tolerant``: an image that fails holds its ValueError in the list instead of raising."""
     def one(data):
         try:
-            return parse(data)
+            return parse(data, inflate)
         except ValueError as e:
             if not tolerant:
                 raise
@@ -182,11 +211,14 @@ class PngDecoder:
     (a single image is at most MAX_PIXELS, whatever ``max_pixels`` says).  The library's staging
     grows with the largest launch, up to its own cap, and is reused."""
 
-    def __init__(self, device=None, max_images: int = 256, max_pixels: int = 1 << 26):
+    def __init__(self, device=None, max_images: int = 256, max_pixels: int = 1 << 26, inflate: str = "host"):
         import torch
 
         from ._lib import load
 
+        if inflate not in INFLATES:
+            raise ValueError(f"inflate must be one of {INFLATES}, not {inflate!r}")
+        self.inflate = inflate
         self.lib = load()
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else
                                    (device.index if isinstance(device, torch.device) else int(device)))
@@ -199,13 +231,27 @@ class PngDecoder:
 
     def decode(self, datas: Sequence[bytes], stream=None) -> list:
         """PNG byte strings -> device u8 HWC RGB tensors (views into one buffer per chunk), input order."""
-        return self.reconstruct(self.host_stage(datas), stream=stream)
+        return self.reconstruct(stage(datas, inflate=self.inflate), stream=stream)
 
-    def reconstruct(self, staged: Sequence, stream=None) -> list:
-        """The device stage: host_stage()'s results -> device images (one launch per chunk)."""
+    def _call(self, fn, *args):
+        from ._lib import RC_ERR_UNSUPPORTED, check
+
+        status = fn(*args)
+        if status == RC_ERR_UNSUPPORTED:
+            raise PngUnsupported(self.lib.rc_last_error().decode())
+        check(status)
+
+    def reconstruct(self, staged: Sequence, stream=None, tolerant: bool = False) -> list:
+        """The device stage: host_stage()'s results -> device images.  Per chunk, the PngStream
+        entries go through rc_png_decode (device inflate + reconstruction) and the inflated ones,
+        with the streams the device flagged and the host then inflated, through one
+        rc_png_reconstruct.  ``tolerant``: a flagged stream the host refuses too holds its
+        ValueError in the list instead of raising."""
+        import ctypes
+
         import torch
 
-        from ._lib import PngImage, RC_ERR_UNSUPPORTED, check, stream_ptr
+        from ._lib import PngImage, PngStream as CStream, stream_ptr
 
         pixels = [info.width * info.height for info, _, _ in staged]
         if pixels and max(pixels) > min(self.max_pixels, MAX_PIXELS):
@@ -217,24 +263,50 @@ class PngDecoder:
             while e < len(staged) and e - s < self.max_images and px + pixels[e] <= self.max_pixels:
                 px += pixels[e]
                 e += 1
-            chunk = staged[s:e]
-            images = (PngImage * len(chunk))()
-            off = 0
-            for im, (info, raw, palette) in zip(images, chunk):
-                im.width, im.height, im.depth, im.color = info.width, info.height, info.depth, info.color
-                im.palette_entries = len(palette) // 3 if palette else 0
-                im.scanlines, im.scan_bytes, im.palette, im.out_offset = raw, len(raw), palette, off
+            chunk = list(staged[s:e])
+            offs, off = [], 0
+            for info, _, _ in chunk:
+                offs.append(off)
                 off += (info.width * info.height * 3 + 255) & ~255  # every image 256-byte aligned
             buf = torch.empty(off, dtype=torch.uint8, device=self.device)
-            status = self.lib.rc_png_reconstruct(self.device.index, len(chunk), images, buf.data_ptr(), off,
-                                                 stream_ptr(stream or torch.cuda.current_stream(self.device)))
-            if status == RC_ERR_UNSUPPORTED:
-                raise PngUnsupported(self.lib.rc_last_error().decode())
-            check(status)
-            for im, (info, _, _) in zip(images, chunk):
-                outs.append(buf[im.out_offset:im.out_offset + info.width * info.height * 3].view(info.height, info.width, 3))
+            sp = stream_ptr(stream or torch.cuda.current_stream(self.device))
+
+            def fill(rec, k, data_field, size_field):
+                info, body, palette = chunk[k]
+                rec.width, rec.height, rec.depth, rec.color = info.width, info.height, info.depth, info.color
+                rec.palette_entries = len(palette) // 3 if palette else 0
+                rec.palette, rec.out_offset = palette, offs[k]
+                setattr(rec, data_field, body)
+                setattr(rec, size_field, len(body))
+
+            failed = {}
+            dev = [k for k, item in enumerate(chunk) if isinstance(item, PngStream)]
+            if dev:
+                streams, flags = (CStream * len(dev))(), (ctypes.c_int32 * len(dev))()
+                for rec, k in zip(streams, dev):
+                    fill(rec, k, "idat", "idat_bytes")
+                self._call(self.lib.rc_png_decode, self.device.index, len(dev), streams, buf.data_ptr(), off, flags, sp)
+                for k, flagged in zip(dev, flags):
+                    if flagged:  # the host inflates it, with the host kind's result or error
+                        info, idat, palette = chunk[k]
+                        try:
+                            chunk[k] = (info, inflate_idat(info, idat), palette)
+                        except ValueError as err:
+                            if not tolerant:
+                                raise
+                            failed[k] = err
+            host = [k for k, item in enumerate(chunk) if not isinstance(item, PngStream)]
+            if host:
+                images = (PngImage * len(host))()
+                for rec, k in zip(images, host):
+                    fill(rec, k, "scanlines", "scan_bytes")
+                self._call(self.lib.rc_png_reconstruct, self.device.index, len(host), images, buf.data_ptr(), off, sp)
+            for k, (info, _, _) in enumerate(chunk):
+                outs.append(failed.get(k, None) or
+                            buf[offs[k]:offs[k] + info.width * info.height * 3].view(info.height, info.width, 3))
             s = e
         return outs
 
 
-__all__ = ["PngDecoder", "PngInfo", "PngUnsupported", "probe", "is_gpu_decodable", "parse", "stage"]
+__all__ = ["PngDecoder", "PngInfo", "PngStream", "PngUnsupported", "probe", "is_gpu_decodable", "parse", "inflate_idat",
+           "stage"]

@@ -312,15 +312,21 @@ class VitMsnEmbedder:
         resizes host arrays.  Raises png.PngUnsupported / ValueError."""
         from .png import stage
 
-        return self.reconstruct_png(stage(datas))
+        return self.reconstruct_png(stage(datas, inflate=self._png_decoder().inflate))
 
-    def reconstruct_png(self, staged: Sequence) -> list[torch.Tensor]:
-        """The device half of ``decode_png``: ``png.stage`` results → device images."""
+    def _png_decoder(self):
+        from .config import Config
         from .png import PngDecoder
 
-        if self._png is None:
-            self._png = PngDecoder(self.device, max_images=max(self.max_batch, 64))
-        return self._png.reconstruct(staged)
+        if self._png is None:  # Config.GPU_INFLATE: the compressed bytes go up and HIP kernels inflate them
+            self._png = PngDecoder(self.device, max_images=max(self.max_batch, 64),
+                                   inflate="device" if Config.GPU_INFLATE else "host")
+        return self._png
+
+    def reconstruct_png(self, staged: Sequence, tolerant: bool = False) -> list[torch.Tensor]:
+        """The device half of ``decode_png``: ``png.stage`` results (of either inflate kind) →
+        device images.  ``tolerant``: see ``PngDecoder.reconstruct``."""
+        return self._png_decoder().reconstruct(staged, tolerant=tolerant)
 
     def embed_jpeg(self, datas: Sequence[bytes]) -> list[list[float]]:
         """Baseline-JPEG byte strings → raw CLS vectors, decoded (and resized) on the GPU and
@@ -571,9 +577,10 @@ class EmbedderPool:
         decoding its share on its own GPU as in ``decode_jpeg_for_embed``."""
         return self._decode_per_member(datas, assign, lambda m, part: m.decode_png(part))
 
-    def reconstruct_png(self, staged: Sequence, assign: Sequence[int] | None = None) -> list[torch.Tensor]:
+    def reconstruct_png(self, staged: Sequence, assign: Sequence[int] | None = None,
+                        tolerant: bool = False) -> list[torch.Tensor]:
         """``png.stage`` results → device images, every member reconstructing its share."""
-        return self._decode_per_member(staged, assign, lambda m, part: m.reconstruct_png(part))
+        return self._decode_per_member(staged, assign, lambda m, part: m.reconstruct_png(part, tolerant=tolerant))
 
     def _decode_per_member(self, datas: Sequence[bytes], assign, decode) -> list[torch.Tensor]:
         """``decode(member, its byte strings)`` -> images, run for every member that got a share

@@ -858,6 +858,54 @@ typedef struct rc_png_image {
  * exceed 512 MiB, which is as far as the staging grows. */
 int rc_png_reconstruct(int device, int n, const rc_png_image *images, uint8_t *rgb, int64_t rgb_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * PNG decode with the inflate on the device (DESIGN.md "PNG inflate on the
+ * device").  The host has walked the chunks, checked every CRC and the two
+ * zlib header bytes (png.py); what arrives here is the IDAT payload, joined.
+ * One workgroup of RC_PNG_INFLATE_LANES lanes per image decodes the deflate
+ * blocks token-parallel: every lane takes RC_PNG_INFLATE_ROW_BITS bits of the
+ * block and the lanes synchronise on the token boundaries.
+ * ---------------------------------------------------------------------- */
+#define RC_PNG_INFLATE_ROW_BITS 128
+#define RC_PNG_INFLATE_LANES 256
+/* Longest zlib stream the device stage takes: bit positions in it stay below 2^29, so they and
+ * every sum of them with a window's 2^15 bits fit an int32. */
+#define RC_PNG_INFLATE_MAX_BYTES (1 << 26)
+
+typedef struct rc_png_stream {
+    int32_t width, height, depth, color; /* IHDR */
+    int32_t palette_entries, reserved;   /* PLTE entries (colour type 3), else 0 */
+    const uint8_t *idat;                 /* host: the IDAT chunks' bodies joined (a zlib stream) */
+    int64_t idat_bytes;
+    const uint8_t *palette;              /* host: palette_entries * 3 bytes (colour type 3), else NULL */
+    int64_t out_offset;                  /* bytes from rgb: height x width x 3 are written there */
+} rc_png_stream;
+
+/* Inflate n streams on `stream` of `device` into a scanline buffer of the library's, then
+ * reconstruct them as rc_png_reconstruct does.  Descriptors, palettes and the compressed bytes
+ * are staged in a pinned block of the library's and uploaded with one copy; block and scanline
+ * buffer grow with the largest call and are reused (a repeated call leaves rc_alloc_count()
+ * unchanged).  flags_out[i] (host, n entries) is 0 where image i was written and 1 where the
+ * device refused its stream (anything zlib would refuse, a length other than height * (1 +
+ * stride), a filter byte above 4, a wrong Adler-32): that image's range of rgb is left untouched
+ * and the caller inflates it on the host and hands it to rc_png_reconstruct.  The call
+ * synchronises `stream` once, to read the flags.  Checked before any device call,
+ * RC_ERR_INVALID: null pointers, n outside 1..65535, IHDR values, fewer than 6 stream bytes or a
+ * zlib header other than deflate with a window of at most 32 KiB and no dictionary, a missing
+ * palette, an output range outside rgb.  RC_ERR_UNSUPPORTED: what rc_png_reconstruct does not
+ * support; a stream above RC_PNG_INFLATE_MAX_BYTES; a call whose streams and scanlines exceed
+ * 512 MiB. */
+int rc_png_decode(int device, int n, const rc_png_stream *streams, uint8_t *rgb, int64_t rgb_bytes, int32_t *flags_out,
+                  void *stream);
+/* Counters of rc_png_decode on `device` since the library was loaded: images the device
+ * inflated, and images it flagged for the host. */
+int rc_png_decode_stats(int device, int64_t *device_images, int64_t *host_fallbacks);
+/* Measurement: with enable != 0, every later rc_png_decode on `device` brackets png_inflate_kernel
+ * alone with an event pair (read after the call's stream synchronise).  Returns the milliseconds
+ * and launches accumulated since the last call of this function (either pointer may be NULL) and
+ * resets them.  With enable == 0 and timing never enabled, no device call is made. */
+int rc_png_decode_timing(int device, int enable, double *kernel_ms, int64_t *launches);
+
 #ifdef __cplusplus
 }
 #endif

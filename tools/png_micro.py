@@ -13,6 +13,17 @@ and, for the GPU path alone, where the time of a batch of 64 goes:
   inflate_ms   PngDecoder.host_stage: chunk parsing, CRCs and zlib inflate in the thread pool
   reconstruct_ms  PngDecoder.reconstruct between two events on the stream: the copy of the scanlines
                into the pinned staging (the device waits for it), the upload and png_reconstruct_kernel
+``--inflate host device`` runs the GPU path with both inflate kinds (RC_GPU_INFLATE off / on),
+alternating with the host decode round by round in the same process; the device kind's records are
+keyed ``gpu_device_*``, with, for a batch of 64:
+  stage_ms     the host stage that is left (chunk walk, CRCs, zlib header)
+  decode_ms    PngDecoder.reconstruct between two events: the upload of the compressed bytes,
+               png_inflate_kernel, the read-back of the flags (one stream synchronise) and
+               png_reconstruct_kernel
+  upload_bytes_per_image  for both kinds: inflated scanlines (host) or IDAT bytes (device)
+``--inflate-kernel`` is a run of its own: the device kind's decode of 64 images and of one, at both
+sizes, with png_inflate_kernel alone between an event pair inside the library
+(rc_png_decode_timing), one launch per round: ``inflate_kernel_ms``.
 The kernel alone: ``--kernel-only WxH`` stages a batch of 64 once and runs the device stage 20
 times, timing nothing itself; run it under ``rocprofv3 --kernel-trace --stats`` (a run of its own)
 and read png_reconstruct_kernel's row of the kernel statistics.
@@ -57,22 +68,50 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON records to this file")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--kernel-only", metavar="WxH", default=None, help="the profiler's target: 20 device stages of one batch")
+    ap.add_argument("--inflate", nargs="+", choices=("host", "device"), default=["host"],
+                    help="inflate kinds of the GPU path to run, alternating (default: host)")
+    ap.add_argument("--inflate-kernel", action="store_true", help="a run of its own: png_inflate_kernel between events")
     args = ap.parse_args()
     import torch
 
     assert torch.cuda.is_available(), "png_micro needs a GPU"
     if args.kernel_only:
         w, h = map(int, args.kernel_only.split("x"))
-        dec = importlib.import_module(f"{PKG}.png").PngDecoder(0)
-        staged = dec.host_stage([picture(w, h, 1000 + i) for i in range(BATCH)])
+        dec = importlib.import_module(f"{PKG}.png").PngDecoder(0, inflate=args.inflate[-1])
+        staged = dec.host_stage([picture(w, h, 1000 + i) for i in range(BATCH)], inflate=dec.inflate)
         for _ in range(20):
             dec.reconstruct(staged)
         torch.cuda.synchronize()
         return
+    if args.inflate_kernel:
+        import ctypes
+
+        png = importlib.import_module(f"{PKG}.png")
+        dec = png.PngDecoder(0, inflate="device")
+        for w, h in SIZES:
+            blobs = [picture(w, h, 1000 + i) for i in range(BATCH)]
+            for n in (BATCH, 1):
+                staged, ms, t = png.stage(blobs[:n], inflate="device"), [], ctypes.c_double()
+                dec.reconstruct(staged)  # warm: the workspace grows here
+                dec.lib.rc_png_decode_timing(0, 1, None, None)
+                for _ in range(args.rounds):
+                    dec.reconstruct(staged)
+                    dec.lib.rc_png_decode_timing(0, 1, ctypes.byref(t), None)
+                    ms.append(t.value)
+                dec.lib.rc_png_decode_timing(0, 0, None, None)
+                torch.cuda.synchronize()
+                line = json.dumps({"width": w, "height": h, "batch": n, "rounds": args.rounds, "inflate_kernel_ms": stats(ms)})
+                print(line, flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(line + "\n")
+        return
     main_mod = importlib.import_module(f"{PKG}.embedding.main")
     png = importlib.import_module(f"{PKG}.png")
     emb = main_mod.get_embedder()
-    dec = png.PngDecoder(emb.device)
+    decs = {kind: png.PngDecoder(emb.device, inflate=kind) for kind in args.inflate}
+    modes = {"host": None, **{"gpu" if kind == "host" else "gpu_device": kind for kind in args.inflate}}
+    parts = {"host": ("inflate_ms", "reconstruct_ms"), "device": ("stage_ms", "decode_ms")}
 
     def batch(blobs):
         t = time.perf_counter()
@@ -87,38 +126,44 @@ def main():
 
     for w, h in SIZES:
         blobs = [picture(w, h, 1000 + i) for i in range(BATCH)]
-        t = {(m, k): [] for m in ("host", "gpu") for k in ("batch64_ms", "single_ms")}
-        split = {"inflate_ms": [], "reconstruct_ms": []}
-        for rnd in range(-1, args.rounds):  # round -1 warms every shape of both paths
-            for mode in ("host", "gpu"):
-                main_mod.Config.GPU_PNG = mode == "gpu"
+        t = {(m, k): [] for m in modes for k in ("batch64_ms", "single_ms")}
+        split = {(kind, k): [] for kind in args.inflate for k in parts[kind]}
+        upload = {}
+        for rnd in range(-1, args.rounds):  # round -1 warms every shape of every path
+            for mode, kind in modes.items():
+                main_mod.Config.GPU_PNG = kind is not None
+                main_mod.Config.GPU_INFLATE = kind == "device"
                 b, s = batch(blobs), single(blobs[rnd % BATCH])
                 if rnd >= 0:
                     t[mode, "batch64_ms"].append(b)
                     t[mode, "single_ms"].append(s)
-            t0 = time.perf_counter()
-            staged = dec.host_stage(blobs)
-            t1 = time.perf_counter()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            dec.reconstruct(staged)
-            e1.record()
-            torch.cuda.synchronize()
-            if rnd >= 0:
-                split["inflate_ms"].append((t1 - t0) * 1e3)
-                split["reconstruct_ms"].append(e0.elapsed_time(e1))
+            for kind, dec in decs.items():
+                t0 = time.perf_counter()
+                staged = dec.host_stage(blobs, inflate=kind)
+                t1 = time.perf_counter()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                dec.reconstruct(staged)
+                e1.record()
+                torch.cuda.synchronize()
+                upload[kind] = sum(len(item[1]) for item in staged) // BATCH
+                if rnd >= 0:
+                    split[kind, parts[kind][0]].append((t1 - t0) * 1e3)
+                    split[kind, parts[kind][1]].append(e0.elapsed_time(e1))
         rec = {"width": w, "height": h, "batch": BATCH, "rounds": args.rounds,
                "png_bytes_mean": sum(map(len, blobs)) // BATCH}
         for (mode, k), v in t.items():
             rec[f"{mode}_{k}"] = stats(v)
-        for k, v in split.items():
-            rec[f"gpu_{k}"] = stats(v)
-        rec["batch64_images_per_s"] = {m: BATCH / rec[f"{m}_batch64_ms"]["median"] * 1e3 for m in ("host", "gpu")}
+        for (kind, k), v in split.items():
+            rec[("gpu_" if kind == "host" else "gpu_device_") + k] = stats(v)
+        rec["upload_bytes_per_image"] = upload
+        rec["batch64_images_per_s"] = {m: BATCH / rec[f"{m}_batch64_ms"]["median"] * 1e3 for m in modes}
         line = json.dumps(rec)
         print(line, flush=True)
         if args.out:
             with open(args.out, "a") as f:
                 f.write(line + "\n")
+    main_mod.Config.GPU_INFLATE = False
     main_mod.reset_embedder()
 
 
