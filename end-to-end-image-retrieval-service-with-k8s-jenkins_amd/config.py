@@ -54,6 +54,8 @@ class Config:
     # embedding GPUs (data parallel, one model per entry; entries may repeat): "" = the
     # distinct GPUs of the index shards (RC_INDEX_DEVICES), "all", or a comma list
     EMBED_DEVICES = os.getenv("RC_EMBED_DEVICES", "")
+    # the MLP's hidden activation and fc2: "bf16", or "mxfp8" for bulk ingest (DESIGN.md "MXFP8 MLP")
+    EMBED_MLP_DTYPE = os.getenv("RC_EMBED_MLP_DTYPE", "bf16")
     MODEL_PATH = os.getenv("RC_MODEL_PATH", "")  # local checkpoint dir (config.json + weights)
     WEIGHT_SEED = int(os.getenv("RC_WEIGHT_SEED", "1907"))
     GPU_JPEG = os.getenv("RC_GPU_JPEG", "1") != "0"  # decode baseline JPEGs on the GPU (bit-exact with PIL)

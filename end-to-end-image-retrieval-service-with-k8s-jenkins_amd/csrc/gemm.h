@@ -72,6 +72,22 @@ __device__ __forceinline__ void nt_store16(T *dst, const T &v) {
     __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), reinterpret_cast<u32x4 *>(dst));
 }
 
+// MXFP8 (gemm_mx.h has the format): E8M0 scale byte of a block with maximum magnitude amax.
+// On the f32 bits: the exponent field is floor(log2 a) + 127, and a > 448·2^e = 1.75·2^(e+8) is
+// a mantissa above 0x600000.  The clamp at 0 is e = −127 (zero and f32 subnormal maxima).
+__device__ __forceinline__ uint32_t mx_scale_byte(float amax) {
+    const uint32_t u = __float_as_uint(amax);
+    const int b = (int)(u >> 23) - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return (uint32_t)min(max(b, 0), 254);
+}
+// 2^−e of a scale byte, exact: exponent field 254 − byte (a finite maximum gives a byte <= 247)
+__device__ __forceinline__ float mx_inv_scale(uint32_t byte) { return __uint_as_float((254u - byte) << 23); }
+// four values, already scaled, to four e4m3 bytes (hardware convert, round to nearest even)
+__device__ __forceinline__ uint32_t mx_pack4(float v0, float v1, float v2, float v3) {
+    const int w = __builtin_amdgcn_cvt_pk_fp8_f32(v0, v1, 0, false);
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v2, v3, w, true);
+}
+
 // f32 epilogues (residual add / patch scatter + position embedding, optionally the bf16
 // copy and LayerNorm partials), straight from the accumulators — no LDS, no barrier.
 // One wave, NR output rows per lane (rows[r]: lane li's row of row slot r, the same for
@@ -198,6 +214,92 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs &a, f32x4 (&acc)[2][2
     // Round 6 measured fc1 through the LDS-staged path below with its nontemporal 512-B row
     // stores: fc1 itself +1.5…6 us per launch, the fc2 after it −8 us, step +0.3 % (r06s, r06t)
     // — within the run-to-run spread, so fc1 keeps this form.
+    // fc1 with an MXFP8 hidden activation (EPI_GELU_MX / EPI_GELU_MX_LN): GELU in f32, then per
+    // row the wave's 64 columns are two MX blocks (nq), each held by the row's four lanes g as
+    // 2 x 4 values.  Block maximum: the lane's 8 values, then lanes g ^ 1 and g ^ 2 by one
+    // v_permlane16_swap and one v_permlane32_swap — every lane has it, so every lane derives the
+    // same scale and converts its own values (v_cvt_pk_fp8_f32).  The row's 64 bytes are then a
+    // 4 x 4 dword matrix D[q][g] (q = 2 nq + ni: columns 16 q + 4 g + 0..3) with lane g holding
+    // column g; two permlane32 and two permlane16 swaps transpose it, so lane g stores D[g][0..3],
+    // 16 consecutive bytes: one 16-B store per lane per row where the bf16 form has two, and
+    // the wave's store covers 16 rows x 64 contiguous bytes.  No LDS.  Scale bytes: lane g = 0
+    // stores the row's two as one 2-B store.  out: bytes [round_up(M, 256)][N], then the scales.
+    if constexpr (epi_mx(EPI)) {
+        uint8_t *const qout = reinterpret_cast<uint8_t *>(a.out_bf16);
+        uint8_t *const sout = qout + (int64_t)((a.M + 255) / 256 * 256) * a.N;
+        const int SB = a.N / 32;
+        float4 bq[2][2], cq[2][2];
+#pragma unroll
+        for (int nq = 0; nq < 2; ++nq)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                const int cl = n0 + wc * 64 + nq * 32 + ni * 16 + 4 * g;
+                bq[nq][ni] = *reinterpret_cast<const float4 *>(a.bias + cl);
+                if constexpr (epi_ln(EPI)) cq[nq][ni] = *reinterpret_cast<const float4 *>(a.ln_c + cl);
+            }
+#pragma unroll
+        for (int mq = 0; mq < 2; ++mq)
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const int rl = grp * 128 + mq * 64 + mi * 16 + li;
+                const int row = m0 + rl;
+                float2 r = make_float2(1.f, 0.f);
+                if constexpr (epi_ln(EPI)) r = *reinterpret_cast<const float2 *>(smem + ln_off + rl * 8);
+                uint32_t d[4], sb[2];
+#pragma unroll
+                for (int nq = 0; nq < 2; ++nq) {
+                    f32x2 v[2][2];
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni) {
+                        const f32x4 v4 = acc[mq][nq][mi][ni];
+                        const float4 b4 = bq[nq][ni];
+                        if constexpr (epi_ln(EPI)) {
+                            const float4 t = ln_apply4(r, v4, cq[nq][ni], b4);
+                            v[ni][0] = f32x2{t.x, t.y};
+                            v[ni][1] = f32x2{t.z, t.w};
+                        } else {
+                            v[ni][0] = f32x2{v4[0] + b4.x, v4[1] + b4.y};
+                            v[ni][1] = f32x2{v4[2] + b4.z, v4[3] + b4.w};
+                        }
+                        v[ni][0] = gelu_fast2(v[ni][0]);
+                        v[ni][1] = gelu_fast2(v[ni][1]);
+                    }
+                    float am = 0.f;
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) am = fmaxf(am, fmaxf(fabsf(v[ni][h].x), fabsf(v[ni][h].y)));
+                    const auto m16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(am), __float_as_uint(am), false, false);
+                    am = fmaxf(__uint_as_float(m16[0]), __uint_as_float(m16[1]));
+                    const auto m32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(am), __float_as_uint(am), false, false);
+                    am = fmaxf(__uint_as_float(m32[0]), __uint_as_float(m32[1]));
+                    sb[nq] = mx_scale_byte(am);
+                    const float inv = mx_inv_scale(sb[nq]);
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni)
+                        d[2 * nq + ni] = mx_pack4(v[ni][0].x * inv, v[ni][0].y * inv, v[ni][1].x * inv, v[ni][1].y * inv);
+                }
+                // transpose D across the four 16-lane groups: 2 x 2 blocks (lanes 32 apart), then inside them
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const auto t = __builtin_amdgcn_permlane32_swap(d[q], d[q + 2], false, false);
+                    d[q] = t[0];
+                    d[q + 2] = t[1];
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q += 2) {
+                    const auto t = __builtin_amdgcn_permlane16_swap(d[q], d[q + 1], false, false);
+                    d[q] = t[0];
+                    d[q + 1] = t[1];
+                }
+                if (row < mlim) {
+                    const int col = n0 + wc * 64;
+                    *reinterpret_cast<uint4 *>(qout + (int64_t)row * a.N + col + 16 * g) = make_uint4(d[0], d[1], d[2], d[3]);
+                    if (g == 0) *reinterpret_cast<uint16_t *>(sout + (int64_t)row * SB + (col >> 5)) = (uint16_t)(sb[0] | (sb[1] << 8));
+                }
+            }
+        return;
+    }
     if constexpr (EPI == EPI_GELU_BF16_LN) {
         float4 bq[2][2], cq[2][2];
 #pragma unroll
@@ -608,11 +710,15 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs a) {
 // Epilogue of a 128 x 256 tile held as acc[mi][ni] by 4 waves (wave w: columns
 // [64w, 64w + 64)): acc[mi][ni][j] = C[m0 + mi*16 + li][n0 + w*64 + ni*16 + 4g + j].
 // The bf16 epilogues stage through `smem` (>= 64 KB; the caller's main loop must be done
-// with it); the f32 ones store from the accumulators.
-template <int EPI, int MI = 8>
-__device__ __forceinline__ void w2_epilogue(const GemmArgs &a, f32x4 (&acc)[MI][4], uint8_t *smem, int m0, int n0) {
+// with it); the f32 ones store from the accumulators.  wcol: the wave's column block where it
+// is not the wave's index (WCOL: gemm_mx_kernel's 8 waves, f32 epilogues only).
+template <int EPI, int MI = 8, bool WCOL = false>
+__device__ __forceinline__ void w2_epilogue(const GemmArgs &a, f32x4 (&acc)[MI][4], uint8_t *smem, int m0, int n0,
+                                            int wcol = 0) {
+    static_assert(!WCOL || !epi_bf16_out(EPI), "the bf16 epilogues stage by wave index");
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if constexpr (WCOL) wave = wcol;
     const int g = lane >> 4, li = lane & 15;
     if constexpr (epi_bf16_out(EPI)) {
         static_assert(MI == 8, "bf16 epilogues stage a 128-row tile");

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "gemm.h"
+#include "gemm_mx.h"
 #include "qkv_attention.h"
 #include "resample.h"
 #include "vit_kernels.h"
@@ -43,6 +44,8 @@ struct Layer {
     // LayerNorm folded into QKV / fc1 (vit_kernels.h "LayerNorm fold"): W′ = W·diag(γ) in
     // bf16, c = Σ_k W′ (of the bf16 values), b′ = b + W·β
     uint16_t *w_qkv_f = nullptr, *w_fc1_f = nullptr;
+    // W_fc2 in MXFP8 (gemm_mx.h): e4m3 bytes [H][MLP] and E8M0 scales [H][MLP / 32], blocks along K
+    uint8_t *w_fc2_q = nullptr, *w_fc2_s = nullptr;
     float *b_qkv_f = nullptr, *c_qkv = nullptr, *b_fc1_f = nullptr, *c_fc1 = nullptr;
 };
 
@@ -83,6 +86,7 @@ struct rc_model {
     float *ln_stats = nullptr;     // [Mp][LN_PARTS][2] LayerNorm-fold partials (per 64-column block: mean, M2)
     bool ln_fold = true;           // rc_model_set_ln_fold: LN folded into QKV / fc1, at every M
     int qkv_fusion = 1;            // rc_model_set_qkv_fusion: 0 off, 1 auto (kQkvFusionMinImages), 2 any batch
+    int mlp_dtype = 0;             // rc_model_set_mlp_dtype: 0 bf16, 1 MXFP8 hidden rows + fc2 (tiled MLPs only)
     // last layer on the CLS rows only (compact [max_batch + pad][·] streams)
     bool cls_only_last = true;     // rc_model_set_last_layer
     float *cls_hidden = nullptr, *cls_stats = nullptr;
@@ -388,18 +392,29 @@ int diag_variant(const GemmArgs &a, int variant, bool patch_epilogue, bool ln_ep
 #endif
 
 // role: T_QKV / T_OPROJ / T_FC1 / T_FC2 (its own timer besides T_GEMM), or -1
-template <int EPI>
-void gemm(rc_model *m, const GemmArgs &a, hipStream_t s, int role = -1) {
+template <typename Launch>
+void timed_gemm(rc_model *m, const GemmArgs &a, hipStream_t s, int role, Launch &&launch) {
     const double flops = 2.0 * a.M * a.N * a.K;
     const int t0 = m->timers[T_GEMM].begin(s);
     const int t1 = role >= 0 ? m->timers[role].begin(s) : -1;
-    int variant = GEMM_AUTO;
-#if defined(RC_GEMM_ABLATION)
-    variant = diag_variant(a, m->gemm_variant, epi_patch(EPI), epi_ln(EPI));
-#endif
-    launch_gemm<EPI>(a, variant, s);
+    launch();
     if (role >= 0) m->timers[role].end(t1, s, flops);
     m->timers[T_GEMM].end(t0, s, flops);
+}
+
+template <int EPI>
+void gemm(rc_model *m, const GemmArgs &a, hipStream_t s, int role = -1) {
+    timed_gemm(m, a, s, role, [&] {
+        if constexpr (epi_mx(EPI)) {
+            launch_gemm_mx_out<EPI>(a, s);
+        } else {
+            int variant = GEMM_AUTO;
+#if defined(RC_GEMM_ABLATION)
+            variant = diag_variant(a, m->gemm_variant, epi_patch(EPI), epi_ln(EPI));
+#endif
+            launch_gemm<EPI>(a, variant, s);
+        }
+    });
 }
 
 // LayerNorm-fold consumer (QKV, fc1): `a` carries W∘γ and b + W·β; c = the row sums of W∘γ,
@@ -600,18 +615,35 @@ void encode(rc_model *m, const uint8_t *images, int i0, int n, float *raw, float
             o.row_step = T;  // rows per image (diagnostic builds: image-aligned tiles, gemm_pp_kernel<.., 224>)
             resid_gemm(m, o, s, T_OPROJ);
         }
+        // MXFP8 MLP: the tiled kernels only (M > 256); a small batch keeps bf16 on the skinny ones.
+        // The MXFP8 rows go where the part's bf16 hidden rows go: M byte rows, then the scale rows
+        // behind round_up(M, 256) byte rows.  They must end inside the part's own M·mlp·2 bytes (the
+        // next part writes right behind them on another stream), which holds from M = 264 at mlp
+        // 3072; a part of 257 .. 263 rows keeps bf16.
+        const int64_t mx_scales = (int64_t)round_up(M, 256) * c.mlp;  // byte offset of the part's scale rows
+        const bool mx = m->mlp_dtype == 1 && M > 256 && L.w_fc2_q != nullptr &&
+                        mx_scales + (int64_t)M * (c.mlp / 32) <= (int64_t)M * c.mlp * 2;
         if (fold) {
             const GemmArgs a{ln, L.w_fc1_f, L.b_fc1_f, M, c.mlp, H, mlp, nullptr, nullptr, T};
-            gemm<EPI_GELU_BF16_LN>(m, ln_consumer(a, L.c_fc1, st, c.ln_eps), s, T_FC1);
+            if (mx) gemm<EPI_GELU_MX_LN>(m, ln_consumer(a, L.c_fc1, st, c.ln_eps), s, T_FC1);
+            else gemm<EPI_GELU_BF16_LN>(m, ln_consumer(a, L.c_fc1, st, c.ln_eps), s, T_FC1);
         } else {
             layernorm(m, hidden, L.ln2_w, L.ln2_b, ln, M, s);
-            gemm<EPI_GELU_BF16>(m, GemmArgs{ln, L.w_fc1, L.b_fc1, M, c.mlp, H, mlp, nullptr, nullptr, T}, s, T_FC1);
+            const GemmArgs a{ln, L.w_fc1, L.b_fc1, M, c.mlp, H, mlp, nullptr, nullptr, T};
+            if (mx) gemm<EPI_GELU_MX>(m, a, s, T_FC1);
+            else gemm<EPI_GELU_BF16>(m, a, s, T_FC1);
         }
         // the last layer's fc2 feeds only the final LN of the CLS rows (cls_final_kernel)
         {
             GemmArgs f2 = produce(GemmArgs{mlp, L.w_fc2, L.b_fc2, M, H, c.mlp, nullptr, hidden, nullptr, T}, l + 1 < c.layers);
             f2.row_step = T;
-            resid_gemm(m, f2, s, T_FC2);
+            if (mx) {
+                const uint8_t *a8 = reinterpret_cast<const uint8_t *>(mlp);
+                const MxGemmArgs p{a8, a8 + mx_scales, L.w_fc2_q, L.w_fc2_s, f2};
+                timed_gemm(m, f2, s, T_FC2, [&] { launch_gemm_mx(p, s); });
+            } else {
+                resid_gemm(m, f2, s, T_FC2);
+            }
         }
     }
     // 4. final LayerNorm on the CLS rows → raw (the /embed body) and L2-normalised copy
@@ -872,6 +904,12 @@ int rc_model_finalize(rc_model *m) {
             L.b_fc1 = upload_f32(m, h[p + "intermediate.dense.bias"]);
             L.w_fc2 = upload_bf16(m, {&h[p + "output.dense.weight"]});
             L.b_fc2 = upload_f32(m, h[p + "output.dense.bias"]);
+            if (m->cfg.mlp % MX_BK == 0 && m->cfg.hidden % MX_BN == 0) {  // the MXFP8 copy (the bf16 one serves M <= 256)
+                const int64_t nw = (int64_t)m->cfg.hidden * m->cfg.mlp;
+                L.w_fc2_q = (uint8_t *)m->alloc((size_t)nw);
+                L.w_fc2_s = (uint8_t *)m->alloc((size_t)nw / 32);
+                launch_mxfp8_quantize(L.w_fc2, true, m->cfg.hidden, m->cfg.mlp, L.w_fc2_q, L.w_fc2_s, nullptr);
+            }
             L.ln1_w = upload_f32(m, h[p + "layernorm_before.weight"]);
             L.ln1_b = upload_f32(m, h[p + "layernorm_before.bias"]);
             L.ln2_w = upload_f32(m, h[p + "layernorm_after.weight"]);
@@ -887,6 +925,7 @@ int rc_model_finalize(rc_model *m) {
                            h[p + "layernorm_after.weight"], h[p + "layernorm_after.bias"], &L.w_fc1_f, &L.b_fc1_f,
                            &L.c_fc1);
         }
+        RC_HIP(hipStreamSynchronize(nullptr));  // the W_fc2 quantise launches
         m->host.clear();
         m->ready = true;
     });
@@ -993,6 +1032,24 @@ int rc_model_set_qkv_fusion(rc_model *m, int mode) {
     });
 }
 
+int rc_model_set_mlp_dtype(rc_model *m, int kind) {
+    return guard([&] {
+        RC_REQUIRE(m, RC_ERR_INVALID, "null model");
+        RC_REQUIRE(kind == 0 || kind == 1, RC_ERR_INVALID, "mlp dtype: 0 bf16, 1 mxfp8");
+        std::lock_guard<std::mutex> lk(m->mu);
+        m->clear_graphs();
+        m->mlp_dtype = kind;
+    });
+}
+
+int rc_model_get_mlp_dtype(rc_model *m, int *kind) {
+    return guard([&] {
+        RC_REQUIRE(m && kind, RC_ERR_INVALID, "null model or output");
+        std::lock_guard<std::mutex> lk(m->mu);
+        *kind = m->mlp_dtype;
+    });
+}
+
 int rc_model_set_last_layer(rc_model *m, int cls_only) {
     return guard([&] {
         RC_REQUIRE(m, RC_ERR_INVALID, "null model");
@@ -1066,6 +1123,9 @@ extern "C" int rc_gemm_bf16(int epi, int variant, const uint16_t *A, const uint1
             case EPI_BF16: launch_gemm<EPI_BF16>(a, variant, s); break;
             case EPI_GELU_BF16: launch_gemm<EPI_GELU_BF16>(a, variant, s); break;
             case EPI_RESID_F32: launch_gemm<EPI_RESID_F32>(a, variant, s); break;
+            case 4:  // GELU, MXFP8 out (EPI_GELU_MX): the tiled ping-pong kernel, whatever `variant`
+                launch_gemm_mx_out<EPI_GELU_MX>(a, s);
+                break;
             case EPI_PATCH_F32:
                 RC_REQUIRE(pos && tokens > 1, RC_ERR_INVALID, "patch epilogue needs pos and tokens");
                 launch_gemm<EPI_PATCH_F32>(a, variant, s);
@@ -1096,5 +1156,28 @@ extern "C" int rc_attention_bf16(int kind, const uint16_t *qkv, const uint16_t *
         }
         const float scale = 1.0f / std::sqrt(64.0f);  // head dim 64, as encode()
         launch_attention(kind, qkv, q_cls, out, images, tokens, heads, scale, qsplit == 0 ? 1 : qsplit, (hipStream_t)stream);
+    });
+}
+
+extern "C" int rc_mxfp8_quantize(const void *src, int src_bf16, int64_t rows, int K, uint8_t *q, uint8_t *scales, void *stream) {
+    return guard([&] {
+        RC_REQUIRE(src && q && scales, RC_ERR_INVALID, "null buffer");
+        RC_REQUIRE(rows >= 1 && K >= 32 && K % 32 == 0 && rows * (int64_t)(K / 32) <= INT32_MAX, RC_ERR_INVALID,
+                   "rows >= 1, K a multiple of 32");
+        launch_mxfp8_quantize(src, src_bf16 != 0, rows, K, q, scales, (hipStream_t)stream);
+    });
+}
+
+extern "C" int rc_gemm_mxfp8(const uint8_t *A8, const uint8_t *As, const uint8_t *W8, const uint8_t *Ws, const float *bias, int M,
+                             int N, int K, float *out_resid, int tokens, void *stream) {
+    return guard([&] {
+        // everything refused here is refused before any device call
+        RC_REQUIRE(A8 && As && W8 && Ws && bias && out_resid, RC_ERR_INVALID, "null operand");
+        RC_REQUIRE(M >= 1 && N >= MX_BN && N % MX_BN == 0 && K >= MX_BK && K % MX_BK == 0, RC_ERR_INVALID,
+                   "MXFP8 GEMM: M >= 1, N % 256 == 0, K % 128 == 0");
+        RC_REQUIRE(((uintptr_t)A8 | (uintptr_t)W8) % 16 == 0 && ((uintptr_t)As | (uintptr_t)Ws) % 4 == 0, RC_ERR_INVALID,
+                   "MXFP8 GEMM: operand rows 16-byte aligned, scale rows 4-byte aligned");
+        const GemmArgs g{nullptr, nullptr, bias, M, N, K, nullptr, out_resid, nullptr, tokens};
+        launch_gemm_mx(MxGemmArgs{A8, As, W8, Ws, g}, (hipStream_t)stream);
     });
 }

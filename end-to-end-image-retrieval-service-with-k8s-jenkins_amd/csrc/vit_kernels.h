@@ -28,14 +28,17 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
 // EPI_BF16_LN / EPI_GELU_BF16_LN: the bf16 epilogues as consumers of the LayerNorm fold
 // EPI_RESID_BF16 / EPI_PATCH_BF16: the residual-stream producers with the stream kept in bf16
 // (see "Residual stream in bf16"; GemmArgs::ln_x)
+// EPI_GELU_MX / EPI_GELU_MX_LN: fc1's GELU output stored as MXFP8 (gemm_mx.h), plain and as
+// LayerNorm-fold consumer
 enum GemmEpi { EPI_BF16 = 0, EPI_GELU_BF16 = 1, EPI_RESID_F32 = 2, EPI_PATCH_F32 = 3, EPI_BF16_LN = 4, EPI_GELU_BF16_LN = 5,
-               EPI_RESID_BF16 = 6, EPI_PATCH_BF16 = 7 };
+               EPI_RESID_BF16 = 6, EPI_PATCH_BF16 = 7, EPI_GELU_MX = 8, EPI_GELU_MX_LN = 9 };
+constexpr bool epi_mx(int e) { return e == EPI_GELU_MX || e == EPI_GELU_MX_LN; }
 constexpr bool epi_bf16_out(int e) { return e == EPI_BF16 || e == EPI_GELU_BF16 || e == EPI_BF16_LN || e == EPI_GELU_BF16_LN; }
 constexpr bool epi_resid(int e) { return e == EPI_RESID_F32 || e == EPI_RESID_BF16; }
 constexpr bool epi_patch(int e) { return e == EPI_PATCH_F32 || e == EPI_PATCH_BF16; }
 constexpr bool epi_bf16_stream(int e) { return e == EPI_RESID_BF16 || e == EPI_PATCH_BF16; }
-constexpr bool epi_gelu(int e) { return e == EPI_GELU_BF16 || e == EPI_GELU_BF16_LN; }
-constexpr bool epi_ln(int e) { return e == EPI_BF16_LN || e == EPI_GELU_BF16_LN; }
+constexpr bool epi_gelu(int e) { return e == EPI_GELU_BF16 || e == EPI_GELU_BF16_LN || epi_mx(e); }
+constexpr bool epi_ln(int e) { return e == EPI_BF16_LN || e == EPI_GELU_BF16_LN || e == EPI_GELU_MX_LN; }
 
 struct GemmArgs {
     const uint16_t *A;  // [rows >= roundup(M, BM)][K] bf16, row-major

@@ -73,10 +73,11 @@ def get_embedder():
             else:  # no checkpoint offline: deterministic seeded weights
                 sd, cfg, pre = random_state_dict(Config.WEIGHT_SEED), None, None
             if len(devs) > 1:
-                _embedder = EmbedderPool(sd, devs, max_batch=Config.EMBED_MAX_BATCH, model_config=cfg, preprocess=pre)
+                _embedder = EmbedderPool(sd, devs, max_batch=Config.EMBED_MAX_BATCH, model_config=cfg, preprocess=pre,
+                                         mlp_dtype=Config.EMBED_MLP_DTYPE)
             else:
                 _embedder = VitMsnEmbedder(sd, device=devs[0] if devs else None, max_batch=Config.EMBED_MAX_BATCH,
-                                           model_config=cfg, preprocess=pre)
+                                           model_config=cfg, preprocess=pre, mlp_dtype=Config.EMBED_MLP_DTYPE)
         return _embedder
 
 

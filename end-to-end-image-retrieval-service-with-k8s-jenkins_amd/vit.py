@@ -152,11 +152,30 @@ def _packed_view(ims: Sequence, device) -> "torch.Tensor | None":
     return first.as_strided((n,) + tuple(first.shape), (z,) + tuple(first.stride()))
 
 
+MLP_DTYPES = {"bf16": 0, "mxfp8": 1}  # rc_model_set_mlp_dtype kinds
+
+
+def mlp_dtype_kind(mlp_dtype: str) -> int:
+    """The ``rc_model_set_mlp_dtype`` kind of a ``mlp_dtype`` name; ``ValueError`` for any other."""
+    if mlp_dtype not in MLP_DTYPES:
+        raise ValueError(f"mlp_dtype must be one of {sorted(MLP_DTYPES)}, not {mlp_dtype!r}")
+    return MLP_DTYPES[mlp_dtype]
+
+
 class VitMsnEmbedder:
-    """One ``rc_model`` on one GPU: fixed weights, workspace for ``max_batch`` images."""
+    """One ``rc_model`` on one GPU: fixed weights, workspace for ``max_batch`` images.
+
+    ``mlp_dtype="mxfp8"`` (default ``"bf16"``) keeps the MLP's hidden activation, and runs fc2,
+    in MXFP8 wherever the MLP runs on the tiled kernels (batches of two images and more; the
+    last layer too when it runs on every row).  It is meant for bulk ingest at the bf16 precision
+    tier (1e-2 cosine to the fp32 oracle).  A single image, and the CLS-only last layer, keep
+    bf16, so in this mode an image's bits depend on its batch: ingest in bulk with ``"mxfp8"``,
+    query with ``"bf16"``, and expect a self-match cosine slightly below 1.  The promise that an
+    embedding does not depend on its batch holds for ``"bf16"`` only."""
 
     def __init__(self, state_dict: Mapping, device=None, max_batch: int = 32, model_config: dict | None = None,
-                 preprocess: dict | None = None):
+                 preprocess: dict | None = None, mlp_dtype: str = "bf16"):
+        kind = mlp_dtype_kind(mlp_dtype)  # before any GPU work
         self.lib = _lib.load()
         cfg = dict(VIT_MSN_BASE)
         cfg.update(model_config or {})
@@ -188,6 +207,8 @@ class VitMsnEmbedder:
             std = (_lib.C.c_float * 3)(*p["image_std"])
             check(self.lib.rc_model_set_preprocess(self._h, int(p["resample"]), float(p["rescale_factor"]), mean, std))
             check(self.lib.rc_model_finalize(self._h))
+            if kind:
+                check(self.lib.rc_model_set_mlp_dtype(self._h, kind))
         except Exception:
             self.close()
             raise
@@ -394,6 +415,16 @@ class VitMsnEmbedder:
         """Run the last encoder layer on the CLS rows only (default) or on every row."""
         check(self.lib.rc_model_set_last_layer(self._h, int(bool(cls_only))))
 
+    def set_mlp_dtype(self, mlp_dtype: str) -> None:
+        """``"bf16"`` or ``"mxfp8"`` (the class docstring has the scope)."""
+        check(self.lib.rc_model_set_mlp_dtype(self._h, mlp_dtype_kind(mlp_dtype)))
+
+    @property
+    def mlp_dtype(self) -> str:
+        kind = _lib.C.c_int(-1)
+        check(self.lib.rc_model_get_mlp_dtype(self._h, _lib.C.byref(kind)))
+        return {v: k for k, v in MLP_DTYPES.items()}[kind.value]
+
     def set_graphs(self, on: bool) -> None:
         """Replay a one-image embed's launch chain as a captured HIP graph (default) or launch
         every kernel from the host (the same bits)."""
@@ -445,14 +476,16 @@ class EmbedderPool:
     parts).  Devices may repeat (two models on one GPU: the parity test)."""
 
     def __init__(self, state_dict: Mapping, devices: Sequence, max_batch: int = 32, model_config: dict | None = None,
-                 preprocess: dict | None = None):
+                 preprocess: dict | None = None, mlp_dtype: str = "bf16"):
+        mlp_dtype_kind(mlp_dtype)
         if not devices:
             raise ValueError("an embedder pool needs at least one device")
         self.members: list[VitMsnEmbedder] = []
         try:
             for d in devices:
                 self.members.append(VitMsnEmbedder(state_dict, device=d, max_batch=max_batch,
-                                                   model_config=model_config, preprocess=preprocess))
+                                                   model_config=model_config, preprocess=preprocess,
+                                                   mlp_dtype=mlp_dtype))
         except Exception:
             self.close()
             raise
@@ -634,6 +667,10 @@ class EmbedderPool:
     def set_qkv_fusion(self, mode: int) -> None:
         for m in self.members:
             m.set_qkv_fusion(mode)
+
+    def set_mlp_dtype(self, mlp_dtype: str) -> None:
+        for m in self.members:
+            m.set_mlp_dtype(mlp_dtype)
 
     def set_last_layer(self, cls_only: bool) -> None:
         for m in self.members:

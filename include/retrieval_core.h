@@ -688,6 +688,18 @@ int rc_model_set_parts(rc_model *m, int parts);
  * cls_only = 0 runs the whole layer (A/B and parity tests). */
 int rc_model_set_last_layer(rc_model *m, int cls_only);
 
+/* Data type of the MLP's hidden activation and of fc2 (default 0).  kind 0: bf16.  kind 1:
+ * MXFP8 (OCP MX: 32 consecutive e4m3 elements along K share one E8M0 scale byte, see
+ * rc_mxfp8_quantize) — every full-batch MLP (a part of more than 256 token rows, the tiled
+ * kernels) has fc1 store its GELU output as MXFP8 and fc2 multiply it with an MXFP8 copy of W2 on
+ * the block-scaled fp8 MFMA.  Batches of at most 256 rows, the CLS-only last layer and the batch-1
+ * graph keep bf16, so under kind 1 an image's bits depend on whether its batch took the tiled
+ * path: the batch-invariance promise holds for kind 0 only.  Meant for the bf16 precision tier
+ * (1e-2 cosine to the fp32 oracle).  Any other kind, or a null model, is RC_ERR_INVALID before
+ * any device call.  Drops captured graphs, like every setter. */
+int rc_model_set_mlp_dtype(rc_model *m, int kind);
+int rc_model_get_mlp_dtype(rc_model *m, int *kind);
+
 /* LayerNorm fold (default 1): the two LayerNorms of each layer
  * (modeling_vit_msn.py:258-259) are folded into the GEMMs around them — the residual producers (patch embed, O-proj, fc2) also
  * write bf16(x) and per-256-column (mean, M2) partials, and QKV / fc1 apply
@@ -729,9 +741,28 @@ int rc_model_timing_reset(rc_model *m);
  * variant: 0 auto, 4 256x256 ping-pong, 8 128x256 two-workgroup, 9 skinny (M <= 256),
  * 10 image-aligned 224-row tiles (the model's O-proj / fc2 kernel; epi 2 only, `tokens` =
  * rows per image, tile t = rows [t·tokens, t·tokens + tokens); A must then hold
- * ceil(M / tokens)·tokens + 224 − tokens readable rows). */
+ * ceil(M / tokens)·tokens + 224 − tokens readable rows).
+ * epi 4 → MXFP8 GELU(out) (the MXFP8 MLP's fc1): M > 256 on the ping-pong kernel whatever
+ * `variant`; out holds [round_up(M, 256)][N] e4m3 bytes, then [round_up(M, 256)][N / 32] scale
+ * bytes (rows past M are not written). */
 int rc_gemm_bf16(int epi, int variant, const uint16_t *A, const uint16_t *W, const float *bias, int M, int N, int K,
                  void *out, const float *pos, int tokens, void *stream);
+
+/* MXFP8 (OCP MX) quantisation of src [rows][K], f32 or bf16 (src_bf16 != 0), K % 32 == 0, on the
+ * device: q [rows][K] e4m3fn bytes, scales [rows][K / 32] E8M0 bytes.  A block is 32 consecutive
+ * elements along K; with a = max|x| over it, e = floor(log2 a) − 8, one more if a > 448·2^e (so
+ * nothing saturates), clamped to [−127, 127]; a == 0 gives e = −127 and zero bytes.  The scale
+ * byte is e + 127; an element is the e4m3fn value nearest x·2^−e, ties to even.  src and q must
+ * be 16-byte aligned.  (rc_model_finalize builds each layer's MXFP8 W2 with it.) */
+int rc_mxfp8_quantize(const void *src, int src_bf16, int64_t rows, int K, uint8_t *q, uint8_t *scales, void *stream);
+
+/* Kernel-level entry to the MXFP8 MLP's fc2 (parity tests): out_resid[M][N] f32 +=
+ * dequant(A8, As)[M][K] · dequant(W8, Ws)[N][K]ᵀ + bias, operands as rc_mxfp8_quantize lays them
+ * out, on the block-scaled fp8 MFMA (256 x 256 tiles; rows past M are neither read nor written).
+ * Null operands, K % 128 != 0, N % 256 != 0, operand rows not 16-byte or scale rows not 4-byte
+ * aligned are RC_ERR_INVALID before any device call.  `tokens` is not used by this epilogue. */
+int rc_gemm_mxfp8(const uint8_t *A8, const uint8_t *As, const uint8_t *W8, const uint8_t *Ws, const float *bias, int M, int N,
+                  int K, float *out_resid, int tokens, void *stream);
 
 /* Kernel-level entry to the attention kernels (parity tests; inside rc_embed this is the eager
  * attention of modeling_vit_msn.py:161-186), launched by the launcher the model uses.
