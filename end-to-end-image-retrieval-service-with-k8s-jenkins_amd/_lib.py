@@ -62,8 +62,9 @@ def is_f8(dtype: str) -> bool:
     return DTYPES.get(dtype) == RC_F8
 
 
-RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8, RC_FILTER_METRIC, RC_FILTER_F32 = 0, 1, 2, 3, 4
-FILTERS = {"native": RC_FILTER_NATIVE, "i8": RC_FILTER_I8, "f8": RC_FILTER_F8, "metric": RC_FILTER_METRIC, "f32": RC_FILTER_F32}
+RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8, RC_FILTER_METRIC, RC_FILTER_F32, RC_FILTER_I8_STREAM = 0, 1, 2, 3, 4, 5
+FILTERS = {"native": RC_FILTER_NATIVE, "i8": RC_FILTER_I8, "f8": RC_FILTER_F8, "metric": RC_FILTER_METRIC, "f32": RC_FILTER_F32,
+           "i8_stream": RC_FILTER_I8_STREAM}
 RC_METRIC_COSINE, RC_METRIC_DOT, RC_METRIC_EUCLIDEAN = 0, 1, 2
 METRICS = {"cosine": RC_METRIC_COSINE, "dotproduct": RC_METRIC_DOT, "euclidean": RC_METRIC_EUCLIDEAN}  # Pinecone's names
 

@@ -465,6 +465,26 @@ constexpr int kF32BatchMinPassesMid = 8;          // ... or with at least
 constexpr int64_t kF32BatchMinRowsMid = 131072;   // this many rows
 constexpr int kF32BatchMinPassesLarge = 4;        // ... or with at least
 constexpr int64_t kF32BatchMinRowsLarge = 1000000;  // this many
+// The streaming int8 filter (RC_FILTER_I8_STREAM, 1 to 8 queries) competes with the exact scan of the stored
+// rows, which it beats by reading ld + 8 bytes per row instead of the row, at the staged search's fixed cost
+// (0.2-0.3 ms a call).  Wall ms per call, scan / streaming, median of 5 interleaved rounds, dim 512, top-100
+// ("int8 streaming filter", has dim 768, top-10 and every round's ratio):
+//        rows      f32 1 q        f32 4 q        f32 8 q        f16 1 q        f16 4 q        f16 8 q
+//      65 536   0.061 / 0.277  0.141 / 0.313  0.264 / 0.349  0.059 / 0.244  0.144 / 0.284  0.270 / 0.327
+//     262 144   0.127 / 0.338  0.270 / 0.372  0.515 / 0.420  0.091 / 0.300  0.210 / 0.340  0.393 / 0.395
+//   1 048 576   0.372 / 0.450  0.772 / 0.488  1.512 / 0.547  0.230 / 0.406  0.574 / 0.447  1.107 / 0.509
+//   4 194 304   1.299 / 0.757  2.592 / 0.798  5.146 / 0.893  0.691 / 0.693  1.471 / 0.739  2.904 / 0.813
+// RC_SEARCH_AUTO without a mask takes it where every measured cell (f32 / f16 / bf16, dim 512 and 768, top-10 and
+// top-100) was at least 1.10x ahead in every round: 4 or more queries from 2^20 rows (1.27x at the least), and on a
+// float32 index any query count from 2^22 rows (1.62-14.6x).  One or two queries over f16 / bf16 rows reach at
+// most 1.30x at 2^22 rows and 0.92x in the worst cell: they scan.  Row width 256 (dim <= 256) was not measured
+// and scans: there the scan serves 4 queries in one pass over rows half as wide, and the table's 4-query gains,
+// which come from its 2 and 4 passes at widths 512 and 768, do not carry over.  RC_SEARCH_MFMA reaches the
+// kernel at any size and width.
+constexpr int kI8StreamMinQueries = 4;                  // from
+constexpr int64_t kI8StreamMinRows = int64_t(1) << 20;  // this many rows; a float32 index with any query count from
+constexpr int64_t kI8StreamMinRowsF32 = int64_t(1) << 22;
+constexpr int64_t kI8StreamMinLd = 512;  // the measured row widths: 512 and 768
 // The batched search over pages (rc_index_search_pages_ex) competes with the paged scan of the same
 // slot (f16 x 512 on a shuffled page list in a 4M-row pool, wall ms per call, median of 5 interleaved
 // rounds, paged MFMA / paged scan, tools/paged_batched_micro.py, profiles/paged_batched/; DESIGN.md,
@@ -640,6 +660,17 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
     launch_merge_partials(h, h->partial, nullptr, nblk, nq, nq_pad, k, scores, out_rows, s);
 }
 
+// RC_FILTER_I8_STREAM's own kernel serves this request (else the kind is RC_FILTER_I8 in every respect):
+// 1 to 8 queries, and not the MASKED form, which stays filter_i8_kernel's.
+bool i8_stream_serves(const rc_index *h, int nq, const uint32_t *mask, bool mask_filter) {
+    return h->filter == RC_FILTER_I8_STREAM && h->rows8 != nullptr && nq <= I8_STREAM_MAX_QUERIES && !(mask_filter && mask != nullptr);
+}
+// ... and RC_SEARCH_AUTO takes it over n rows (no mask)
+bool i8_stream_auto(const rc_index *h, int nq, int64_t n) {
+    return i8_stream_serves(h, nq, nullptr, false) && h->ld >= kI8StreamMinLd &&
+           ((nq >= kI8StreamMinQueries && n >= kI8StreamMinRows) || (h->dtype == RC_F32 && n >= kI8StreamMinRowsF32));
+}
+
 // bytes per element of BatchWs::qh: the storage dtype's, and two byte planes (q_hi, q_lo) on a float8 index
 int batch_query_bytes(const rc_index *h) { return h->dtype == RC_F8 ? 2 : (int)dtype_size(h->dtype); }
 
@@ -657,8 +688,10 @@ int batch_query_bytes(const rc_index *h) { return h->dtype == RC_F8 ? 2 : (int)d
 // queries as every paged scan does.
 void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_rows, int k, const uint32_t *mask,
                           bool mask_filter, float *scores, int64_t *out_rows, hipStream_t s, const int32_t *pages = nullptr) {
-    h->bws.ensure(nq, k, h->ld, batch_query_bytes(h));
+    const bool stream = pages == nullptr && i8_stream_serves(h, nq, mask, mask_filter);
+    h->bws.ensure(nq, k, h->ld, batch_query_bytes(h), stream ? I8_STREAM_MAX_QUERIES : 256);
     BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, n_rows, h->row_base, h->row_stride, queries, nq, k, scores, out_rows};
+    p.i8_stream = stream;
     p.f8_filter = h->filter == RC_FILTER_F8;
     p.f32_filter = h->filter == RC_FILTER_F32;
     p.rows8 = h->rows8;
@@ -839,7 +872,9 @@ void topk_search(rc_index *h, const SearchArgs &a, int mode) {
     // makes the scan cheaper while the filter GEMM still reads every row (MFMA on request; the
     // masked paged forms are unmeasured)
     bool auto_mfma = a.nq >= kBatchMinQueries && a.n >= kBatchMinRows;
-    if (pages != nullptr) {  // its own corner (see kPagedBatchMinQueries)
+    if (pages == nullptr && i8_stream_serves(h, a.nq, nullptr, false)) {  // its own corner (see kI8StreamMinQueries)
+        auto_mfma = i8_stream_auto(h, a.nq, a.n);
+    } else if (pages != nullptr) {  // its own corner (see kPagedBatchMinQueries)
         auto_mfma = (a.nq >= kPagedBatchMinQueries && a.n >= kPagedBatchMinPositions) ||
                     (a.nq >= kPagedBatchMinQueriesLarge && a.n >= kPagedBatchMinPositionsLarge);
     } else if (h->filter == RC_FILTER_F8) {  // its own corner (see kF8BatchMinPasses)
@@ -938,6 +973,7 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
                   int64_t *out_rows, float *out_values, hipStream_t s, volatile unsigned **done, unsigned *seq) {
     if (h->dim > QUERY1_MAX_DIM || h->nch > 6 || topk_cap(k) > 256 || n_rows < 1 || n_rows > QUERY1_MAX_ROWS) return false;
     std::lock_guard<std::mutex> lk(h->mu);
+    if (i8_stream_auto(h, 1, n_rows)) return false;  // RC_FILTER_I8_STREAM from its AUTO bound: the multi-kernel path reaches it
     DeviceScope ds(h->device);
     ensure_workspace(h, 1, k);
     Query1Args a{};
@@ -1199,12 +1235,17 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
         RC_REQUIRE(kind == RC_FILTER_NATIVE || kind == RC_FILTER_I8 || kind == RC_FILTER_F8 || kind == RC_FILTER_METRIC ||
-                       kind == RC_FILTER_F32,
-                   RC_ERR_INVALID, "filter must be RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8, RC_FILTER_METRIC or RC_FILTER_F32");
+                       kind == RC_FILTER_F32 || kind == RC_FILTER_I8_STREAM,
+                   RC_ERR_INVALID,
+                   "filter must be RC_FILTER_NATIVE, RC_FILTER_I8, RC_FILTER_F8, RC_FILTER_METRIC, RC_FILTER_F32 or RC_FILTER_I8_STREAM");
         std::lock_guard<std::mutex> lk(h->mu);
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
         if (kind == h->filter) return;
+        if (h->rows8 != nullptr && (kind == RC_FILTER_I8 || kind == RC_FILTER_I8_STREAM)) {
+            h->filter = kind;  // the two int8 kinds share the copy: no device call, nothing requantised
+            return;
+        }
         if (kind == RC_FILTER_NATIVE) {
             RC_HIP(hipDeviceSynchronize());  // no search may still read the copy
             free_filter(h);
@@ -1255,7 +1296,7 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
             free_filter(h);
             throw;
         }
-        h->filter = RC_FILTER_I8;
+        h->filter = kind;  // RC_FILTER_I8 or RC_FILTER_I8_STREAM: the same copy
     });
 }
 
@@ -1588,9 +1629,19 @@ int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t ro
         if (nq == 0 || n == 0) return;
         RC_REQUIRE(queries && out_scores && out_eps, RC_ERR_INVALID, "null buffer");
         std::lock_guard<std::mutex> lk(h->mu);
-        RC_REQUIRE(h->filter == RC_FILTER_F8 || h->filter == RC_FILTER_F32, RC_ERR_UNSUPPORTED,
-                   "filter scores are the float8 filter's (RC_FILTER_F8) and the float32 filter's (RC_FILTER_F32)");
+        RC_REQUIRE(h->filter == RC_FILTER_F8 || h->filter == RC_FILTER_F32 || h->filter == RC_FILTER_I8_STREAM, RC_ERR_UNSUPPORTED,
+                   "filter scores are the float8 filter's (RC_FILTER_F8), the float32 filter's (RC_FILTER_F32) and the streaming "
+                   "int8 filter's (RC_FILTER_I8_STREAM)");
         DeviceScope ds(h->device);
+        if (h->filter == RC_FILTER_I8_STREAM) {  // the keep test's left side u of up to 8 queries, and eps
+            RC_REQUIRE(nq <= I8_STREAM_MAX_QUERIES, RC_ERR_INVALID, "the streaming int8 filter takes at most 8 queries");
+            h->bws.ensure(nq, 16, h->ld, batch_query_bytes(h), I8_STREAM_MAX_QUERIES);
+            BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, row0 + n, h->row_base, h->row_stride, queries, nq, 16, nullptr, nullptr};
+            p.rows8 = h->rows8;
+            p.rsx = h->rsx;
+            p.rex = h->rex;
+            return filter_scores_i8_stream(p, h->bws, row0, n, out_scores, out_eps, (hipStream_t)stream);
+        }
         h->bws.ensure(nq, 16, h->ld, batch_query_bytes(h));
         BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, row0 + n, h->row_base, h->row_stride, queries, nq, 16, nullptr, nullptr};
         if (h->filter == RC_FILTER_F32) {  // s' and eps in cosine space, whatever the metric (p.metric stays cosine)

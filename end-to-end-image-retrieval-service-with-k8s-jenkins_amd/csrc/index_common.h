@@ -398,7 +398,9 @@ struct BatchWs {
     int *ovf = nullptr;         // overflowed queries since the last timing read (device counter)
     int fb_blocks = 0;               // blocks of the fallback scan: FB_BUDGET_BYTES / (nq_cap * k_cap * 8), clamped
     uint64_t *fb_partial = nullptr;  // [fb_blocks][nq_cap][k_cap] partial keys of the exact fallback scan
-    void ensure(int nq, int k, int64_t ld, int dtype_bytes);
+    // qtile: the query slots come in multiples of it (256, the MFMA filters' query tile; 8 for the
+    // streaming int8 filter, which has no such tile)
+    void ensure(int nq, int k, int64_t ld, int dtype_bytes, int qtile = 256);
     void release();
 };
 
@@ -424,6 +426,9 @@ struct BatchPlan {
     const uint32_t *mask = nullptr;
     // RC_SEARCH_MFMA_MASKED (mask != null): the filter kernels' MASKED forms apply the bitmap too
     bool mask_filter = false;
+    // RC_FILTER_I8_STREAM with nq <= I8_STREAM_MAX_QUERIES: the streaming int8 filter (filter_i8_stream.hip)
+    // over rows8 in place of filter_i8_kernel, on 8 query slots instead of 256
+    bool i8_stream = false;
     // float8 index with rc_index_set_filter(RC_FILTER_F8): the filter GEMM reads the stored e4m3 rows
     bool f8_filter = false;
     // float32 index with rc_index_set_filter(RC_FILTER_F32): the filter GEMM reads the stored f32 rows and
@@ -466,5 +471,13 @@ void launch_filter_f32(const BatchPlan &p, const BatchWs &ws, int nq_pad, int64_
                        hipStream_t s);
 void filter_scores_f32(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, float *out_scores, float *out_eps,
                        hipStream_t s);
+// The streaming int8 filter (filter_i8_stream.hip) for p.nq <= I8_STREAM_MAX_QUERIES queries prepared by
+// prepare_queries_i8_kernel on I8_STREAM_MAX_QUERIES slots: one dispatch over local rows [c0, c1), c0 a
+// multiple of 128 (dump != null: the DUMP form, the keep test's left side u into dump), and
+// rc_index_filter_scores' body (u [nq][n] and eps [nq]; search_mfma.hip).
+constexpr int I8_STREAM_MAX_QUERIES = 8;
+void launch_filter_i8_stream(const BatchPlan &p, const BatchWs &ws, int64_t c0, int64_t c1, float *dump, hipStream_t s);
+void filter_scores_i8_stream(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, float *out_scores, float *out_eps,
+                             hipStream_t s);
 
 }  // namespace rc

@@ -30,9 +30,10 @@
 // row tiles are readable), queries q̂ [nqb*256][ld] T (zero rows past nq).
 //
 // In this file: the query preparation, the int8 and float8 filter kernels, and every host function
-// (run_stages, the five filters' run_batched_*).  The native f16 / bf16 filter kernels and their
-// dispatch are filter_native.h's (their PAGED forms compile in search_mfma_paged.hip), the float32
-// filter is search_mfma_f32.hip's, the rescoring rescore.h's.
+// (run_stages, the filters' run_batched_*).  The native f16 / bf16 filter kernels and their dispatch
+// are filter_native.h's (their PAGED forms compile in search_mfma_paged.hip), the float32 filter is
+// search_mfma_f32.hip's, the streaming int8 filter's kernel filter_i8_stream.hip's, the rescoring
+// rescore.h's.
 #include <algorithm>
 #include <vector>
 
@@ -813,15 +814,17 @@ int batch_stage_ratio(int k, int cap, int inflation) {
 // The stages: stage 1 takes the first cap rows as candidates (thr = -inf), each later
 // stage filters the next g-times-larger row range against the running thresholds, then
 // rescore_kernel merges its candidates.  filter(c0, c1, nchunk) enqueues one filter
-// dispatch over rows [c0, c1) split into nchunk row chunks.
+// dispatch over rows [c0, c1) split into nchunk row chunks.  qtile: the query slots are a multiple
+// of it (BatchWs::ensure): SB_TILE for the MFMA filters, whose nchunk is sized for its query blocks.
 #if defined(RC_GEMM_ABLATION)
 int g_diag_filter_split_log2 = 31;
 int g_diag_filter_aux = 0;  // the int8 filter's row DMA cache policy (rc_diag_set_filter_aux)
 #endif
 template <typename T, typename F>
-void run_stages(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer, int g, int64_t row_bytes, F &&filter) {
-    const int nqb = (p.nq + SB_TILE - 1) / SB_TILE;
-    const int nq_pad = nqb * SB_TILE;
+void run_stages(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer, int g, int64_t row_bytes, F &&filter,
+                int qtile = SB_TILE) {
+    const int nqb = (p.nq + qtile - 1) / qtile;
+    const int nq_pad = nqb * qtile;
     RC_HIP(hipMemsetAsync(ws.keys, 0xFF, (size_t)p.nq * p.k * sizeof(uint64_t), s));
     RC_HIP(hipMemsetAsync(ws.cnt, 0, (size_t)nq_pad * sizeof(uint32_t), s));
     RC_HIP(hipMemsetAsync(ws.flags, 0, (size_t)p.nq * sizeof(int), s));
@@ -912,6 +915,29 @@ void run_batched_i8(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
         else hipLaunchKernelGGL((filter_i8_kernel<2, 128>), gr, bl, 0, s, fa);
     };
     run_stages<T>(p, ws, s, timer, batch_stage_ratio(p.k, ws.cap, I8_STAGE_INFLATION), p.ld, filter);
+}
+
+// RC_FILTER_I8_STREAM with 1 to 8 queries: the same preparation on 8 query slots, the same stage ratio and
+// rescoring, and filter_i8_stream.hip's kernel as the filter.  It sizes its own grid (the hook's nchunk
+// is a count of 256-query blocks' chunks) and does not read the mask: the rescoring applies it.
+template <typename T>
+void run_batched_i8_stream(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
+    hipLaunchKernelGGL(prepare_queries_i8_kernel, dim3(I8_STREAM_MAX_QUERIES), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn,
+                       (int8_t *)ws.qh, ws.sq, ws.aq, ws.eps, ws.thr);
+    RC_LAUNCH_CHECK();
+    auto filter = [&](int64_t c0, int64_t c1, int64_t, int) { launch_filter_i8_stream(p, ws, c0, c1, nullptr, s); };
+    run_stages<T>(p, ws, s, timer, batch_stage_ratio(p.k, ws.cap, I8_STAGE_INFLATION), p.ld, filter, I8_STREAM_MAX_QUERIES);
+}
+
+// rc_index_filter_scores under RC_FILTER_I8_STREAM: the keep test's left side u (DUMP form) and eps
+void filter_scores_i8_stream(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, float *out_scores, float *out_eps,
+                             hipStream_t s) {
+    RC_REQUIRE(i8_filter_supported(p.ld), RC_ERR_UNSUPPORTED, "int8 filter needs ld 256, 512 or 768");
+    hipLaunchKernelGGL(prepare_queries_i8_kernel, dim3(I8_STREAM_MAX_QUERIES), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn,
+                       (int8_t *)ws.qh, ws.sq, ws.aq, ws.eps, ws.thr);
+    RC_LAUNCH_CHECK();
+    launch_filter_i8_stream(p, ws, row0, row0 + n, out_scores, s);
+    RC_HIP(hipMemcpyAsync(out_eps, ws.eps, (size_t)p.nq * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
 
 // The float8 filter (filter_f8_kernel): two e4m3 query terms, no stage inflation.  ld 768 runs
@@ -1010,7 +1036,10 @@ void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
         RC_REQUIRE(i8_filter_supported(p.ld), RC_ERR_UNSUPPORTED, "int8 filter needs ld 256, 512 or 768");
         if (p.dtype == RC_F16 || p.dtype == RC_BF16 || p.dtype == RC_F32)
             return dispatch_dtype(p.dtype, [&](auto t) {  // (no batched search on f8 rows: nothing instantiated)
-                if constexpr (!std::is_same_v<decltype(t), f8_t>) run_batched_i8<decltype(t)>(p, ws, s, timer);
+                if constexpr (!std::is_same_v<decltype(t), f8_t>) {
+                    if (p.i8_stream) run_batched_i8_stream<decltype(t)>(p, ws, s, timer);
+                    else run_batched_i8<decltype(t)>(p, ws, s, timer);
+                }
             });
     }
     if (p.dtype == RC_F16 || p.dtype == RC_BF16)  // the MFMA operand dtypes
@@ -1020,11 +1049,11 @@ void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
     throw Error(RC_ERR_UNSUPPORTED, "batched MFMA search needs an f16 or bf16 index (or the int8 filter copy)");
 }
 
-void BatchWs::ensure(int nq, int k, int64_t ld, int dtype_bytes) {
-    const int nq_pad = (nq + SB_TILE - 1) / SB_TILE * SB_TILE;
+void BatchWs::ensure(int nq, int k, int64_t ld, int dtype_bytes, int qtile) {
+    const int nq_pad = (nq + qtile - 1) / qtile * qtile;
     if (nq_pad <= nq_cap && k <= k_cap && ld <= ld_cap) return;
     release();
-    nq_cap = std::max(nq_pad, 256);
+    nq_cap = nq_pad;
     k_cap = std::max(k, 16);
     ld_cap = ld;
     qn = (float *)dmalloc((size_t)nq_cap * ld * sizeof(float));

@@ -1148,6 +1148,8 @@ void query_host_checked(rc_sharded *h, const float *queries, int nq, int64_t n_r
         if (slot < 0 && h->n == 1 && nq == 1 && mask == nullptr) {
             // the request path: one launch pair (query in the kernel arguments, results written
             // straight into the pinned block), no copies; the host polls the completion word
+            // (refused, as for a shape outside its range, by a shard whose filter is RC_FILTER_I8_STREAM once the
+            // rows reach that filter's AUTO bound: the multi-kernel path below then takes the streaming filter)
             float *hs = (float *)(h->qh + L.sc);
             int64_t *hr = (int64_t *)(h->qh + L.rw);
             float *hv = (float *)(h->qh + L.val);

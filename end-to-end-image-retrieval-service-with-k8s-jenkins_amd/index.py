@@ -170,8 +170,10 @@ class DeviceIndex:
         a bound on the metric's own score, which is what gives a non-cosine index
         ``mode="mfma"``; no copy) or "f32" (a float32 index only: the filter GEMM reads the stored
         f32 rows and rounds them to f16 in registers, its bound carrying the rounding; no copy,
-        every metric; it is what gives a float32 index ``mode="mfma"`` on its own rows).  "i8" and
-        "f8" are cosine-only.  Results never change — candidates are rescored exactly on the
+        every metric; it is what gives a float32 index ``mode="mfma"`` on its own rows) or
+        "i8_stream" ("i8" in every respect, the same copy, plus a streaming int8 filter kernel that
+        ``mode="mfma"`` runs for 1 to 8 queries; switching between the two keeps the copy).  "i8",
+        "i8_stream" and "f8" are cosine-only.  Results never change — candidates are rescored exactly on the
         stored rows."""
         if kind not in _lib.FILTERS:
             raise ValueError(f"unknown filter {kind!r} (expected one of {sorted(_lib.FILTERS)})")
@@ -194,7 +196,9 @@ class DeviceIndex:
         """What the "f8" or the "f32" filter computes (rc_index_filter_scores): its scores ``s'``
         of the queries against local rows [row0, row0 + n) (``row0`` a multiple of 128), f32
         [nq, n], and each query's bound ``eps`` on ``|s' - exact score|`` (the cosine, whatever
-        the metric), f32 [nq].  Raises unless the filter kind is "f8" or "f32"."""
+        the metric), f32 [nq].  Under "i8_stream" (at most 8 queries): the left side ``u`` of the
+        streaming kernel's keep test ``u >= kth - eps`` and ``eps``.  Raises unless the filter
+        kind is "f8", "f32" or "i8_stream"."""
         q = self._vecs(queries)
         out = torch.empty((q.shape[0], int(n)), dtype=torch.float32, device=self.device)
         eps = torch.empty((q.shape[0],), dtype=torch.float32, device=self.device)
@@ -1100,7 +1104,7 @@ class Index:
     metric is a scoring rule over unchanged storage: ``upsert``, ``fetch``, ``delete``,
     ``query(id=...)`` and metadata filters work alike under all three, and ``save`` / ``load``
     keep it.  By default the batched MFMA search is cosine-only: a non-cosine index scans,
-    ``mode="mfma"`` and ``filter="i8"`` raise ``ValueError`` on it.  ``filter="metric"`` (an
+    ``mode="mfma"``, ``filter="i8"`` and ``filter="i8_stream"`` raise ``ValueError`` on it.  ``filter="metric"`` (an
     f16/bf16 index) gives it the batched search — ``mode="mfma"``, and ``"auto"`` under the
     usual conditions — with the scan's ids and score bits, and ``filter="f32"`` does the same
     for a float32 index.  All-zero vectors and queries are rejected under every metric.
@@ -1110,13 +1114,13 @@ class Index:
     rounded to 3 mantissa bits).  A float8 index scans by default (``mode="mfma"`` raises
     ``ValueError``, ``"auto"`` scans); ``filter="f8"`` gives it the batched search on the
     block-scaled fp8 MFMA (cosine, dimensions up to 768), with unchanged results.
-    ``filter="i8"`` raises on it, ``filter="f8"`` on every other dtype.  A float32 index (the
+    ``filter="i8"`` and ``filter="i8_stream"`` raise on it, ``filter="f8"`` on every other dtype.  A float32 index (the
     default) has no batched search of its own rows either (``mode="mfma"`` raises, ``"auto"``
     scans) until ``filter="f32"``: the filter GEMM then streams the stored float32 rows and rounds
     them to f16 on their way to the matrix cores, with the rounding inside its error bound — no
-    copy of the rows (``filter="i8"`` keeps one, and is cosine-only), every metric, dimensions up
+    copy of the rows (``filter="i8"`` and ``"i8_stream"`` keep one, and are cosine-only), every metric, dimensions up
     to 128, 256, 512 or 768 after rounding up to 128, unchanged results.  ``filter="f32"`` raises
-    on every other dtype, and with ``paged_search="mfma"``.
+    on every other dtype, and with ``paged_search="mfma"``, as ``"i8"`` and ``"i8_stream"`` do.
 
     ``upsert(vectors)`` accepts ``(id, values)``, ``(id, values, metadata)``
     tuples or ``{"id", "values", "metadata"}`` dicts and overwrites existing
@@ -1133,9 +1137,10 @@ class Index:
     same vectors.  Capacity grows on demand (doubling), as a Pinecone index
     has no fixed size.
 
-    Two things are called "filter" here.  The constructor's ``filter="native" | "i8" | "f8" | "metric" | "f32"`` is
-    the kind of filter GEMM the batched search runs (``DeviceIndex.set_filter``); it never
-    changes a result.  ``query(..., filter={...})`` / ``query_batch(..., filter={...})`` is
+    Two things are called "filter" here.  The constructor's
+    ``filter="native" | "i8" | "i8_stream" | "f8" | "metric" | "f32"`` is the kind of filter the batched
+    search runs (``DeviceIndex.set_filter``; "i8_stream" is "i8" plus a streaming kernel for 1 to 8
+    queries, refused wherever "i8" is); it never changes a result.  ``query(..., filter={...})`` / ``query_batch(..., filter={...})`` is
     Pinecone's metadata filter (``metafilter``): only vectors whose metadata satisfies it can
     be returned, and the restriction happens inside the exact search (a row-eligibility
     bitmap the masked scan takes), so the top-k of the eligible vectors is exact however
@@ -1217,7 +1222,7 @@ class Index:
         _deep_select_kind(deep_select)
         if paged_search not in ("scan", "mfma"):
             raise ValueError(f"unknown paged_search {paged_search!r} (expected 'scan' or 'mfma')")
-        if paged_search == "mfma" and (_lib.is_f8(dtype) or dtype in ("float32", "f32") or filter in ("i8", "f8", "f32")):
+        if paged_search == "mfma" and (_lib.is_f8(dtype) or dtype in ("float32", "f32") or filter in ("i8", "i8_stream", "f8", "f32")):
             raise ValueError("paged_search='mfma' runs the native f16 / bf16 kernels over pages: it needs dtype float16 or "
                              f"bfloat16 and filter 'native' or 'metric' (dtype={dtype!r}, filter={filter!r})")
         if metric not in _lib.METRICS:
@@ -1229,8 +1234,8 @@ class Index:
                              "(filter='f32' on a float32 index)")
         if filter == "metric" and (_lib.is_f8(dtype) or dtype in ("float32", "f32")):
             raise ValueError(f"filter='metric' reads stored f16 / bf16 rows: it needs dtype float16 or bfloat16 (dtype={dtype!r})")
-        if _lib.is_f8(dtype) and filter == "i8":
-            raise ValueError("filter='i8' is not available on a float8 index (its batched search is filter='f8')")
+        if _lib.is_f8(dtype) and filter in ("i8", "i8_stream"):
+            raise ValueError(f"filter={filter!r} is not available on a float8 index (its batched search is filter='f8')")
         if filter == "f8" and not _lib.is_f8(dtype):
             raise ValueError(f"filter='f8' reads stored float8 rows: it needs dtype='f8' (dtype={dtype!r})")
         if filter == "f32" and dtype not in ("float32", "f32"):
@@ -1945,8 +1950,9 @@ class Index:
         elif self.metric != "cosine":  # the "metric" filter's corner, as the library's unmasked "auto"
             size_ok = per_shard >= 65536 and (nq >= 16 or (nq >= 8 and per_shard * self._set.ld * 2 >= 1 << 28))
         else:
-            mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter == "i8"
-            size_ok = mfma_ok and nq >= 8 and per_shard >= 65536
+            mfma_ok = self._set.dtype not in ("float32", "f32") or self._set.filter in ("i8", "i8_stream")
+            # (8 queries under "i8_stream" are its streaming kernel's, which has no measured masked corner)
+            size_ok = mfma_ok and nq >= (9 if self._set.filter == "i8_stream" else 8) and per_shard >= 65536
             if self._set.filter == "f32":  # the widths it serves, and where every measured unmasked cell is ahead of the scan
                 size_ok = self._set.ld in (128, 256, 512, 768) and nq >= 16 and per_shard >= 262144
         if size_ok and eligible >= MASKED_MFMA_MIN_SHARE * n:

@@ -229,12 +229,27 @@ int rc_index_search_masked(rc_index *h, const float *queries, int nq, int64_t n_
  *                      768: on another width RC_SEARCH_MFMA is RC_ERR_UNSUPPORTED (the
  *                      message names the width) and RC_SEARCH_AUTO scans.  It allocates
  *                      nothing; RC_FILTER_NATIVE switches it off, RC_FILTER_I8 replaces it
- *                      (cosine only).  All three metrics may be set on it.  No paged form. */
+ *                      (cosine only).  All three metrics may be set on it.  No paged form.
+ *   RC_FILTER_I8_STREAM — RC_FILTER_I8 in every respect (the same int8 copy, maintained alike; the
+ *                      same refusals: cosine only, not on an RC_F8 index, row widths 256, 512 or
+ *                      768, no paged form; the same kernels for 9 or more queries), plus a
+ *                      filter kernel of its own for 1 to 8 queries: an HBM-bound stream over the
+ *                      int8 copy (ld + 8 bytes per row instead of the stored row) with a packed
+ *                      int8 dot per (query, row) and RC_FILTER_I8's keep rule, the candidates
+ *                      rescored exactly on the stored rows.  With 1 to 8 queries RC_SEARCH_MFMA
+ *                      runs it (a mask is applied by the rescoring), RC_SEARCH_MFMA_MASKED with a
+ *                      mask keeps the MFMA kernel, and RC_SEARCH_AUTO without a mask takes it where
+ *                      it measured at least 1.10x ahead of the scan (row widths 512 and 768 only: 4 or more queries from 2^20
+ *                      rows; on an RC_F32 index any count from 2^22 rows) and scans elsewhere,
+ *                      row width 256, which was not measured, included.  Rows
+ *                      and score bits are the scan's.  Switching between RC_FILTER_I8 and
+ *                      RC_FILTER_I8_STREAM keeps the copy: nothing is requantised or allocated. */
 #define RC_FILTER_NATIVE 0
 #define RC_FILTER_I8 1
 #define RC_FILTER_F8 2
 #define RC_FILTER_METRIC 3
 #define RC_FILTER_F32 4
+#define RC_FILTER_I8_STREAM 5
 int rc_index_set_filter(rc_index *h, int kind, void *stream);
 int rc_index_get_filter(const rc_index *h, int *kind);
 /* What the RC_FILTER_F8 or the RC_FILTER_F32 filter computes (a diagnostic: no reference counterpart).  Runs the
@@ -243,8 +258,11 @@ int rc_index_get_filter(const rc_index *h, int *kind);
  * e4m3 query against the stored rows, or the f16 query against the f16-rounded f32 rows (in
  * cosine space, whatever the index's metric), before any threshold — to out_scores (device f32
  * [nq][n]) and each query's bound on |s' − exact score| to out_eps (device f32 [nq]).
- * queries: device f32 [nq][dim].  RC_ERR_UNSUPPORTED unless the filter kind is RC_FILTER_F8 or
- * RC_FILTER_F32. */
+ * queries: device f32 [nq][dim].  Under RC_FILTER_I8_STREAM (nq <= 8, else RC_ERR_INVALID) the
+ * streaming kernel's own dot and reduction run, out_scores holds the keep test's left side
+ * u = sq·(sx·D) + ex·aq of each (query, row) — an upper bound of the exact cosine up to eps — and
+ * out_eps the query's eps; a row is kept iff u >= k-th best − eps.  RC_ERR_UNSUPPORTED unless the
+ * filter kind is RC_FILTER_F8, RC_FILTER_F32 or RC_FILTER_I8_STREAM (RC_FILTER_I8 stays refused). */
 int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t row0, int64_t n, float *out_scores,
                            float *out_eps, void *stream);
 
