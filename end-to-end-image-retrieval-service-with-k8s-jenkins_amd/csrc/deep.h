@@ -55,15 +55,12 @@ struct DeepStream {
 // candidate counts — its candidate lists are the caller's k output slots.  Grows, never shrinks.
 struct DeepSel {
     int nq_cap = 0;
-    int64_t keys_cap = 0;
-    uint64_t *partial = nullptr;  // [DEEP_SELECT_BLOCKS][nq_cap][RC_TOPK_MAX]
-    uint64_t *lower = nullptr;    // [nq_cap]
-    uint64_t *keys = nullptr;     // [keys_cap]
-    int radix_cap = 0;
-    uint32_t *radix = nullptr;  // deep_radix.hip's RadixWs for radix_cap queries
+    DevBuf<uint64_t> partial;  // [DEEP_SELECT_BLOCKS][nq_cap][RC_TOPK_MAX]
+    DevBuf<uint64_t> lower;    // [nq_cap]
+    DevBuf<uint64_t> keys;     // the nkeys of the largest ensure
+    DevBuf<uint32_t> radix;    // deep_radix.hip's RadixWs for the most queries of a radix call
     void ensure(int nq, int64_t nkeys);
     void ensure_radix(int nq);
-    void release();
 };
 constexpr int DEEP_SELECT_BLOCKS = 256;  // partial lists per query, at most
 constexpr int DEEP_RADIX_BINS = 4096;    // a digit is at most 12 bits: a block's histogram is 16 KB of LDS

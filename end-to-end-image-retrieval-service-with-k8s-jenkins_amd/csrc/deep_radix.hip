@@ -293,12 +293,7 @@ void launch_sort(int nq, int k, uint32_t *base, uint64_t *out_keys, hipStream_t 
 }  // namespace
 
 void DeepSel::ensure_radix(int nq) {
-    if (nq <= radix_cap) return;
-    dfree(radix);
-    radix = nullptr;
-    radix_cap = 0;
-    radix = (uint32_t *)dmalloc(radix_ws_words(nq) * sizeof(uint32_t));
-    radix_cap = nq;
+    radix.reserve(radix_ws_words(nq));  // grows with nq
 }
 
 void deep_select_radix(const DeepStream &st, DeepSel &ws, int nq, int k, uint64_t *out_keys, hipStream_t s) {
@@ -323,24 +318,24 @@ void deep_select_radix(const DeepStream &st, DeepSel &ws, int nq, int k, uint64_
     nblk = (int)((st.n + per_block - 1) / per_block);
     const bool lists = st.keys != nullptr;
     const int64_t nh = (int64_t)plan.npass * nq * DEEP_RADIX_BINS;
-    hipLaunchKernelGGL(radix_init_kernel, dim3((unsigned)std::min<int64_t>(1024, (nh + 255) / 256)), dim3(256), 0, s, ws.radix, nq,
+    hipLaunchKernelGGL(radix_init_kernel, dim3((unsigned)std::min<int64_t>(1024, (nh + 255) / 256)), dim3(256), 0, s, ws.radix.get(), nq,
                        plan.npass, k);
     RC_LAUNCH_CHECK();
     for (int p = 0; p < plan.npass; ++p) {
-        if (lists) hipLaunchKernelGGL(radix_pass_kernel<true>, dim3(nblk, nq), dim3(RADIX_THREADS), 0, s, st, per_block, nq, p, plan, ws.radix);
-        else hipLaunchKernelGGL(radix_pass_kernel<false>, dim3(nblk, nq), dim3(RADIX_THREADS), 0, s, st, per_block, nq, p, plan, ws.radix);
+        if (lists) hipLaunchKernelGGL(radix_pass_kernel<true>, dim3(nblk, nq), dim3(RADIX_THREADS), 0, s, st, per_block, nq, p, plan, ws.radix.get());
+        else hipLaunchKernelGGL(radix_pass_kernel<false>, dim3(nblk, nq), dim3(RADIX_THREADS), 0, s, st, per_block, nq, p, plan, ws.radix.get());
         RC_LAUNCH_CHECK();
     }
     if (lists)
-        hipLaunchKernelGGL(radix_compact_kernel<true>, dim3(nblk, nq), dim3(RADIX_THREADS), 0, s, st, per_block, nq, k, plan, ws.radix, out_keys);
+        hipLaunchKernelGGL(radix_compact_kernel<true>, dim3(nblk, nq), dim3(RADIX_THREADS), 0, s, st, per_block, nq, k, plan, ws.radix.get(), out_keys);
     else
-        hipLaunchKernelGGL(radix_compact_kernel<false>, dim3(nblk, nq), dim3(RADIX_THREADS), 0, s, st, per_block, nq, k, plan, ws.radix, out_keys);
+        hipLaunchKernelGGL(radix_compact_kernel<false>, dim3(nblk, nq), dim3(RADIX_THREADS), 0, s, st, per_block, nq, k, plan, ws.radix.get(), out_keys);
     RC_LAUNCH_CHECK();
     // the LDS the sort asks for follows k: 4 KB to 128 KB
-    if (k <= 512) launch_sort<512>(nq, k, ws.radix, out_keys, s);
-    else if (k <= 2048) launch_sort<2048>(nq, k, ws.radix, out_keys, s);
-    else if (k <= 8192) launch_sort<8192>(nq, k, ws.radix, out_keys, s);
-    else launch_sort<DEEP_RADIX_SORT_MAX>(nq, k, ws.radix, out_keys, s);
+    if (k <= 512) launch_sort<512>(nq, k, ws.radix.get(), out_keys, s);
+    else if (k <= 2048) launch_sort<2048>(nq, k, ws.radix.get(), out_keys, s);
+    else if (k <= 8192) launch_sort<8192>(nq, k, ws.radix.get(), out_keys, s);
+    else launch_sort<DEEP_RADIX_SORT_MAX>(nq, k, ws.radix.get(), out_keys, s);
     RC_LAUNCH_CHECK();
 }
 

@@ -104,33 +104,12 @@ __global__ __launch_bounds__(256) void deep_emit_kernel(const uint64_t *__restri
 
 void DeepSel::ensure(int nq, int64_t nkeys) {
     if (nq > nq_cap) {
-        dfree(partial);
-        dfree(lower);
-        partial = lower = nullptr;
         nq_cap = 0;
-        partial = (uint64_t *)dmalloc((size_t)DEEP_SELECT_BLOCKS * nq * RC_TOPK_MAX * sizeof(uint64_t));
-        lower = (uint64_t *)dmalloc((size_t)nq * sizeof(uint64_t));
+        partial.reserve((size_t)DEEP_SELECT_BLOCKS * nq * RC_TOPK_MAX);
+        lower.reserve((size_t)nq);
         nq_cap = nq;
     }
-    if (nkeys > keys_cap) {
-        dfree(keys);
-        keys = nullptr;
-        keys_cap = 0;
-        keys = (uint64_t *)dmalloc((size_t)nkeys * sizeof(uint64_t));
-        keys_cap = nkeys;
-    }
-}
-
-void DeepSel::release() {
-    dfree(partial);
-    dfree(lower);
-    dfree(keys);
-    dfree(radix);
-    partial = lower = keys = nullptr;
-    radix = nullptr;
-    nq_cap = 0;
-    keys_cap = 0;
-    radix_cap = 0;
+    keys.reserve((size_t)nkeys);
 }
 
 void deep_select_rounds(const DeepStream &st, DeepSel &ws, int nq, int k, uint64_t *out_keys, hipStream_t s) {
@@ -146,15 +125,15 @@ void deep_select_rounds(const DeepStream &st, DeepSel &ws, int nq, int k, uint64
     int64_t per_block = (st.n + nblk - 1) / nblk;
     per_block = (per_block + 31) / 32 * 32;
     nblk = (int)((st.n + per_block - 1) / per_block);
-    RC_HIP(hipMemsetAsync(ws.lower, 0, (size_t)nq * sizeof(uint64_t), s));  // round 0 admits every key
+    RC_HIP(hipMemsetAsync(ws.lower.get(), 0, (size_t)nq * sizeof(uint64_t), s));  // round 0 admits every key
     for (int off = 0; off < k; off += RC_TOPK_MAX) {
         const int kr = std::min(RC_TOPK_MAX, k - off);
         if (st.keys != nullptr)
-            hipLaunchKernelGGL(select_after_kernel<true>, dim3(nblk, nq), dim3(256), 0, s, st, per_block, nq, kr, ws.lower, ws.partial);
+            hipLaunchKernelGGL(select_after_kernel<true>, dim3(nblk, nq), dim3(256), 0, s, st, per_block, nq, kr, ws.lower.get(), ws.partial.get());
         else
-            hipLaunchKernelGGL(select_after_kernel<false>, dim3(nblk, nq), dim3(256), 0, s, st, per_block, nq, kr, ws.lower, ws.partial);
+            hipLaunchKernelGGL(select_after_kernel<false>, dim3(nblk, nq), dim3(256), 0, s, st, per_block, nq, kr, ws.lower.get(), ws.partial.get());
         RC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(select_finish_kernel, dim3(nq), dim3(256), 0, s, ws.partial, nblk, nq, kr, ws.lower, out_keys, (int64_t)k,
+        hipLaunchKernelGGL(select_finish_kernel, dim3(nq), dim3(256), 0, s, ws.partial.get(), nblk, nq, kr, ws.lower.get(), out_keys, (int64_t)k,
                            (int64_t)off);
         RC_LAUNCH_CHECK();
     }

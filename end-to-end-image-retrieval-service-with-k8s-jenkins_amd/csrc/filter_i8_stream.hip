@@ -172,11 +172,11 @@ __global__ __launch_bounds__(256) void filter_i8_stream_kernel(FilterI8StreamArg
 void launch_filter_i8_stream(const BatchPlan &p, const BatchWs &ws, int64_t c0, int64_t c1, float *dump, hipStream_t s) {
     RC_REQUIRE(p.nq >= 1 && p.nq <= I8_STREAM_MAX_QUERIES, RC_ERR_INVALID, "internal: the streaming int8 filter takes 1 to 8 queries");
     RC_REQUIRE(c0 % I8S_TILE == 0 && c0 < c1, RC_ERR_INVALID, "internal: streaming int8 filter range not tile-aligned");
-    FilterI8StreamArgs fa{FilterArgs{p.rows8, ws.qh, p.ld, 0, c0, c1, 0, 1, ws.thr, ws.cnt, ws.cand, ws.cap}, dump, p.nq};
+    FilterI8StreamArgs fa{FilterArgs{p.rows8, ws.qh.get(), p.ld, 0, c0, c1, 0, 1, ws.thr.get(), ws.cnt.get(), ws.cand.get(), ws.cap}, dump, p.nq};
     fa.a.rsx = p.rsx;
     fa.a.rex = p.rex;
-    fa.a.sq = ws.sq;
-    fa.a.aq = ws.aq;
+    fa.a.sq = ws.sq.get();
+    fa.a.aq = ws.aq.get();
     const int64_t nt = (c1 - c0 + I8S_TILE - 1) / I8S_TILE;
     auto launch = [&](auto ld, auto nq) {
         constexpr int LD = decltype(ld)::value, NQ = decltype(nq)::value;

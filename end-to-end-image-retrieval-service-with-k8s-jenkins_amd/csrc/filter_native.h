@@ -541,9 +541,9 @@ template <typename T, bool PAGED>
 void launch_filter_native(const BatchPlan &p, const BatchWs &ws, int64_t c0, int64_t c1, int64_t nchunk, int nqb, hipStream_t s) {
     const int nkt = (int)(p.ld / 64);
     const bool qs = nkt == 2 || nkt == 4 || nkt == 8;
-    const FilterNativeArgs fa{FilterArgs{p.rows, ws.qh, p.ld, nkt, c0, c1, tiles_per_chunk(c0, c1, qs ? QS_RT : SB_TILE, nchunk), nqb,
-                                         ws.thr, ws.cnt, ws.cand, ws.cap},
-                              FilterMetric{p.norms, ws.mcoef}, p.mask, p.pages};
+    const FilterNativeArgs fa{FilterArgs{p.rows, ws.qh.get(), p.ld, nkt, c0, c1, tiles_per_chunk(c0, c1, qs ? QS_RT : SB_TILE, nchunk), nqb,
+                                         ws.thr.get(), ws.cnt.get(), ws.cand.get(), ws.cap},
+                              FilterMetric{p.norms, ws.mcoef.get()}, p.mask, p.pages};
     const dim3 gr((unsigned)(nchunk * nqb)), bl(512);
     auto launch = [&](auto metric, auto masked) {
         constexpr bool ME = decltype(metric)::value, MA = decltype(masked)::value;

@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "deep.h"
@@ -371,17 +372,17 @@ struct rc_index {
     int64_t row_base = 0;    // a search returns row_base + local row * row_stride (shard → global rows)
     int64_t row_stride = 1;
     int ncu = 256;           // compute units of the device (scan grid rounds)
-    void *rows = nullptr;
-    float *norms = nullptr;
+    DevBuf<void> rows;
+    DevBuf<float> norms;
     // int8 filter copy (RC_FILTER_I8): [cap_pad][ld] x8, sx / ex [cap_pad] at i8_slot(row)
     int filter = RC_FILTER_NATIVE;
     int metric = RC_METRIC_COSINE;  // scoring rule of the searches (rc_index_set_metric); storage does not depend on it
-    int8_t *rows8 = nullptr;
-    float *rsx = nullptr, *rex = nullptr;
+    DevBuf<int8_t> rows8;
+    DevBuf<float> rsx, rex;
     // search workspace
     int ws_nq = 0, ws_k = 0, ws_nblk = 0;
-    float *qn = nullptr;
-    uint64_t *partial = nullptr;
+    DevBuf<float> qn;
+    DevBuf<uint64_t> partial;
     unsigned *q1_done = nullptr;    // host-coherent completion word of the polled query1 path
     unsigned q1_seq = 0;
     BatchWs bws;         // batched MFMA search workspace (search_mfma.hip)
@@ -389,20 +390,20 @@ struct rc_index {
     KernelTimer gtimer;  // the batched search's filter launches, whichever filter kernel (flops)
     // page tables (rc_index_pages_set), by slot: one device allocation each, doubled when it grows
     struct PageTable {
-        int32_t *dev = nullptr;
-        int n_pages = 0, cap = 0;
+        DevBuf<int32_t> dev;
+        int n_pages = 0;
     };
     std::vector<PageTable> tables;
-    int64_t *pg_rows = nullptr;  // [pg_rows_cap] local rows of a paged value gather
-    int64_t pg_rows_cap = 0;
+    DevBuf<int64_t> pg_rows;  // local rows of a paged value gather
     // deep top-k (rc_index_search_deep): the score arrays of the queries in flight and the selection's workspace
-    float *dscores = nullptr;  // [dscores_cap]
-    int64_t dscores_cap = 0;
+    DevBuf<float> dscores;
     DeepSel dsel;
     int deep_select = RC_DEEP_SELECT_ROUNDS;  // the selection of the deep and hybrid calls (rc_index_set_deep_select)
     // sparse-dense hybrid (rc_index_sparse_enable): the store, [width][capacity] slot-major, and the staging of
     // sparse queries and store writes
-    SparseStore sparse;
+    SparseStore sparse;  // the view the kernels get of sp_idx / sp_val
+    DevBuf<uint32_t> sp_idx;
+    DevBuf<float> sp_val;
     SparseWs sws;
 };
 
@@ -520,12 +521,11 @@ int pick_nch(int dim, int dtype) {
 void ensure_workspace(rc_index *h, int nq, int k) {
     if (nq <= h->ws_nq && k <= h->ws_k) return;
     const int nq2 = std::max(nq, h->ws_nq), k2 = std::max(k, h->ws_k);
-    dfree(h->qn);
-    dfree(h->partial);
-    h->qn = nullptr;
-    h->partial = nullptr;
-    h->qn = (float *)dmalloc((size_t)nq2 * h->ld * sizeof(float));
-    h->partial = (uint64_t *)dmalloc((size_t)kMaxBlocks * nq2 * k2 * sizeof(uint64_t));
+    h->ws_nq = h->ws_k = 0;
+    h->qn.reset();
+    h->partial.reset();
+    h->qn.reserve((size_t)nq2 * h->ld);
+    h->partial.reserve((size_t)kMaxBlocks * nq2 * k2);
     h->ws_nq = nq2;
     h->ws_k = k2;
 }
@@ -535,26 +535,24 @@ int64_t cap_pad(int64_t capacity) { return (capacity + INDEX_ROW_PAD - 1) / INDE
 // refresh the int8 filter copy of rows slots[0..n) (or row0 .. row0 + n) after a write
 template <typename T>
 void launch_quantize(rc_index *h, const int64_t *slots, int64_t row0, int64_t n, hipStream_t s) {
-    if (h->rows8 == nullptr || n == 0) return;
+    if (h->rows8.empty() || n == 0) return;
     const unsigned grid = (unsigned)std::min<int64_t>((n + 3) / 4, 256 * 32);
-    hipLaunchKernelGGL(quantize_rows_kernel<T>, dim3(grid), dim3(256), 0, s, (const T *)h->rows, h->ld, slots, row0, n,
-                       h->capacity, h->rows8, h->rsx, h->rex);
+    hipLaunchKernelGGL(quantize_rows_kernel<T>, dim3(grid), dim3(256), 0, s, (const T *)h->rows.get(), h->ld, slots, row0, n,
+                       h->capacity, h->rows8.get(), h->rsx.get(), h->rex.get());
     RC_LAUNCH_CHECK();
 }
 
 void free_filter(rc_index *h) {
-    dfree(h->rows8);
-    dfree(h->rsx);
-    dfree(h->rex);
-    h->rows8 = nullptr;
-    h->rsx = h->rex = nullptr;
+    h->rows8.reset();
+    h->rsx.reset();
+    h->rex.reset();
     h->filter = RC_FILTER_NATIVE;
 }
 
 template <typename T>
 void launch_upsert(rc_index *h, const float *vecs, const int64_t *src_idx, int64_t n, const int64_t *slots, hipStream_t s) {
     const unsigned grid = (unsigned)((n + 3) / 4);
-    hipLaunchKernelGGL(upsert_kernel<T>, dim3(grid), dim3(256), 0, s, (T *)h->rows, h->norms, h->ld, h->dim, vecs, src_idx,
+    hipLaunchKernelGGL(upsert_kernel<T>, dim3(grid), dim3(256), 0, s, (T *)h->rows.get(), h->norms.get(), h->ld, h->dim, vecs, src_idx,
                        slots, n, h->capacity);
     RC_LAUNCH_CHECK();
     launch_quantize<T>(h, slots, 0, n, s);
@@ -567,9 +565,9 @@ template <typename T>
 void launch_move_rows(rc_index *from, const int64_t *src_idx, rc_index *to, const int64_t *dst_idx, const RowBlock &stage,
                       int64_t n, hipStream_t s) {
     const unsigned grid = (unsigned)std::min<int64_t>((n + 3) / 4, kMaxBlocks);
-    hipLaunchKernelGGL(move_rows_kernel<T>, dim3(grid), dim3(256), 0, s, (const T *)(from ? from->rows : stage.rows),
-                       (const float *)(from ? from->norms : stage.norms), src_idx, from ? from->capacity : stage.cap,
-                       (T *)(to ? to->rows : stage.rows), to ? to->norms : stage.norms, dst_idx,
+    hipLaunchKernelGGL(move_rows_kernel<T>, dim3(grid), dim3(256), 0, s, (const T *)(from ? from->rows.get() : stage.rows),
+                       (const float *)(from ? from->norms.get() : stage.norms), src_idx, from ? from->capacity : stage.cap,
+                       (T *)(to ? to->rows.get() : stage.rows), to ? to->norms.get() : stage.norms, dst_idx,
                        to ? to->capacity : stage.cap, (from ? from : to)->ld, n);
     RC_LAUNCH_CHECK();
     if (to != nullptr) launch_quantize<T>(to, dst_idx, 0, n, s);
@@ -578,7 +576,7 @@ void launch_move_rows(rc_index *from, const int64_t *src_idx, rc_index *to, cons
 template <typename T>
 void launch_fetch(rc_index *h, const int64_t *slots, int64_t n, float *out, bool stored, hipStream_t s) {
     const unsigned grid = (unsigned)((n + 3) / 4);
-    hipLaunchKernelGGL(fetch_kernel<T>, dim3(grid), dim3(256), 0, s, (const T *)h->rows, stored ? nullptr : h->norms, h->ld,
+    hipLaunchKernelGGL(fetch_kernel<T>, dim3(grid), dim3(256), 0, s, (const T *)h->rows.get(), stored ? nullptr : h->norms.get(), h->ld,
                        h->dim, slots, n, out, h->capacity);
     RC_LAUNCH_CHECK();
 }
@@ -587,7 +585,7 @@ template <typename T>
 void launch_fill(rc_index *h, uint64_t seed, int64_t row0, int64_t n, hipStream_t s) {
     const unsigned grid = (unsigned)std::min<int64_t>((n + 3) / 4, 256 * 32);
     if (grid == 0) return;
-    hipLaunchKernelGGL(fill_random_kernel<T>, dim3(grid), dim3(256), 0, s, (T *)h->rows, h->norms, h->ld, h->dim, seed, row0, n);
+    hipLaunchKernelGGL(fill_random_kernel<T>, dim3(grid), dim3(256), 0, s, (T *)h->rows.get(), h->norms.get(), h->ld, h->dim, seed, row0, n);
     RC_LAUNCH_CHECK();
     launch_quantize<T>(h, nullptr, row0, n, s);
 }
@@ -646,24 +644,24 @@ void scan_search(rc_index *h, const float *queries, int nq, int64_t n_rows, int 
     if (h->timer.enabled) h->timer.create();
     for (int q0 = 0; q0 < nq_pad; q0 += qb) {
         const int slot = h->timer.begin(s);
-        ScanArgs a{h->rows, h->ld, h->nch, n_rows, rpb, nblk, h->qn, q0, qb, nq_pad, k, h->partial, s};
+        ScanArgs a{h->rows.get(), h->ld, h->nch, n_rows, rpb, nblk, h->qn.get(), q0, qb, nq_pad, k, h->partial.get(), s};
         a.qraw = queries;
         a.dim = h->dim;
         a.nq_real = nq;
         a.mask = mask;
         a.metric = h->metric;  // non-cosine: the metric kernels, which also read the norms
-        a.norms = h->norms;
+        a.norms = h->norms.get();
         if (pages != nullptr) launch_scan_paged(h, a, pages);
         else launch_scan(h, a);
         h->timer.end(slot, s, bytes);
     }
-    launch_merge_partials(h, h->partial, nullptr, nblk, nq, nq_pad, k, scores, out_rows, s);
+    launch_merge_partials(h, h->partial.get(), nullptr, nblk, nq, nq_pad, k, scores, out_rows, s);
 }
 
 // RC_FILTER_I8_STREAM's own kernel serves this request (else the kind is RC_FILTER_I8 in every respect):
 // 1 to 8 queries, and not the MASKED form, which stays filter_i8_kernel's.
 bool i8_stream_serves(const rc_index *h, int nq, const uint32_t *mask, bool mask_filter) {
-    return h->filter == RC_FILTER_I8_STREAM && h->rows8 != nullptr && nq <= I8_STREAM_MAX_QUERIES && !(mask_filter && mask != nullptr);
+    return h->filter == RC_FILTER_I8_STREAM && !h->rows8.empty() && nq <= I8_STREAM_MAX_QUERIES && !(mask_filter && mask != nullptr);
 }
 // ... and RC_SEARCH_AUTO takes it over n rows (no mask)
 bool i8_stream_auto(const rc_index *h, int nq, int64_t n) {
@@ -690,17 +688,17 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
                           bool mask_filter, float *scores, int64_t *out_rows, hipStream_t s, const int32_t *pages = nullptr) {
     const bool stream = pages == nullptr && i8_stream_serves(h, nq, mask, mask_filter);
     h->bws.ensure(nq, k, h->ld, batch_query_bytes(h), stream ? I8_STREAM_MAX_QUERIES : 256);
-    BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, n_rows, h->row_base, h->row_stride, queries, nq, k, scores, out_rows};
+    BatchPlan p{h->rows.get(), h->dtype, h->dim, h->nch, h->ld, n_rows, h->row_base, h->row_stride, queries, nq, k, scores, out_rows};
     p.i8_stream = stream;
     p.f8_filter = h->filter == RC_FILTER_F8;
     p.f32_filter = h->filter == RC_FILTER_F32;
-    p.rows8 = h->rows8;
-    p.rsx = h->rsx;
-    p.rex = h->rex;
+    p.rows8 = h->rows8.get();
+    p.rsx = h->rsx.get();
+    p.rex = h->rex.get();
     p.mask = mask;
     p.mask_filter = mask_filter && mask != nullptr;
     p.metric = h->metric;  // non-cosine (RC_FILTER_METRIC): the filter and rescore kernels' metric forms
-    p.norms = h->norms;
+    p.norms = h->norms.get();
     p.pages = pages;
     if (h->gtimer.enabled) h->gtimer.create();
     batched_search(p, h->bws, s, h->gtimer.enabled ? &h->gtimer : nullptr);
@@ -708,20 +706,20 @@ void batched_search_exact(rc_index *h, const float *queries, int nq, int64_t n_r
     int64_t rpb = (n_rows + nblk - 1) / nblk;
     rpb = std::max<int64_t>(32, (rpb + 31) / 32 * 32);
     nblk = (int)std::max<int64_t>(1, (n_rows + rpb - 1) / rpb);
-    ScanArgs a{h->rows, h->ld, h->nch, n_rows, rpb, nblk, h->bws.qn, 0, 1, nq, k, h->bws.fb_partial, s};
-    a.flags = h->bws.flags;
+    ScanArgs a{h->rows.get(), h->ld, h->nch, n_rows, rpb, nblk, h->bws.qn.get(), 0, 1, nq, k, h->bws.fb_partial.get(), s};
+    a.flags = h->bws.flags.get();
     a.grid_y = std::min(nq, FB_QSTRIDE);
     a.mask = mask;
     if (h->metric != RC_METRIC_COSINE || pages != nullptr) {  // the metric fallback kernel (scan_metric.h) and the paged
         a.metric = h->metric;                                 // ones (scan_paged.h): raw queries, as every such scan
-        a.norms = h->norms;
+        a.norms = h->norms.get();
         a.qraw = queries;
         a.dim = h->dim;
         a.nq_real = nq;
     }
     if (pages != nullptr) launch_scan_paged(h, a, pages);
     else launch_scan(h, a);
-    launch_merge_partials(h, h->bws.fb_partial, h->bws.flags, nblk, nq, nq, k, scores, out_rows, s);
+    launch_merge_partials(h, h->bws.fb_partial.get(), h->bws.flags.get(), nblk, nq, nq, k, scores, out_rows, s);
 }
 
 void empty_search(int nq, int k, float *scores, int64_t *out_rows, hipStream_t s) {
@@ -739,7 +737,7 @@ void deep_score_pass(rc_index *h, const float *queries, int nq, int64_t n, const
     int64_t rpb = (n + nblk - 1) / nblk;
     rpb = std::max<int64_t>(32, (rpb + 31) / 32 * 32);
     nblk = (int)std::max<int64_t>(1, (n + rpb - 1) / rpb);
-    const DeepScoreArgs a{h->rows, h->norms, h->ld, h->nch, h->dim, n, rpb, nblk, queries, nq, h->metric, pages, out, s};
+    const DeepScoreArgs a{h->rows.get(), h->norms.get(), h->ld, h->nch, h->dim, n, rpb, nblk, queries, nq, h->metric, pages, out, s};
     dispatch_dtype(h->dtype, [&](auto t) { launch_deep_scores<decltype(t)>(a); });
 }
 
@@ -756,25 +754,19 @@ void deep_search_locked(rc_index *h, const float *queries, int nq, int64_t n, in
         return;
     }
     const int qc = deep_chunk_queries(nq, n);
-    if ((int64_t)qc * n > h->dscores_cap) {
-        dfree(h->dscores);
-        h->dscores = nullptr;
-        h->dscores_cap = 0;
-        h->dscores = (float *)dmalloc((size_t)qc * n * sizeof(float));
-        h->dscores_cap = (int64_t)qc * n;
-    }
+    h->dscores.reserve((size_t)qc * n);
     h->dsel.ensure(qc, out_keys != nullptr ? 0 : (int64_t)qc * k);
     for (int q0 = 0; q0 < nq; q0 += qc) {
         const int m = std::min(qc, nq - q0);
-        deep_score_pass(h, queries + (int64_t)q0 * h->dim, m, n, pages, h->dscores, s);
-        if (after != nullptr) (*after)(q0, m, h->dscores, s);
+        deep_score_pass(h, queries + (int64_t)q0 * h->dim, m, n, pages, h->dscores.get(), s);
+        if (after != nullptr) (*after)(q0, m, h->dscores.get(), s);
         DeepStream st;
-        st.scores = h->dscores;
+        st.scores = h->dscores.get();
         st.n = n;
         st.row_base = h->row_base;
         st.row_stride = h->row_stride;
         st.mask = mask;
-        uint64_t *ko = out_keys != nullptr ? out_keys + (int64_t)q0 * k : h->dsel.keys;
+        uint64_t *ko = out_keys != nullptr ? out_keys + (int64_t)q0 * k : h->dsel.keys.get();
         deep_select(h->deep_select, st, h->dsel, m, k, ko, s);
         if (out_keys == nullptr) deep_emit(ko, (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, s);
     }
@@ -787,7 +779,7 @@ DeepAfterScores sparse_step(rc_index *h, const SparseQueries &sq, int nq, int64_
     if (sq.off[nq] == 0 || n == 0) return nullptr;
     h->sws.stage_queries(sq, nq, s);
     return [h, n, pages](int q0, int m, float *scores, hipStream_t st) {
-        const SparseAddArgs a{h->sparse.idx, h->sparse.val, h->sparse.width, h->capacity, h->sws.off_d, h->sws.idx_d, h->sws.val_d,
+        const SparseAddArgs a{h->sparse.idx, h->sparse.val, h->sparse.width, h->capacity, h->sws.off_d.get(), h->sws.idx_d.get(), h->sws.val_d.get(),
                               q0,            m,             n,               pages,       scores,       st};
         launch_sparse_add(a);
     };
@@ -825,7 +817,7 @@ const int32_t *resolve_range(const rc_index *h, int slot, int64_t n) {
                "unknown slot (no page table was set for it)");
     const rc_index::PageTable &t = h->tables[slot];
     RC_REQUIRE(n >= 0 && n <= (int64_t)t.n_pages * RC_PAGE_ROWS, RC_ERR_INVALID, "n_pos beyond the slot's pages");
-    return t.dev;
+    return t.dev.get();
 }
 
 // rc_index_search_masked / rc_index_search_pages_ex: the top-k searches' mode resolution.  Over a
@@ -854,9 +846,9 @@ void topk_search(rc_index *h, const SearchArgs &a, int mode) {
     // (a float8 index scans unless its own filter is switched on: RC_FILTER_F8); the paged kernels are
     // the native f16 / bf16 ones, cosine or RC_FILTER_METRIC: the int8 and float8 filters have no paged form
     const bool mfma_ok =
-        metric_ok && (pages != nullptr ? (h->dtype == RC_F16 || h->dtype == RC_BF16) && h->rows8 == nullptr &&
+        metric_ok && (pages != nullptr ? (h->dtype == RC_F16 || h->dtype == RC_BF16) && h->rows8.empty() &&
                                              (h->filter == RC_FILTER_NATIVE || h->filter == RC_FILTER_METRIC)
-                                       : (h->dtype != RC_F32 && h->dtype != RC_F8) || h->rows8 != nullptr || h->filter == RC_FILTER_F8 ||
+                                       : (h->dtype != RC_F32 && h->dtype != RC_F8) || !h->rows8.empty() || h->filter == RC_FILTER_F8 ||
                                              h->filter == RC_FILTER_F32);
     RC_REQUIRE(mode != RC_SEARCH_MFMA || mfma_ok, RC_ERR_UNSUPPORTED,
                pages != nullptr ? "batched MFMA search over pages needs an f16/bf16 index with the native or the metric filter "
@@ -977,8 +969,8 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
     DeviceScope ds(h->device);
     ensure_workspace(h, 1, k);
     Query1Args a{};
-    a.rows = h->rows;
-    a.norms = h->norms;
+    a.rows = h->rows.get();
+    a.norms = h->norms.get();
     a.ld = h->ld;
     a.dim = h->dim;
     a.nch = h->nch;
@@ -993,7 +985,7 @@ bool index_query1(rc_index *h, const float *query, int64_t n_rows, int k, int wi
     a.metric = h->metric;
     a.row_base = h->row_base;
     a.row_stride = h->row_stride;
-    a.partial = h->partial;
+    a.partial = h->partial.get();
     a.out_scores = out_scores;
     a.out_rows = out_rows;
     a.out_values = out_values;
@@ -1020,17 +1012,13 @@ void index_fetch_pages(rc_index *h, int slot, int64_t n_pos, const int64_t *pos,
     std::lock_guard<std::mutex> lk(h->mu);
     const int32_t *pages = resolve_range(h, paged_slot(slot), n_pos);
     DeviceScope ds(h->device);
-    if (n > h->pg_rows_cap) {
+    if ((size_t)n > h->pg_rows.capacity()) {
         RC_HIP(hipDeviceSynchronize());  // no gather may still read the old list
-        dfree(h->pg_rows);
-        h->pg_rows = nullptr;
-        h->pg_rows_cap = 0;
-        h->pg_rows = (int64_t *)dmalloc((size_t)n * sizeof(int64_t));
-        h->pg_rows_cap = n;
+        h->pg_rows.reserve((size_t)n);
     }
-    hipLaunchKernelGGL(pages_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pos, n, pages, n_pos, h->pg_rows);
+    hipLaunchKernelGGL(pages_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pos, n, pages, n_pos, h->pg_rows.get());
     RC_LAUNCH_CHECK();
-    dispatch_dtype(h->dtype, [&](auto tt) { launch_fetch<decltype(tt)>(h, h->pg_rows, n, out, false, s); });
+    dispatch_dtype(h->dtype, [&](auto tt) { launch_fetch<decltype(tt)>(h, h->pg_rows.get(), n, out, false, s); });
 }
 
 // Internal (sharded.hip, rc_sharded_search_deep / _hybrid): a shard's own deep top-k on stream `s`,
@@ -1062,7 +1050,7 @@ int rc_index_create(int device, int dim, int dtype, int64_t capacity, int64_t ro
         const int nch = pick_nch(dim, dtype);
         RC_REQUIRE(nch > 0, RC_ERR_UNSUPPORTED, "dimension > 2048 is not supported");
         DeviceScope ds(device);
-        auto *h = new rc_index();
+        std::unique_ptr<rc_index> h(new rc_index());
         h->device = device;
         h->dim = dim;
         h->dtype = dtype;
@@ -1070,24 +1058,15 @@ int rc_index_create(int device, int dim, int dtype, int64_t capacity, int64_t ro
         h->ld = 128LL * nch;
         h->capacity = capacity;
         h->row_base = row_base;
-        try {
-            RC_HIP(hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, device));
-            // whole 256-row tiles: the batched search reads row tiles without a bounds check
-            const int64_t cap_pad = (capacity + INDEX_ROW_PAD - 1) / INDEX_ROW_PAD * INDEX_ROW_PAD;
-            h->rows = dmalloc((size_t)cap_pad * h->ld * dtype_size(dtype));
-            h->norms = (float *)dmalloc((size_t)capacity * sizeof(float));
-            RC_HIP(hipMemset(h->rows, 0, (size_t)cap_pad * h->ld * dtype_size(dtype)));
-            RC_HIP(hipMemset(h->norms, 0, (size_t)capacity * sizeof(float)));
-            ensure_workspace(h, 4, 16);
-        } catch (...) {
-            dfree(h->rows);
-            dfree(h->norms);
-            dfree(h->qn);
-            dfree(h->partial);
-            delete h;
-            throw;
-        }
-        *out = h;
+        RC_HIP(hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, device));
+        // whole 256-row tiles: the batched search reads row tiles without a bounds check
+        const int64_t cap_pad = (capacity + INDEX_ROW_PAD - 1) / INDEX_ROW_PAD * INDEX_ROW_PAD;
+        h->rows.reserve((size_t)cap_pad * h->ld * dtype_size(dtype));
+        h->norms.reserve((size_t)capacity);
+        RC_HIP(hipMemset(h->rows.get(), 0, (size_t)cap_pad * h->ld * dtype_size(dtype)));
+        RC_HIP(hipMemset(h->norms.get(), 0, (size_t)capacity * sizeof(float)));
+        ensure_workspace(h.get(), 4, 16);
+        *out = h.release();
     });
 }
 
@@ -1097,21 +1076,9 @@ int rc_index_destroy(rc_index *h) {
         DeviceScope ds(h->device);
         h->timer.destroy();
         h->gtimer.destroy();
-        h->bws.release();
-        free_filter(h);
-        dfree(h->rows);
-        dfree(h->norms);
-        dfree(h->qn);
-        dfree(h->partial);
         if (h->q1_done != nullptr) (void)hipHostFree(h->q1_done);
-        for (auto &t : h->tables) dfree(t.dev);
-        dfree(h->pg_rows);
-        dfree(h->dscores);
-        h->dsel.release();
-        dfree(h->sparse.idx);
-        dfree(h->sparse.val);
         h->sws.release();
-        delete h;
+        delete h;  // the buffers free themselves
     });
 }
 
@@ -1128,8 +1095,8 @@ int rc_index_info(const rc_index *h, int *dim, int *dtype, int64_t *capacity, in
 int rc_index_data(const rc_index *h, void **rows_dev, float **norms_dev) {
     return guard([&] {
         RC_REQUIRE(h, RC_ERR_INVALID, "null index");
-        if (rows_dev) *rows_dev = h->rows;
-        if (norms_dev) *norms_dev = h->norms;
+        if (rows_dev) *rows_dev = h->rows.get();
+        if (norms_dev) *norms_dev = h->norms.get();
     });
 }
 
@@ -1158,64 +1125,49 @@ int rc_index_grow(rc_index *h, int64_t new_capacity, void *stream) {
         const size_t rb = (size_t)h->ld * dtype_size(h->dtype);
         const int64_t old_pad = (h->capacity + INDEX_ROW_PAD - 1) / INDEX_ROW_PAD * INDEX_ROW_PAD;
         const int64_t new_pad = (new_capacity + INDEX_ROW_PAD - 1) / INDEX_ROW_PAD * INDEX_ROW_PAD;
-        void *rows = dmalloc((size_t)new_pad * rb);
-        float *norms = nullptr;
-        int8_t *rows8 = nullptr;
-        float *rsx = nullptr, *rex = nullptr;
-        uint32_t *sp_idx = nullptr;
-        float *sp_val = nullptr;
-        try {
-            norms = (float *)dmalloc((size_t)new_capacity * sizeof(float));
-            RC_HIP(hipMemcpyAsync(rows, h->rows, (size_t)old_pad * rb, hipMemcpyDeviceToDevice, s));
-            RC_HIP(hipMemsetAsync((uint8_t *)rows + (size_t)old_pad * rb, 0, (size_t)(new_pad - old_pad) * rb, s));
-            RC_HIP(hipMemcpyAsync(norms, h->norms, (size_t)h->capacity * sizeof(float), hipMemcpyDeviceToDevice, s));
-            RC_HIP(hipMemsetAsync(norms + h->capacity, 0, (size_t)(new_capacity - h->capacity) * sizeof(float), s));
-            if (h->rows8) {  // the filter copy keeps its slots (i8_slot is position-stable)
-                const size_t rb8 = (size_t)h->ld;
-                rows8 = (int8_t *)dmalloc((size_t)new_pad * rb8);
-                rsx = (float *)dmalloc((size_t)new_pad * sizeof(float));
-                rex = (float *)dmalloc((size_t)new_pad * sizeof(float));
-                RC_HIP(hipMemcpyAsync(rows8, h->rows8, (size_t)old_pad * rb8, hipMemcpyDeviceToDevice, s));
-                RC_HIP(hipMemsetAsync(rows8 + (size_t)old_pad * rb8, 0, (size_t)(new_pad - old_pad) * rb8, s));
-                RC_HIP(hipMemcpyAsync(rsx, h->rsx, (size_t)old_pad * sizeof(float), hipMemcpyDeviceToDevice, s));
-                RC_HIP(hipMemsetAsync(rsx + old_pad, 0, (size_t)(new_pad - old_pad) * sizeof(float), s));
-                RC_HIP(hipMemcpyAsync(rex, h->rex, (size_t)old_pad * sizeof(float), hipMemcpyDeviceToDevice, s));
-                RC_HIP(hipMemsetAsync(rex + old_pad, 0, (size_t)(new_pad - old_pad) * sizeof(float), s));
-            }
-            if (h->sparse.width > 0) {  // the sparse store keeps its rows; the new ones are padding
-                sp_idx = (uint32_t *)dmalloc((size_t)h->sparse.width * new_capacity * sizeof(uint32_t));
-                sp_val = (float *)dmalloc((size_t)h->sparse.width * new_capacity * sizeof(float));
-                launch_sparse_regrow(h->sparse, h->capacity, sp_idx, sp_val, new_capacity, s);
-            }
-            RC_HIP(hipStreamSynchronize(s));  // work queued earlier on other streams is the caller's to order
-        } catch (...) {
-            dfree(sp_idx);
-            dfree(sp_val);
-            dfree(rows);
-            dfree(norms);
-            dfree(rows8);
-            dfree(rsx);
-            dfree(rex);
-            throw;
+        // the new blocks are locals until every copy into them is done: an error frees them and leaves the index as it was
+        DevBuf<void> rows;
+        DevBuf<float> norms, rsx, rex, sp_val;
+        DevBuf<int8_t> rows8;
+        DevBuf<uint32_t> sp_idx;
+        rows.reserve((size_t)new_pad * rb);
+        norms.reserve((size_t)new_capacity);
+        RC_HIP(hipMemcpyAsync(rows.get(), h->rows.get(), (size_t)old_pad * rb, hipMemcpyDeviceToDevice, s));
+        RC_HIP(hipMemsetAsync((uint8_t *)rows.get() + (size_t)old_pad * rb, 0, (size_t)(new_pad - old_pad) * rb, s));
+        RC_HIP(hipMemcpyAsync(norms.get(), h->norms.get(), (size_t)h->capacity * sizeof(float), hipMemcpyDeviceToDevice, s));
+        RC_HIP(hipMemsetAsync(norms.get() + h->capacity, 0, (size_t)(new_capacity - h->capacity) * sizeof(float), s));
+        const bool filter_copy = !h->rows8.empty();
+        if (filter_copy) {  // the filter copy keeps its slots (i8_slot is position-stable)
+            const size_t rb8 = (size_t)h->ld;
+            rows8.reserve((size_t)new_pad * rb8);
+            rsx.reserve((size_t)new_pad);
+            rex.reserve((size_t)new_pad);
+            RC_HIP(hipMemcpyAsync(rows8.get(), h->rows8.get(), (size_t)old_pad * rb8, hipMemcpyDeviceToDevice, s));
+            RC_HIP(hipMemsetAsync(rows8.get() + (size_t)old_pad * rb8, 0, (size_t)(new_pad - old_pad) * rb8, s));
+            RC_HIP(hipMemcpyAsync(rsx.get(), h->rsx.get(), (size_t)old_pad * sizeof(float), hipMemcpyDeviceToDevice, s));
+            RC_HIP(hipMemsetAsync(rsx.get() + old_pad, 0, (size_t)(new_pad - old_pad) * sizeof(float), s));
+            RC_HIP(hipMemcpyAsync(rex.get(), h->rex.get(), (size_t)old_pad * sizeof(float), hipMemcpyDeviceToDevice, s));
+            RC_HIP(hipMemsetAsync(rex.get() + old_pad, 0, (size_t)(new_pad - old_pad) * sizeof(float), s));
         }
-        RC_HIP(hipDeviceSynchronize());  // no kernel may still read the old buffers
-        dfree(h->rows);
-        dfree(h->norms);
-        h->rows = rows;
-        h->norms = norms;
-        if (h->rows8) {
-            dfree(h->rows8);
-            dfree(h->rsx);
-            dfree(h->rex);
-            h->rows8 = rows8;
-            h->rsx = rsx;
-            h->rex = rex;
+        if (h->sparse.width > 0) {  // the sparse store keeps its rows; the new ones are padding
+            sp_idx.reserve((size_t)h->sparse.width * new_capacity);
+            sp_val.reserve((size_t)h->sparse.width * new_capacity);
+            launch_sparse_regrow(h->sparse, h->capacity, sp_idx.get(), sp_val.get(), new_capacity, s);
+        }
+        RC_HIP(hipStreamSynchronize(s));  // work queued earlier on other streams is the caller's to order
+        RC_HIP(hipDeviceSynchronize());   // no kernel may still read the old buffers
+        h->rows = std::move(rows);
+        h->norms = std::move(norms);
+        if (filter_copy) {
+            h->rows8 = std::move(rows8);
+            h->rsx = std::move(rsx);
+            h->rex = std::move(rex);
         }
         if (h->sparse.width > 0) {
-            dfree(h->sparse.idx);
-            dfree(h->sparse.val);
-            h->sparse.idx = sp_idx;
-            h->sparse.val = sp_val;
+            h->sp_idx = std::move(sp_idx);
+            h->sp_val = std::move(sp_val);
+            h->sparse.idx = h->sp_idx.get();
+            h->sparse.val = h->sp_val.get();
         }
         h->capacity = new_capacity;
     });
@@ -1242,7 +1194,7 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
         if (kind == h->filter) return;
-        if (h->rows8 != nullptr && (kind == RC_FILTER_I8 || kind == RC_FILTER_I8_STREAM)) {
+        if (!h->rows8.empty() && (kind == RC_FILTER_I8 || kind == RC_FILTER_I8_STREAM)) {
             h->filter = kind;  // the two int8 kinds share the copy: no device call, nothing requantised
             return;
         }
@@ -1272,7 +1224,7 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
                        "the float8 filter serves the batched MFMA search, which is cosine-only");
             RC_REQUIRE(f8_filter_supported(h->ld), RC_ERR_UNSUPPORTED,
                        "the float8 filter needs a row width (dim rounded up to 256) of 256, 512 or 768");
-            h->filter = RC_FILTER_F8;  // (h->rows8 is null: the int8 copy is refused on a float8 index)
+            h->filter = RC_FILTER_F8;  // (h->rows8 is empty: the int8 copy is refused on a float8 index)
             return;
         }
         RC_REQUIRE(h->metric == RC_METRIC_COSINE, RC_ERR_UNSUPPORTED,
@@ -1284,12 +1236,12 @@ int rc_index_set_filter(rc_index *h, int kind, void *stream) {
                    "the int8 filter needs a row width (dim rounded up to 128) of 256, 512 or 768");
         const int64_t pad = cap_pad(h->capacity);
         try {
-            h->rows8 = (int8_t *)dmalloc((size_t)pad * h->ld);
-            h->rsx = (float *)dmalloc((size_t)pad * sizeof(float));
-            h->rex = (float *)dmalloc((size_t)pad * sizeof(float));
-            RC_HIP(hipMemsetAsync(h->rows8, 0, (size_t)pad * h->ld, s));
-            RC_HIP(hipMemsetAsync(h->rsx, 0, (size_t)pad * sizeof(float), s));
-            RC_HIP(hipMemsetAsync(h->rex, 0, (size_t)pad * sizeof(float), s));
+            h->rows8.reserve((size_t)pad * h->ld);
+            h->rsx.reserve((size_t)pad);
+            h->rex.reserve((size_t)pad);
+            RC_HIP(hipMemsetAsync(h->rows8.get(), 0, (size_t)pad * h->ld, s));
+            RC_HIP(hipMemsetAsync(h->rsx.get(), 0, (size_t)pad * sizeof(float), s));
+            RC_HIP(hipMemsetAsync(h->rex.get(), 0, (size_t)pad * sizeof(float), s));
             dispatch_dtype(h->dtype, [&](auto t) { launch_quantize<decltype(t)>(h, nullptr, 0, h->capacity, s); });
             RC_HIP(hipStreamSynchronize(s));
         } catch (...) {
@@ -1404,8 +1356,8 @@ int rc_index_export(rc_index *h, int64_t row0, int64_t n, void *rows_out, float 
         DeviceScope ds(h->device);
         const size_t rb = (size_t)h->ld * dtype_size(h->dtype);
         hipStream_t s = (hipStream_t)stream;
-        RC_HIP(hipMemcpyAsync(rows_out, (const uint8_t *)h->rows + (size_t)row0 * rb, (size_t)n * rb, hipMemcpyDefault, s));
-        RC_HIP(hipMemcpyAsync(norms_out, h->norms + row0, (size_t)n * sizeof(float), hipMemcpyDefault, s));
+        RC_HIP(hipMemcpyAsync(rows_out, (const uint8_t *)h->rows.get() + (size_t)row0 * rb, (size_t)n * rb, hipMemcpyDefault, s));
+        RC_HIP(hipMemcpyAsync(norms_out, h->norms.get() + row0, (size_t)n * sizeof(float), hipMemcpyDefault, s));
     });
 }
 
@@ -1419,8 +1371,8 @@ int rc_index_import(rc_index *h, int64_t row0, int64_t n, const void *rows_in, c
         DeviceScope ds(h->device);
         const size_t rb = (size_t)h->ld * dtype_size(h->dtype);
         hipStream_t s = (hipStream_t)stream;
-        RC_HIP(hipMemcpyAsync((uint8_t *)h->rows + (size_t)row0 * rb, rows_in, (size_t)n * rb, hipMemcpyDefault, s));
-        RC_HIP(hipMemcpyAsync(h->norms + row0, norms_in, (size_t)n * sizeof(float), hipMemcpyDefault, s));
+        RC_HIP(hipMemcpyAsync((uint8_t *)h->rows.get() + (size_t)row0 * rb, rows_in, (size_t)n * rb, hipMemcpyDefault, s));
+        RC_HIP(hipMemcpyAsync(h->norms.get() + row0, norms_in, (size_t)n * sizeof(float), hipMemcpyDefault, s));
         dispatch_dtype(h->dtype, [&](auto t) { launch_quantize<decltype(t)>(h, nullptr, row0, n, s); });
     });
 }
@@ -1457,19 +1409,16 @@ int rc_index_pages_set(rc_index *h, int slot, const int32_t *pages_host, int n_p
         if (slot >= (int)h->tables.size()) h->tables.resize((size_t)slot + 1);
         rc_index::PageTable &t = h->tables[slot];
         if (n_pages == 0) {
-            dfree(t.dev);
             t = rc_index::PageTable{};
             return;
         }
-        if (n_pages > t.cap) {
-            const int cap2 = std::max(std::max(16, n_pages), 2 * t.cap);
-            int32_t *dev = (int32_t *)dmalloc((size_t)cap2 * sizeof(int32_t));
-            dfree(t.dev);
-            t.dev = dev;
-            t.cap = cap2;
+        if ((size_t)n_pages > t.dev.capacity()) {
+            DevBuf<int32_t> dev;  // allocated before the old table goes: a failure keeps the slot as it was
+            dev.reserve(std::max<size_t>(std::max(16, n_pages), 2 * t.dev.capacity()));
+            t.dev = std::move(dev);
             t.n_pages = 0;
         }
-        RC_HIP(hipMemcpyAsync(t.dev, pages_host, (size_t)n_pages * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RC_HIP(hipMemcpyAsync(t.dev.get(), pages_host, (size_t)n_pages * sizeof(int32_t), hipMemcpyHostToDevice, s));
         RC_HIP(hipStreamSynchronize(s));  // the host list may be reused; later searches on any stream see the table
         t.n_pages = n_pages;
     });
@@ -1517,21 +1466,16 @@ int rc_index_sparse_enable(rc_index *h, int width, void *stream) {
         DeviceScope ds(h->device);
         hipStream_t s = (hipStream_t)stream;
         const size_t slots = (size_t)width * h->capacity;
-        uint32_t *idx = (uint32_t *)dmalloc(slots * sizeof(uint32_t));
-        float *val = nullptr;
-        try {
-            val = (float *)dmalloc(slots * sizeof(float));
-            RC_HIP(hipMemsetAsync(idx, 0xff, slots * sizeof(uint32_t), s));  // SPARSE_PAD everywhere
-            RC_HIP(hipMemsetAsync(val, 0, slots * sizeof(float), s));
-            RC_HIP(hipStreamSynchronize(s));
-        } catch (...) {
-            dfree(idx);
-            dfree(val);
-            throw;
-        }
-        h->sparse.idx = idx;
-        h->sparse.val = val;
-        h->sparse.width = width;
+        DevBuf<uint32_t> idx;
+        DevBuf<float> val;
+        idx.reserve(slots);
+        val.reserve(slots);
+        RC_HIP(hipMemsetAsync(idx.get(), 0xff, slots * sizeof(uint32_t), s));  // SPARSE_PAD everywhere
+        RC_HIP(hipMemsetAsync(val.get(), 0, slots * sizeof(float), s));
+        RC_HIP(hipStreamSynchronize(s));
+        h->sp_idx = std::move(idx);
+        h->sp_val = std::move(val);
+        h->sparse = SparseStore{h->sp_idx.get(), h->sp_val.get(), width};
     });
 }
 
@@ -1574,19 +1518,19 @@ int rc_index_sparse_write(rc_index *h, const int64_t *rows, const int64_t *off, 
             const int64_t m = std::min(round, n - r0);
             w.wait();
             for (int64_t i = 0; i < m; ++i) {
-                w.wrow_h[i] = rows[r0 + i];
+                w.wrow_h.get()[i] = rows[r0 + i];
                 const int64_t b = off[r0 + i], cnt = off[r0 + i + 1] - b;
                 for (int64_t j = 0; j < width; ++j) {
-                    w.widx_h[i * width + j] = j < cnt ? idx[b + j] : SPARSE_PAD;
-                    w.wval_h[i * width + j] = j < cnt ? val[b + j] : 0.0f;
+                    w.widx_h.get()[i * width + j] = j < cnt ? idx[b + j] : SPARSE_PAD;
+                    w.wval_h.get()[i * width + j] = j < cnt ? val[b + j] : 0.0f;
                 }
             }
-            RC_HIP(hipMemcpyAsync(w.wrow_d, w.wrow_h, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            RC_HIP(hipMemcpyAsync(w.widx_d, w.widx_h, (size_t)m * width * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            RC_HIP(hipMemcpyAsync(w.wval_d, w.wval_h, (size_t)m * width * sizeof(float), hipMemcpyHostToDevice, s));
+            RC_HIP(hipMemcpyAsync(w.wrow_d.get(), w.wrow_h.get(), (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            RC_HIP(hipMemcpyAsync(w.widx_d.get(), w.widx_h.get(), (size_t)m * width * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            RC_HIP(hipMemcpyAsync(w.wval_d.get(), w.wval_h.get(), (size_t)m * width * sizeof(float), hipMemcpyHostToDevice, s));
             RC_HIP(hipEventRecord(w.ev, s));
             w.pending = true;
-            launch_sparse_scatter(h->sparse, h->capacity, w.wrow_d, w.widx_d, w.wval_d, m, s);
+            launch_sparse_scatter(h->sparse, h->capacity, w.wrow_d.get(), w.widx_d.get(), w.wval_d.get(), m, s);
         }
         RC_HIP(hipStreamSynchronize(s));  // synchronous, as the sharded write: the caller's lists are free and the store is written
         w.pending = false;
@@ -1636,14 +1580,14 @@ int rc_index_filter_scores(rc_index *h, const float *queries, int nq, int64_t ro
         if (h->filter == RC_FILTER_I8_STREAM) {  // the keep test's left side u of up to 8 queries, and eps
             RC_REQUIRE(nq <= I8_STREAM_MAX_QUERIES, RC_ERR_INVALID, "the streaming int8 filter takes at most 8 queries");
             h->bws.ensure(nq, 16, h->ld, batch_query_bytes(h), I8_STREAM_MAX_QUERIES);
-            BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, row0 + n, h->row_base, h->row_stride, queries, nq, 16, nullptr, nullptr};
-            p.rows8 = h->rows8;
-            p.rsx = h->rsx;
-            p.rex = h->rex;
+            BatchPlan p{h->rows.get(), h->dtype, h->dim, h->nch, h->ld, row0 + n, h->row_base, h->row_stride, queries, nq, 16, nullptr, nullptr};
+            p.rows8 = h->rows8.get();
+            p.rsx = h->rsx.get();
+            p.rex = h->rex.get();
             return filter_scores_i8_stream(p, h->bws, row0, n, out_scores, out_eps, (hipStream_t)stream);
         }
         h->bws.ensure(nq, 16, h->ld, batch_query_bytes(h));
-        BatchPlan p{h->rows, h->dtype, h->dim, h->nch, h->ld, row0 + n, h->row_base, h->row_stride, queries, nq, 16, nullptr, nullptr};
+        BatchPlan p{h->rows.get(), h->dtype, h->dim, h->nch, h->ld, row0 + n, h->row_base, h->row_stride, queries, nq, 16, nullptr, nullptr};
         if (h->filter == RC_FILTER_F32) {  // s' and eps in cosine space, whatever the metric (p.metric stays cosine)
             p.f32_filter = true;
             return filter_scores_f32(p, h->bws, row0, n, out_scores, out_eps, (hipStream_t)stream);
@@ -1707,10 +1651,10 @@ int rc_index_gemm_timing_read(rc_index *h, double *total_ms, int64_t *launches, 
         if (flops) *flops = h->gtimer.work;
         if (fallbacks) {
             int ovf = 0;
-            if (h->bws.ovf) {
+            if (h->bws.ovf.get()) {
                 RC_HIP(hipDeviceSynchronize());
-                RC_HIP(hipMemcpy(&ovf, h->bws.ovf, sizeof(int), hipMemcpyDeviceToHost));
-                RC_HIP(hipMemset(h->bws.ovf, 0, sizeof(int)));
+                RC_HIP(hipMemcpy(&ovf, h->bws.ovf.get(), sizeof(int), hipMemcpyDeviceToHost));
+                RC_HIP(hipMemset(h->bws.ovf.get(), 0, sizeof(int)));
             }
             *fallbacks = ovf;
         }

@@ -384,24 +384,23 @@ struct BatchWs {
     int nq_cap = 0, k_cap = 0;
     int64_t ld_cap = 0;
     int cap = BATCH_CAND_CAP;
-    float *qn = nullptr;        // [nq_cap][ld] normalised queries (f32)
-    void *qh = nullptr;         // [nq_cap][ld] queries in the storage dtype (MFMA operand); float8: two byte planes
-    float *eps = nullptr;       // [nq_cap] bound on |s' - s|
-    float *thr = nullptr;       // [nq_cap] current filter threshold
-    uint32_t *cnt = nullptr;    // [nq_cap] candidates appended this stage
-    uint32_t *cand = nullptr;   // [nq_cap][cap] candidate rows
-    uint64_t *keys = nullptr;   // [nq_cap][k_cap] running top-k keys (sorted)
-    int *flags = nullptr;       // [nq_cap] 1 = candidate overflow, exact fallback needed
-    float *sq = nullptr;        // [nq_cap] int8 filter: query scale (q̃ = sq · q8)
-    float *aq = nullptr;        // [nq_cap] int8 filter: coefficient of a row's residual norm in the bound
-    float *mcoef = nullptr;     // [nq_cap][4] metric filter: (eps, alpha, beta, gamma) of each query (metric_coef)
-    int *ovf = nullptr;         // overflowed queries since the last timing read (device counter)
-    int fb_blocks = 0;               // blocks of the fallback scan: FB_BUDGET_BYTES / (nq_cap * k_cap * 8), clamped
-    uint64_t *fb_partial = nullptr;  // [fb_blocks][nq_cap][k_cap] partial keys of the exact fallback scan
+    DevBuf<float> qn;        // [nq_cap][ld] normalised queries (f32)
+    DevBuf<void> qh;         // [nq_cap][ld] queries in the storage dtype (MFMA operand); float8: two byte planes
+    DevBuf<float> eps;       // [nq_cap] bound on |s' - s|
+    DevBuf<float> thr;       // [nq_cap] current filter threshold
+    DevBuf<uint32_t> cnt;    // [nq_cap] candidates appended this stage
+    DevBuf<uint32_t> cand;   // [nq_cap][cap] candidate rows
+    DevBuf<uint64_t> keys;   // [nq_cap][k_cap] running top-k keys (sorted)
+    DevBuf<int> flags;       // [nq_cap] 1 = candidate overflow, exact fallback needed
+    DevBuf<float> sq;        // [nq_cap] int8 filter: query scale (q̃ = sq · q8)
+    DevBuf<float> aq;        // [nq_cap] int8 filter: coefficient of a row's residual norm in the bound
+    DevBuf<float> mcoef;     // [nq_cap][4] metric filter: (eps, alpha, beta, gamma) of each query (metric_coef)
+    DevBuf<int> ovf;         // overflowed queries since the last timing read (device counter)
+    int fb_blocks = 0;            // blocks of the fallback scan: FB_BUDGET_BYTES / (nq_cap * k_cap * 8), clamped
+    DevBuf<uint64_t> fb_partial;  // [fb_blocks][nq_cap][k_cap] partial keys of the exact fallback scan
     // qtile: the query slots come in multiples of it (256, the MFMA filters' query tile; 8 for the
     // streaming int8 filter, which has no such tile)
     void ensure(int nq, int k, int64_t ld, int dtype_bytes, int qtile = 256);
-    void release();
 };
 
 struct BatchPlan {

@@ -1145,8 +1145,9 @@ struct JpegDecoder {
     int device = 0;
     int max_images = 0;
     int64_t max_blocks = 0;
-    uint8_t *h_stage = nullptr, *d_stage = nullptr;
-    size_t stage_cap = 0, stage_used = 0;
+    PinBuf<uint8_t> h_stage;
+    DevBuf<uint8_t> d_stage;
+    size_t stage_used = 0;
     // views into the staging (set per call by stage_layout)
     int16_t *h_coef = nullptr;
     int32_t *h_qsel = nullptr;
@@ -1156,17 +1157,16 @@ struct JpegDecoder {
     int32_t *d_qsel = nullptr;
     uint16_t *d_qtab = nullptr;
     jpeg::Desc *d_desc = nullptr;
-    uint8_t *d_planes = nullptr;
+    DevBuf<uint8_t> d_planes;
     hipEvent_t staged = nullptr;  // the last H2D copy out of the pinned staging
     std::mutex mu;
     // fused decode → resize: per-image plans (in the staging), the two-pass path's horizontal
     // output, Pillow coefficient tables per (size in, size out, filter, y0 shift) built on first use
     jpeg::RDesc *h_rdesc = nullptr, *d_rdesc = nullptr;
-    uint8_t *d_tmp = nullptr;
-    size_t tmp_bytes = 0;
+    DevBuf<uint8_t> d_tmp;
     struct Coeffs {
         int ksize = 0, first = 0, last = 0;
-        int *bounds = nullptr, *coef = nullptr;
+        DevBuf<int> bounds, coef;
         std::vector<int> hbounds;  // host copy of bounds (the band planner reads it)
     };
     std::map<std::tuple<int, int, int, int>, Coeffs> coeffs;
@@ -1213,17 +1213,17 @@ static size_t stage_layout(JpegDecoder *h, int n, int64_t nb) {
     const size_t o_qsel = o_qtab + al((size_t)n * 3 * 128);
     const size_t o_coef = o_qsel + al((size_t)nb * 4);
     const size_t total = o_coef + (size_t)nb * 128;
-    if (h->h_stage != nullptr) {
-        h->h_desc = reinterpret_cast<jpeg::Desc *>(h->h_stage);
-        h->h_rdesc = reinterpret_cast<jpeg::RDesc *>(h->h_stage + o_rdesc);
-        h->h_qtab = reinterpret_cast<uint16_t *>(h->h_stage + o_qtab);
-        h->h_qsel = reinterpret_cast<int32_t *>(h->h_stage + o_qsel);
-        h->h_coef = reinterpret_cast<int16_t *>(h->h_stage + o_coef);
-        h->d_desc = reinterpret_cast<jpeg::Desc *>(h->d_stage);
-        h->d_rdesc = reinterpret_cast<jpeg::RDesc *>(h->d_stage + o_rdesc);
-        h->d_qtab = reinterpret_cast<uint16_t *>(h->d_stage + o_qtab);
-        h->d_qsel = reinterpret_cast<int32_t *>(h->d_stage + o_qsel);
-        h->d_coef = reinterpret_cast<int16_t *>(h->d_stage + o_coef);
+    if (!h->h_stage.empty()) {
+        h->h_desc = reinterpret_cast<jpeg::Desc *>(h->h_stage.get());
+        h->h_rdesc = reinterpret_cast<jpeg::RDesc *>(h->h_stage.get() + o_rdesc);
+        h->h_qtab = reinterpret_cast<uint16_t *>(h->h_stage.get() + o_qtab);
+        h->h_qsel = reinterpret_cast<int32_t *>(h->h_stage.get() + o_qsel);
+        h->h_coef = reinterpret_cast<int16_t *>(h->h_stage.get() + o_coef);
+        h->d_desc = reinterpret_cast<jpeg::Desc *>(h->d_stage.get());
+        h->d_rdesc = reinterpret_cast<jpeg::RDesc *>(h->d_stage.get() + o_rdesc);
+        h->d_qtab = reinterpret_cast<uint16_t *>(h->d_stage.get() + o_qtab);
+        h->d_qsel = reinterpret_cast<int32_t *>(h->d_stage.get() + o_qsel);
+        h->d_coef = reinterpret_cast<int16_t *>(h->d_stage.get() + o_coef);
         h->stage_used = total;
     }
     return total;
@@ -1238,10 +1238,10 @@ extern "C" int rc_jpeg_decoder_create(int device, int max_images, int64_t max_bl
         h->max_images = max_images;
         h->max_blocks = max_blocks;
         try {
-            h->stage_cap = stage_layout(h, max_images, max_blocks);
-            RC_HIP(hipHostMalloc((void **)&h->h_stage, h->stage_cap, hipHostMallocDefault));
-            h->d_stage = (uint8_t *)dmalloc(h->stage_cap);
-            h->d_planes = (uint8_t *)dmalloc((size_t)max_blocks * 64);
+            const size_t stage_bytes = stage_layout(h, max_images, max_blocks);
+            h->h_stage.reserve(stage_bytes);
+            h->d_stage.reserve(stage_bytes);
+            h->d_planes.reserve((size_t)max_blocks * 64);
             RC_HIP(hipEventCreateWithFlags(&h->staged, hipEventDisableTiming));
         } catch (...) {
             rc_jpeg_decoder_destroy(h);
@@ -1256,15 +1256,7 @@ extern "C" int rc_jpeg_decoder_destroy(rc_jpeg_decoder *h) {
         if (!h) return;
         DeviceScope ds(h->device);
         if (h->staged) (void)hipEventSynchronize(h->staged);
-        if (h->h_stage) (void)hipHostFree(h->h_stage);
-        dfree(h->d_stage);
-        dfree(h->d_planes);
-        dfree(h->d_tmp);
         jpeg::entropy_destroy(h->ent);
-        for (auto &kv : h->coeffs) {
-            dfree(kv.second.bounds);
-            dfree(kv.second.coef);
-        }
         if (h->staged) (void)hipEventDestroy(h->staged);
         delete h;
     });
@@ -1377,8 +1369,8 @@ void stage_host(rc_jpeg_decoder *h, int n, const uint8_t *const *jpgs, const int
 void upload_idct(rc_jpeg_decoder *h, const std::vector<jpeg::Header> &hd, int64_t nb, hipStream_t s) {
     if (h->entropy == RC_JPEG_ENTROPY_DEVICE) {
         const int n = (int)hd.size();
-        const size_t head = reinterpret_cast<uint8_t *>(h->h_coef) - h->h_stage;
-        RC_HIP(hipMemcpyAsync(h->d_stage, h->h_stage, head, hipMemcpyHostToDevice, s));
+        const size_t head = reinterpret_cast<uint8_t *>(h->h_coef) - h->h_stage.get();
+        RC_HIP(hipMemcpyAsync(h->d_stage.get(), h->h_stage.get(), head, hipMemcpyHostToDevice, s));
         std::vector<int32_t> flags(n, 0);
         const size_t sent = jpeg::entropy_decode(h->ent, n, nb, reinterpret_cast<const uint8_t *>(h->h_coef), h->d_coef, s,
                                                  flags.data());
@@ -1401,12 +1393,12 @@ void upload_idct(rc_jpeg_decoder *h, const std::vector<jpeg::Header> &hd, int64_
             h->upload_bytes.fetch_add(hd[i].blocks * 128);
         }
     } else {
-        RC_HIP(hipMemcpyAsync(h->d_stage, h->h_stage, h->stage_used, hipMemcpyHostToDevice, s));
+        RC_HIP(hipMemcpyAsync(h->d_stage.get(), h->h_stage.get(), h->stage_used, hipMemcpyHostToDevice, s));
         h->upload_bytes.fetch_add((int64_t)h->stage_used);
     }
     RC_HIP(hipEventRecord(h->staged, s));
     hipLaunchKernelGGL(jpeg::jpeg_idct_kernel, dim3((unsigned)((nb + 7) / 8)), dim3(64), 0, s, h->d_coef, h->d_qsel,
-                       h->d_qtab, nb, h->d_planes);
+                       h->d_qtab, nb, h->d_planes.get());
     RC_LAUNCH_CHECK();
 }
 
@@ -1422,19 +1414,13 @@ const rc_jpeg_decoder::Coeffs &resize_coeffs(rc_jpeg_decoder *h, int in_size, in
     d.last = c.bounds[2 * (out_size - 1)] + c.bounds[2 * (out_size - 1) + 1];
     for (int i = 0; i < out_size; ++i) c.bounds[2 * i] -= shift;
     d.hbounds = c.bounds;
-    d.bounds = (int *)dmalloc(c.bounds.size() * sizeof(int));
-    try {
-        // padded by BAND_MAXV zeros: the band kernel reads a row's first BAND_MAXV taps unguarded
-        c.coef.resize(c.coef.size() + jpeg::BAND_MAXV, 0);
-        d.coef = (int *)dmalloc(c.coef.size() * sizeof(int));
-        RC_HIP(hipMemcpy(d.bounds, c.bounds.data(), c.bounds.size() * sizeof(int), hipMemcpyHostToDevice));
-        RC_HIP(hipMemcpy(d.coef, c.coef.data(), c.coef.size() * sizeof(int), hipMemcpyHostToDevice));
-    } catch (...) {
-        dfree(d.bounds);
-        dfree(d.coef);
-        throw;
-    }
-    return h->coeffs.emplace(key, d).first->second;
+    d.bounds.reserve(c.bounds.size());
+    // padded by BAND_MAXV zeros: the band kernel reads a row's first BAND_MAXV taps unguarded
+    c.coef.resize(c.coef.size() + jpeg::BAND_MAXV, 0);
+    d.coef.reserve(c.coef.size());
+    RC_HIP(hipMemcpy(d.bounds.get(), c.bounds.data(), c.bounds.size() * sizeof(int), hipMemcpyHostToDevice));
+    RC_HIP(hipMemcpy(d.coef.get(), c.coef.data(), c.coef.size() * sizeof(int), hipMemcpyHostToDevice));
+    return h->coeffs.emplace(key, std::move(d)).first->second;
 }
 
 }  // namespace
@@ -1454,7 +1440,7 @@ extern "C" int rc_jpeg_decode(rc_jpeg_decoder *h, int n, const uint8_t *const *j
         stage_host(h, n, jpgs, lens, rgb_offsets, hd, maxpix, nb);
         upload_idct(h, hd, nb, s);
         hipLaunchKernelGGL(jpeg::jpeg_color_kernel, dim3((unsigned)((maxpix + 255) / 256), (unsigned)n), dim3(256), 0, s,
-                           h->d_planes, h->d_desc, rgb);
+                           h->d_planes.get(), h->d_desc, rgb);
         RC_LAUNCH_CHECK();
     });
 }
@@ -1489,8 +1475,8 @@ extern "C" int rc_jpeg_decode_resized(rc_jpeg_decoder *h, int n, const uint8_t *
             r.Hs = H;
             if (r.need_h) {
                 const auto &ch = resize_coeffs(h, W, S, resample, 0);
-                r.hb = ch.bounds;
-                r.hc = ch.coef;
+                r.hb = ch.bounds.get();
+                r.hc = ch.coef.get();
                 r.hk = ch.ksize;
                 max_hk = std::max(max_hk, r.hk);
             }
@@ -1503,8 +1489,8 @@ extern "C" int rc_jpeg_decode_resized(rc_jpeg_decoder *h, int n, const uint8_t *
                     r.Hs = cv.last - cv.first;
                 }
                 const auto &cvs = r.y0 != 0 ? resize_coeffs(h, H, S, resample, r.y0) : cv;
-                r.vb = cvs.bounds;
-                r.vc = cvs.coef;
+                r.vb = cvs.bounds.get();
+                r.vc = cvs.coef.get();
                 r.vk = cvs.ksize;
                 vb = &cvs.hbounds;
                 r.tmp_off = tmp_need;
@@ -1550,31 +1536,26 @@ extern "C" int rc_jpeg_decode_resized(rc_jpeg_decoder *h, int n, const uint8_t *
             // horizontal taps in registers: 5 (any bicubic upscale, e.g. the fixture's 168 -> 224), 7
             // (down to 1.5x), else (or S > 256) the general form
             if (max_hk <= 5 && S <= 64 * jpeg::BAND_NXO)
-                hipLaunchKernelGGL(jpeg::jpeg_band_resize_kernel<5>, gr, dim3(64 * jpeg::BAND_WAVES), (size_t)band_lds, s, h->d_planes,
+                hipLaunchKernelGGL(jpeg::jpeg_band_resize_kernel<5>, gr, dim3(64 * jpeg::BAND_WAVES), (size_t)band_lds, s, h->d_planes.get(),
                                    h->d_desc, h->d_rdesc, out);
             else if (max_hk <= 7 && S <= 64 * jpeg::BAND_NXO)
-                hipLaunchKernelGGL(jpeg::jpeg_band_resize_kernel<7>, gr, dim3(64 * jpeg::BAND_WAVES), (size_t)band_lds, s, h->d_planes,
+                hipLaunchKernelGGL(jpeg::jpeg_band_resize_kernel<7>, gr, dim3(64 * jpeg::BAND_WAVES), (size_t)band_lds, s, h->d_planes.get(),
                                    h->d_desc, h->d_rdesc, out);
             else
-                hipLaunchKernelGGL(jpeg::jpeg_band_resize_kernel<0>, gr, dim3(64 * jpeg::BAND_WAVES), (size_t)band_lds, s, h->d_planes,
+                hipLaunchKernelGGL(jpeg::jpeg_band_resize_kernel<0>, gr, dim3(64 * jpeg::BAND_WAVES), (size_t)band_lds, s, h->d_planes.get(),
                                    h->d_desc, h->d_rdesc, out);
             RC_LAUNCH_CHECK();
             return;
         }
-        if ((size_t)tmp_need > h->tmp_bytes) {  // grows geometrically with the largest batch seen
-            const size_t want = std::max<size_t>((size_t)tmp_need, 2 * h->tmp_bytes);
+        if ((size_t)tmp_need > h->d_tmp.capacity()) {  // grows geometrically with the largest batch seen
             RC_HIP(hipStreamSynchronize(s));
-            dfree(h->d_tmp);
-            h->d_tmp = nullptr;
-            h->tmp_bytes = 0;
-            h->d_tmp = (uint8_t *)dmalloc(want);
-            h->tmp_bytes = want;
+            h->d_tmp.reserve(std::max<size_t>((size_t)tmp_need, 2 * h->d_tmp.capacity()));
         }
         hipLaunchKernelGGL(jpeg::jpeg_color_resize_h_kernel, dim3((unsigned)maxrows, (unsigned)n), dim3(256), 0, s,
-                           h->d_planes, h->d_desc, h->d_rdesc, h->d_tmp, out);
+                           h->d_planes.get(), h->d_desc, h->d_rdesc, h->d_tmp.get(), out);
         RC_LAUNCH_CHECK();
         hipLaunchKernelGGL(jpeg::jpeg_resize_v_kernel, dim3((unsigned)((S * S + 255) / 256), (unsigned)n), dim3(256), 0, s,
-                           h->d_rdesc, h->d_tmp, out);
+                           h->d_rdesc, h->d_tmp.get(), out);
         RC_LAUNCH_CHECK();
     });
 }

@@ -29,6 +29,7 @@
 // the host built, positions and states are clamped, ordinals are tested before a store.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "jpeg_host.h"
@@ -455,55 +456,41 @@ struct EntropyWork {
     int64_t max_blocks = 0;
     int gmax = 0;
     // pinned [flags × max_images | EDesc × max_images | GroupEnt × gmax] and its device twin
-    uint8_t *h_meta = nullptr, *d_meta = nullptr;
+    PinBuf<uint8_t> h_meta;
+    DevBuf<uint8_t> d_meta;
     size_t o_desc = 0, o_group = 0;
-    int32_t *h_flags_out = nullptr;  // pinned read-back
-    uint8_t *d_ent = nullptr;        // the uploaded segment tables and scans
-    uint32_t *d_lexit = nullptr, *d_lcnt = nullptr, *d_group = nullptr;  // d_group: gentry, gexit × 2, gtail
+    PinBuf<int32_t> h_flags_out;  // pinned read-back
+    DevBuf<uint8_t> d_ent;        // the uploaded segment tables and scans
+    DevBuf<uint32_t> d_lexit, d_lcnt, d_group;  // d_group: gentry, gexit × 2, gtail
     std::vector<size_t> roff, rcap;  // each image's slice of the staging (begin): offset, bytes (0: not taken)
     size_t rtotal = 0;               // bytes of the staging the slices cover
-    int32_t *h_flags() const { return reinterpret_cast<int32_t *>(h_meta); }
-    EDesc *h_desc() const { return reinterpret_cast<EDesc *>(h_meta + o_desc); }
-    GroupEnt *h_group() const { return reinterpret_cast<GroupEnt *>(h_meta + o_group); }
+    int32_t *h_flags() const { return reinterpret_cast<int32_t *>(h_meta.get()); }
+    EDesc *h_desc() const { return reinterpret_cast<EDesc *>(h_meta.get() + o_desc); }
+    GroupEnt *h_group() const { return reinterpret_cast<GroupEnt *>(h_meta.get() + o_group); }
 };
 
 EntropyWork *entropy_create(int max_images, int64_t max_blocks) {
-    auto *w = new EntropyWork();
+    std::unique_ptr<EntropyWork> w(new EntropyWork());
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    try {
-        w->max_images = max_images;
-        w->max_blocks = max_blocks;
-        w->gmax = (int)(max_blocks / LANES) + max_images;
-        w->o_desc = al((size_t)max_images * 4);
-        w->o_group = w->o_desc + al((size_t)max_images * sizeof(EDesc));
-        const size_t meta = w->o_group + (size_t)w->gmax * sizeof(GroupEnt);
-        w->h_meta = (uint8_t *)hmalloc(meta);
-        w->d_meta = (uint8_t *)dmalloc(meta);
-        w->h_flags_out = (int32_t *)hmalloc((size_t)max_images * 4);
-        w->d_ent = (uint8_t *)dmalloc((size_t)max_blocks * 128);
-        w->d_lexit = (uint32_t *)dmalloc((size_t)max_blocks * 4);
-        w->d_lcnt = (uint32_t *)dmalloc((size_t)max_blocks * 4);
-        w->d_group = (uint32_t *)dmalloc((size_t)w->gmax * 4 * 4);
-        w->roff.assign(max_images, 0);
-        w->rcap.assign(max_images, 0);
-    } catch (...) {
-        entropy_destroy(w);
-        throw;
-    }
-    return w;
+    w->max_images = max_images;
+    w->max_blocks = max_blocks;
+    w->gmax = (int)(max_blocks / LANES) + max_images;
+    w->o_desc = al((size_t)max_images * 4);
+    w->o_group = w->o_desc + al((size_t)max_images * sizeof(EDesc));
+    const size_t meta = w->o_group + (size_t)w->gmax * sizeof(GroupEnt);
+    w->h_meta.reserve(meta);
+    w->d_meta.reserve(meta);
+    w->h_flags_out.reserve((size_t)max_images);
+    w->d_ent.reserve((size_t)max_blocks * 128);
+    w->d_lexit.reserve((size_t)max_blocks);
+    w->d_lcnt.reserve((size_t)max_blocks);
+    w->d_group.reserve((size_t)w->gmax * 4);
+    w->roff.assign(max_images, 0);
+    w->rcap.assign(max_images, 0);
+    return w.release();
 }
 
-void entropy_destroy(EntropyWork *w) {
-    if (!w) return;
-    hfree(w->h_meta);
-    hfree(w->h_flags_out);
-    dfree(w->d_meta);
-    dfree(w->d_ent);
-    dfree(w->d_lexit);
-    dfree(w->d_lcnt);
-    dfree(w->d_group);
-    delete w;
-}
+void entropy_destroy(EntropyWork *w) { delete w; }
 
 // Segments of the scan: restart intervals, or one.
 static int64_t segment_count(const Header &hd) {
@@ -656,35 +643,35 @@ size_t entropy_decode(EntropyWork *w, int n, int64_t nb, const uint8_t *staging,
         }
     }
     size_t uploaded = w->o_desc + (size_t)n * sizeof(EDesc);
-    RC_HIP(hipMemcpyAsync(w->d_meta, w->h_meta, uploaded, hipMemcpyHostToDevice, s));
-    int32_t *d_flags = reinterpret_cast<int32_t *>(w->d_meta);
+    RC_HIP(hipMemcpyAsync(w->d_meta.get(), w->h_meta.get(), uploaded, hipMemcpyHostToDevice, s));
+    int32_t *d_flags = reinterpret_cast<int32_t *>(w->d_meta.get());
     if (G > 0) {
-        RC_HIP(hipMemcpyAsync(w->d_meta + w->o_group, gr, (size_t)G * sizeof(GroupEnt), hipMemcpyHostToDevice, s));
+        RC_HIP(hipMemcpyAsync(w->d_meta.get() + w->o_group, gr, (size_t)G * sizeof(GroupEnt), hipMemcpyHostToDevice, s));
         // the scans: the images' slices lie back to back, one copy of about the files' bytes
-        RC_HIP(hipMemcpyAsync(w->d_ent, staging, w->rtotal, hipMemcpyHostToDevice, s));
+        RC_HIP(hipMemcpyAsync(w->d_ent.get(), staging, w->rtotal, hipMemcpyHostToDevice, s));
         uploaded += (size_t)G * sizeof(GroupEnt) + w->rtotal;
-        const EDesc *d_desc = reinterpret_cast<const EDesc *>(w->d_meta + w->o_desc);
-        const GroupEnt *d_gr = reinterpret_cast<const GroupEnt *>(w->d_meta + w->o_group);
-        uint32_t *gentry = w->d_group, *gexit = w->d_group + w->gmax, *gtail = w->d_group + 3 * (size_t)w->gmax;
+        const EDesc *d_desc = reinterpret_cast<const EDesc *>(w->d_meta.get() + w->o_desc);
+        const GroupEnt *d_gr = reinterpret_cast<const GroupEnt *>(w->d_meta.get() + w->o_group);
+        uint32_t *gentry = w->d_group.get(), *gexit = w->d_group.get() + w->gmax, *gtail = w->d_group.get() + 3 * (size_t)w->gmax;
         const int64_t n16 = nb * 8;
         hipLaunchKernelGGL(jpeg_clear_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s,
                            reinterpret_cast<uint4 *>(d_coef), n16);
         RC_LAUNCH_CHECK();
         const int passes = chained ? SYNC_PASSES : 1;
         for (int pass = 0; pass < passes; ++pass) {
-            hipLaunchKernelGGL(jpeg_entropy_sync_kernel, dim3((unsigned)G), dim3(LANES), 0, s, d_desc, d_gr, w->d_ent,
-                               w->d_lexit, w->d_lcnt, gentry, gexit, gtail, w->gmax, pass);
+            hipLaunchKernelGGL(jpeg_entropy_sync_kernel, dim3((unsigned)G), dim3(LANES), 0, s, d_desc, d_gr, w->d_ent.get(),
+                               w->d_lexit.get(), w->d_lcnt.get(), gentry, gexit, gtail, w->gmax, pass);
             RC_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(jpeg_entropy_write_kernel, dim3((unsigned)G), dim3(LANES), 0, s, d_desc, d_gr, w->d_ent,
-                           w->d_lexit, w->d_lcnt, gentry, gexit + (size_t)((passes - 1) & 1) * w->gmax, gtail, d_coef, d_flags);
+        hipLaunchKernelGGL(jpeg_entropy_write_kernel, dim3((unsigned)G), dim3(LANES), 0, s, d_desc, d_gr, w->d_ent.get(),
+                           w->d_lexit.get(), w->d_lcnt.get(), gentry, gexit + (size_t)((passes - 1) & 1) * w->gmax, gtail, d_coef, d_flags);
         RC_LAUNCH_CHECK();
         hipLaunchKernelGGL(jpeg_dc_kernel, dim3(3, (unsigned)n), dim3(LANES), 0, s, d_desc, d_coef);
         RC_LAUNCH_CHECK();
     }
-    RC_HIP(hipMemcpyAsync(w->h_flags_out, d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    RC_HIP(hipMemcpyAsync(w->h_flags_out.get(), d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     RC_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < n; ++i) flags[i] = w->h_flags_out[i];
+    for (int i = 0; i < n; ++i) flags[i] = w->h_flags_out.get()[i];
     return uploaded;
 }
 

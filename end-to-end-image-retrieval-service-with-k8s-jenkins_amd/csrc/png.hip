@@ -204,13 +204,13 @@ __global__ __launch_bounds__(64 * kNW) void png_reconstruct_kernel(const uint8_t
 // and of the last kernel (a later call's stream waits for it before overwriting the device copy).
 struct Workspace {
     std::mutex mu;
-    uint8_t *h_stage = nullptr, *d_stage = nullptr;
-    size_t cap = 0;
+    PinBuf<uint8_t> h_stage;
+    DevBuf<uint8_t> d_stage;
     hipEvent_t staged = nullptr, done = nullptr;
 };
 
 static Workspace &workspace(int device) {
-    static Workspace ws[64];
+    static Workspace *const ws = new Workspace[64];  // never destroyed: no device call runs at process exit
     RC_REQUIRE(device >= 0 && device < 64, RC_ERR_INVALID, "device ordinal out of range");
     return ws[device];
 }
@@ -263,33 +263,28 @@ extern "C" int rc_png_reconstruct(int device, int n, const rc_png_image *images,
         if (!ws.staged) RC_HIP(hipEventCreateWithFlags(&ws.staged, hipEventDisableTiming));
         if (!ws.done) RC_HIP(hipEventCreateWithFlags(&ws.done, hipEventDisableTiming));
         RC_HIP(hipEventSynchronize(ws.staged));  // the last upload has left the pinned block
-        if (total > ws.cap) {
-            const size_t want = std::min(std::max(total, ws.cap * 2), png::kMaxStageBytes);
-            hfree(ws.h_stage);
+        if (const size_t cap = min_capacity(ws.h_stage, ws.d_stage); total > cap) {
+            const size_t want = std::min(std::max(total, cap * 2), png::kMaxStageBytes);
             RC_HIP(hipDeviceSynchronize());  // a kernel may still read the old device copy
-            dfree(ws.d_stage);
-            ws.h_stage = ws.d_stage = nullptr;
-            ws.cap = 0;
-            ws.h_stage = (uint8_t *)hmalloc(want);
-            ws.d_stage = (uint8_t *)dmalloc(want);
-            ws.cap = want;
+            ws.h_stage.reserve(want);
+            ws.d_stage.reserve(want);
         }
-        auto *desc = reinterpret_cast<png::Desc *>(ws.h_stage);
-        auto *pal = reinterpret_cast<uint32_t *>(ws.h_stage + o_pal);
+        auto *desc = reinterpret_cast<png::Desc *>(ws.h_stage.get());
+        auto *pal = reinterpret_cast<uint32_t *>(ws.h_stage.get() + o_pal);
         size_t at = o_scan;
         int ipal = 0;
         for (int i = 0; i < n; ++i) {
             const rc_png_image &p = images[i];
             png::fill_desc(desc[i], p, (int64_t)at, pal, ipal);
-            std::memcpy(ws.h_stage + at, p.scanlines, (size_t)p.scan_bytes);
+            std::memcpy(ws.h_stage.get() + at, p.scanlines, (size_t)p.scan_bytes);
             at += al((size_t)p.scan_bytes);
         }
         hipStream_t s = (hipStream_t)stream;
         RC_HIP(hipStreamWaitEvent(s, ws.done, 0));
-        RC_HIP(hipMemcpyAsync(ws.d_stage, ws.h_stage, total, hipMemcpyHostToDevice, s));
+        RC_HIP(hipMemcpyAsync(ws.d_stage.get(), ws.h_stage.get(), total, hipMemcpyHostToDevice, s));
         RC_HIP(hipEventRecord(ws.staged, s));
-        png::launch_reconstruct(ws.d_stage, reinterpret_cast<png::Desc *>(ws.d_stage),
-                                reinterpret_cast<uint32_t *>(ws.d_stage + o_pal), rgb, n, s);
+        png::launch_reconstruct(ws.d_stage.get(), reinterpret_cast<png::Desc *>(ws.d_stage.get()),
+                                reinterpret_cast<uint32_t *>(ws.d_stage.get() + o_pal), rgb, n, s);
         RC_HIP(hipEventRecord(ws.done, s));
     });
 }

@@ -383,9 +383,9 @@ __global__ __launch_bounds__(LANES) void png_inflate_kernel(const uint32_t *__re
 // kernels) by the stream before it overwrites the device copies.
 struct Workspace {
     std::mutex mu;
-    uint8_t *h_stage = nullptr, *d_stage = nullptr, *d_scan = nullptr;
-    int32_t *h_flags = nullptr;  // pinned read-back, kMaxImages entries
-    size_t cap = 0, scan_cap = 0;
+    PinBuf<uint8_t> h_stage;
+    DevBuf<uint8_t> d_stage, d_scan;
+    PinBuf<int32_t> h_flags;  // pinned read-back, kMaxImages entries
     hipEvent_t staged = nullptr, done = nullptr;
     int64_t device_images = 0, host_fallbacks = 0;
     // rc_png_decode_timing: an event pair around png_inflate_kernel alone, read after the call's
@@ -398,7 +398,7 @@ struct Workspace {
 constexpr int kMaxImages = 65535;
 
 static Workspace &workspace(int device) {
-    static Workspace ws[64];
+    static Workspace *const ws = new Workspace[64];  // never destroyed: no device call runs at process exit
     RC_REQUIRE(device >= 0 && device < 64, RC_ERR_INVALID, "device ordinal out of range");
     return ws[device];
 }
@@ -445,32 +445,22 @@ extern "C" int rc_png_decode(int device, int n, const rc_png_stream *streams, ui
         DeviceScope ds(device);
         if (!ws.staged) RC_HIP(hipEventCreateWithFlags(&ws.staged, hipEventDisableTiming));
         if (!ws.done) RC_HIP(hipEventCreateWithFlags(&ws.done, hipEventDisableTiming));
-        if (!ws.h_flags) ws.h_flags = (int32_t *)hmalloc((size_t)pngz::kMaxImages * 4);
+        ws.h_flags.reserve((size_t)pngz::kMaxImages);
         RC_HIP(hipEventSynchronize(ws.staged));  // the last upload has left the pinned block
-        if (total > ws.cap) {
-            const size_t want = std::min(std::max(total, ws.cap * 2), png::kMaxStageBytes);
-            hfree(ws.h_stage);
+        if (const size_t cap = min_capacity(ws.h_stage, ws.d_stage); total > cap) {
+            const size_t want = std::min(std::max(total, cap * 2), png::kMaxStageBytes);
             RC_HIP(hipDeviceSynchronize());  // a kernel may still read the old device copy
-            dfree(ws.d_stage);
-            ws.h_stage = ws.d_stage = nullptr;
-            ws.cap = 0;
-            ws.h_stage = (uint8_t *)hmalloc(want);
-            ws.d_stage = (uint8_t *)dmalloc(want);
-            ws.cap = want;
+            ws.h_stage.reserve(want);
+            ws.d_stage.reserve(want);
         }
-        if (scan_total > ws.scan_cap) {
-            const size_t want = std::min(std::max(scan_total, ws.scan_cap * 2), png::kMaxStageBytes);
+        if (scan_total > ws.d_scan.capacity()) {
             RC_HIP(hipDeviceSynchronize());
-            dfree(ws.d_scan);
-            ws.d_scan = nullptr;
-            ws.scan_cap = 0;
-            ws.d_scan = (uint8_t *)dmalloc(want);
-            ws.scan_cap = want;
+            ws.d_scan.reserve(std::min(std::max(scan_total, ws.d_scan.capacity() * 2), png::kMaxStageBytes));
         }
-        auto *idesc = reinterpret_cast<pngz::IDesc *>(ws.h_stage);
-        auto *rdesc = reinterpret_cast<png::Desc *>(ws.h_stage + o_rdesc);
-        auto *pal = reinterpret_cast<uint32_t *>(ws.h_stage + o_pal);
-        std::memset(ws.h_stage + o_flags, 0, (size_t)n * 4);
+        auto *idesc = reinterpret_cast<pngz::IDesc *>(ws.h_stage.get());
+        auto *rdesc = reinterpret_cast<png::Desc *>(ws.h_stage.get() + o_rdesc);
+        auto *pal = reinterpret_cast<uint32_t *>(ws.h_stage.get() + o_pal);
+        std::memset(ws.h_stage.get() + o_flags, 0, (size_t)n * 4);
         size_t at = o_data, sat = 0;
         int ipal = 0;
         for (int i = 0; i < n; ++i) {
@@ -486,23 +476,23 @@ extern "C" int rc_png_decode(int device, int n, const rc_png_stream *streams, ui
             d.scan_bytes = (int32_t)((int64_t)p.height * d.pitch);  // <= 2^24 * 4 + 2^24
             d.pad = 0;
             png::fill_desc(rdesc[i], p, (int64_t)sat, pal, ipal);
-            std::memcpy(ws.h_stage + at, p.idat, nb);
-            std::memset(ws.h_stage + at + nb, 0, al(nb + 4) - nb);
+            std::memcpy(ws.h_stage.get() + at, p.idat, nb);
+            std::memset(ws.h_stage.get() + at + nb, 0, al(nb + 4) - nb);
             at += al(nb + 4);
             sat += al((size_t)d.scan_bytes);
         }
         hipStream_t s = (hipStream_t)stream;
         RC_HIP(hipStreamWaitEvent(s, ws.done, 0));
-        RC_HIP(hipMemcpyAsync(ws.d_stage, ws.h_stage, total, hipMemcpyHostToDevice, s));
+        RC_HIP(hipMemcpyAsync(ws.d_stage.get(), ws.h_stage.get(), total, hipMemcpyHostToDevice, s));
         RC_HIP(hipEventRecord(ws.staged, s));
-        int32_t *d_flags = reinterpret_cast<int32_t *>(ws.d_stage + o_flags);
+        int32_t *d_flags = reinterpret_cast<int32_t *>(ws.d_stage.get() + o_flags);
         if (ws.timing) RC_HIP(hipEventRecord(ws.t0, s));
-        pngz::png_inflate_kernel<<<n, pngz::LANES, 0, s>>>(reinterpret_cast<const uint32_t *>(ws.d_stage),
-                                                          reinterpret_cast<const pngz::IDesc *>(ws.d_stage), ws.d_scan,
+        pngz::png_inflate_kernel<<<n, pngz::LANES, 0, s>>>(reinterpret_cast<const uint32_t *>(ws.d_stage.get()),
+                                                          reinterpret_cast<const pngz::IDesc *>(ws.d_stage.get()), ws.d_scan.get(),
                                                           d_flags);
         RC_LAUNCH_CHECK();
         if (ws.timing) RC_HIP(hipEventRecord(ws.t1, s));
-        RC_HIP(hipMemcpyAsync(ws.h_flags, d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        RC_HIP(hipMemcpyAsync(ws.h_flags.get(), d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         RC_HIP(hipStreamSynchronize(s));
         if (ws.timing) {
             float ms = 0.f;
@@ -511,16 +501,16 @@ extern "C" int rc_png_decode(int device, int n, const rc_png_stream *streams, ui
             ++ws.kernel_launches;
         }
         // reconstruct every run of images the device accepted; the others are the caller's
-        const auto *d_rdesc = reinterpret_cast<const png::Desc *>(ws.d_stage + o_rdesc);
+        const auto *d_rdesc = reinterpret_cast<const png::Desc *>(ws.d_stage.get() + o_rdesc);
         for (int i = 0; i < n;) {
-            if (ws.h_flags[i]) {
+            if (ws.h_flags.get()[i]) {
                 flags_out[i++] = 1;
                 ++ws.host_fallbacks;
                 continue;
             }
             int e = i;
-            while (e < n && !ws.h_flags[e]) flags_out[e++] = 0;
-            png::launch_reconstruct(ws.d_scan, d_rdesc + i, reinterpret_cast<const uint32_t *>(ws.d_stage + o_pal), rgb,
+            while (e < n && !ws.h_flags.get()[e]) flags_out[e++] = 0;
+            png::launch_reconstruct(ws.d_scan.get(), d_rdesc + i, reinterpret_cast<const uint32_t *>(ws.d_stage.get() + o_pal), rgb,
                                     e - i, s);
             ws.device_images += e - i;
             i = e;

@@ -3,12 +3,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
 
 #include "retrieval_core.h"
 
@@ -119,6 +122,82 @@ inline void *hmalloc(size_t bytes) {
 
 inline void hfree(void *p) {
     if (p) (void)hipHostFree(p);
+}
+
+// Move-only owner of one block of device (DevBuf) or pinned host (PinBuf) memory, counted in
+// elements (bytes for T = void).  reserve() grows only, to exactly the count it is given (the
+// growth policy is the caller's), frees the old block before it allocates and keeps no contents;
+// if the allocation throws the buffer is empty.  Nothing here synchronises: a caller whose
+// kernels may still read the block waits before it lets go of it.
+// A size recorded beside several buffers (rc_index::ws_nq / ws_k, BatchWs's caps) is never larger
+// than what every one of its buffers holds, at every exit: zero the sizes, reserve everything,
+// then record them.
+template <typename T, bool Pinned>
+class Buffer {
+    using Elem = std::conditional_t<std::is_void_v<T>, char, T>;
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+    int dev_ = -1;  // the device current at allocation (device memory only): the free runs on it
+
+  public:
+    Buffer() = default;
+    Buffer(Buffer &&o) noexcept { swap(o); }
+    Buffer &operator=(Buffer &&o) noexcept {
+        if (this != &o) {
+            reset();
+            swap(o);
+        }
+        return *this;
+    }
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
+    ~Buffer() { reset(); }
+
+    T *get() const { return p_; }
+    size_t capacity() const { return cap_; }
+    bool empty() const { return p_ == nullptr; }
+
+    void swap(Buffer &o) noexcept {
+        std::swap(p_, o.p_);
+        std::swap(cap_, o.cap_);
+        std::swap(dev_, o.dev_);
+    }
+
+    void reserve(size_t count) {
+        if (count <= cap_) return;
+        reset();
+        if constexpr (Pinned) {
+            p_ = static_cast<T *>(hmalloc(count * sizeof(Elem)));
+        } else {
+            p_ = static_cast<T *>(dmalloc(count * sizeof(Elem)));
+            (void)hipGetDevice(&dev_);
+        }
+        cap_ = count;
+    }
+
+    void reset() noexcept {
+        if (p_ == nullptr) return;
+        if constexpr (Pinned) {
+            hfree(p_);
+        } else {
+            int cur = dev_;
+            (void)hipGetDevice(&cur);
+            if (cur != dev_) (void)hipSetDevice(dev_);
+            dfree(p_);
+            if (cur != dev_) (void)hipSetDevice(cur);
+        }
+        p_ = nullptr;
+        cap_ = 0;
+    }
+};
+template <typename T>
+using DevBuf = Buffer<T, false>;
+template <typename T>
+using PinBuf = Buffer<T, true>;
+// What every buffer of a group holds: the size to test before the group is reserved together.
+template <typename... B>
+size_t min_capacity(const B &...b) {
+    return std::min({b.capacity()...});
 }
 
 // Host f32 → bf16 bits, round to nearest even (NaN kept NaN).

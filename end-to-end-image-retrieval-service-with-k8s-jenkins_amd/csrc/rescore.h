@@ -77,9 +77,9 @@ void launch_rescore_metric(const BatchPlan &p, const BatchWs &ws, int final_pass
         with_topk_cap(topk_cap(p.k), [&](auto cap) {
             auto launch = [&](auto masked) {
                 hipLaunchKernelGGL((rescore_metric_kernel<T, decltype(nch)::value, decltype(cap)::value, decltype(masked)::value>),
-                                   dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn, p.k, ws.cnt, ws.cand, ws.cap, ws.keys,
-                                   ws.thr, ws.flags, ws.ovf, final_pass, p.row_base, p.row_stride, p.out_scores, p.out_rows, p.mask,
-                                   p.norms, ws.mcoef);
+                                   dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn.get(), p.k, ws.cnt.get(), ws.cand.get(), ws.cap, ws.keys.get(),
+                                   ws.thr.get(), ws.flags.get(), ws.ovf.get(), final_pass, p.row_base, p.row_stride, p.out_scores, p.out_rows, p.mask,
+                                   p.norms, ws.mcoef.get());
             };
             if (p.mask != nullptr) launch(std::true_type{});
             else launch(std::false_type{});
@@ -116,9 +116,9 @@ void launch_rescore_paged(const BatchPlan &p, const BatchWs &ws, int final_pass,
             auto launch = [&](auto masked, auto metric) {
                 hipLaunchKernelGGL((rescore_paged_kernel<T, decltype(nch)::value, decltype(cap)::value, decltype(masked)::value,
                                                          decltype(metric)::value>),
-                                   dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn, p.k, ws.cnt, ws.cand, ws.cap, ws.keys,
-                                   ws.eps, ws.thr, ws.flags, ws.ovf, final_pass, p.row_base, p.row_stride, p.out_scores, p.out_rows,
-                                   p.mask, p.norms, ws.mcoef, p.pages);
+                                   dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn.get(), p.k, ws.cnt.get(), ws.cand.get(), ws.cap, ws.keys.get(),
+                                   ws.eps.get(), ws.thr.get(), ws.flags.get(), ws.ovf.get(), final_pass, p.row_base, p.row_stride, p.out_scores, p.out_rows,
+                                   p.mask, p.norms, ws.mcoef.get(), p.pages);
             };
             auto with_mask = [&](auto metric) {
                 if (p.mask != nullptr) launch(std::true_type{}, metric);

@@ -794,8 +794,8 @@ void launch_rescore(const BatchPlan &p, const BatchWs &ws, int final_pass, hipSt
         with_topk_cap(topk_cap(p.k), [&](auto cap) {
             auto launch = [&](auto masked) {
                 hipLaunchKernelGGL((rescore_kernel<T, decltype(nch)::value, decltype(cap)::value, decltype(masked)::value>),
-                                   dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn, p.k, ws.cnt, ws.cand, ws.cap, ws.keys,
-                                   ws.eps, ws.thr, ws.flags, ws.ovf, final_pass, p.row_base, p.row_stride, p.out_scores, p.out_rows,
+                                   dim3(p.nq), dim3(256), 0, s, (const T *)p.rows, p.ld, ws.qn.get(), p.k, ws.cnt.get(), ws.cand.get(), ws.cap, ws.keys.get(),
+                                   ws.eps.get(), ws.thr.get(), ws.flags.get(), ws.ovf.get(), final_pass, p.row_base, p.row_stride, p.out_scores, p.out_rows,
                                    p.mask);
             };
             if (p.mask != nullptr) launch(std::true_type{});
@@ -825,9 +825,9 @@ void run_stages(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *tim
                 int qtile = SB_TILE) {
     const int nqb = (p.nq + qtile - 1) / qtile;
     const int nq_pad = nqb * qtile;
-    RC_HIP(hipMemsetAsync(ws.keys, 0xFF, (size_t)p.nq * p.k * sizeof(uint64_t), s));
-    RC_HIP(hipMemsetAsync(ws.cnt, 0, (size_t)nq_pad * sizeof(uint32_t), s));
-    RC_HIP(hipMemsetAsync(ws.flags, 0, (size_t)p.nq * sizeof(int), s));
+    RC_HIP(hipMemsetAsync(ws.keys.get(), 0xFF, (size_t)p.nq * p.k * sizeof(uint64_t), s));
+    RC_HIP(hipMemsetAsync(ws.cnt.get(), 0, (size_t)nq_pad * sizeof(uint32_t), s));
+    RC_HIP(hipMemsetAsync(ws.flags.get(), 0, (size_t)p.nq * sizeof(int), s));
     int64_t b0 = 0, b1 = std::min<int64_t>(p.n_rows, ws.cap);
     // With nq > 256 the nqb query blocks that read one row chunk run side by side on one
     // XCD so that its L2 serves the second to last reader; over a long chunk their
@@ -865,10 +865,10 @@ void run_batched(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *ti
     const bool metric = p.metric != RC_METRIC_COSINE;  // the METRIC forms of the same kernels (RC_FILTER_METRIC)
     if (metric)
         hipLaunchKernelGGL(prepare_queries_metric_kernel<T>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, p.metric,
-                           ws.qn, (T *)ws.qh, ws.eps, ws.thr, ws.mcoef);
+                           ws.qn.get(), (T *)ws.qh.get(), ws.eps.get(), ws.thr.get(), ws.mcoef.get());
     else
-        hipLaunchKernelGGL(prepare_queries_kernel<T>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn,
-                           (T *)ws.qh, ws.eps, ws.thr);
+        hipLaunchKernelGGL(prepare_queries_kernel<T>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn.get(),
+                           (T *)ws.qh.get(), ws.eps.get(), ws.thr.get());
     RC_LAUNCH_CHECK();
     auto filter = [&](int64_t c0, int64_t c1, int64_t nchunk, int nqb) {
         if (p.pages != nullptr) launch_filter_native<T, true>(p, ws, c0, c1, nchunk, nqb, s);  // search_mfma_paged.hip
@@ -884,19 +884,19 @@ constexpr int I8_STAGE_INFLATION = 3;
 template <typename T>
 void run_batched_i8(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
     const int nq_pad = (p.nq + SB_TILE - 1) / SB_TILE * SB_TILE;
-    hipLaunchKernelGGL(prepare_queries_i8_kernel, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn,
-                       (int8_t *)ws.qh, ws.sq, ws.aq, ws.eps, ws.thr);
+    hipLaunchKernelGGL(prepare_queries_i8_kernel, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn.get(),
+                       (int8_t *)ws.qh.get(), ws.sq.get(), ws.aq.get(), ws.eps.get(), ws.thr.get());
     RC_LAUNCH_CHECK();
     const int nkt = (int)(p.ld / 128);
     auto filter = [&](int64_t c0, int64_t c1, int64_t nchunk, int nqb) {
         const int rt = nkt == 6 ? 64 : 128;
         RC_REQUIRE(c0 % rt == 0, RC_ERR_INVALID, "internal: int8 filter range not tile-aligned");
-        FilterI8Args fa{FilterArgs{p.rows8, ws.qh, p.ld, nkt, c0, c1, tiles_per_chunk(c0, c1, rt, nchunk), nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
+        FilterI8Args fa{FilterArgs{p.rows8, ws.qh.get(), p.ld, nkt, c0, c1, tiles_per_chunk(c0, c1, rt, nchunk), nqb, ws.thr.get(), ws.cnt.get(), ws.cand.get(), ws.cap},
                         p.mask};
         fa.a.rsx = p.rsx;
         fa.a.rex = p.rex;
-        fa.a.sq = ws.sq;
-        fa.a.aq = ws.aq;
+        fa.a.sq = ws.sq.get();
+        fa.a.aq = ws.aq.get();
         const dim3 gr((unsigned)(nchunk * nqb)), bl(64 * 16 / QS_QT);
         if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED
             if (nkt == 4) hipLaunchKernelGGL((filter_i8_kernel<4, 128, 0, true>), gr, bl, 0, s, fa);
@@ -922,8 +922,8 @@ void run_batched_i8(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
 // is a count of 256-query blocks' chunks) and does not read the mask: the rescoring applies it.
 template <typename T>
 void run_batched_i8_stream(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
-    hipLaunchKernelGGL(prepare_queries_i8_kernel, dim3(I8_STREAM_MAX_QUERIES), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn,
-                       (int8_t *)ws.qh, ws.sq, ws.aq, ws.eps, ws.thr);
+    hipLaunchKernelGGL(prepare_queries_i8_kernel, dim3(I8_STREAM_MAX_QUERIES), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn.get(),
+                       (int8_t *)ws.qh.get(), ws.sq.get(), ws.aq.get(), ws.eps.get(), ws.thr.get());
     RC_LAUNCH_CHECK();
     auto filter = [&](int64_t c0, int64_t c1, int64_t, int) { launch_filter_i8_stream(p, ws, c0, c1, nullptr, s); };
     run_stages<T>(p, ws, s, timer, batch_stage_ratio(p.k, ws.cap, I8_STAGE_INFLATION), p.ld, filter, I8_STREAM_MAX_QUERIES);
@@ -933,11 +933,11 @@ void run_batched_i8_stream(const BatchPlan &p, BatchWs &ws, hipStream_t s, Kerne
 void filter_scores_i8_stream(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, float *out_scores, float *out_eps,
                              hipStream_t s) {
     RC_REQUIRE(i8_filter_supported(p.ld), RC_ERR_UNSUPPORTED, "int8 filter needs ld 256, 512 or 768");
-    hipLaunchKernelGGL(prepare_queries_i8_kernel, dim3(I8_STREAM_MAX_QUERIES), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn,
-                       (int8_t *)ws.qh, ws.sq, ws.aq, ws.eps, ws.thr);
+    hipLaunchKernelGGL(prepare_queries_i8_kernel, dim3(I8_STREAM_MAX_QUERIES), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, ws.qn.get(),
+                       (int8_t *)ws.qh.get(), ws.sq.get(), ws.aq.get(), ws.eps.get(), ws.thr.get());
     RC_LAUNCH_CHECK();
     launch_filter_i8_stream(p, ws, row0, row0 + n, out_scores, s);
-    RC_HIP(hipMemcpyAsync(out_eps, ws.eps, (size_t)p.nq * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RC_HIP(hipMemcpyAsync(out_eps, ws.eps.get(), (size_t)p.nq * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
 
 // The float8 filter (filter_f8_kernel): two e4m3 query terms, no stage inflation.  ld 768 runs
@@ -952,8 +952,8 @@ void launch_filter_f8(const BatchPlan &p, const BatchWs &ws, int nq_pad, int64_t
     const int rt = nkt >= 4 ? 64 : 128, qt = nkt == 6 ? 1 : QS_QT;
     const int nqb = nq_pad / (128 * qt);
     RC_REQUIRE(c0 % rt == 0, RC_ERR_INVALID, "internal: float8 filter range not tile-aligned");
-    const FilterF8Args fa{FilterArgs{p.rows, ws.qh, p.ld, nkt, c0, c1, tiles_per_chunk(c0, c1, rt, nchunk), nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
-                          (const uint8_t *)ws.qh + (int64_t)nq_pad * p.ld, dump, p.nq, p.mask};
+    const FilterF8Args fa{FilterArgs{p.rows, ws.qh.get(), p.ld, nkt, c0, c1, tiles_per_chunk(c0, c1, rt, nchunk), nqb, ws.thr.get(), ws.cnt.get(), ws.cand.get(), ws.cap},
+                          (const uint8_t *)ws.qh.get() + (int64_t)nq_pad * p.ld, dump, p.nq, p.mask};
     const dim3 gr((unsigned)(nchunk * nqb)), bl(512);
     if constexpr (!DUMP) {
         if (p.mask_filter) {  // RC_SEARCH_MFMA_MASKED
@@ -970,7 +970,7 @@ void launch_filter_f8(const BatchPlan &p, const BatchWs &ws, int nq_pad, int64_t
 
 void prepare_queries_f8(const BatchPlan &p, const BatchWs &ws, int nq_pad, hipStream_t s) {
     hipLaunchKernelGGL(prepare_queries_f8_kernel<F8_TERMS>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld,
-                       (int64_t)nq_pad * p.ld, ws.qn, (f8_t *)ws.qh, ws.eps, ws.thr);
+                       (int64_t)nq_pad * p.ld, ws.qn.get(), (f8_t *)ws.qh.get(), ws.eps.get(), ws.thr.get());
     RC_LAUNCH_CHECK();
 }
 
@@ -1006,7 +1006,7 @@ void filter_scores_f8(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n, 
     prepare_queries_f8(p, ws, nq_pad, s);
     launch_filter_f8<true>(p, ws, nq_pad, row0, row0 + n, 8, out_scores, s);
     RC_LAUNCH_CHECK();
-    RC_HIP(hipMemcpyAsync(out_eps, ws.eps, (size_t)p.nq * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RC_HIP(hipMemcpyAsync(out_eps, ws.eps.get(), (size_t)p.nq * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
 
 void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer *timer) {
@@ -1052,35 +1052,31 @@ void batched_search(const BatchPlan &p, BatchWs &ws, hipStream_t s, KernelTimer 
 void BatchWs::ensure(int nq, int k, int64_t ld, int dtype_bytes, int qtile) {
     const int nq_pad = (nq + qtile - 1) / qtile * qtile;
     if (nq_pad <= nq_cap && k <= k_cap && ld <= ld_cap) return;
-    release();
-    nq_cap = nq_pad;
-    k_cap = std::max(k, 16);
-    ld_cap = ld;
-    qn = (float *)dmalloc((size_t)nq_cap * ld * sizeof(float));
-    qh = dmalloc((size_t)nq_cap * ld * dtype_bytes);
-    eps = (float *)dmalloc((size_t)nq_cap * sizeof(float));
-    thr = (float *)dmalloc((size_t)nq_cap * sizeof(float));
-    cnt = (uint32_t *)dmalloc((size_t)nq_cap * sizeof(uint32_t));
-    cand = (uint32_t *)dmalloc((size_t)nq_cap * cap * sizeof(uint32_t));
-    keys = (uint64_t *)dmalloc((size_t)nq_cap * k_cap * sizeof(uint64_t));
-    flags = (int *)dmalloc((size_t)nq_cap * sizeof(int));
-    sq = (float *)dmalloc((size_t)nq_cap * sizeof(float));
-    aq = (float *)dmalloc((size_t)nq_cap * sizeof(float));
-    mcoef = (float *)dmalloc((size_t)nq_cap * 4 * sizeof(float));
-    ovf = (int *)dmalloc(sizeof(int));
-    RC_HIP(hipMemset(ovf, 0, sizeof(int)));
+    *this = BatchWs{};  // frees every block before the first allocation; the sizes read 0 until all are there
+    const int k2 = std::max(k, 16);
+    const size_t nq2 = (size_t)nq_pad;
+    qn.reserve(nq2 * ld);
+    qh.reserve(nq2 * ld * dtype_bytes);
+    eps.reserve(nq2);
+    thr.reserve(nq2);
+    cnt.reserve(nq2);
+    cand.reserve(nq2 * cap);
+    keys.reserve(nq2 * k2);
+    flags.reserve(nq2);
+    sq.reserve(nq2);
+    aq.reserve(nq2);
+    mcoef.reserve(nq2 * 4);
+    ovf.reserve(1);
+    RC_HIP(hipMemset(ovf.get(), 0, sizeof(int)));
     // the fallback scan's partial lists are sized by a memory budget, not by the row count:
     // 1024 queries x top-100 keep all 256 blocks (210 MB); 4096 x 256 get 32 (268 MB) instead of 2.1 GB
-    const int64_t per_block = (int64_t)nq_cap * k_cap * (int64_t)sizeof(uint64_t);
-    fb_blocks = (int)std::max<int64_t>(FB_MIN_BLOCKS, std::min<int64_t>(FB_BLOCKS, FB_BUDGET_BYTES / per_block));
-    fb_partial = (uint64_t *)dmalloc((size_t)fb_blocks * per_block);
-}
-
-void BatchWs::release() {
-    for (void *p : {(void *)qn, qh, (void *)eps, (void *)thr, (void *)cnt, (void *)cand, (void *)keys, (void *)flags, (void *)sq,
-                    (void *)aq, (void *)mcoef, (void *)ovf, (void *)fb_partial})
-        dfree(p);
-    *this = BatchWs{};
+    const int64_t per_block = (int64_t)nq_pad * k2 * (int64_t)sizeof(uint64_t);
+    const int blocks = (int)std::max<int64_t>(FB_MIN_BLOCKS, std::min<int64_t>(FB_BLOCKS, FB_BUDGET_BYTES / per_block));
+    fb_partial.reserve((size_t)blocks * nq2 * k2);
+    nq_cap = nq_pad;
+    k_cap = k2;
+    ld_cap = ld;
+    fb_blocks = blocks;
 }
 
 }  // namespace rc

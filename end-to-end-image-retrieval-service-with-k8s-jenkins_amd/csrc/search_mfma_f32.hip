@@ -362,11 +362,11 @@ bool f32_filter_supported(int64_t ld) { return ld == 128 || ld == 256 || ld == 5
 
 void prepare_queries_f32(const BatchPlan &p, const BatchWs &ws, int nq_pad, hipStream_t s) {
     if (p.metric != RC_METRIC_COSINE)
-        hipLaunchKernelGGL(prepare_queries_f32_kernel<true>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, p.metric, ws.qn,
-                           (f16_t *)ws.qh, ws.eps, ws.thr, ws.mcoef);
+        hipLaunchKernelGGL(prepare_queries_f32_kernel<true>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, p.metric, ws.qn.get(),
+                           (f16_t *)ws.qh.get(), ws.eps.get(), ws.thr.get(), ws.mcoef.get());
     else
-        hipLaunchKernelGGL(prepare_queries_f32_kernel<false>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, p.metric, ws.qn,
-                           (f16_t *)ws.qh, ws.eps, ws.thr, ws.mcoef);
+        hipLaunchKernelGGL(prepare_queries_f32_kernel<false>, dim3(nq_pad), dim3(64), 0, s, p.queries, p.nq, p.dim, p.ld, p.metric, ws.qn.get(),
+                           (f16_t *)ws.qh.get(), ws.eps.get(), ws.thr.get(), ws.mcoef.get());
     RC_LAUNCH_CHECK();
 }
 
@@ -377,8 +377,8 @@ void launch_filter_f32_shape(const BatchPlan &p, const BatchWs &ws, int nq_pad, 
     const int nqb = nq_pad / (128 * QT);
     RC_REQUIRE(c0 % RT == 0, RC_ERR_INVALID, "internal: float32 filter range not tile-aligned");
     const bool metric = p.metric != RC_METRIC_COSINE, masked = p.mask_filter;
-    const FilterF32Args fa{FilterArgs{p.rows, ws.qh, p.ld, NKS, c0, c1, tiles_per_chunk(c0, c1, RT, nchunk), nqb, ws.thr, ws.cnt, ws.cand, ws.cap},
-                           FilterMetric{p.norms, ws.mcoef}, p.mask, dump, p.nq};
+    const FilterF32Args fa{FilterArgs{p.rows, ws.qh.get(), p.ld, NKS, c0, c1, tiles_per_chunk(c0, c1, RT, nchunk), nqb, ws.thr.get(), ws.cnt.get(), ws.cand.get(), ws.cap},
+                           FilterMetric{p.norms, ws.mcoef.get()}, p.mask, dump, p.nq};
     const dim3 gr((unsigned)(nchunk * nqb)), bl(512);
     if (dump != nullptr) hipLaunchKernelGGL((filter_f32_kernel<NKS, RT, QT, false, false, true>), gr, bl, 0, s, fa);
     else if (metric && masked) hipLaunchKernelGGL((filter_f32_kernel<NKS, RT, QT, true, true>), gr, bl, 0, s, fa);
@@ -406,7 +406,7 @@ void filter_scores_f32(const BatchPlan &p, BatchWs &ws, int64_t row0, int64_t n,
     prepare_queries_f32(p, ws, nq_pad, s);
     launch_filter_f32(p, ws, nq_pad, row0, row0 + n, 8, out_scores, s);
     RC_LAUNCH_CHECK();
-    RC_HIP(hipMemcpyAsync(out_eps, ws.eps, (size_t)p.nq * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RC_HIP(hipMemcpyAsync(out_eps, ws.eps.get(), (size_t)p.nq * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
 
 }  // namespace rc

@@ -74,6 +74,13 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restric
 
 using namespace rc;
 
+// The owning form of a RowBlock: the staging blocks of a row move.
+struct RowStage {
+    DevBuf<void> rows;
+    DevBuf<float> norms;
+    RowBlock view() const { return RowBlock{rows.get(), norms.get(), (int64_t)norms.capacity()}; }
+};
+
 struct rc_sharded {
     std::mutex mu;
     int n = 0, dim = 0, dtype = 0;
@@ -89,76 +96,72 @@ struct rc_sharded {
     std::vector<hipEvent_t> ev_start;  // per shard, recorded on the caller's (leader) stream
     // search buffers
     int nq_cap = 0, k_cap = 0;
-    std::vector<float *> q;       // [nq_cap][dim] query copy on a non-leader shard's device
-    std::vector<float *> s_loc;   // [nq_cap][k_cap] a non-leader shard's own result
-    std::vector<int64_t *> r_loc;
-    float *g_s = nullptr;         // leader [n][nq_cap][k_cap] gathered lists
-    int64_t *g_r = nullptr;
-    // upsert / fetch staging (grown on demand, reused: no allocation in steady state)
-    int64_t st_cap = 0;
-    std::vector<int64_t *> idx_d;  // [st_cap] source index per shard (on the leader for a remote shard)
-    std::vector<int64_t *> row_d;  // [st_cap] local row per shard (on the shard's device)
-    std::vector<float *> vec_d;    // [st_cap][dim] a remote shard's subset of the batch, on its device
-    std::vector<float *> gat_d;    // [st_cap][dim] that subset gathered on the leader (peer-copy source)
-    std::vector<float *> fo_d;     // [st_cap][dim] fetched rows on the shard's device
-    std::vector<int64_t *> idx_h;  // [st_cap] pinned host copies of the per-shard lists
-    std::vector<int64_t *> row_h;
-    std::vector<float *> fo_h;     // [st_cap][dim] pinned host landing of fetched rows
+    std::vector<DevBuf<float>> q;      // [nq_cap][dim] query copy on a non-leader shard's device
+    std::vector<DevBuf<void>> s_loc;   // [nq_cap][k_cap] f32: a non-leader shard's own result
+    std::vector<DevBuf<void>> r_loc;   // ... and its int64 rows
+    DevBuf<float> g_s;                 // leader [n][nq_cap][k_cap] gathered lists
+    DevBuf<int64_t> g_r;
+    // upsert / fetch staging for st_cap() rows per shard (grown on demand, reused: no allocation in steady state)
+    std::vector<DevBuf<int64_t>> idx_d;  // source index per shard (on the leader for a remote shard)
+    std::vector<DevBuf<int64_t>> row_d;  // local row per shard (on the shard's device)
+    std::vector<DevBuf<float>> vec_d;    // [..][dim] a remote shard's subset of the batch, on its device
+    std::vector<DevBuf<float>> gat_d;    // [..][dim] that subset gathered on the leader (peer-copy source)
+    std::vector<DevBuf<float>> fo_d;     // [..][dim] fetched rows on the shard's device
+    std::vector<PinBuf<int64_t>> idx_h;  // pinned host copies of the per-shard lists
+    std::vector<PinBuf<int64_t>> row_h;
+    std::vector<PinBuf<float>> fo_h;     // [..][dim] pinned host landing of fetched rows
     hipEvent_t ev_gather = nullptr;  // leader stream: the remote subsets are gathered
     // row moves (rc_sharded_move_rows): per shard the local source / destination rows of one
     // round (kMoveRound entries, pinned + device, made on the first move), and the staging
     // blocks of stored rows that cross devices: mv_out on the source, mv_in on the destination
-    // (mv_cap rows each, grown on demand up to kMoveRound, reused)
+    // (mv_cap() rows each, grown on demand up to kMoveRound, reused)
     bool mv_lists = false;
-    int64_t mv_cap = 0;
-    std::vector<int64_t *> mv_src_h, mv_dst_h, mv_src_d, mv_dst_d;
-    std::vector<RowBlock> mv_out, mv_in;
+    std::vector<PinBuf<int64_t>> mv_src_h, mv_dst_h;
+    std::vector<DevBuf<int64_t>> mv_src_d, mv_dst_d;
+    std::vector<RowStage> mv_out, mv_in;
     std::vector<hipEvent_t> ev_pack;  // per shard, on st[s]: its lists are copied and its outgoing rows packed
     // masked search (rc_sharded_search_masked): the caller's global bitmap de-interleaved into one
     // local bitmap per shard (pinned), and its copy on the shard's device; grown on demand
-    int64_t mk_cap = 0;                // words per shard
-    std::vector<uint32_t *> mk_h;      // [mk_cap] pinned
-    std::vector<uint32_t *> mk_d;      // [mk_cap] on the shard's device
+    std::vector<PinBuf<uint32_t>> mk_h;  // pinned, mk_cap() words per shard
+    std::vector<DevBuf<uint32_t>> mk_d;  // on the shard's device
     std::vector<hipEvent_t> ev_mask;   // per shard: its bitmap's H2D copy is done (the pinned words are free again)
     // host-in / host-out query (rc_sharded_query_host): its own leader stream, one pinned
     // staging block and one device block, each laid out [queries | scores | rows | values]
     hipStream_t qs = nullptr;
-    int64_t qh_bytes = 0;
-    uint8_t *qh = nullptr;  // pinned
-    uint8_t *qd = nullptr;  // leader device
+    PinBuf<uint8_t> qh;
+    DevBuf<uint8_t> qd;  // leader device
     // page tables (rc_sharded_pages_set), by slot: the host copy of the list every shard holds
     // on its device (one page number = the same local rows on every shard); empty = no table
     std::vector<std::vector<int32_t>> tables;
     // deep top-k (rc_sharded_search_deep), several shards: a shard s > 0 keeps a query copy and its
-    // own k keys per query on its device, the leader the gathered lists [n][dnq_cap x dk_cap
+    // own k keys per query on its device, the leader the gathered lists [n][dkeys_cap()
     // entries used as [n][nq][k]] and the workspace of its selection over them
     int dnq_cap = 0;
-    int64_t dkeys_cap = 0;              // keys per shard: nq * k of the largest call
-    std::vector<float *> dq;            // [dnq_cap][dim]
-    std::vector<uint64_t *> dk_loc;     // [dkeys_cap]
-    uint64_t *dg_keys = nullptr;        // leader [n][dkeys_cap]
+    std::vector<DevBuf<float>> dq;      // [dnq_cap][dim]
+    std::vector<DevBuf<void>> dk_loc;   // dkeys_cap() uint64 keys: nq * k of the largest call
+    DevBuf<uint64_t> dg_keys;           // leader [n][dkeys_cap()]
     DeepSel dsel;
     int deep_select = RC_DEEP_SELECT_ROUNDS;  // the selection of the leader's merge (rc_sharded_set_deep_select)
 };
 
 namespace {
 
+// The sizes of the staging groups below are read off the block each group reserves last: every
+// ensure_* frees its whole group before it reserves, so that block is there only if all are.
+int64_t dkeys_cap(const rc_sharded *h) { return (int64_t)h->dg_keys.capacity() / h->n; }
+int64_t st_cap(const rc_sharded *h) { return (int64_t)h->row_h.back().capacity(); }
+int64_t mv_cap(const rc_sharded *h) { return (int64_t)h->mv_in.back().norms.capacity(); }
+int64_t mk_cap(const rc_sharded *h) { return (int64_t)h->mk_h.back().capacity(); }
+
 void free_search(rc_sharded *h) {
-    for (int s = 0; s < h->n; ++s) {
-        DeviceScope ds(h->dev[s]);
-        dfree(h->q[s]);
-        dfree(h->s_loc[s]);
-        dfree(h->r_loc[s]);
-        h->q[s] = nullptr;
-        h->s_loc[s] = nullptr;
-        h->r_loc[s] = nullptr;
-    }
-    DeviceScope ds(h->dev[0]);
-    dfree(h->g_s);
-    dfree(h->g_r);
-    h->g_s = nullptr;
-    h->g_r = nullptr;
     h->nq_cap = h->k_cap = 0;
+    for (int s = 0; s < h->n; ++s) {
+        h->q[s].reset();
+        h->s_loc[s].reset();
+        h->r_loc[s].reset();
+    }
+    h->g_s.reset();
+    h->g_r.reset();
 }
 
 void ensure_search(rc_sharded *h, int nq, int k) {
@@ -168,174 +171,116 @@ void ensure_search(rc_sharded *h, int nq, int k) {
     for (int s = 0; s < h->n; ++s) {
         if (!h->remote[s]) continue;
         DeviceScope ds(h->dev[s]);
-        h->q[s] = (float *)dmalloc((size_t)nq2 * h->dim * sizeof(float));
-        h->s_loc[s] = (float *)dmalloc((size_t)nq2 * k2 * sizeof(float));
-        h->r_loc[s] = (int64_t *)dmalloc((size_t)nq2 * k2 * sizeof(int64_t));
+        h->q[s].reserve((size_t)nq2 * h->dim);
+        h->s_loc[s].reserve((size_t)nq2 * k2 * sizeof(float));
+        h->r_loc[s].reserve((size_t)nq2 * k2 * sizeof(int64_t));
     }
     DeviceScope ds(h->dev[0]);
-    h->g_s = (float *)dmalloc((size_t)h->n * nq2 * k2 * sizeof(float));
-    h->g_r = (int64_t *)dmalloc((size_t)h->n * nq2 * k2 * sizeof(int64_t));
+    h->g_s.reserve((size_t)h->n * nq2 * k2);
+    h->g_r.reserve((size_t)h->n * nq2 * k2);
     h->nq_cap = nq2;
     h->k_cap = k2;
-}
-
-void free_deep(rc_sharded *h) {
-    for (int s = 0; s < h->n; ++s) {
-        DeviceScope ds(h->dev[s]);
-        dfree(h->dq[s]);
-        dfree(h->dk_loc[s]);
-        h->dq[s] = nullptr;
-        h->dk_loc[s] = nullptr;
-    }
-    DeviceScope dl(h->dev[0]);
-    dfree(h->dg_keys);
-    h->dg_keys = nullptr;
-    h->dnq_cap = 0;
-    h->dkeys_cap = 0;
 }
 
 // Room for a deep search of nq queries x k keys over several shards.  Every shard past the leader
 // gets its buffers whether or not it is remote now (rc_sharded_force_remote changes that later).
 void ensure_deep(rc_sharded *h, int nq, int k) {
     const int64_t nk = (int64_t)nq * k;
-    if (nq <= h->dnq_cap && nk <= h->dkeys_cap) return;
+    if (nq <= h->dnq_cap && nk <= dkeys_cap(h)) return;
     const int nq2 = std::max(nq, h->dnq_cap);
-    const int64_t nk2 = std::max(nk, h->dkeys_cap);
-    free_deep(h);
+    const int64_t nk2 = std::max(nk, dkeys_cap(h));
+    h->dnq_cap = 0;
+    h->dg_keys.reset();
+    for (int s = 1; s < h->n; ++s) {
+        h->dq[s].reset();
+        h->dk_loc[s].reset();
+    }
     for (int s = 1; s < h->n; ++s) {
         DeviceScope ds(h->dev[s]);
-        h->dq[s] = (float *)dmalloc((size_t)nq2 * h->dim * sizeof(float));
-        h->dk_loc[s] = (uint64_t *)dmalloc((size_t)nk2 * sizeof(uint64_t));
+        h->dq[s].reserve((size_t)nq2 * h->dim);
+        h->dk_loc[s].reserve((size_t)nk2 * sizeof(uint64_t));
     }
     DeviceScope dl(h->dev[0]);
-    h->dg_keys = (uint64_t *)dmalloc((size_t)h->n * nk2 * sizeof(uint64_t));
+    h->dg_keys.reserve((size_t)h->n * nk2);
     h->dnq_cap = nq2;
-    h->dkeys_cap = nk2;
 }
 
 void free_staging(rc_sharded *h) {
     for (int s = 0; s < h->n; ++s) {
-        DeviceScope ds(h->dev[s]);
-        dfree(h->row_d[s]);
-        dfree(h->vec_d[s]);
-        dfree(h->fo_d[s]);
-        hfree(h->idx_h[s]);
-        hfree(h->row_h[s]);
-        hfree(h->fo_h[s]);
-        h->row_d[s] = nullptr;
-        h->vec_d[s] = h->fo_d[s] = h->fo_h[s] = nullptr;
-        h->idx_h[s] = h->row_h[s] = nullptr;
+        h->row_d[s].reset();
+        h->vec_d[s].reset();
+        h->fo_d[s].reset();
+        h->idx_d[s].reset();
+        h->gat_d[s].reset();
+        h->idx_h[s].reset();
+        h->fo_h[s].reset();
+        h->row_h[s].reset();
     }
-    DeviceScope dl(h->dev[0]);
-    for (int s = 0; s < h->n; ++s) {
-        dfree(h->idx_d[s]);
-        dfree(h->gat_d[s]);
-        h->idx_d[s] = nullptr;
-        h->gat_d[s] = nullptr;
-    }
-    h->st_cap = 0;
 }
 
 // Per shard, room for m rows of one call: index lists (pinned host + device), the
 // remote shards' gathered subset (leader) and its landing (shard device), fetch
 // buffers.  Grows geometrically, so a steady stream of calls allocates nothing.
 void ensure_staging(rc_sharded *h, int64_t m) {
-    if (m <= h->st_cap) return;
-    const int64_t m2 = std::max<int64_t>(m, 2 * h->st_cap);
+    if (m <= st_cap(h)) return;
+    const size_t m2 = (size_t)std::max<int64_t>(m, 2 * st_cap(h));
     free_staging(h);
-    const size_t vb = (size_t)m2 * h->dim * sizeof(float);
+    const size_t vn = m2 * h->dim;
     for (int s = 0; s < h->n; ++s) {
         const bool remote = h->remote[s];
         {
             DeviceScope ds(h->dev[s]);
-            h->row_d[s] = (int64_t *)dmalloc((size_t)m2 * sizeof(int64_t));
-            h->fo_d[s] = (float *)dmalloc(vb);
-            if (remote) h->vec_d[s] = (float *)dmalloc(vb);
+            h->row_d[s].reserve(m2);
+            h->fo_d[s].reserve(vn);
+            if (remote) h->vec_d[s].reserve(vn);
         }
         DeviceScope dl(h->dev[0]);  // the source index lists are read on the leader (gather / local upsert)
-        h->idx_d[s] = (int64_t *)dmalloc((size_t)m2 * sizeof(int64_t));
-        if (remote) h->gat_d[s] = (float *)dmalloc(vb);
-        h->idx_h[s] = (int64_t *)hmalloc((size_t)m2 * sizeof(int64_t));
-        h->row_h[s] = (int64_t *)hmalloc((size_t)m2 * sizeof(int64_t));
-        h->fo_h[s] = (float *)hmalloc(vb);
+        h->idx_d[s].reserve(m2);
+        if (remote) h->gat_d[s].reserve(vn);
+        h->idx_h[s].reserve(m2);
+        h->fo_h[s].reserve(vn);
+        h->row_h[s].reserve(m2);
     }
-    h->st_cap = m2;
 }
 
 // Row moves run in rounds of this many (source, destination) pairs: the lists and the staging
 // blocks are sized by it, not by the call (a delete of millions of rows allocates no more).
 constexpr int64_t kMoveRound = 16384;
 
-void free_move_blocks(rc_sharded *h) {
-    for (int s = 0; s < h->n; ++s) {
-        DeviceScope ds(h->dev[s]);
-        for (RowBlock *b : {&h->mv_out[s], &h->mv_in[s]}) {
-            dfree(b->rows);
-            dfree(b->norms);
-            *b = RowBlock{};
-        }
-    }
-    h->mv_cap = 0;
-}
-
-void free_move(rc_sharded *h) {
-    free_move_blocks(h);
-    for (int s = 0; s < h->n; ++s) {
-        DeviceScope ds(h->dev[s]);
-        dfree(h->mv_src_d[s]);
-        dfree(h->mv_dst_d[s]);
-        hfree(h->mv_src_h[s]);
-        hfree(h->mv_dst_h[s]);
-        h->mv_src_d[s] = h->mv_dst_d[s] = h->mv_src_h[s] = h->mv_dst_h[s] = nullptr;
-        if (h->ev_pack[s]) (void)hipEventDestroy(h->ev_pack[s]);
-        h->ev_pack[s] = nullptr;
-    }
-    h->mv_lists = false;
-}
-
 // The lists of one round per shard, once; and staging blocks of at least m rows on every shard
 // that stages (callers pass m <= kMoveRound; m = 0: no pair crosses devices).
 void ensure_move(rc_sharded *h, int64_t m, size_t row_bytes) {
-    if (!h->mv_lists) {
-        try {
-            for (int s = 0; s < h->n; ++s) {
-                DeviceScope ds(h->dev[s]);
-                h->mv_src_d[s] = (int64_t *)dmalloc((size_t)kMoveRound * sizeof(int64_t));
-                h->mv_dst_d[s] = (int64_t *)dmalloc((size_t)kMoveRound * sizeof(int64_t));
-                h->mv_src_h[s] = (int64_t *)hmalloc((size_t)kMoveRound * sizeof(int64_t));
-                h->mv_dst_h[s] = (int64_t *)hmalloc((size_t)kMoveRound * sizeof(int64_t));
-                RC_HIP(hipEventCreateWithFlags(&h->ev_pack[s], hipEventDisableTiming));
-                // stored rows go straight from their source GPU to their destination GPU
-                for (int t = 0; t < s; ++t) {
-                    if (h->dev[t] == h->dev[s]) continue;
-                    if (hipDeviceEnablePeerAccess(h->dev[t], 0) != hipSuccess) (void)hipGetLastError();
-                    DeviceScope dt(h->dev[t]);
-                    if (hipDeviceEnablePeerAccess(h->dev[s], 0) != hipSuccess) (void)hipGetLastError();
-                }
+    if (!h->mv_lists) {  // (a failure part of the way: the next call takes it up from there)
+        for (int s = 0; s < h->n; ++s) {
+            DeviceScope ds(h->dev[s]);
+            h->mv_src_d[s].reserve((size_t)kMoveRound);
+            h->mv_dst_d[s].reserve((size_t)kMoveRound);
+            h->mv_src_h[s].reserve((size_t)kMoveRound);
+            h->mv_dst_h[s].reserve((size_t)kMoveRound);
+            if (h->ev_pack[s] == nullptr) RC_HIP(hipEventCreateWithFlags(&h->ev_pack[s], hipEventDisableTiming));
+            // stored rows go straight from their source GPU to their destination GPU
+            for (int t = 0; t < s; ++t) {
+                if (h->dev[t] == h->dev[s]) continue;
+                if (hipDeviceEnablePeerAccess(h->dev[t], 0) != hipSuccess) (void)hipGetLastError();
+                DeviceScope dt(h->dev[t]);
+                if (hipDeviceEnablePeerAccess(h->dev[s], 0) != hipSuccess) (void)hipGetLastError();
             }
-        } catch (...) {
-            free_move(h);
-            throw;
         }
         h->mv_lists = true;
     }
-    if (m <= h->mv_cap) return;
-    const int64_t m2 = std::min<int64_t>(kMoveRound, std::max<int64_t>(m, 2 * h->mv_cap));
-    free_move_blocks(h);
-    try {
-        for (int s = 0; s < h->n; ++s) {
-            DeviceScope ds(h->dev[s]);
-            for (RowBlock *b : {&h->mv_out[s], &h->mv_in[s]}) {
-                b->rows = dmalloc((size_t)m2 * row_bytes);
-                b->norms = (float *)dmalloc((size_t)m2 * sizeof(float));
-                b->cap = m2;
-            }
-        }
-    } catch (...) {
-        free_move_blocks(h);
-        throw;
+    if (m <= mv_cap(h)) return;
+    const size_t m2 = (size_t)std::min<int64_t>(kMoveRound, std::max<int64_t>(m, 2 * mv_cap(h)));
+    for (int s = 0; s < h->n; ++s) {
+        h->mv_out[s] = RowStage{};
+        h->mv_in[s] = RowStage{};
     }
-    h->mv_cap = m2;
+    for (int s = 0; s < h->n; ++s) {
+        DeviceScope ds(h->dev[s]);
+        for (RowStage *b : {&h->mv_out[s], &h->mv_in[s]}) {
+            b->rows.reserve(m2 * row_bytes);
+            b->norms.reserve(m2);
+        }
+    }
 }
 
 // rows of the global range [0, n_rows) that shard s holds
@@ -344,13 +289,10 @@ int64_t shard_rows(const rc_sharded *h, int s, int64_t n_rows) { return n_rows >
 void free_mask(rc_sharded *h) {
     for (int s = 0; s < h->n; ++s) {
         DeviceScope ds(h->dev[s]);
-        if (h->mk_d[s] != nullptr) (void)hipDeviceSynchronize();  // no search may still read the bitmap
-        dfree(h->mk_d[s]);
-        hfree(h->mk_h[s]);
-        h->mk_d[s] = nullptr;
-        h->mk_h[s] = nullptr;
+        if (!h->mk_d[s].empty()) (void)hipDeviceSynchronize();  // no search may still read the bitmap
+        h->mk_d[s].reset();
+        h->mk_h[s].reset();
     }
-    h->mk_cap = 0;
 }
 
 // Split the caller's bitmap over global rows [0, n_rows) into the shards' local bitmaps (global
@@ -364,20 +306,19 @@ void stage_mask(rc_sharded *h, const uint32_t *mask, int64_t n_rows, hipStream_t
     const int n = h->n;
     const int64_t words = (n_rows + 31) / 32;
     const int64_t lw_max = std::max<int64_t>(1, (shard_rows(h, 0, n_rows) + 31) / 32);
-    if (lw_max > h->mk_cap) {
-        const int64_t w2 = std::max<int64_t>(lw_max, 2 * h->mk_cap);
+    if (lw_max > mk_cap(h)) {
+        const size_t w2 = (size_t)std::max<int64_t>(lw_max, 2 * mk_cap(h));
         free_mask(h);
         for (int s = 0; s < n; ++s) {
             DeviceScope ds(h->dev[s]);
-            h->mk_d[s] = (uint32_t *)dmalloc((size_t)w2 * sizeof(uint32_t));
-            h->mk_h[s] = (uint32_t *)hmalloc((size_t)w2 * sizeof(uint32_t));
+            h->mk_d[s].reserve(w2);
+            h->mk_h[s].reserve(w2);
         }
-        h->mk_cap = w2;
     }
     if (n == 1) {
-        std::memcpy(h->mk_h[0], mask, (size_t)words * sizeof(uint32_t));
+        std::memcpy(h->mk_h[0].get(), mask, (size_t)words * sizeof(uint32_t));
     } else {
-        for (int s = 0; s < n; ++s) std::memset(h->mk_h[s], 0, (size_t)lw_max * sizeof(uint32_t));
+        for (int s = 0; s < n; ++s) std::memset(h->mk_h[s].get(), 0, (size_t)lw_max * sizeof(uint32_t));
         for (int64_t w = 0; w < words; ++w) {
             uint32_t bits = mask[w];
             while (bits) {  // the set bits only: a selective filter costs its eligible count
@@ -385,14 +326,14 @@ void stage_mask(rc_sharded *h, const uint32_t *mask, int64_t n_rows, hipStream_t
                 bits &= bits - 1;
                 if (g >= n_rows) break;
                 const int64_t l = g / n;
-                h->mk_h[g - l * n][l >> 5] |= 1u << (l & 31);
+                h->mk_h[g - l * n].get()[l >> 5] |= 1u << (l & 31);
             }
         }
     }
     for (int s = 0; s < n; ++s) {
         DeviceScope ds(h->dev[s]);
         const int64_t lw = std::max<int64_t>(1, (shard_rows(h, s, n_rows) + 31) / 32);
-        RC_HIP(hipMemcpyAsync(h->mk_d[s], h->mk_h[s], (size_t)lw * sizeof(uint32_t), hipMemcpyHostToDevice, h->st[s]));
+        RC_HIP(hipMemcpyAsync(h->mk_d[s].get(), h->mk_h[s].get(), (size_t)lw * sizeof(uint32_t), hipMemcpyHostToDevice, h->st[s]));
         RC_HIP(hipEventRecord(h->ev_mask[s], h->st[s]));
     }
     if (n == 1) RC_HIP(hipStreamWaitEvent(ls, h->ev_mask[0], 0));  // the single shard searches on the caller's stream
@@ -413,15 +354,6 @@ void wait_mask(rc_sharded *h) {
     }
 }
 
-void free_query(rc_sharded *h) {
-    DeviceScope dl(h->dev[0]);
-    hfree(h->qh);
-    dfree(h->qd);
-    h->qh = nullptr;
-    h->qd = nullptr;
-    h->qh_bytes = 0;
-}
-
 // offsets of the query block for nq queries, top-k, with or without values (16-B aligned parts)
 struct QueryLayout {
     int64_t q, sc, rw, val, total;
@@ -438,28 +370,17 @@ QueryLayout query_layout(const rc_sharded *h, int nq, int k, bool values) {
 }
 
 void ensure_query(rc_sharded *h, int64_t bytes) {
-    if (bytes <= h->qh_bytes) return;
-    const int64_t b2 = std::max<int64_t>(bytes, 2 * h->qh_bytes);
+    if ((size_t)bytes <= min_capacity(h->qh, h->qd)) return;
+    const size_t b2 = std::max<size_t>(bytes, 2 * min_capacity(h->qh, h->qd));
     RC_HIP(hipStreamSynchronize(h->qs));
-    free_query(h);
     DeviceScope dl(h->dev[0]);
-    h->qh = (uint8_t *)hmalloc((size_t)b2);
-    h->qd = (uint8_t *)dmalloc((size_t)b2);
-    h->qh_bytes = b2;
+    h->qh.reserve(b2);
+    h->qd.reserve(b2);
 }
 
 void destroy(rc_sharded *h) {
-    free_search(h);
-    free_staging(h);
-    free_move(h);
-    free_mask(h);
-    free_deep(h);
-    {
-        DeviceScope dl(h->dev[0]);
-        h->dsel.release();
-    }
+    free_mask(h);  // (waits for the searches that read the bitmaps)
     if (h->qs) {
-        free_query(h);
         DeviceScope dl(h->dev[0]);
         (void)hipStreamDestroy(h->qs);
     }
@@ -469,13 +390,14 @@ void destroy(rc_sharded *h) {
         if (h->ev_done[s]) (void)hipEventDestroy(h->ev_done[s]);
         if (h->ev_start[s]) (void)hipEventDestroy(h->ev_start[s]);
         if (h->ev_mask[s]) (void)hipEventDestroy(h->ev_mask[s]);
+        if (h->ev_pack[s]) (void)hipEventDestroy(h->ev_pack[s]);
         if (h->shard[s]) (void)rc_index_destroy(h->shard[s]);
     }
     if (h->ev_gather) {
         DeviceScope dl(h->dev[0]);
         (void)hipEventDestroy(h->ev_gather);
     }
-    delete h;
+    delete h;  // the buffers free themselves
 }
 
 void check_status(int st) {
@@ -504,29 +426,17 @@ int rc_sharded_create(int n_shards, const int *devices, int dim, int dtype, int6
         h->st.assign(n_shards, nullptr);
         h->ev_done.assign(n_shards, nullptr);
         h->ev_start.assign(n_shards, nullptr);
-        h->q.assign(n_shards, nullptr);
-        h->s_loc.assign(n_shards, nullptr);
-        h->r_loc.assign(n_shards, nullptr);
-        h->idx_d.assign(n_shards, nullptr);
-        h->row_d.assign(n_shards, nullptr);
-        h->vec_d.assign(n_shards, nullptr);
-        h->gat_d.assign(n_shards, nullptr);
-        h->fo_d.assign(n_shards, nullptr);
-        h->idx_h.assign(n_shards, nullptr);
-        h->row_h.assign(n_shards, nullptr);
-        h->fo_h.assign(n_shards, nullptr);
-        h->mv_src_h.assign(n_shards, nullptr);
-        h->mv_dst_h.assign(n_shards, nullptr);
-        h->mv_src_d.assign(n_shards, nullptr);
-        h->mv_dst_d.assign(n_shards, nullptr);
-        h->mv_out.assign(n_shards, RowBlock{});
-        h->mv_in.assign(n_shards, RowBlock{});
+        for (auto *v : {&h->q, &h->vec_d, &h->gat_d, &h->fo_d, &h->dq}) v->resize(n_shards);
+        for (auto *v : {&h->s_loc, &h->r_loc, &h->dk_loc}) v->resize(n_shards);
+        for (auto *v : {&h->idx_d, &h->row_d, &h->mv_src_d, &h->mv_dst_d}) v->resize(n_shards);
+        for (auto *v : {&h->idx_h, &h->row_h, &h->mv_src_h, &h->mv_dst_h}) v->resize(n_shards);
+        h->fo_h.resize(n_shards);
+        h->mv_out.resize(n_shards);
+        h->mv_in.resize(n_shards);
         h->ev_pack.assign(n_shards, nullptr);
-        h->mk_h.assign(n_shards, nullptr);
-        h->mk_d.assign(n_shards, nullptr);
+        h->mk_h.resize(n_shards);
+        h->mk_d.resize(n_shards);
         h->ev_mask.assign(n_shards, nullptr);
-        h->dq.assign(n_shards, nullptr);
-        h->dk_loc.assign(n_shards, nullptr);
         try {
             for (int s = 0; s < n_shards; ++s) {
                 check_status(rc_index_create(h->dev[s], dim, dtype, capacity_per_shard, s, &h->shard[s]));
@@ -672,8 +582,8 @@ int rc_sharded_upsert(rc_sharded *h, const float *vecs, int64_t n, const int64_t
         for (int64_t i = 0; i < n; ++i) {  // per-shard (source index, local row) lists, pinned
             const int64_t g = rows[i];
             const int s = (int)(g % h->n);
-            h->idx_h[s][cnt[s]] = i;
-            h->row_h[s][cnt[s]] = g / h->n;
+            h->idx_h[s].get()[cnt[s]] = i;
+            h->row_h[s].get()[cnt[s]] = g / h->n;
             ++cnt[s];
         }
         hipStream_t ls = (hipStream_t)stream;
@@ -683,10 +593,10 @@ int rc_sharded_upsert(rc_sharded *h, const float *vecs, int64_t n, const int64_t
             DeviceScope dl(h->dev[0]);
             for (int s = 0; s < h->n; ++s) {
                 if (cnt[s] == 0) continue;
-                RC_HIP(hipMemcpyAsync(h->idx_d[s], h->idx_h[s], cnt[s] * sizeof(int64_t), hipMemcpyHostToDevice, ls));
+                RC_HIP(hipMemcpyAsync(h->idx_d[s].get(), h->idx_h[s].get(), cnt[s] * sizeof(int64_t), hipMemcpyHostToDevice, ls));
                 if (h->remote[s]) {
                     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((cnt[s] + 3) / 4)), dim3(256), 0, ls, vecs,
-                                       h->idx_d[s], cnt[s], h->dim, h->gat_d[s]);
+                                       h->idx_d[s].get(), cnt[s], h->dim, h->gat_d[s].get());
                     RC_LAUNCH_CHECK();
                 }
             }
@@ -697,13 +607,13 @@ int rc_sharded_upsert(rc_sharded *h, const float *vecs, int64_t n, const int64_t
             DeviceScope ds(h->dev[s]);
             const int64_t ms = cnt[s];
             RC_HIP(hipStreamWaitEvent(h->st[s], h->ev_gather, 0));
-            RC_HIP(hipMemcpyAsync(h->row_d[s], h->row_h[s], ms * sizeof(int64_t), hipMemcpyHostToDevice, h->st[s]));
+            RC_HIP(hipMemcpyAsync(h->row_d[s].get(), h->row_h[s].get(), ms * sizeof(int64_t), hipMemcpyHostToDevice, h->st[s]));
             if (h->remote[s]) {
-                RC_HIP(hipMemcpyPeerAsync(h->vec_d[s], h->dev[s], h->gat_d[s], h->dev[0], (size_t)ms * h->dim * sizeof(float),
+                RC_HIP(hipMemcpyPeerAsync(h->vec_d[s].get(), h->dev[s], h->gat_d[s].get(), h->dev[0], (size_t)ms * h->dim * sizeof(float),
                                           h->st[s]));
-                index_upsert_gather(h->shard[s], h->vec_d[s], nullptr, ms, h->row_d[s], h->st[s]);
+                index_upsert_gather(h->shard[s], h->vec_d[s].get(), nullptr, ms, h->row_d[s].get(), h->st[s]);
             } else {
-                index_upsert_gather(h->shard[s], vecs, h->idx_d[s], ms, h->row_d[s], h->st[s]);
+                index_upsert_gather(h->shard[s], vecs, h->idx_d[s].get(), ms, h->row_d[s].get(), h->st[s]);
             }
         }
         // the pinned lists are reused by the next call: finish here (upsert is synchronous,
@@ -774,8 +684,8 @@ int rc_sharded_move_rows(rc_sharded *h, const int64_t *src_rows, const int64_t *
                 const int a = (int)(gs % ns), b = (int)(gd % ns);
                 const size_t ab = (size_t)a * ns + b;
                 const int64_t k = cur[ab]++;
-                h->mv_src_h[a][soff[ab] + k] = gs / ns;
-                h->mv_dst_h[b][doff[ab] + k] = gd / ns;
+                h->mv_src_h[a].get()[soff[ab] + k] = gs / ns;
+                h->mv_dst_h[b].get()[doff[ab] + k] = gd / ns;
             }
             // Sources and destinations never overlap (validated above; Index.delete's sources are
             // rows at or past the new length, its destinations rows below it), so no row is read
@@ -786,13 +696,13 @@ int rc_sharded_move_rows(rc_sharded *h, const int64_t *src_rows, const int64_t *
                 DeviceScope ds(h->dev[a]);
                 hipStream_t sa = h->st[a];
                 if (s_tot[a])
-                    RC_HIP(hipMemcpyAsync(h->mv_src_d[a], h->mv_src_h[a], s_tot[a] * sizeof(int64_t), hipMemcpyHostToDevice, sa));
+                    RC_HIP(hipMemcpyAsync(h->mv_src_d[a].get(), h->mv_src_h[a].get(), s_tot[a] * sizeof(int64_t), hipMemcpyHostToDevice, sa));
                 if (d_tot[a])
-                    RC_HIP(hipMemcpyAsync(h->mv_dst_d[a], h->mv_dst_h[a], d_tot[a] * sizeof(int64_t), hipMemcpyHostToDevice, sa));
+                    RC_HIP(hipMemcpyAsync(h->mv_dst_d[a].get(), h->mv_dst_h[a].get(), d_tot[a] * sizeof(int64_t), hipMemcpyHostToDevice, sa));
                 const size_t aa = (size_t)a * ns + a;
-                index_move_rows(h->shard[a], h->mv_src_d[a] + soff[aa], h->shard[a], h->mv_dst_d[a] + doff[aa], RowBlock{},
+                index_move_rows(h->shard[a], h->mv_src_d[a].get() + soff[aa], h->shard[a], h->mv_dst_d[a].get() + doff[aa], RowBlock{},
                                 cnt[aa], sa);
-                index_move_rows(h->shard[a], h->mv_src_d[a] + s_stg[a], nullptr, nullptr, h->mv_out[a], s_tot[a] - s_stg[a], sa);
+                index_move_rows(h->shard[a], h->mv_src_d[a].get() + s_stg[a], nullptr, nullptr, h->mv_out[a].view(), s_tot[a] - s_stg[a], sa);
                 RC_HIP(hipEventRecord(h->ev_pack[a], sa));
             }
             for (int b = 0; b < ns; ++b) {  // each destination's stream: what other shards send it
@@ -804,18 +714,18 @@ int rc_sharded_move_rows(rc_sharded *h, const int64_t *src_rows, const int64_t *
                     if (a == b || cnt[ab] == 0) continue;
                     RC_HIP(hipStreamWaitEvent(sb, h->ev_pack[a], 0));
                     if (!staged(a, b)) {  // one GPU: a's source list is readable here
-                        index_move_rows(h->shard[a], h->mv_src_d[a] + soff[ab], h->shard[b], h->mv_dst_d[b] + doff[ab],
+                        index_move_rows(h->shard[a], h->mv_src_d[a].get() + soff[ab], h->shard[b], h->mv_dst_d[b].get() + doff[ab],
                                         RowBlock{}, cnt[ab], sb);
                         continue;
                     }
                     const int64_t from = soff[ab] - s_stg[a], to = doff[ab] - d_stg[b];
-                    RC_HIP(hipMemcpyPeerAsync((uint8_t *)h->mv_in[b].rows + (size_t)to * rb, h->dev[b],
-                                              (const uint8_t *)h->mv_out[a].rows + (size_t)from * rb, h->dev[a],
+                    RC_HIP(hipMemcpyPeerAsync((uint8_t *)h->mv_in[b].rows.get() + (size_t)to * rb, h->dev[b],
+                                              (const uint8_t *)h->mv_out[a].rows.get() + (size_t)from * rb, h->dev[a],
                                               (size_t)cnt[ab] * rb, sb));
-                    RC_HIP(hipMemcpyPeerAsync(h->mv_in[b].norms + to, h->dev[b], h->mv_out[a].norms + from, h->dev[a],
+                    RC_HIP(hipMemcpyPeerAsync(h->mv_in[b].norms.get() + to, h->dev[b], h->mv_out[a].norms.get() + from, h->dev[a],
                                               (size_t)cnt[ab] * sizeof(float), sb));
                 }
-                index_move_rows(nullptr, nullptr, h->shard[b], h->mv_dst_d[b] + d_stg[b], h->mv_in[b], d_tot[b] - d_stg[b], sb);
+                index_move_rows(nullptr, nullptr, h->shard[b], h->mv_dst_d[b].get() + d_stg[b], h->mv_in[b].view(), d_tot[b] - d_stg[b], sb);
             }
             // the pinned lists and the staging blocks are reused by the next round: finish here
             for (int s = 0; s < ns; ++s) {
@@ -849,8 +759,8 @@ void fetch_locked(rc_sharded *h, const int64_t *rows, int64_t n, float *out, int
         for (int64_t i = 0; i < n; ++i) {
             const int64_t g = rows[i];
             const int s = (int)(g % h->n);
-            h->idx_h[s][cnt[s]] = i;  // destination row of out
-            h->row_h[s][cnt[s]] = g / h->n;
+            h->idx_h[s].get()[cnt[s]] = i;  // destination row of out
+            h->row_h[s].get()[cnt[s]] = g / h->n;
             ++cnt[s];
         }
         // every shard's fetch and D2H copy in flight at once, one wait at the end
@@ -858,10 +768,10 @@ void fetch_locked(rc_sharded *h, const int64_t *rows, int64_t n, float *out, int
             if (cnt[s] == 0) continue;
             DeviceScope ds(h->dev[s]);
             const int64_t ms = cnt[s];
-            RC_HIP(hipMemcpyAsync(h->row_d[s], h->row_h[s], ms * sizeof(int64_t), hipMemcpyHostToDevice, h->st[s]));
-            check_status(stored ? rc_index_fetch_stored(h->shard[s], h->row_d[s], ms, h->fo_d[s], h->st[s])
-                                : rc_index_fetch(h->shard[s], h->row_d[s], ms, h->fo_d[s], h->st[s]));
-            RC_HIP(hipMemcpyAsync(h->fo_h[s], h->fo_d[s], (size_t)ms * h->dim * sizeof(float), hipMemcpyDeviceToHost,
+            RC_HIP(hipMemcpyAsync(h->row_d[s].get(), h->row_h[s].get(), ms * sizeof(int64_t), hipMemcpyHostToDevice, h->st[s]));
+            check_status(stored ? rc_index_fetch_stored(h->shard[s], h->row_d[s].get(), ms, h->fo_d[s].get(), h->st[s])
+                                : rc_index_fetch(h->shard[s], h->row_d[s].get(), ms, h->fo_d[s].get(), h->st[s]));
+            RC_HIP(hipMemcpyAsync(h->fo_h[s].get(), h->fo_d[s].get(), (size_t)ms * h->dim * sizeof(float), hipMemcpyDeviceToHost,
                                   h->st[s]));
         }
         for (int s = 0; s < h->n; ++s) {
@@ -869,7 +779,7 @@ void fetch_locked(rc_sharded *h, const int64_t *rows, int64_t n, float *out, int
             DeviceScope ds(h->dev[s]);
             RC_HIP(hipStreamSynchronize(h->st[s]));
             for (int64_t j = 0; j < cnt[s]; ++j)
-                std::memcpy(out + h->idx_h[s][j] * h->dim, h->fo_h[s] + j * h->dim, (size_t)h->dim * sizeof(float));
+                std::memcpy(out + h->idx_h[s].get()[j] * h->dim, h->fo_h[s].get() + j * h->dim, (size_t)h->dim * sizeof(float));
         }
 }
 
@@ -880,7 +790,7 @@ struct FanBuf {
     size_t bytes;
     void *single;
     void *gather;
-    void *const *loc;
+    const DevBuf<void> *loc;
 };
 
 // The fan-out of a search over the shards (caller holds h->mu; `queries` on the leader, ls = the
@@ -893,13 +803,13 @@ struct FanBuf {
 // merges, then wait_mask()s if it gave a mask (the next call may overwrite the staged words).
 template <typename Call>
 bool fan_out(rc_sharded *h, const float *queries, int nq, int64_t n_rows, const uint32_t *mask, hipStream_t ls,
-             const std::vector<float *> &qcopy, const FanBuf *buf, int nbuf, Call call) {
+             const std::vector<DevBuf<float>> &qcopy, const FanBuf *buf, int nbuf, Call call) {
     const bool masked = mask != nullptr;
     if (masked) stage_mask(h, mask, n_rows, ls);
     void *out[2] = {nullptr, nullptr};
     if (h->n == 1) {
         for (int b = 0; b < nbuf; ++b) out[b] = buf[b].single;
-        call(0, queries, n_rows, masked ? h->mk_d[0] : nullptr, out, ls);
+        call(0, queries, n_rows, masked ? h->mk_d[0].get() : nullptr, out, ls);
         if (masked) {
             fence_mask_single(h, ls);
             wait_mask(h);
@@ -916,11 +826,11 @@ bool fan_out(rc_sharded *h, const float *queries, int nq, int64_t n_rows, const 
         const bool local = !h->remote[s];
         const float *q = queries;
         if (!local) {
-            RC_HIP(hipMemcpyPeerAsync(qcopy[s], h->dev[s], queries, h->dev[0], (size_t)nq * h->dim * sizeof(float), h->st[s]));
-            q = qcopy[s];
+            RC_HIP(hipMemcpyPeerAsync(qcopy[s].get(), h->dev[s], queries, h->dev[0], (size_t)nq * h->dim * sizeof(float), h->st[s]));
+            q = qcopy[s].get();
         }
-        for (int b = 0; b < nbuf; ++b) out[b] = local ? (uint8_t *)buf[b].gather + s * buf[b].bytes : buf[b].loc[s];
-        call(s, q, shard_rows(h, s, n_rows), masked ? h->mk_d[s] : nullptr, out, h->st[s]);
+        for (int b = 0; b < nbuf; ++b) out[b] = local ? (uint8_t *)buf[b].gather + s * buf[b].bytes : buf[b].loc[s].get();
+        call(s, q, shard_rows(h, s, n_rows), masked ? h->mk_d[s].get() : nullptr, out, h->st[s]);
         for (int b = 0; b < nbuf && !local; ++b)
             RC_HIP(hipMemcpyPeerAsync((uint8_t *)buf[b].gather + s * buf[b].bytes, h->dev[0], out[b], h->dev[s], buf[b].bytes, h->st[s]));
         RC_HIP(hipEventRecord(h->ev_done[s], h->st[s]));
@@ -939,8 +849,8 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
                    int mode, void *stream, const uint32_t *mask = nullptr, int slot = -1) {
     if (h->n > 1) ensure_search(h, nq, k);
     const size_t slice = (size_t)nq * k;
-    const FanBuf out[2] = {{slice * sizeof(float), scores, h->g_s, (void *const *)h->s_loc.data()},
-                           {slice * sizeof(int64_t), out_rows, h->g_r, (void *const *)h->r_loc.data()}};
+    const FanBuf out[2] = {{slice * sizeof(float), scores, h->g_s.get(), h->s_loc.data()},
+                           {slice * sizeof(int64_t), out_rows, h->g_r.get(), h->r_loc.data()}};
     const bool gathered = fan_out(h, queries, nq, n_rows, mask, (hipStream_t)stream, h->q, out, 2,
                                   [&](int s, const float *q, int64_t n_local, const uint32_t *m, void *const *o, hipStream_t st) {
         check_status(slot >= 0 ? rc_index_search_pages_ex(h->shard[s], q, nq, slot, n_local, k, m, (float *)o[0], (int64_t *)o[1], mode, st)
@@ -948,7 +858,7 @@ void search_locked(rc_sharded *h, const float *queries, int nq, int64_t n_rows, 
     });
     if (!gathered) return;
     DeviceScope dl(h->dev[0]);
-    check_status(rc_topk_merge(h->g_s, h->g_r, h->n, nq, k, k, scores, out_rows, stream));
+    check_status(rc_topk_merge(h->g_s.get(), h->g_r.get(), h->n, nq, k, k, scores, out_rows, stream));
     if (mask != nullptr) wait_mask(h);
 }
 
@@ -964,7 +874,7 @@ void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_r
                         void *stream, const uint32_t *mask, int slot, const SparseQueries *sq = nullptr) {
     hipStream_t ls = (hipStream_t)stream;
     if (h->n > 1) ensure_deep(h, nq, k);
-    const FanBuf out{(size_t)nq * k * sizeof(uint64_t), nullptr, h->dg_keys, (void *const *)h->dk_loc.data()};
+    const FanBuf out{(size_t)nq * k * sizeof(uint64_t), nullptr, h->dg_keys.get(), h->dk_loc.data()};
     const bool gathered = fan_out(h, queries, nq, n_rows, mask, ls, h->dq, &out, 1,
                                   [&](int s, const float *q, int64_t n_local, const uint32_t *m, void *const *o, hipStream_t st) {
         index_search_deep(h->shard[s], q, nq, n_local, k, m, slot, (uint64_t *)o[0], scores, out_rows, st, sq);
@@ -976,13 +886,13 @@ void search_deep_locked(rc_sharded *h, const float *queries, int nq, int64_t n_r
     for (int q0 = 0; q0 < nq; q0 += qc) {
         const int m = std::min(qc, nq - q0);
         DeepStream st;
-        st.keys = h->dg_keys;  // list s of query q at [(s * nq + q) * k]
+        st.keys = h->dg_keys.get();  // list s of query q at [(s * nq + q) * k]
         st.n = (int64_t)h->n * k;
         st.klist = k;
         st.nq_total = nq;
         st.q0 = q0;
-        deep_select(h->deep_select, st, h->dsel, m, k, h->dsel.keys, ls);
-        deep_emit(h->dsel.keys, (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, ls);
+        deep_select(h->deep_select, st, h->dsel, m, k, h->dsel.keys.get(), ls);
+        deep_emit(h->dsel.keys.get(), (int64_t)m * k, scores + (int64_t)q0 * k, out_rows + (int64_t)q0 * k, ls);
     }
     if (mask != nullptr) wait_mask(h);
 }
@@ -1150,9 +1060,9 @@ void query_host_checked(rc_sharded *h, const float *queries, int nq, int64_t n_r
             // straight into the pinned block), no copies; the host polls the completion word
             // (refused, as for a shape outside its range, by a shard whose filter is RC_FILTER_I8_STREAM once the
             // rows reach that filter's AUTO bound: the multi-kernel path below then takes the streaming filter)
-            float *hs = (float *)(h->qh + L.sc);
-            int64_t *hr = (int64_t *)(h->qh + L.rw);
-            float *hv = (float *)(h->qh + L.val);
+            float *hs = (float *)(h->qh.get() + L.sc);
+            int64_t *hr = (int64_t *)(h->qh.get() + L.rw);
+            float *hv = (float *)(h->qh.get() + L.val);
             volatile unsigned *word = nullptr;
             unsigned want = 0;
             if (index_query1(h->shard[0], queries, n_rows, k, with_values, hs, hr, hv, h->qs, &word, &want)) {
@@ -1164,22 +1074,22 @@ void query_host_checked(rc_sharded *h, const float *queries, int nq, int64_t n_r
                 return;
             }
         }
-        std::memcpy(h->qh + L.q, queries, (size_t)nq * h->dim * sizeof(float));
-        RC_HIP(hipMemcpyAsync(h->qd + L.q, h->qh + L.q, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, h->qs));
-        float *dsc = (float *)(h->qd + L.sc);
-        int64_t *drw = (int64_t *)(h->qd + L.rw);
-        search_locked(h, (const float *)(h->qd + L.q), nq, n_rows, k, dsc, drw, slot >= 0 ? RC_SEARCH_SCAN : RC_SEARCH_AUTO, h->qs, mask,
+        std::memcpy(h->qh.get() + L.q, queries, (size_t)nq * h->dim * sizeof(float));
+        RC_HIP(hipMemcpyAsync(h->qd.get() + L.q, h->qh.get() + L.q, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, h->qs));
+        float *dsc = (float *)(h->qd.get() + L.sc);
+        int64_t *drw = (int64_t *)(h->qd.get() + L.rw);
+        search_locked(h, (const float *)(h->qd.get() + L.q), nq, n_rows, k, dsc, drw, slot >= 0 ? RC_SEARCH_SCAN : RC_SEARCH_AUTO, h->qs, mask,
                       slot);  // a slot scans, as before the paged batched search
         if (dev_values) {
-            if (slot >= 0) index_fetch_pages(h->shard[0], slot, n_rows, drw, nk, (float *)(h->qd + L.val), h->qs);
-            else check_status(rc_index_fetch(h->shard[0], drw, nk, (float *)(h->qd + L.val), h->qs));
+            if (slot >= 0) index_fetch_pages(h->shard[0], slot, n_rows, drw, nk, (float *)(h->qd.get() + L.val), h->qs);
+            else check_status(rc_index_fetch(h->shard[0], drw, nk, (float *)(h->qd.get() + L.val), h->qs));
         }
-        RC_HIP(hipMemcpyAsync(h->qh + L.sc, h->qd + L.sc, (size_t)(L.total - L.sc), hipMemcpyDeviceToHost, h->qs));
+        RC_HIP(hipMemcpyAsync(h->qh.get() + L.sc, h->qd.get() + L.sc, (size_t)(L.total - L.sc), hipMemcpyDeviceToHost, h->qs));
         RC_HIP(hipStreamSynchronize(h->qs));
-        std::memcpy(scores, h->qh + L.sc, (size_t)nk * sizeof(float));
-        std::memcpy(out_rows, h->qh + L.rw, (size_t)nk * sizeof(int64_t));
+        std::memcpy(scores, h->qh.get() + L.sc, (size_t)nk * sizeof(float));
+        std::memcpy(out_rows, h->qh.get() + L.rw, (size_t)nk * sizeof(int64_t));
         if (dev_values) {
-            std::memcpy(values, h->qh + L.val, (size_t)nk * h->dim * sizeof(float));
+            std::memcpy(values, h->qh.get() + L.val, (size_t)nk * h->dim * sizeof(float));
         } else if (with_values) {
             std::vector<int64_t> live;
             std::vector<int64_t> at;

@@ -34,14 +34,18 @@ void sparse_check_queries(const SparseQueries &sq, int nq);
 // host blocks, their device twins and the event after which the pinned words are free again.
 // Grows, never shrinks.
 struct SparseWs {
-    int64_t q_cap = 0, off_cap = 0;  // entries / offsets of the query copy
-    int32_t *off_h = nullptr, *off_d = nullptr;
-    uint32_t *idx_h = nullptr, *idx_d = nullptr;
-    float *val_h = nullptr, *val_d = nullptr;
-    int64_t w_rows = 0, w_slots = 0;  // rows / slots (rows x width) of one write round
-    int64_t *wrow_h = nullptr, *wrow_d = nullptr;
-    uint32_t *widx_h = nullptr, *widx_d = nullptr;
-    float *wval_h = nullptr, *wval_d = nullptr;
+    PinBuf<int32_t> off_h;  // offsets / entries of the query copy
+    DevBuf<int32_t> off_d;
+    PinBuf<uint32_t> idx_h;
+    DevBuf<uint32_t> idx_d;
+    PinBuf<float> val_h;
+    DevBuf<float> val_d;
+    PinBuf<int64_t> wrow_h;  // rows / slots (rows x width) of one write round
+    DevBuf<int64_t> wrow_d;
+    PinBuf<uint32_t> widx_h;
+    DevBuf<uint32_t> widx_d;
+    PinBuf<float> wval_h;
+    DevBuf<float> wval_d;
     hipEvent_t ev = nullptr;
     bool pending = false;  // ev was recorded and not waited for yet
     void wait();           // until the last staged copy left the pinned blocks

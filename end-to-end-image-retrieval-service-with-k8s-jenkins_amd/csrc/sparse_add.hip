@@ -101,17 +101,6 @@ __global__ __launch_bounds__(256) void sparse_regrow_kernel(const uint32_t *__re
     }
 }
 
-// a pinned block and its device twin, replaced by larger ones
-template <typename T>
-void realloc_pair(T *&h, T *&d, size_t count) {
-    hfree(h);
-    dfree(d);
-    h = nullptr;
-    d = nullptr;
-    h = (T *)hmalloc(count * sizeof(T));
-    d = (T *)dmalloc(count * sizeof(T));
-}
-
 }  // namespace
 
 void sparse_check_queries(const SparseQueries &sq, int nq) {
@@ -139,25 +128,23 @@ void SparseWs::stage_queries(const SparseQueries &sq, int nq, hipStream_t s) {
     const int64_t total = sq.off[nq];
     if (ev == nullptr) RC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     wait();
-    if (nq + 1 > off_cap) {
-        off_cap = 0;
-        realloc_pair(off_h, off_d, (size_t)nq + 1);
-        off_cap = nq + 1;
+    off_h.reserve((size_t)nq + 1);
+    off_d.reserve((size_t)nq + 1);
+    const size_t q_cap = min_capacity(idx_h, idx_d, val_h, val_d);
+    if ((size_t)total > q_cap) {
+        const size_t c2 = std::max<size_t>(total, 2 * q_cap);
+        idx_h.reserve(c2);
+        idx_d.reserve(c2);
+        val_h.reserve(c2);
+        val_d.reserve(c2);
     }
-    if (total > q_cap) {
-        const int64_t c2 = std::max<int64_t>(total, 2 * q_cap);
-        q_cap = 0;
-        realloc_pair(idx_h, idx_d, (size_t)c2);
-        realloc_pair(val_h, val_d, (size_t)c2);
-        q_cap = c2;
-    }
-    std::memcpy(off_h, sq.off, ((size_t)nq + 1) * sizeof(int32_t));
-    RC_HIP(hipMemcpyAsync(off_d, off_h, ((size_t)nq + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    std::memcpy(off_h.get(), sq.off, ((size_t)nq + 1) * sizeof(int32_t));
+    RC_HIP(hipMemcpyAsync(off_d.get(), off_h.get(), ((size_t)nq + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (total > 0) {
-        std::memcpy(idx_h, sq.idx, (size_t)total * sizeof(uint32_t));
-        std::memcpy(val_h, sq.val, (size_t)total * sizeof(float));
-        RC_HIP(hipMemcpyAsync(idx_d, idx_h, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        RC_HIP(hipMemcpyAsync(val_d, val_h, (size_t)total * sizeof(float), hipMemcpyHostToDevice, s));
+        std::memcpy(idx_h.get(), sq.idx, (size_t)total * sizeof(uint32_t));
+        std::memcpy(val_h.get(), sq.val, (size_t)total * sizeof(float));
+        RC_HIP(hipMemcpyAsync(idx_d.get(), idx_h.get(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        RC_HIP(hipMemcpyAsync(val_d.get(), val_h.get(), (size_t)total * sizeof(float), hipMemcpyHostToDevice, s));
     }
     RC_HIP(hipEventRecord(ev, s));
     pending = true;
@@ -165,23 +152,16 @@ void SparseWs::stage_queries(const SparseQueries &sq, int nq, hipStream_t s) {
 
 void SparseWs::ensure_write(int64_t rows, int width) {
     if (ev == nullptr) RC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    if (rows > w_rows) {
-        w_rows = 0;
-        realloc_pair(wrow_h, wrow_d, (size_t)rows);
-        w_rows = rows;
-    }
-    const int64_t slots = rows * width;
-    if (slots > w_slots) {
-        w_slots = 0;
-        realloc_pair(widx_h, widx_d, (size_t)slots);
-        realloc_pair(wval_h, wval_d, (size_t)slots);
-        w_slots = slots;
-    }
+    const size_t slots = (size_t)rows * width;
+    wrow_h.reserve((size_t)rows);
+    wrow_d.reserve((size_t)rows);
+    widx_h.reserve(slots);
+    widx_d.reserve(slots);
+    wval_h.reserve(slots);
+    wval_d.reserve(slots);
 }
 
 void SparseWs::release() {
-    for (void *p : {(void *)off_h, (void *)idx_h, (void *)val_h, (void *)wrow_h, (void *)widx_h, (void *)wval_h}) hfree(p);
-    for (void *p : {(void *)off_d, (void *)idx_d, (void *)val_d, (void *)wrow_d, (void *)widx_d, (void *)wval_d}) dfree(p);
     if (ev != nullptr) (void)hipEventDestroy(ev);
     *this = SparseWs{};
 }

@@ -67,7 +67,7 @@ struct rc_model {
     std::map<std::string, std::vector<int64_t>> shapes;  // expected tensors
     std::map<std::string, std::vector<float>> host;      // staged until finalize
     bool ready = false;
-    std::vector<void *> allocs;
+    std::vector<DevBuf<void>> allocs;  // the weight arena
     // device weights
     uint16_t *w_patch = nullptr;
     float *b_patch = nullptr, *cls = nullptr, *pos = nullptr, *lnf_w = nullptr, *lnf_b = nullptr;
@@ -92,8 +92,8 @@ struct rc_model {
     float *cls_hidden = nullptr, *cls_stats = nullptr;
     float *cls_part = nullptr;     // split-K partials of the CLS-row fc2 [SKINNY_KS][Cp][H]
     uint16_t *cls_ln = nullptr, *cls_attn = nullptr, *cls_mlp = nullptr;
-    uint8_t *resized = nullptr, *resize_tmp = nullptr;
-    size_t resize_tmp_bytes = 0;
+    uint8_t *resized = nullptr;
+    DevBuf<uint8_t> resize_tmp;
     KernelTimer timers[T_COUNT];
     int gemm_variant = GEMM_AUTO;  // diagnostic builds only: rc_diag_set_gemm_variant
     int qkv_sched = -1;            // diagnostic builds only: rc_diag_set_qkv_sched (-1: the product kernel)
@@ -128,9 +128,10 @@ struct rc_model {
     }
 
     void *alloc(size_t bytes) {
-        void *p = dmalloc(bytes);
-        allocs.push_back(p);
-        return p;
+        DevBuf<void> b;
+        b.reserve(bytes);
+        allocs.push_back(std::move(b));
+        return allocs.back().get();
     }
     ~rc_model() {
         clear_graphs();
@@ -140,8 +141,6 @@ struct rc_model {
             if (e) (void)hipEventDestroy(e);
         for (auto &q : sp)
             if (q) (void)hipStreamDestroy(q);
-        for (void *p : allocs) dfree(p);
-        dfree(resize_tmp);
     }
 };
 
@@ -336,17 +335,14 @@ const uint8_t *resize_batch(rc_model *m, const uint8_t *images, int n, int h, in
     if (need_h) {
         const int y0 = need_v ? cv.first : 0, Hs = need_v ? cv.last - cv.first : h;
         const size_t bytes = (size_t)n * Hs * S * 3;
-        if (bytes > m->resize_tmp_bytes) {
+        if (bytes > m->resize_tmp.capacity()) {
             RC_HIP(hipStreamSynchronize(s));
-            dfree(m->resize_tmp);
-            m->resize_tmp = nullptr;
-            m->resize_tmp = (uint8_t *)dmalloc(bytes);
-            m->resize_tmp_bytes = bytes;
+            m->resize_tmp.reserve(bytes);
         }
         hipLaunchKernelGGL(resize_h_kernel, dim3(grid_for((int64_t)n * Hs * S)), dim3(256), 0, s, images, h, w, y0, Hs,
-                           m->resize_tmp, S, ch.bounds, ch.coef, ch.ksize, n);
+                           m->resize_tmp.get(), S, ch.bounds, ch.coef, ch.ksize, n);
         RC_LAUNCH_CHECK();
-        cur = m->resize_tmp;
+        cur = m->resize_tmp.get();
         cur_h = Hs;
         if (!need_v) {
             RC_HIP(hipMemcpyAsync(m->resized, cur, (size_t)n * S * S * 3, hipMemcpyDeviceToDevice, s));
